@@ -8,11 +8,12 @@ Inputs are resident in HBM before the timed region.  Weak scaling: every rank in
 4096 streams; value = total uncompressed MiB / s over all GPUs.
 
     python bench.py --gpus 1 --steps 10 --warmup 2
-    python bench.py --gpus 8            # re-executes itself under torch.distributed.run, one rank per GPU
+    python bench.py --gpus 8            # runs itself under torch.distributed.run (a child), one rank per GPU
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+    python bench.py --dump-outputs DIR  # also writes what the last timed step returned, DIR/<name>.npy (dump_outputs)
 
-Prints ONE JSON line (rank 0).
+Prints ONE JSON line (rank 0); `ms_per_step` = wall milliseconds of one of the --steps timed steps.
   roofline      the hot path's one kernel, md::wv::inflate_wave_kernel: algorithmic bytes = compressed bytes
                 read + uncompressed bytes written per launch, over the launch duration
                 measured with HIP events on the stream the kernel runs on; peak = 8 TB/s HBM3E
@@ -45,6 +46,7 @@ import argparse
 import json
 import os
 import socket
+import subprocess
 import sys
 import time
 import zlib
@@ -130,7 +132,14 @@ def parse(argv=None):
     ap.add_argument("--inflate-waves", type=int, default=2, choices=[1, 2], help="wavefronts per stream of the inflate kernel (2 = decoder + copier, the default form)")
     ap.add_argument("--deflate-cap-mib", type=int, default=None, help="md_set_option deflate_workspace_cap_mib (default: the library's, a sixth of the device; 0 = none)")
     ap.add_argument("--profile", action="store_true", help="print the in-kernel phase profile of stream 0 (stderr)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed inflate path returned in its last step as DIR/<name>.npy (rank 0; see dump_outputs)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (the number of timed steps)")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 def share_device():
@@ -145,6 +154,15 @@ def _xdev(dev):
     """the device of the tensors that cross ranks"""
     import torch
     return torch.device("cpu") if share_device() else dev
+
+
+def device_count():
+    """md_device_count() in a child process, so that the process that launches the ranks holds no device open"""
+    r = subprocess.run([sys.executable, "-c", "from decompress_amd import _lib; print(_lib.load().md_device_count())"],
+                       cwd=ROOT, capture_output=True, text=True, timeout=300)
+    if r.returncode != 0:
+        raise SystemExit("bench: counting the gfx950 devices failed:\n" + r.stderr[-2000:])
+    return int(r.stdout.split()[-1])
 
 
 def respawn_command(args, argv, device_count):
@@ -677,13 +695,66 @@ def lzo_leg(args, eng, dev):
             "compressed_ratio": round(comp / total, 4), "parity_ok": ok}
 
 
+DUMP_ROWS = 1 << 19           # --dump-outputs: per-stream results of at most this many streams (36 B each: 18 MiB)
+DUMP_SAMPLE_FILE = 36 << 20   # ... and at most this much of out_sample (4 B a byte) + sample_offsets (8 B a position)
+DUMP_SEED = 0xD0              # 18 + 36 MiB = 56.6 MB: under 64 MB in all
+
+
+def dump_outputs(path, results, d_out, out_off, nbytes):
+    """--dump-outputs DIR: what a caller of the timed path (Engine.inflate_batch) receives from its last step, as .npy files
+    of float32 / float64 (every value exact), so that two builds can be compared output for output on the same inputs:
+      out_len, consumed, checksum (float64; checksum = the Adler-32 as an unsigned number), status (float32): one per
+        stream of stream_index (float64) - every stream, or a fixed seeded sample when there are more than DUMP_ROWS;
+      out_sample (float32, streams x positions): decompressed bytes of a fixed seeded sample of streams (sample_streams) at
+        fixed positions inside each (sample_offsets): whole streams (34 of the default 256 KiB ones), or evenly spaced
+        positions of one stream when a stream is too long for that; -1 where the position lies at or beyond the stream's
+        out_len (bytes the call did not write).
+    Returns {name: bytes written}."""
+    import torch
+    n = len(out_off)
+    rng = np.random.default_rng(DUMP_SEED)
+    out_len, consumed, status, checksum = (r.cpu().numpy() for r in results)
+    rows = np.arange(n) if n <= DUMP_ROWS else np.sort(rng.choice(n, DUMP_ROWS, replace=False))
+    k = min(n, (DUMP_SAMPLE_FILE - 8 * nbytes) // (4 * nbytes))  # whole streams: 4 B a byte of each, 8 B an offset
+    m = nbytes
+    if k < 1:
+        k, m = 1, DUMP_SAMPLE_FILE // 12
+    streams = np.sort(rng.choice(n, k, replace=False))
+    stride = nbytes // m
+    cols = np.arange(m, dtype=np.int64) * stride + (int(rng.integers(stride)) if stride > 1 else 0)
+    idx = torch.from_numpy((out_off[streams].astype(np.int64)[:, None] + cols[None, :]).reshape(-1)).to(d_out.device)
+    sample = d_out[idx].cpu().numpy().reshape(k, m).astype(np.float32)
+    del idx
+    sample[cols[None, :] >= out_len[streams][:, None]] = -1.0
+    arrays = {
+        "stream_index": rows.astype(np.float64),
+        "out_len": out_len[rows].astype(np.float64),
+        "consumed": consumed[rows].astype(np.float64),
+        "status": status[rows].astype(np.float32),
+        "checksum": checksum[rows].view(np.uint32).astype(np.float64),
+        "sample_streams": streams.astype(np.float64),
+        "sample_offsets": cols.astype(np.float64),
+        "out_sample": sample,
+    }
+    os.makedirs(path, exist_ok=True)
+    written = {}
+    for name, a in arrays.items():
+        f = os.path.join(path, name + ".npy")
+        np.save(f, a)
+        written[name] = os.path.getsize(f)
+    assert sum(written.values()) <= 64 * 10**6, written
+    return written
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "RANK" not in os.environ:
-        from decompress_amd import _lib
-        cmd = respawn_command(args, sys.argv[1:], _lib.load().md_device_count())
-        os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-        os.execv(sys.executable, cmd)
+        # the launcher never opens the device itself: the count comes from a child that exits before the ranks start,
+        # and the ranks run under a child launcher whose exit status this process passes on
+        cmd = respawn_command(args, sys.argv[1:], device_count())
+        env = dict(os.environ)
+        env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+        sys.exit(subprocess.run(cmd, env=env).returncode)
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -771,6 +842,9 @@ def main():
         tt = torch.tensor([elapsed], dtype=torch.float64, device=_xdev(dev))
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        # outside the timed region, before anything else writes d_out (the r01_workload leg reuses it)
+        dump_outputs(args.dump_outputs, results, d_out, out_off, nbytes)
 
     # ---- verification (outside the timed region): every stream Ok, bytes exact
     out_len, consumed, status, checksum = results

@@ -35,3 +35,39 @@ def test_too_few_devices_fails_loudly(monkeypatch):
     with pytest.raises(SystemExit) as e:
         bench.respawn_command(bench.parse(["--gpus", "8"]), ["--gpus", "8"], 1)
     assert "only 1 gfx950" in str(e.value)
+
+
+def test_steps_must_be_at_least_one():
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+    assert bench.parse(["--steps", "3"]).steps == 3 and bench.parse([]).dump_outputs is None
+    assert bench.parse(["--dump-outputs", "d"]).dump_outputs == "d"
+
+
+@pytest.mark.parametrize("n,nbytes", [(64, 64 * 1024), (2, 4 << 20)])
+def test_dump_outputs_writes_exact_bounded_float_arrays(tmp_path, n, nbytes):
+    """--dump-outputs on CPU tensors: float32 / float64 files under 64 MB, the same files for the same results, the sampled
+    bytes where the offsets say, -1 beyond a stream's out_len"""
+    import numpy as np
+    import torch
+    out_off = np.arange(n, dtype=np.int64) * nbytes
+    d_out = torch.from_numpy(np.random.default_rng(1).integers(0, 256, n * nbytes, dtype=np.uint8))
+    out_len = torch.full((n,), nbytes, dtype=torch.int64)
+    out_len[1] = nbytes // 3
+    res = (out_len, torch.arange(n, dtype=torch.int64) + 7, torch.zeros(n, dtype=torch.int32),
+           torch.tensor([-1, 5] + [123456] * (n - 2), dtype=torch.int32))
+    dirs = [str(tmp_path / "a"), str(tmp_path / "b")]
+    sizes = [bench.dump_outputs(d, res, d_out, out_off, nbytes) for d in dirs]
+    assert sizes[0] == sizes[1] and sum(sizes[0].values()) <= 64 * 10**6
+    load = lambda d, k: np.load(os.path.join(d, k + ".npy"))
+    for k in sizes[0]:
+        a, b = load(dirs[0], k), load(dirs[1], k)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), k
+    assert load(dirs[0], "checksum")[0] == 0xffffffff and list(load(dirs[0], "out_len")[:2]) == [nbytes, nbytes // 3]
+    streams, cols = load(dirs[0], "sample_streams").astype(np.int64), load(dirs[0], "sample_offsets").astype(np.int64)
+    s, raw = load(dirs[0], "out_sample"), d_out.numpy()
+    assert s.shape == (len(streams), len(cols)) and cols.max() < nbytes
+    for r, i in enumerate(streams):
+        want = raw[i * nbytes + cols].astype(np.float32)
+        want[cols >= int(out_len[i])] = -1
+        assert np.array_equal(s[r], want)
