@@ -6,7 +6,8 @@
 // zones of round r + 1, and it waits for the copier only before it writes round r + 1 into the staging buffer.  One
 // stream's rounds are serial, its two halves are not: a stream finishes 1.4x sooner than with one wavefront doing both
 // in turn (that form is still here: md_set_option "inflate_waves" = 1, same results), and with 8 streams = 16
-// wavefronts per CU the kernel is 1.13x faster on C2.
+// wavefronts per CU the kernel is 1.13x faster on C2.  Since round 7 a stream's LDS (17 872 B) and the PAIR form's
+// VGPRs (<= 96) leave room for 9 streams = 18 wavefronts per CU: 2.6 % faster on C2.
 //
 // The decoder's 64 lanes decode 64 consecutive zones (48 .. S bits, re-sized every round from what the last one produced) of
 // the compressed block per round:
@@ -73,8 +74,22 @@ constexpr uint32_t KMAX = 64;      // walk steps per lane per pass
 constexpr uint32_t RUNIN_NUM = MD_RUNIN_NUM, RUNIN_DEN = MD_RUNIN_DEN;  // run-in of the speculative pass, as a fraction of the zone
 constexpr uint32_t PASSES = 5;     // walks after the first one: at least this many are allowed, more when the zones are small
 constexpr uint32_t PASS_BITS = 1600, PASSES_MAX = 16;  // (a walk costs in proportion to the zone size)
-constexpr uint32_t RMAX = 768;     // match records per round, all lanes together (in stream order)
-constexpr uint32_t STAGE = 5568;   // staging bytes (one round of output)
+// Record pool and staging buffer: together with the table and the window they decide how many streams a CU holds.
+// 576 records are nine far rows (copy_far), which keeps the PAIR form at <= 96 VGPRs without scratch (five wavefronts per
+// SIMD); with 5248 staging bytes a stream needs 17 872 B of LDS, 9 streams per CU.  Measured on C2 (ms): 768 / 5568 at 8
+// streams 4.24; 576 / 5248 at 9 streams 4.11; 576 / 5568 (18 192 B, still 8: the LDS is allocated in coarser units)
+// 4.29; 576 / 3760 at 10 streams 4.78 (rounds too short).  -DMD_RMAX / -DMD_STAGE / -DMD_PAIR_OCC: measurement builds.
+#ifndef MD_RMAX
+#define MD_RMAX 576
+#endif
+#ifndef MD_STAGE
+#define MD_STAGE 5248
+#endif
+#ifndef MD_PAIR_OCC
+#define MD_PAIR_OCC 5  // wavefronts per SIMD the PAIR form is compiled for (launch bounds): 18 per CU need 5 on two SIMDs
+#endif
+constexpr uint32_t RMAX = MD_RMAX;     // match records per round, all lanes together (in stream order)
+constexpr uint32_t STAGE = MD_STAGE;   // staging bytes (one round of output)
 constexpr uint32_t WIN_WORDS = 544;  // input window: 31 + 64*S + 47 bits and the two words a peek touches
 
 // LUT entry: n[4:0] | xb[8:5] | val8[16:9] | next.nbits[20:17] | next.tb[31:21]
@@ -134,7 +149,10 @@ struct HScratch {       // aliases the tail of Smem::win (hscratch_of)
   uint16_t work[320];   // symbols sorted by (code length, symbol)
   uint32_t ctr;         // sub-table allocation counter
 };
-static_assert(sizeof(Smem) <= 20480, "8 streams (16 wavefronts) per CU");
+#if MD_RMAX == 576 && MD_STAGE == 5248
+static_assert(sizeof(Smem) <= 17920, "9 streams (18 wavefronts) per CU: 160 KiB / 9, in whole 512-byte units");
+#endif
+static_assert(RMAX % 64 == 0 && STAGE % 16 == 0 && RMAX * 2 >= (kHxUni + 6) * 4, "record rows, staging chunks, the emit job's words in `list`");
 // A dynamic header is at most 17 + 19 x 3 + 320 x 14 bits = 570 bytes and starts in the window's first word: the window's
 // tail is free while a header is parsed (the staging buffer is not: the copier wavefront may still be writing a round out)
 constexpr uint32_t kHScratchAt = 1136;
@@ -1435,7 +1453,7 @@ struct Cont {
 
 // PAIR = two wavefronts per stream (decoder + copier, see inflate_block); otherwise one wavefront does both in turn.
 template <bool PROF, bool PAIR>
-__global__ __launch_bounds__(PAIR ? 2 * kWave : kWave, PAIR ? 4 : 2) void inflate_wave_kernel(
+__global__ __launch_bounds__(PAIR ? 2 * kWave : kWave, PAIR ? MD_PAIR_OCC : 2) void inflate_wave_kernel(
     int format, uint32_t n, const uint8_t *__restrict__ in, const uint64_t *__restrict__ in_off,
     const uint64_t *__restrict__ in_len, uint8_t *out, const uint64_t *__restrict__ out_off,
     const uint64_t *__restrict__ out_cap, uint64_t *__restrict__ out_len,
