@@ -980,7 +980,8 @@ __device__ __forceinline__ void copy_far(const lds_u32 *mrec, const lds_u16 *mpo
         if (j < ln[k]) lds_put(stage + lqs[k] + j, d[k], ln[k] - j < 8 ? ln[k] - j : 8);
     }
   }
-  if (spill) {  // (never seen: more long records than `list` has room for) one record at a time, all its bytes beyond 16
+  if (spill) {  // (rare: more long records than `list` has room for) one record at a time, all its bytes beyond 16
+    pf.count(C_FAR_SPILL);
     for (uint32_t c0 = 0; c0 < nrec; c0 += kWave) {
       const FarRow f = far_row(mrec, mpos, c0 + lane, nrec, rb, R0);
       for (uint64_t lm = __ballot(f.n > 16); lm; lm &= lm - 1) {
@@ -1522,6 +1523,7 @@ __global__ __launch_bounds__(PAIR ? 2 * kWave : kWave, PAIR ? MD_PAIR_OCC : 2) v
           for (int i : mine) dbg[i] = pf.acc[i];
           dbg[P_COUNT + C_NEAR_IT] = pf.cnt[C_NEAR_IT];
           dbg[P_COUNT + C_LONG_NEAR] = pf.cnt[C_LONG_NEAR];
+          dbg[P_COUNT + C_FAR_SPILL] = pf.cnt[C_FAR_SPILL];
         }
       }
       return;
@@ -1684,7 +1686,7 @@ __global__ __launch_bounds__(PAIR ? 2 * kWave : kWave, PAIR ? MD_PAIR_OCC : 2) v
         const int mine[] = {P_ENSURE, P_DECODE1, P_DECODE2, P_EMIT_A, P_HEADER, P_HDR_LENS, P_HDR_LIT, P_WAIT_DEC};
         for (int i : mine) dbg[i] = pf.acc[i];
         for (int i = 0; i < C_COUNT; i++)
-          if (i != C_NEAR_IT && i != C_LONG_NEAR) dbg[P_COUNT + i] = pf.cnt[i];
+          if (i != C_NEAR_IT && i != C_LONG_NEAR && i != C_FAR_SPILL) dbg[P_COUNT + i] = pf.cnt[i];
       } else {
         for (int i = 0; i < P_COUNT; i++) dbg[i] = pf.acc[i];
         for (int i = 0; i < C_COUNT; i++) dbg[P_COUNT + i] = pf.cnt[i];
