@@ -127,7 +127,7 @@ class GzMeta(ctypes.Structure):
                [(k, ctypes.c_int) for k in ("has_extra", "has_name", "has_comment")] + \
                [(k, c_sz) for k in ("extra_off", "extra_len", "name_off", "name_len", "comment_off", "comment_len")]
 # exported but not part of the public header (tuning knobs)
-EXTRA = [("md_get_profile", ctypes.c_int, [c_vp, c_vp])]
+EXTRA = [("md_get_profile", ctypes.c_int, [c_vp, c_vp]), ("md_i_link_segments", ctypes.c_int, [c_vp])]
 
 _lib = None
 

@@ -68,15 +68,16 @@ def run(deflate, fmt, level, data, now=None):
         if fmt == "lzo":
             return 0, lzo.compress(data), None
         if fmt == "deflate":
-            st, out, _ = eng.deflate_many([data], decompress_amd.FORMAT_DEFLATE, level=level, queue=QUEUE,
-                                          driver=engine.DRIVER_CLI)[0]
+            st, out, _ = eng.deflate_one(data, decompress_amd.FORMAT_DEFLATE, level=level, queue=QUEUE,
+                                         driver=engine.DRIVER_CLI)
         elif fmt == "zlib":
-            st, out, _ = eng.deflate_many([data], decompress_amd.FORMAT_ZLIB, level=level, queue=QUEUE,
-                                          driver=engine.DRIVER_ZL)[0]
+            st, out, _ = eng.deflate_one(data, decompress_amd.FORMAT_ZLIB, level=level, queue=QUEUE,
+                                         driver=engine.DRIVER_ZL)
         else:
             mtime = int(time.time() if now is None else now) & 0xffffffff
-            st, out, _ = gz.Def.deflate_batch([data], level=level, queue=QUEUE, mtime=mtime, os=gz.OS["Unix"])[0]
-        if st != 0:  # cannot happen with the room deflate_many gives a stream
+            hdr = dict(mtime=mtime, os=gz.OS["Unix"], hcrc=0, ascii=0, filename=None, comment=None)
+            st, out, _ = eng.deflate_one(data, decompress_amd.FORMAT_GZIP, level=level, queue=QUEUE, header=hdr)
+        if st != 0:  # cannot happen with the room deflate_one gives a stream
             return CLI_ERROR, b"", engine.STATUS_NAMES[st]
         return 0, out, None
     if fmt == "lzo":

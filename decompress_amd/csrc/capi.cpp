@@ -40,6 +40,11 @@ extern "C" int md_launch_deflate_plan(uint32_t n, const uint64_t *in_len, int dr
 extern "C" int md_launch_deflate_front(uint32_t n, uint32_t nchunks_max, const uint8_t *in, const uint64_t *in_off,
                                        const uint64_t *in_len, int matcher, uint32_t max_chain, uint32_t nice,
                                        const md_front *f, const uint32_t *order, uint32_t match_skip, hipStream_t stream);
+extern "C" int md_launch_deflate_match(uint32_t n, uint32_t nchunks_max, const uint8_t *in, const uint64_t *in_off,
+                                       const uint64_t *in_len, uint32_t max_chain, uint32_t nice, const md_front *f,
+                                       uint32_t match_skip, hipStream_t stream);
+extern "C" int md_launch_link_chunked(const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len, uint32_t p_end,
+                                      uint32_t seg, uint32_t cus, const md_front *f, hipStream_t stream);
 extern "C" int md_i_debug_inflate_lds_pad(uint32_t bytes);
 extern "C" int md_i_debug_known_bounds(int mode, uint32_t nstreams);
 extern "C" int md_launch_stream_order(uint32_t n, const uint64_t *in_len, uint32_t *order, hipStream_t stream);
@@ -133,6 +138,12 @@ struct md_ctx {
   size_t par_min = (size_t)96 << 10, par_chunk = (size_t)64 << 10;  // (measured: the pieces pay from ~100 KB of input, ~1 ms flat up to 4 MiB of text)
   int par_last_pieces = 0, par_last_rounds = 0;  // of the last stream that went this way (md_get_option, tests)
   int host_slices_max = 16;  // md_set_option "host_pipeline_slices": 1 = copy-in / kernels / copy-out one after the other
+  // ONE long stream's hash chains in segments on the whole chip (link_segments): md_set_option
+  // "deflate_link_segment_min" (input bytes from which a single stream of md_deflate_batch_host goes this way, 0 = never)
+  // and "deflate_link_segment" (positions per segment, 0 = by the stream's length); link_last_segments: the segments
+  // the last deflate batch call built its chains in (0 = one workgroup per stream; md_i_link_segments, tests)
+  size_t link_seg_min = (size_t)128 << 10, link_seg = 0;
+  uint32_t link_last_segments = 0;
   std::string err;
 };
 
@@ -430,6 +441,16 @@ int md_set_option(md_ctx *ctx, const char *key, int value) {
   }
   if (!strcmp(key, "inflate_parallel_last")) {  // (query, value ignored) pieces of the last stream that went that way | rounds << 24; 0: it did not
     return ctx->par_last_pieces | (ctx->par_last_rounds << 24);
+  }
+  if (!strcmp(key, "deflate_link_segment_min")) {  // KiB of input from which ONE stream's hash chains are built in segments; 0 = never
+    if (value < 0) return fail(ctx, MD_E_INVALID_ARGUMENT, "deflate_link_segment_min >= 0 (KiB)");
+    ctx->link_seg_min = (size_t)value << 10;
+    return MD_OK;
+  }
+  if (!strcmp(key, "deflate_link_segment")) {  // KiB of input per segment; 0 = by the stream's length
+    if (value < 0 || value > (1 << 20)) return fail(ctx, MD_E_INVALID_ARGUMENT, "deflate_link_segment is 0 .. 2^20 (KiB)");
+    ctx->link_seg = (size_t)value << 10;
+    return MD_OK;
   }
   if (!strcmp(key, "host_pipeline_slices")) {  // md_*_batch_host: slices of streams in flight (1 = no overlap of copies and kernels)
     if (value < 1 || value > 64) return fail(ctx, MD_E_INVALID_ARGUMENT, "host_pipeline_slices is 1 .. 64");
@@ -978,6 +999,12 @@ struct PieceArgs {
   uint32_t match_skip;          // leading positions of the text no stream of the launch will take (the window brought along)
 };
 
+// ONE long stream whose hash chains are built in segments (deflate_chunked.hip): seg positions per segment, p_end the
+// stream's first position not inserted ahead (len - 3)
+struct LinkSegs {
+  uint32_t seg, p_end;
+};
+
 // total_in: an upper bound of the sum of in_len when the caller knows one (md_deflate_params.total_in_bytes), else 0:
 // the front workspace is then sized from the totals the plan kernel computes, which costs one 16-byte read-back
 // (a synchronisation with the context's stream).
@@ -985,7 +1012,7 @@ static int deflate_launch(md_ctx *ctx, int format, int level, int queue_len, int
                           const md_gz_header *gz, size_t n, const uint8_t *d_in, const uint64_t *d_in_off,
                           const uint64_t *d_in_len, uint8_t *d_out, const uint64_t *d_out_off, const uint64_t *d_out_cap,
                           uint64_t *d_out_len, int32_t *d_status, uint32_t *d_checksum, uint32_t *d_hist, size_t total_in,
-                          const PieceArgs *pa = nullptr) {
+                          const PieceArgs *pa = nullptr, const LinkSegs *ls = nullptr) {
   int grc_ = MD_OK;
   // (the Lz77-alone / encode-alone / scripted drivers leave the kernel before it saves a piece's state)
   if (pa && driver >= 3) return fail(ctx, MD_E_INVALID_ARGUMENT, "a stream in pieces needs one of the three public drivers");
@@ -1059,7 +1086,18 @@ static int deflate_launch(md_ctx *ctx, int format, int level, int queue_len, int
     if (oe != 0) return fail(ctx, MD_E_HIP, "launch order kernel", (hipError_t)oe);
   }
   if (matcher_runs && chunks != 0) {
-    int frc = md_launch_deflate_front((uint32_t)n, chunks, d_in, d_in_off, d_front_len, matcher, max_chain, nice, &fr, order, pa ? pa->match_skip : 0u, ctx->stream);
+    bool linked = false;
+    if (ls && n == 1 && !pa && matcher == MD_MATCHER_DE) {
+      // ONE long stream (link_segments): its hash chains by segments on the whole chip, the same link[] and tails
+      if (md_launch_link_chunked(d_in, d_in_off, d_front_len, ls->p_end, ls->seg, (uint32_t)ctx->cus, &fr, ctx->stream) == 0) {
+        linked = true;
+        ctx->link_last_segments = (ls->p_end + ls->seg - 1) / ls->seg;
+      } else {
+        (void)hipGetLastError();  // a launch that failed: the one-workgroup link kernel instead
+      }
+    }
+    int frc = linked ? md_launch_deflate_match((uint32_t)n, chunks, d_in, d_in_off, d_front_len, max_chain, nice, &fr, 0u, ctx->stream)
+                     : md_launch_deflate_front((uint32_t)n, chunks, d_in, d_in_off, d_front_len, matcher, max_chain, nice, &fr, order, pa ? pa->match_skip : 0u, ctx->stream);
     if (frc != 0) return fail(ctx, MD_E_HIP, "deflate front kernel launch", (hipError_t)frc);
   }
   int rc = md_launch_deflate(format, level, queue_len, driver, dynamic, (uint32_t)n, d_in, d_in_off, d_in_len, d_out,
@@ -1406,10 +1444,13 @@ static int deflate_capped(md_ctx *ctx, int format, const md_deflate_params &q, s
   return MD_OK;
 }
 
-int md_deflate_batch_device(md_ctx *ctx, int format, const md_deflate_params *params, size_t n, const uint8_t *d_in,
-                            const uint64_t *d_in_off, const uint64_t *d_in_len, uint8_t *d_out, const uint64_t *d_out_off,
-                            const uint64_t *d_out_cap, uint64_t *d_out_len, int32_t *d_status, uint32_t *d_checksum) {
+// ls: ONE stream whose hash chains go in segments (md_deflate_batch_host), else null
+static int deflate_batch_device(md_ctx *ctx, int format, const md_deflate_params *params, size_t n, const uint8_t *d_in,
+                                const uint64_t *d_in_off, const uint64_t *d_in_len, uint8_t *d_out, const uint64_t *d_out_off,
+                                const uint64_t *d_out_cap, uint64_t *d_out_len, int32_t *d_status, uint32_t *d_checksum,
+                                const LinkSegs *ls) {
   if (!ctx) return MD_E_INVALID_ARGUMENT;
+  ctx->link_last_segments = 0;
   md_deflate_params q;
   int rc = check_params(ctx, format, params, &q);
   if (rc != MD_OK) return rc;
@@ -1436,7 +1477,15 @@ int md_deflate_batch_device(md_ctx *ctx, int format, const md_deflate_params *pa
     }
   }
   return deflate_launch(ctx, format, q.level, q.queue_len, q.driver, q.dynamic, q.matcher, q.gz_header, n, d_in, d_in_off,
-                        d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status, d_checksum, nullptr, q.total_in_bytes);
+                        d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status, d_checksum, nullptr, q.total_in_bytes,
+                        nullptr, ls);
+}
+
+int md_deflate_batch_device(md_ctx *ctx, int format, const md_deflate_params *params, size_t n, const uint8_t *d_in,
+                            const uint64_t *d_in_off, const uint64_t *d_in_len, uint8_t *d_out, const uint64_t *d_out_off,
+                            const uint64_t *d_out_cap, uint64_t *d_out_len, int32_t *d_status, uint32_t *d_checksum) {
+  return deflate_batch_device(ctx, format, params, n, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status,
+                              d_checksum, nullptr);
 }
 
 // ---- the encoder shim's stream in pieces (stream_shim.cpp): not part of the public ABI ------------------------------
@@ -1715,11 +1764,11 @@ static int deflate_host_positions(md_ctx *ctx, int format, const md_deflate_para
 }
 }  // extern "C++"
 
-int md_deflate_batch_host(md_ctx *ctx, int format, const md_deflate_params *params,
-                          size_t n, const uint8_t *h_in, size_t in_bytes, const uint64_t *in_off,
-                          const uint64_t *in_len, uint8_t *h_out, size_t out_bytes,
-                          const uint64_t *out_off, const uint64_t *out_cap, uint64_t *out_len,
-                          int32_t *status, uint32_t *checksum) {
+static int deflate_batch_host(md_ctx *ctx, int format, const md_deflate_params *params,
+                              size_t n, const uint8_t *h_in, size_t in_bytes, const uint64_t *in_off,
+                              const uint64_t *in_len, uint8_t *h_out, size_t out_bytes,
+                              const uint64_t *out_off, const uint64_t *out_cap, uint64_t *out_len,
+                              int32_t *status, uint32_t *checksum, const LinkSegs *ls) {
   if (!ctx) return MD_E_INVALID_ARGUMENT;
   if (n == 0) return MD_OK;
   if (!params || !in_off || !in_len || !out_off || !out_cap || !out_len || !status)
@@ -1758,8 +1807,8 @@ int md_deflate_batch_host(md_ctx *ctx, int format, const md_deflate_params *para
     hp.total_in_bytes = 0;
     for (size_t i = i0; i < i0 + cnt; i++) hp.total_in_bytes += (size_t)in_len[i];
     if (hp.total_in_bytes == 0) hp.total_in_bytes = 1;  // all empty: still no read-back
-    return md_deflate_batch_device(ctx, format, &hp, cnt, din, d64 + i0, d64 + n + i0, dout, d64 + 2 * n + i0, d64 + 3 * n + i0,
-                                   d64 + 4 * n + i0, dstatus + i0, dsum + i0);
+    return deflate_batch_device(ctx, format, &hp, cnt, din, d64 + i0, d64 + n + i0, dout, d64 + 2 * n + i0, d64 + 3 * n + i0,
+                                d64 + 4 * n + i0, dstatus + i0, dsum + i0, cnt == 1 ? ls : nullptr);
   });
   if (rc != MD_OK) return rc;
   HIP_TRY(ctx, hipMemcpyAsync(out_len, d64 + 4 * n, n * 8, hipMemcpyDeviceToHost, st));
@@ -1768,6 +1817,49 @@ int md_deflate_batch_host(md_ctx *ctx, int format, const md_deflate_params *para
   HIP_TRY(ctx, hipStreamSynchronize(st));
   return MD_OK;
 }
+
+// ONE long stream: whether its hash chains are built in segments by the whole chip (deflate_chunked.hip)
+// instead of by one workgroup, and in which.  This changes only who computes link[] and the tails, not their values, so
+// every status, byte and checksum is the one-workgroup path's whatever happens afterwards (a dst_cap too small included).
+// Taken: DEFLATE / ZLIB / GZIP, drivers ZL / HIGHER / CLI, levels 1..9 (HIGHER: 4), De's matcher, at least
+// "deflate_link_segment_min" of input and at least two segments of positions [0, len - 3).  Segments:
+// "deflate_link_segment", or by default the stream spread over the CUs - a multiple of 32 KiB and at least 64 KiB (a
+// segment inserts 32 KiB in front of its own positions without writing).  The segmented kernel needs no workspace of its
+// own; a launch that fails leaves the one-workgroup kernel to do it (deflate_launch).
+static bool link_segments(const md_ctx *ctx, int format, const md_deflate_params *params, uint64_t len, LinkSegs *ls) {
+  if (ctx->link_seg_min == 0 || len < ctx->link_seg_min || len > MD_MAX_STREAM || len < 4) return false;
+  if (format != MD_FORMAT_DEFLATE && format != MD_FORMAT_ZLIB && format != MD_FORMAT_GZIP) return false;
+  const int d = params->driver, lv = d == MD_DRIVER_HIGHER ? 4 : params->level;
+  if (d != MD_DRIVER_ZL && d != MD_DRIVER_HIGHER && d != MD_DRIVER_CLI) return false;
+  if (lv < 1 || lv > 9 || params->matcher != MD_MATCHER_DE) return false;
+  const uint64_t p_end = len - 3;  // (deflate_common.hpp stream_p_end: De's matcher, a level above 0)
+  uint64_t seg = ctx->link_seg;
+  if (seg == 0) {
+    const uint64_t cus = ctx->cus > 0 ? (uint64_t)ctx->cus : 256;
+    seg = ((p_end + cus - 1) / cus + 32767) / 32768 * 32768;
+    if (seg < 65536) seg = 65536;
+  }
+  if (p_end <= seg) return false;  // (one segment: nothing to spread)
+  ls->seg = (uint32_t)seg;
+  ls->p_end = (uint32_t)p_end;
+  return true;
+}
+
+int md_deflate_batch_host(md_ctx *ctx, int format, const md_deflate_params *params,
+                          size_t n, const uint8_t *h_in, size_t in_bytes, const uint64_t *in_off,
+                          const uint64_t *in_len, uint8_t *h_out, size_t out_bytes,
+                          const uint64_t *out_off, const uint64_t *out_cap, uint64_t *out_len,
+                          int32_t *status, uint32_t *checksum) {
+  if (!ctx) return MD_E_INVALID_ARGUMENT;
+  ctx->link_last_segments = 0;
+  LinkSegs ls;
+  const bool seg = n == 1 && params && in_len && link_segments(ctx, format, params, in_len[0], &ls);
+  return deflate_batch_host(ctx, format, params, n, h_in, in_bytes, in_off, in_len, h_out, out_bytes, out_off, out_cap, out_len,
+                            status, checksum, seg ? &ls : nullptr);
+}
+
+// (tests) segments the last deflate batch call of ctx built its hash chains in; 0 = one workgroup per stream
+int md_i_link_segments(const md_ctx *ctx) { return ctx ? (int)ctx->link_last_segments : -1; }
 
 static int deflate_one(md_ctx *ctx, int format, int level, int queue_len, int driver, int dynamic, const md_gz_header *gz,
                        const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap, size_t *written) {

@@ -18,12 +18,10 @@
 // Neither kernel takes a decision: the lazy evaluation, the queue, the trees and the bit encoder read these
 // arrays in deflate_kernel.hip.  Before this split the same work sat inside the sequential kernel with the head
 // table in HBM (one atomic and ~3 dependent HBM round trips per position): 66x the algorithmic traffic.
-#include "deflate_common.hpp"
+#include "deflate_link.hpp"
 
 namespace md {
 namespace defl {
-
-constexpr int PGL = 8;  // steps of 64 positions whose LDS atomics are in flight together (link kernel)
 
 // ---- per-stream slots ---------------------------------------------------------------------------
 constexpr uint32_t kPlanThreads = 1024;
@@ -86,33 +84,9 @@ __global__ __launch_bounds__(kPlanThreads) void deflate_plan_kernel(uint32_t n, 
   }
 }
 
-// the 4 bytes at pos (little-endian) for pos < p_end (something for the others), without a branch: Lz's last string (pos = len - 3) has
-// only 3 bytes — it is taken from the word one byte earlier; len >= 4 whenever p_end > 1
-__device__ __forceinline__ uint32_t load_w4(const uint8_t *__restrict__ src, uint32_t slen, uint32_t p_end, uint32_t pos) {
-  uint32_t a = pos + 4 <= slen ? pos : slen - 4;
-  a = pos < p_end ? a : 0u;
-  uint32_t v;
-  __builtin_memcpy(&v, src + a, 4);
-  return v >> ((8 * (pos - a)) & 31);  // (whatever for pos >= p_end: nobody looks at it)
-}
-
 // ---- hash chains ----------------------------------------------------------------------------------
-// head[h] <- max(pos), one LDS atomic per position.  The head table of a stream is 128 KiB of LDS, so a CU holds one
-// stream — and one wavefront alone runs at the latency of its own instruction stream (9 cycles per instruction
-// measured).  LW wavefronts therefore share the stream: wavefront w takes the groups k = w, w + LW, ... of 8 x 64
-// positions, loads and hashes them ahead, and only the atomics themselves are taken in stream order — a turn counter
-// in LDS lets group k issue its eight atomics once group k - 1 has got its results back (a wavefront's own LDS
-// operations execute in order).  Everything after the atomics (sorting out equal hashes, the stores) overlaps with
-// the other wavefronts' groups.  Measured per GiB of input: 4 wavefronts 4.9 ms (word text 7.0), 8: 3.1 (4.5), 16:
-// 3.2 (3.8) — from 8 on the chain of turns is what is left.
-// The values a set of equal hashes gets back are >= the head before the set and one of them is exactly that value: a
-// lane that shares its hash with another lane of its step is recognised by a returned position inside the step, and
-// such steps sort themselves out by ballots (the predecessor of a lane is the nearest lower lane with its hash, else
-// the smallest value the set got back).
-// NS = De.Def.Ns's hc_matchfinder (lib/de.ml:3765-3856): the hash is 16 bits of 4 bytes times 0x1E35A7BD — twice the
-// table LDS has room for, so the stream is gone through twice, once per half of the hash range (a chain never leaves
-// its half) —, position 0 goes into bucket 0 whatever its bytes (next_hash4 starts at 0), and there is no tail.
-constexpr int LW = 16;  // wavefronts per stream
+// The insertion itself is link_insert (deflate_link.hpp): one workgroup of LW wavefronts per stream, the whole stream in
+// one range.
 template <bool NS>
 __global__ __launch_bounds__(LW *kWave) void deflate_link_kernel(uint32_t n, const uint8_t *__restrict__ in,
                                                                  const uint64_t *__restrict__ in_off,
@@ -124,10 +98,7 @@ __global__ __launch_bounds__(LW *kWave) void deflate_link_kernel(uint32_t n, con
   __shared__ uint32_t head[HASH_SIZE];  // absolute position, 0 = NIL (position 0 can never match, like the reference)
   __shared__ uint32_t gmin_all[LW][kWave];
   __shared__ uint32_t turn;  // the group whose atomics may be issued
-  // De.Lz77: position 0 is NIL (it can never be a match source there); Def.Ns: position 0 is an ordinary candidate, so
-  // the table holds position + 1
-  constexpr uint32_t bias = NS ? 1u : 0u;
-  const uint32_t lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
+  const uint32_t wv = threadIdx.x / kWave;
   if (blockIdx.x >= n || flags[0]) return;
   const uint32_t sid = order ? order[blockIdx.x] : blockIdx.x;  // a CU holds one stream: the longest go first
   const uint32_t p_end = p_end_a[sid];
@@ -135,106 +106,16 @@ __global__ __launch_bounds__(LW *kWave) void deflate_link_kernel(uint32_t n, con
   const uint32_t slen = l64 > MD_MAX_STREAM ? 0u : (uint32_t)l64;
   const uint8_t *src = in + in_off[sid];
   uint32_t *lk = link + slot[sid];
-  uint32_t *gmin = gmin_all[wv];
   if (slen < 4) {  // at most one string (Lz, 3 bytes): nothing before it
     if (threadIdx.x < p_end) lk[threadIdx.x] = 0;  // (nobody compares its fingerprint)
     if (threadIdx.x < 2 && !NS) tail[2 * sid + threadIdx.x] = 0;
     return;
   }
-  for (uint32_t pass = 0; pass < (NS ? 2u : 1u); pass++) {
-  __syncthreads();
-  {
-    uint4 *h4 = reinterpret_cast<uint4 *>(head);
-    for (uint32_t i = threadIdx.x; i < (uint32_t)HASH_SIZE / 4; i += LW * kWave) h4[i] = make_uint4(0, 0, 0, 0);
-    if (threadIdx.x == 0) turn = 0;
-  }
-  __syncthreads();
-  // the input of a wavefront's next two groups is requested before the current one is worked on
-  // (branch-free: a branch around a load makes the compiler wait for every load in flight)
-  auto load_group = [&](uint32_t pe, uint32_t (&w)[PGL]) {
-#pragma unroll
-    for (int g = 0; g < PGL; g++) w[g] = load_w4(src, slen, p_end, pe + g * kWave + lane);
-  };
-  constexpr uint32_t kGroup = PGL * kWave;
-  const uint32_t ngroups = (p_end + kGroup - 1) / kGroup;
-  uint32_t wa[PGL], wb[PGL];
-  load_group(wv * kGroup, wa);
-  load_group((wv + LW) * kGroup, wb);
-  for (uint32_t k = wv; k < ngroups; k += LW) {
-    const uint32_t pe = k * kGroup;
-    uint32_t w4[PGL], hv[PGL], ret[PGL];
-    bool mine[PGL];  // the position's hash is in this pass's half of the range
-#pragma unroll
-    for (int g = 0; g < PGL; g++) {
-      w4[g] = wa[g];
-      wa[g] = wb[g];
-      if (NS) {
-        const uint32_t h = (pe + g * kWave + lane) == 0 ? 0u : (uint32_t)(w4[g] * 0x1E35A7BDu) >> 16;
-        hv[g] = h & (HASH_SIZE - 1);
-        mine[g] = (h >> HASH_BITS) == pass;
-      } else {
-        hv[g] = hash_of(matcher, w4[g]);
-        mine[g] = true;
-      }
-    }
-    load_group(pe + 2 * LW * kGroup, wb);
-    while (__hip_atomic_load(&turn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != k) __builtin_amdgcn_s_sleep(1);
-#pragma unroll
-    for (int g = 0; g < PGL; g++) {
-      const uint32_t pos = pe + g * kWave + lane;
-      ret[g] = (pos < p_end && mine[g]) ? atomicMax(&head[hv[g]], pos + bias) : 0xffffffffu;
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the group's atomics have been performed: the next group may go
-    if (lane == 0) __hip_atomic_store(&turn, k + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#pragma unroll
-    for (int g = 0; g < PGL; g++) {
-      const uint32_t s0 = pe + g * kWave;
-      if (s0 >= p_end) break;  // uniform
-      const uint32_t pos = s0 + lane;
-      const bool valid = pos < p_end && mine[g];
-      uint32_t c1;
-      if (__ballot(valid && ret[g] >= s0 + bias) == 0) {
-        c1 = valid ? ret[g] : 0;  // no two lanes share a hash: every returned value is the head before the step
-      } else {
-        const uint32_t h = hv[g];
-        uint64_t same = __ballot(valid);
-#pragma unroll
-        for (int bit = 0; bit < HASH_BITS; bit++) {
-          const bool mine = (h >> bit) & 1;
-          const uint64_t bal = __ballot(mine);
-          same &= mine ? bal : ~bal;
-        }
-        const uint64_t below = same & lanes_below(lane);
-        const uint32_t first = valid ? (uint32_t)__builtin_ctzll(same) : lane;
-        gmin[lane] = 0xffffffffu;
-        __builtin_amdgcn_wave_barrier();
-        if (valid) atomicMin(&gmin[first], ret[g]);
-        __builtin_amdgcn_wave_barrier();
-        c1 = !valid ? 0u : below ? s0 + bias + 63u - (uint32_t)__builtin_clzll(below) : __hip_atomic_load(&gmin[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        __builtin_amdgcn_wave_barrier();
-      }
-      if (valid) {
-        const uint32_t d = pos + bias - c1;
-        lk[pos] = ((c1 != 0 && d <= 32767u) ? d : 0u) | (fp16(w4[g]) << 16);
-      }
-    }
-  }
-  }  // pass
+  for (uint32_t pass = 0; pass < (NS ? 2u : 1u); pass++)
+    link_insert<NS>(head, gmin_all[wv], &turn, src, slen, p_end, 0u, 0u, p_end, lk, matcher, pass);
   __syncthreads();
   if (NS) return;
-  // De's position len - 3 (lookahead 3): hash4 reads a 4th byte beyond the data (H7) — zero before the first slide of
-  // the reference's 64 KiB buffer, the byte 32 KiB earlier after it.  Which one depends on the matcher's trajectory:
-  // both heads are handed over.
-  if (threadIdx.x < 2) {
-    uint32_t res = 0;
-    if (matcher == MD_MATCHER_DE && slen >= 3) {
-      const uint32_t p = slen - 3;
-      const uint32_t b3 = (threadIdx.x == 1 && slen >= (uint32_t)WSIZE) ? src[slen - WSIZE] : 0u;
-      const uint32_t w = (uint32_t)src[p] | ((uint32_t)src[p + 1] << 8) | ((uint32_t)src[p + 2] << 16) | (b3 << 24);
-      res = head[hash_of(matcher, w)];
-    }
-    tail[2 * sid + threadIdx.x] = res;
-  }
+  link_tail(head, src, slen, matcher, tail + 2 * sid);
 }
 
 // ---- longest_match ahead --------------------------------------------------------------------------
@@ -456,6 +337,17 @@ extern "C" int md_launch_deflate_plan(uint32_t n, const uint64_t *in_len, int dr
                      (uint32_t *)f->flags);
   return (int)hipGetLastError();
 }
+// flg[] / m[] / mq[] from link[]: nchunks_max >= chunk0[n]
+extern "C" int md_launch_deflate_match(uint32_t n, uint32_t nchunks_max, const uint8_t *in, const uint64_t *in_off,
+                                       const uint64_t *in_len, uint32_t max_chain, uint32_t nice, const md::defl::Front *f,
+                                       uint32_t match_skip, hipStream_t stream) {
+  using namespace md::defl;
+  if (n == 0 || nchunks_max == 0) return 0;
+  const uint32_t per = (nchunks_max + 7) / 8;
+  hipLaunchKernelGGL(deflate_match_kernel, dim3(per * 8), dim3(kWave), 0, stream, n, nchunks_max, in, in_off, in_len, f->p_end,
+                     f->slot, f->chunk0, f->link, f->flg, f->m, f->mq, f->flags, max_chain, nice, match_skip);
+  return (int)hipGetLastError();
+}
 // link[] / tail[], then flg[] / m[] / mq[]: nchunks_max >= chunk0[n]
 extern "C" int md_launch_deflate_front(uint32_t n, uint32_t nchunks_max, const uint8_t *in, const uint64_t *in_off,
                                        const uint64_t *in_len, int matcher, uint32_t max_chain, uint32_t nice,
@@ -464,10 +356,7 @@ extern "C" int md_launch_deflate_front(uint32_t n, uint32_t nchunks_max, const u
   if (n == 0 || nchunks_max == 0) return 0;
   hipLaunchKernelGGL(deflate_link_kernel<false>, dim3(n), dim3(LW * kWave), 0, stream, n, in, in_off, in_len, f->p_end, f->slot,
                      f->link, (uint32_t *)f->tail, f->flags, matcher, order);
-  const uint32_t per = (nchunks_max + 7) / 8;
-  hipLaunchKernelGGL(deflate_match_kernel, dim3(per * 8), dim3(kWave), 0, stream, n, nchunks_max, in, in_off, in_len, f->p_end,
-                     f->slot, f->chunk0, f->link, f->flg, f->m, f->mq, f->flags, max_chain, nice, match_skip);
-  return (int)hipGetLastError();
+  return md_launch_deflate_match(n, nchunks_max, in, in_off, in_len, max_chain, nice, f, match_skip, stream);
 }
 
 // the chains of De.Def.Ns's hc_matchfinder (deflate_ns.hip)

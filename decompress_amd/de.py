@@ -160,8 +160,8 @@ class Higher:
     def compress(src, queue=4096, device=0):
         """`De.Higher.compress ~w ~q ~refill ~flush i o` / `to_string`: raw DEFLATE at level 4
         (the reference's default: De.Higher has no ?level, lib/de.ml:4519)."""
-        st, out, _ = _engine.default_engine(device).deflate_many(
-            [src], _engine.FORMAT_DEFLATE, level=4, queue=queue, driver=_engine.DRIVER_HIGHER)[0]
+        st, out, _ = _engine.default_engine(device).deflate_one(
+            src, _engine.FORMAT_DEFLATE, level=4, queue=queue, driver=_engine.DRIVER_HIGHER)
         if st != 0:
             raise _engine.Error(_engine.STATUS_NAMES[st])
         return out

@@ -344,6 +344,23 @@ class Engine:
         return [(int(status[i]), out[out_off[i]:out_off[i] + out_len[i]].tobytes(), int(checksum[i]))
                 for i in range(n)]
 
+    def deflate_one(self, data, fmt=FORMAT_DEFLATE, level=6, queue=4096, driver=DRIVER_ZL, dynamic=True, cap=None,
+                    matcher=None, header=None):
+        """ONE stream through md_deflate_batch_host (host buffers: what md_*_higher_compress do; a long stream gets its hash
+        chains from the whole chip) -> (status, compressed bytes, checksum of the input)."""
+        import numpy as np
+
+        n = len(data)
+        src = np.frombuffer(bytes(data), dtype=np.uint8) if n else np.zeros(1, dtype=np.uint8)
+        cap = 2 * n + 8192 if cap is None else int(cap)
+        out = np.zeros(max(cap, 1), dtype=np.uint8)
+        out_len, status, checksum = self.deflate_batch_host(fmt, src, [0], [n], out, [0], [cap], level, queue, driver, dynamic,
+                                                            matcher, header)
+        return int(status[0]), out[:int(out_len[0])].tobytes(), int(checksum[0])
+
+    def link_segments(self):
+        """segments the last deflate batch call built its hash chains in; 0 = one workgroup per stream"""
+        return int(self.lib.md_i_link_segments(self.ctx))
 
     # ------------------------------------------------------------------ De.Def.Ns
     def def_ns_many(self, bufs, level=4, fmt=FORMAT_DEFLATE, caps=None):

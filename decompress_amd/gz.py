@@ -37,7 +37,7 @@ class Higher:
         eng = _engine.default_engine(device)
         hdr = dict(mtime=int(mtime) & 0xffffffff, os=OS[os] if isinstance(os, str) else int(os), hcrc=int(bool(hcrc)),
                    ascii=int(bool(ascii)), filename=filename, comment=comment)
-        st, out, _ = eng.deflate_many([src], _engine.FORMAT_GZIP, level=level, queue=queue, header=hdr)[0]
+        st, out, _ = eng.deflate_one(src, _engine.FORMAT_GZIP, level=level, queue=queue, header=hdr)
         if st != 0:
             raise _engine.Error(_engine.STATUS_NAMES[st])
         return out

@@ -40,8 +40,8 @@ class Higher:
     @staticmethod
     def compress(src, level=6, dynamic=True, queue=4096, device=0):
         """`Zl.Higher.compress ?level ?dynamic ~w ~q ~refill ~flush i o`: a zlib stream."""
-        st, out, _ = _engine.default_engine(device).deflate_many(
-            [src], _engine.FORMAT_ZLIB, level=level, queue=queue, driver=_engine.DRIVER_ZL, dynamic=dynamic)[0]
+        st, out, _ = _engine.default_engine(device).deflate_one(
+            src, _engine.FORMAT_ZLIB, level=level, queue=queue, driver=_engine.DRIVER_ZL, dynamic=dynamic)
         if st != 0:
             raise _engine.Error(_engine.STATUS_NAMES[st])
         return out

@@ -169,6 +169,12 @@ int md_synchronize(md_ctx *ctx);
  *   "inflate_parallel_chunk"     KiB of compressed input per piece (default 64, 4 .. 2^20).
  *   "inflate_parallel_last"      a QUERY (value ignored; the return value is the answer, not a status): pieces of the last
  *                                single stream that went that way | decode rounds << 24; 0 = it took the serial path.
+ *   "deflate_link_segment_min"   KiB (default 128; 0 = never): a SINGLE stream handed to md_deflate_batch_host (and so to
+ *                                md_de/zl/gz_higher_compress) with at least this much input, format DEFLATE / ZLIB / GZIP,
+ *                                driver ZL / HIGHER / CLI, level 1..9 and De's matcher gets its hash chains from the whole
+ *                                device, in segments (csrc/deflate_chunked.hip), instead of from one workgroup.  The chains
+ *                                are the same, so every status, byte and checksum is the same.
+ *   "deflate_link_segment"       KiB of input per segment (0 = default: the stream spread over the CUs, at least 64 KiB).
  *   "debug_inflate_lds_pad", "debug_known_bounds"   measurement aids of tools/dbg (occupancy curve, known-boundaries floor).
  *   "profile"                    0 / 1: in-kernel phase profile of stream 0 (md_get_profile, a debugging aid).
  * Unknown keys and values out of range: MD_E_INVALID_ARGUMENT. */
