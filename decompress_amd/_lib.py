@@ -57,6 +57,18 @@ SYMBOLS = [
     ("md_def_batch_error", ctypes.c_int, [c_vp, c_sz]),
     ("md_def_batch_checksum", ctypes.c_uint32, [c_vp, c_sz]),
     ("md_def_batch_close", None, [c_vp]),
+    ("md_inf_batch_open", c_vp, [c_vp, ctypes.c_int, c_sz]),
+    ("md_inf_batch_src", ctypes.c_int, [c_vp, c_sz, c_vp, c_sz]),
+    ("md_inf_batch_decode", ctypes.c_int, [c_vp]),
+    ("md_inf_batch_pending", c_sz, [c_vp, c_sz]),
+    ("md_inf_batch_out", c_sz, [c_vp, c_sz, c_vp, c_sz]),
+    ("md_inf_batch_status", ctypes.c_int, [c_vp, c_sz]),
+    ("md_inf_batch_error", ctypes.c_int, [c_vp, c_sz]),
+    ("md_inf_batch_message", ctypes.c_char_p, [c_vp, c_sz]),
+    ("md_inf_batch_checksum", ctypes.c_uint32, [c_vp, c_sz]),
+    ("md_inf_batch_src_rem", c_sz, [c_vp, c_sz]),
+    ("md_inf_batch_reset", None, [c_vp, c_sz]),
+    ("md_inf_batch_close", None, [c_vp]),
     ("md_host_alloc", c_vp, [c_vp, c_sz]),
     ("md_host_free", None, [c_vp, c_vp]),
     ("md_timing_begin", ctypes.c_int, [c_vp]),
@@ -127,7 +139,8 @@ class GzMeta(ctypes.Structure):
                [(k, ctypes.c_int) for k in ("has_extra", "has_name", "has_comment")] + \
                [(k, c_sz) for k in ("extra_off", "extra_len", "name_off", "name_len", "comment_off", "comment_len")]
 # exported but not part of the public header (tuning knobs)
-EXTRA = [("md_get_profile", ctypes.c_int, [c_vp, c_vp]), ("md_i_link_segments", ctypes.c_int, [c_vp])]
+EXTRA = [("md_get_profile", ctypes.c_int, [c_vp, c_vp]), ("md_i_link_segments", ctypes.c_int, [c_vp]),
+         ("md_i_inf_batch_launches", ctypes.c_longlong, [c_vp]), ("md_i_inf_batch_attempts", ctypes.c_longlong, [c_vp, c_sz])]
 
 _lib = None
 

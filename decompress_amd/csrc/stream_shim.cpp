@@ -23,29 +23,39 @@
 #include <string>
 #include <vector>
 
+#include "inflate_batch.hpp"
 #include "mdeflate.h"
 
-struct md_inf_stream {
+// The frame around the DEFLATE body of one stream that is decoded in pieces as it arrives, and the steps on it that
+// md_inf_* and md_inf_batch_* share: the GZip / ZLIB header, the bookkeeping of a decoded piece, both trailers with
+// the reference's messages, the end-of-input failures and the rule for when the next piece is worth decoding.
+struct InfFrame {
+  int format = 0;
+  std::vector<uint8_t> in;    // the input not decoded yet (once decoding in pieces: the undecoded tail)
+  bool eoi = false;           // the end of the input was signalled
+  bool hdr_done = false, body_done = false, finished = false;
+  int status = MD_OK;         // MD_* status of the stream
+  std::string message;        // the reference's `Malformed string, with its numbers
+  uint32_t checksum = 0;
+  size_t need = 0;            // input buffered before the NEXT piece is decoded (grows when a piece holds no block end)
+  unsigned in_bit = 0;        // the next block starts this many bits into in[0]
+  uint32_t adler = 1;         // checksum state at the last block boundary
+  uint32_t crc = 0;           // GZip: CRC-32 of the output handed out so far
+  uint64_t total_out = 0;     // ... and its length
+};
+
+struct md_inf_stream : InfFrame {
   md_ctx *ctx;
-  int format;
   uint8_t *o;
   size_t o_len, o_pos;        // caller's output buffer (De.Inf.decoder ~o) and how much of it is filled
-  std::vector<uint8_t> in;    // everything supplied so far
   std::vector<uint8_t> out;   // the decoded stream, once the launch has run
   size_t served;              // bytes of `out` already handed to the caller
-  bool eoi, ran;
-  int status;                 // MD_* status of the launch
+  bool ran;
   size_t consumed;
-  uint32_t checksum;
-  std::string message;        // the reference's `Malformed string, with its numbers
-  // decoding in pieces (DEFLATE / ZLIB): `in` is then the undecoded tail, `out` what the last piece produced
-  size_t chunk, need;         // input buffered before a piece is decoded; before the NEXT piece (grows when a piece holds no block end)
-  bool piecewise, hdr_done, body_done, finished;
-  unsigned in_bit;            // the next block starts this many bits into in[0]
+  // decoding in pieces (DEFLATE / ZLIB / GZIP): `in` is then the undecoded tail, `out` what the last piece produced
+  size_t chunk;               // input buffered before a piece is decoded
+  bool piecewise;
   std::vector<uint8_t> hist;  // the window: the last <= 32 KiB of output
-  uint32_t adler;             // checksum state at the last block boundary
-  uint32_t crc;               // GZip: CRC-32 of the output handed out so far
-  uint64_t total_out;         // ... and its length
 };
 static void inf_clear(md_inf_stream *s) {
   s->in.clear();
@@ -260,40 +270,128 @@ static size_t gz_header_check(const std::vector<uint8_t> &in, int *st) {
   return body;
 }
 
+// ---- the frame steps (md_inf_* below, md_inf_batch_* further down) ----
+static void frame_fail(InfFrame *f, int st) {
+  f->status = st;
+  f->message = md_status_string(st);
+  f->finished = true;
+}
+// the GZip / ZLIB header, once: true when `in` starts at the DEFLATE body; otherwise the stream waits for more input
+// (need) or failed
+static bool frame_head(InfFrame *f) {
+  const bool final = f->eoi;
+  if (f->format == MD_FORMAT_GZIP && !f->hdr_done) {
+    int hst = MD_OK;
+    const size_t body = gz_header_check(f->in, &hst);
+    if (hst != MD_OK) return frame_fail(f, hst), false;
+    if (body == 0) {
+      if (final) frame_fail(f, MD_UNEXPECTED_END_OF_INPUT);
+      else f->need = f->in.size() + 1;
+      return false;
+    }
+    f->in.erase(f->in.begin(), f->in.begin() + body);
+    f->hdr_done = true;
+  }
+  if (f->format == MD_FORMAT_ZLIB && !f->hdr_done) {  // Zl.Inf's header, lib/zl.ml:142-165 (as the kernel checks it)
+    if (f->in.size() < 2) {
+      if (final) frame_fail(f, MD_UNEXPECTED_END_OF_INPUT);
+      else f->need = 2;
+      return false;
+    }
+    const unsigned cmf = f->in[0], flg = f->in[1];
+    if (((cmf << 8) + flg) % 31 != 0 || (cmf & 0xf) != 8) return frame_fail(f, MD_INVALID_HEADER), false;
+    f->in.erase(f->in.begin(), f->in.begin() + 2);
+    f->hdr_done = true;
+  }
+  return true;
+}
+// output that a piece hands out: the GZip CRC-32 goes on over it
+static void frame_took(InfFrame *f, uint32_t crc_piece, uint64_t len) {
+  f->crc = f->total_out ? crc_concat(f->crc, crc_piece, len) : crc_piece;
+  f->total_out += len;
+}
+// the piece ended inside a block before the end of the input: what lies before that block went out, the input from the
+// block boundary (bits from in[0], in_bit included) stays.  A new attempt only once input beyond the undecoded tail has
+// arrived - that tail holds no complete block, decoding it again alone could not find one - and, when the piece held no
+// block end at all, only once the buffered input has doubled (one long block fed in small pieces is decoded again a
+// logarithmic number of times, not once per piece).
+static void frame_continue(InfFrame *f, uint64_t bits, uint32_t crc_piece, uint64_t len, uint32_t adler, size_t chunk) {
+  const bool progress = bits > f->in_bit;
+  frame_took(f, crc_piece, len);
+  f->adler = adler;
+  f->in.erase(f->in.begin(), f->in.begin() + (size_t)(bits >> 3));
+  f->in_bit = (unsigned)(bits & 7);
+  f->need = progress ? (f->in.size() + 1 > chunk ? f->in.size() + 1 : chunk) : (f->in.size() * 2 > chunk ? f->in.size() * 2 : chunk);
+}
+// the body ended (status MD_OK; `consumed` bytes of `in`) or failed with `st`; everything decoded went out, also in front
+// of an error.  True when a trailer follows.
+static bool frame_body_end(InfFrame *f, int st, uint32_t crc_piece, uint64_t len, uint32_t sum, uint64_t consumed) {
+  frame_took(f, crc_piece, len);
+  f->checksum = f->format == MD_FORMAT_GZIP ? f->crc : sum;
+  if (st != MD_OK) return frame_fail(f, st), false;
+  f->body_done = true;
+  f->in.erase(f->in.begin(), f->in.begin() + (size_t)consumed);
+  f->in_bit = 0;
+  if (f->format == MD_FORMAT_DEFLATE) {
+    f->status = MD_OK;
+    f->finished = true;
+    return false;
+  }
+  return true;
+}
+// the trailer after the body: the stream ends here, or waits for the rest of the trailer (need)
+static void frame_trailer(InfFrame *f) {
+  const bool final = f->eoi;
+  if (f->format == MD_FORMAT_GZIP) {  // Gz.Inf's trailer (lib/gz.ml:344-356): CRC-32 first, then ISIZE, little-endian
+    if (f->in.size() < 8) {
+      if (final) frame_fail(f, MD_UNEXPECTED_END_OF_INPUT);
+      else f->need = 8;
+      return;
+    }
+    const uint8_t *t = f->in.data();
+    const uint32_t crc = (uint32_t)t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
+    const uint32_t isize = (uint32_t)t[4] | ((uint32_t)t[5] << 8) | ((uint32_t)t[6] << 16) | ((uint32_t)t[7] << 24);
+    char msg[96];
+    f->status = MD_OK;
+    if (crc != f->crc) {
+      snprintf(msg, sizeof msg, "Invalid checksum (expect:%04lx, has:%04lx)", (unsigned long)crc, (unsigned long)f->crc);
+      f->status = MD_INVALID_CHECKSUM;
+      f->message = msg;
+    } else if (isize != (uint32_t)f->total_out) {
+      snprintf(msg, sizeof msg, "Invalid input size (expect:%ld, inflated:%ld)", (long)(int32_t)isize, (long)(int32_t)(uint32_t)f->total_out);
+      f->status = MD_INVALID_SIZE;
+      f->message = msg;
+    }
+    f->in.erase(f->in.begin(), f->in.begin() + 8);
+    f->finished = true;
+    return;
+  }
+  // Zl.Inf's trailer: the Adler-32 of the output, big-endian (lib/zl.ml:171-186)
+  if (f->in.size() < 4) {
+    if (final) frame_fail(f, MD_UNEXPECTED_END_OF_INPUT);
+    else f->need = 4;
+    return;
+  }
+  const uint32_t expect = ((uint32_t)f->in[0] << 24) | ((uint32_t)f->in[1] << 16) | ((uint32_t)f->in[2] << 8) | f->in[3];
+  f->in.erase(f->in.begin(), f->in.begin() + 4);
+  if (expect != f->checksum) {
+    char msg[96];
+    snprintf(msg, sizeof msg, "Invalid checksum (expect:%04lx, has:%04lx)", (unsigned long)expect, (unsigned long)f->checksum);
+    f->status = MD_INVALID_CHECKSUM;
+    f->message = msg;
+  } else {
+    f->status = MD_OK;
+  }
+  f->finished = true;
+}
+
 // One piece of a stream that is decoded as it arrives: everything up to the last block boundary inside the buffered
 // input goes to `out`, the rest of the input stays; at the end of the input whatever is left is decoded for good.
 static void inf_piece(md_inf_stream *s) {
   const bool final = s->eoi;
   s->out.clear();
   s->served = 0;
-  auto fail_with = [&](int st) {
-    s->status = st;
-    s->message = md_status_string(st);
-    s->finished = true;
-  };
-  if (s->format == MD_FORMAT_GZIP && !s->hdr_done) {
-    int hst = MD_OK;
-    const size_t body = gz_header_check(s->in, &hst);
-    if (hst != MD_OK) return fail_with(hst);
-    if (body == 0) {
-      if (final) fail_with(MD_UNEXPECTED_END_OF_INPUT);
-      else s->need = s->in.size() + 1;
-      return;
-    }
-    s->in.erase(s->in.begin(), s->in.begin() + body);
-    s->hdr_done = true;
-  }
-  if (s->format == MD_FORMAT_ZLIB && !s->hdr_done) {  // Zl.Inf's header, lib/zl.ml:142-165 (as the kernel checks it)
-    if (s->in.size() < 2) {
-      if (final) fail_with(MD_UNEXPECTED_END_OF_INPUT);
-      else s->need = 2;
-      return;
-    }
-    const unsigned cmf = s->in[0], flg = s->in[1];
-    if (((cmf << 8) + flg) % 31 != 0 || (cmf & 0xf) != 8) return fail_with(MD_INVALID_HEADER);
-    s->in.erase(s->in.begin(), s->in.begin() + 2);
-    s->hdr_done = true;
-  }
+  if (!frame_head(s)) return;
   if (!s->body_done) {
     const size_t hl = s->hist.size();
     uint64_t cap = (uint64_t)hl + s->in.size() * 4 + 65536;
@@ -308,7 +406,7 @@ static void inf_piece(md_inf_stream *s) {
       if (hl) memcpy(buf.data(), s->hist.data(), hl);
       const int rc = md_de_inf_continue_host(s->ctx, s->in.empty() ? &none : s->in.data(), s->in.size(), s->in_bit, buf.data(), hl,
                                              (size_t)cap, s->adler, s->format == MD_FORMAT_GZIP ? MD_CONT_CRC32 : 0u, &dst_len, &st, &rs);
-      if (rc != MD_OK) return fail_with(rc);
+      if (rc != MD_OK) return frame_fail(s, rc);
       if (st == MD_UNEXPECTED_END_OF_OUTPUT && cap < MD_MAX_STREAM) {
         cap *= 4;
         continue;
@@ -318,76 +416,16 @@ static void inf_piece(md_inf_stream *s) {
     if (st == MD_UNEXPECTED_END_OF_INPUT && !final) {
       // the piece ends inside a block: hand out what lies before that block, keep the rest of the input
       const size_t upto = (size_t)rs.out;
-      const bool progress = rs.bits > s->in_bit;
       s->out.assign(buf.begin() + hl, buf.begin() + upto);
-      s->crc = s->total_out ? crc_concat(s->crc, rs.crc_out, upto - hl) : rs.crc_out;
-      s->total_out += upto - hl;
       const size_t keep = upto < 32768 ? upto : 32768;
       s->hist.assign(buf.begin() + (upto - keep), buf.begin() + upto);
-      s->adler = rs.adler;
-      s->in.erase(s->in.begin(), s->in.begin() + (size_t)(rs.bits >> 3));
-      s->in_bit = (unsigned)(rs.bits & 7);
-      // (after progress: a new attempt only once input beyond the undecoded tail has arrived - that tail holds no
-      // complete block, decoding it again alone could not find one)
-      s->need = progress ? (s->in.size() + 1 > s->chunk ? s->in.size() + 1 : s->chunk)
-                         : (s->in.size() * 2 > s->chunk ? s->in.size() * 2 : s->chunk);
+      frame_continue(s, rs.bits, rs.crc_out, upto - hl, rs.adler, s->chunk);
       return;
     }
     s->out.assign(buf.begin() + hl, buf.begin() + dst_len);  // everything decoded, also in front of an error
-    s->crc = s->total_out ? crc_concat(s->crc, rs.crc_end, dst_len - hl) : rs.crc_end;
-    s->total_out += dst_len - hl;
-    s->checksum = s->format == MD_FORMAT_GZIP ? s->crc : rs.checksum;
-    if (st != MD_OK) return fail_with(st);
-    s->body_done = true;
-    s->in.erase(s->in.begin(), s->in.begin() + (size_t)rs.consumed);
-    s->in_bit = 0;
-    if (s->format == MD_FORMAT_DEFLATE) {
-      s->status = MD_OK;
-      s->finished = true;
-      return;
-    }
+    if (!frame_body_end(s, st, rs.crc_end, dst_len - hl, rs.checksum, rs.consumed)) return;
   }
-  if (s->format == MD_FORMAT_GZIP) {  // Gz.Inf's trailer (lib/gz.ml:344-356): CRC-32 first, then ISIZE, little-endian
-    if (s->in.size() < 8) {
-      if (final) fail_with(MD_UNEXPECTED_END_OF_INPUT);
-      else s->need = 8;
-      return;
-    }
-    const uint8_t *t = s->in.data();
-    const uint32_t crc = (uint32_t)t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
-    const uint32_t isize = (uint32_t)t[4] | ((uint32_t)t[5] << 8) | ((uint32_t)t[6] << 16) | ((uint32_t)t[7] << 24);
-    char msg[96];
-    s->status = MD_OK;
-    if (crc != s->crc) {
-      snprintf(msg, sizeof msg, "Invalid checksum (expect:%04lx, has:%04lx)", (unsigned long)crc, (unsigned long)s->crc);
-      s->status = MD_INVALID_CHECKSUM;
-      s->message = msg;
-    } else if (isize != (uint32_t)s->total_out) {
-      snprintf(msg, sizeof msg, "Invalid input size (expect:%ld, inflated:%ld)", (long)(int32_t)isize, (long)(int32_t)(uint32_t)s->total_out);
-      s->status = MD_INVALID_SIZE;
-      s->message = msg;
-    }
-    s->in.erase(s->in.begin(), s->in.begin() + 8);
-    s->finished = true;
-    return;
-  }
-  // Zl.Inf's trailer: the Adler-32 of the output, big-endian (lib/zl.ml:171-186)
-  if (s->in.size() < 4) {
-    if (final) fail_with(MD_UNEXPECTED_END_OF_INPUT);
-    else s->need = 4;
-    return;
-  }
-  const uint32_t expect = ((uint32_t)s->in[0] << 24) | ((uint32_t)s->in[1] << 16) | ((uint32_t)s->in[2] << 8) | s->in[3];
-  s->in.erase(s->in.begin(), s->in.begin() + 4);
-  if (expect != s->checksum) {
-    char msg[96];
-    snprintf(msg, sizeof msg, "Invalid checksum (expect:%04lx, has:%04lx)", (unsigned long)expect, (unsigned long)s->checksum);
-    s->status = MD_INVALID_CHECKSUM;
-    s->message = msg;
-  } else {
-    s->status = MD_OK;
-  }
-  s->finished = true;
+  frame_trailer(s);
 }
 
 int md_inf_decode(md_inf_stream *s) {
@@ -910,5 +948,375 @@ int md_def_batch_encode(md_def_batch *b) {
   }
   return MD_OK;
 }
+
+}  // extern "C"
+
+// ---- many streaming decoders at once (md_inf_batch_*, mdeflate.h) ------------------------------------------------------
+// n independent De.Inf / Zl.Inf / Gz.Inf decoders (lib/de.mli:82-144) whose pieces go through the inflate kernel TOGETHER:
+// one launch per md_inf_batch_decode over every decoder that has new input, whatever n is.  A decoder's frame - header,
+// trailer, the need rule - is md_inf_*'s (the frame_* steps above, on the host, which keeps the undecoded tail as md_inf_*
+// keeps `in`); its body is decoded in pieces as md_inf_* decodes it with md_inf_chunk_bytes(1): every piece up to the last
+// block boundary inside it.  Between rounds the undecoded tail and the window (the last <= 32 KiB of output) stay in device
+// memory, in double-buffered blobs: the input of round k + 1 is gathered from the tails in round k's blob and the bytes that
+// arrived since (one packed upload), each output region begins with the window gathered from round k's output blob
+// (piece_gather_kernel both times).  The hand-out kernels (inflate_batch.hip) pack what every decoder hands out into one
+// blob - with its CRC-32 for GZIP - so that a round costs two copies back: the per-decoder results and the packed output.
+struct md_inf_batch {
+  md_ctx *ctx = nullptr;
+  int format = 0;
+  size_t n = 0;
+  struct Dec : InfFrame {
+    std::vector<uint8_t> held;  // output handed out and not fetched yet, from held_pos on
+    size_t held_pos = 0;
+    size_t round_in = 0;        // input handed over since the last md_inf_batch_decode
+    // the body in progress on the device: in[0, dev_tail) at tail_off of the current input blob; the window: win_len bytes
+    // at win_off of the current output blob
+    size_t dev_tail = 0;
+    uint64_t tail_off = 0, win_off = 0;
+    uint32_t win_len = 0;
+    uint64_t room = 1;          // a piece's output room is this multiple of md_inf_*'s (x4 each time it ran out)
+    uint64_t attempts = 0;      // rounds the decoder took part in (md_i_inf_batch_attempts)
+  };
+  std::vector<Dec> d;
+  void *d_in[2] = {nullptr, nullptr}, *d_out[2] = {nullptr, nullptr};
+  size_t in_cap[2] = {0, 0}, out_cap[2] = {0, 0};
+  int cur = 0;
+  void *d_fresh = nullptr, *d_desc = nullptr, *d_pack = nullptr;
+  size_t fresh_cap = 0, desc_cap = 0, pack_cap = 0;
+  uint8_t *h_stage = nullptr, *h_pack = nullptr;  // pinned: the fresh bytes of a round, packed / the packed output
+  size_t stage_cap = 0, hpack_cap = 0;
+  uint64_t launches = 0;      // inflate launches so far (md_i_inf_batch_launches)
+};
+extern "C" int md_launch_inf_handout(uint32_t m, md::ib::HandIn in, const uint8_t *out, md::ib::HandRow *res, uint8_t *pack,
+                                     int with_crc, hipStream_t stream);
+namespace {
+void inf_slot_clear(md_inf_batch::Dec *x, int format) {
+  *x = md_inf_batch::Dec();
+  x->format = format;
+  x->need = 1;  // (md_inf_*'s rule with md_inf_chunk_bytes(1): a piece as soon as input has arrived)
+}
+bool regrow_pinned(uint8_t **p, size_t *cap, size_t need) {
+  if (need <= *cap) return true;
+  if (*p) hipHostFree(*p);
+  *p = nullptr;
+  *cap = 0;
+  const size_t want = need + need / 4 + 4096;
+  if (hipHostMalloc((void **)p, want, hipHostMallocDefault) != hipSuccess) return false;
+  *cap = want;
+  return true;
+}
+// a device blob that must keep its first `keep` bytes when it grows
+bool regrow_keep(void **p, size_t *cap, size_t need, size_t keep, hipStream_t st) {
+  if (need <= *cap) return true;
+  void *q = nullptr;
+  const size_t want = need + need / 4 + 4096;
+  if (hipMalloc(&q, want) != hipSuccess) return false;
+  if (keep && (hipMemcpyAsync(q, *p, keep, hipMemcpyDeviceToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)) {
+    hipFree(q);
+    return false;
+  }
+  if (*p) hipFree(*p);
+  *p = q;
+  *cap = want;
+  return true;
+}
+uint64_t up(uint64_t x, uint64_t a) { return (x + a - 1) & ~(a - 1); }
+
+// One launch of the inflate kernel over `rows` (decoder indices), its hand-out and the two copies back; the results are
+// applied to the decoders.  first: the round's launch - every decoder with a body in progress moves to the blobs `nxt`
+// (the rows with their fresh bytes); otherwise a launch again for rows whose output room ran out: their input is in place,
+// their windows are gathered once more from `old`, behind the *opos bytes of output regions the round has used.
+// `grown` gets the rows that ran out of room.
+int inf_batch_launch(md_inf_batch *b, const std::vector<size_t> &rows, bool first, int old, int nxt, uint64_t *opos_io,
+                     std::vector<size_t> *grown) {
+  using md::ib::HandRow;
+  hipStream_t st = md_i_stream(b->ctx);
+  const size_t m = rows.size();
+  std::vector<char> is_row(first ? b->n : 0, 0);
+  for (size_t i : rows)
+    if (first) is_row[i] = 1;
+  std::vector<size_t> live;  // the decoders whose tail and window the gathers move
+  if (first) {
+    for (size_t i = 0; i < b->n; i++) {
+      const md_inf_batch::Dec &x = b->d[i];
+      if (is_row[i] || (!x.finished && (x.dev_tail || x.win_len))) live.push_back(i);
+    }
+  } else {
+    live = rows;
+  }
+  const size_t L = live.size();
+  // descriptors, u64 words: gather of the inputs (6 L, first only) and of the windows (6 L); per row in_off in_len
+  // out_off out_cap, then start_bit hist adler_in flags (u32) - uploaded -; then out_len consumed resume_bits resume_out,
+  // status checksum resume_adler resume_last (u32), the HandRows
+  const size_t gin_w = first ? 6 * L : 0, up_w = gin_w + 6 * L + 4 * m + 2 * m, all_w = up_w + 4 * m + 2 * m + 6 * m;
+  std::vector<uint64_t> desc(up_w, 0);
+  uint64_t *gin = desc.data(), *gout = gin + gin_w, *r64 = gout + 6 * L;
+  uint32_t *r32 = (uint32_t *)(r64 + 4 * m);
+  std::vector<uint64_t> row_of(L, ~(uint64_t)0);  // live index -> row
+  {
+    std::vector<uint64_t> slot(first ? b->n : 0, 0);
+    for (size_t k = 0; k < m; k++)
+      if (first) slot[rows[k]] = k;
+    for (size_t j = 0; j < L; j++) row_of[j] = first ? (is_row[live[j]] ? slot[live[j]] : ~(uint64_t)0) : j;
+  }
+  uint64_t ipos = 0, fpos = 0, opos = *opos_io, pack = 0;
+  std::vector<uint64_t> moved_in(L), moved_out(L);  // where the decoders that only move go
+  for (size_t j = 0; j < L; j++) {
+    md_inf_batch::Dec &x = b->d[live[j]];
+    const uint64_t k = row_of[j];
+    if (first) {
+      const uint64_t fresh = k != ~(uint64_t)0 ? x.in.size() - x.dev_tail : 0, len = x.dev_tail + fresh;
+      uint64_t *g = gin + 6 * j;
+      g[0] = x.tail_off;
+      g[1] = x.dev_tail;
+      g[2] = fpos;
+      g[3] = fresh;
+      g[4] = ipos;
+      if (k != ~(uint64_t)0) {
+        r64[0 * m + k] = ipos;
+        r64[1 * m + k] = len;
+      } else {
+        moved_in[j] = ipos;
+      }
+      fpos += up(fresh, 16);
+      ipos += up(len, 64) + 64;
+    }
+    uint64_t room = x.win_len;
+    if (k != ~(uint64_t)0) {  // md_inf_*'s room for the piece: the window, 4x the input and 64 KiB
+      const uint64_t in_len = first ? r64[1 * m + k] : x.in.size();
+      uint64_t cap = ((uint64_t)x.win_len + in_len * 4 + 65536) * x.room;
+      if (cap > MD_MAX_STREAM || x.room > ((uint64_t)1 << 40)) cap = MD_MAX_STREAM;
+      room = cap;
+      r64[2 * m + k] = opos;
+      r64[3 * m + k] = cap;
+      r32[0 * m + k] = x.in_bit;
+      r32[1 * m + k] = x.win_len;
+      r32[2 * m + k] = x.adler;
+      r32[3 * m + k] = (x.eoi ? md::ib::kRowFinal : 0u) | (cap < MD_MAX_STREAM ? md::ib::kRowCanGrow : 0u);
+      pack += up(cap - x.win_len, 16);
+    }
+    uint64_t *g = gout + 6 * j;
+    g[0] = x.win_off;
+    g[1] = x.win_len;
+    g[2] = 0;
+    g[3] = 0;
+    g[4] = opos;
+    moved_out[j] = opos;
+    opos += up(room, 64) + 64;
+  }
+  if (!first) {  // (a retry: the rows' input regions of the round's launch)
+    for (size_t k = 0; k < m; k++) {
+      r64[0 * m + k] = b->d[rows[k]].tail_off;
+      r64[1 * m + k] = b->d[rows[k]].in.size();
+    }
+  }
+  if ((first && !regrow(&b->d_in[nxt], &b->in_cap[nxt], (size_t)ipos + 64)) ||
+      !(first ? regrow(&b->d_out[nxt], &b->out_cap[nxt], (size_t)opos + 64)
+              : regrow_keep(&b->d_out[nxt], &b->out_cap[nxt], (size_t)opos + 64, (size_t)*opos_io, st)) ||
+      !regrow(&b->d_fresh, &b->fresh_cap, (size_t)fpos + 64) || !regrow(&b->d_desc, &b->desc_cap, all_w * 8 + 64) ||
+      !regrow(&b->d_pack, &b->pack_cap, (size_t)pack + 64) || !regrow_pinned(&b->h_stage, &b->stage_cap, (size_t)fpos + 64))
+    return MD_E_OUT_OF_MEMORY;
+  if (first) {
+    for (size_t j = 0; j < L; j++) {
+      const md_inf_batch::Dec &x = b->d[live[j]];
+      const uint64_t *g = gin + 6 * j;
+      if (g[3]) memcpy(b->h_stage + g[2], x.in.data() + x.dev_tail, (size_t)g[3]);
+    }
+    if (fpos && hipMemcpyAsync(b->d_fresh, b->h_stage, (size_t)fpos, hipMemcpyHostToDevice, st) != hipSuccess) return MD_E_HIP;
+  }
+  uint64_t *dd = (uint64_t *)b->d_desc;
+  if (hipMemcpyAsync(dd, desc.data(), up_w * 8, hipMemcpyHostToDevice, st) != hipSuccess) return MD_E_HIP;
+  if (first && md_launch_piece_gather((uint32_t)L, (const uint8_t *)b->d_in[old], (const uint8_t *)b->d_fresh, (uint8_t *)b->d_in[nxt],
+                                      dd, st) != 0)
+    return MD_E_HIP;
+  if (md_launch_piece_gather((uint32_t)L, (const uint8_t *)b->d_out[old], (const uint8_t *)b->d_fresh, (uint8_t *)b->d_out[nxt],
+                             dd + gin_w, st) != 0)
+    return MD_E_HIP;
+  uint64_t *d64 = dd + gin_w + 6 * L;
+  uint32_t *d32 = (uint32_t *)(d64 + 4 * m);
+  uint64_t *o64 = d64 + 6 * m;
+  uint32_t *o32 = (uint32_t *)(o64 + 4 * m);
+  HandRow *dres = (HandRow *)(o64 + 6 * m);
+  const int rc = md_inflate_continue_batch_device(b->ctx, m, (const uint8_t *)b->d_in[nxt], d64, d64 + m, (uint8_t *)b->d_out[nxt],
+                                                  d64 + 2 * m, d64 + 3 * m, d32, d32 + m, d32 + 2 * m, o64, o64 + m, (int32_t *)o32,
+                                                  o32 + m, o64 + 2 * m, o64 + 3 * m, o32 + 2 * m, o32 + 3 * m);
+  if (rc != MD_OK) return rc;
+  b->launches++;
+  const md::ib::HandIn hin{d64 + 2 * m, d64 + 3 * m, o64, o64 + m, o64 + 2 * m, o64 + 3 * m, d32 + m, d32 + 3 * m, o32 + m, o32 + 2 * m,
+                           (const int32_t *)o32};
+  if (md_launch_inf_handout((uint32_t)m, hin, (const uint8_t *)b->d_out[nxt], dres, (uint8_t *)b->d_pack,
+                            b->format == MD_FORMAT_GZIP, st) != 0)
+    return MD_E_HIP;
+  std::vector<HandRow> res(m);
+  if (hipMemcpyAsync(res.data(), dres, m * sizeof(HandRow), hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipStreamSynchronize(st) != hipSuccess)
+    return MD_E_HIP;
+  const uint64_t total = m ? res[m - 1].pack_off + res[m - 1].len : 0;
+  if (total > pack) return MD_E_HIP;  // (cannot happen: every range lies inside its row's room)
+  if (total) {
+    if (!regrow_pinned(&b->h_pack, &b->hpack_cap, (size_t)total)) return MD_E_OUT_OF_MEMORY;
+    if (hipMemcpyAsync(b->h_pack, b->d_pack, (size_t)total, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+      return MD_E_HIP;
+  }
+  // the launch went through: the decoders that only moved are at their new places, the rows take their results
+  *opos_io = opos;
+  for (size_t j = 0; j < L; j++) {
+    if (row_of[j] != ~(uint64_t)0) continue;
+    b->d[live[j]].tail_off = moved_in[j];
+    b->d[live[j]].win_off = moved_out[j];
+  }
+  for (size_t k = 0; k < m; k++) {
+    md_inf_batch::Dec &x = b->d[rows[k]];
+    const HandRow &h = res[k];
+    const uint64_t in_off = r64[0 * m + k], in_len = r64[1 * m + k], out_off = r64[2 * m + k];
+    if (h.kind == md::ib::kKindGrow) {
+      x.room *= 4;
+      x.tail_off = in_off;  // (the input stays where this launch read it, the window where it was)
+      x.dev_tail = (size_t)in_len;
+      grown->push_back(rows[k]);
+      continue;
+    }
+    if (h.len) x.held.insert(x.held.end(), b->h_pack + h.pack_off, b->h_pack + h.pack_off + h.len);
+    if (h.kind == md::ib::kKindContinue) {
+      const uint64_t skip = h.tail_bits >> 3, keep = h.end < 32768 ? h.end : 32768;
+      frame_continue(&x, h.tail_bits, h.crc, h.len, h.sum, 1);
+      x.tail_off = in_off + skip;
+      x.dev_tail = (size_t)(in_len - skip);
+      x.win_off = out_off + h.end - keep;
+      x.win_len = (uint32_t)keep;
+      continue;
+    }
+    x.dev_tail = 0;
+    x.win_len = 0;
+    if (frame_body_end(&x, h.status, h.crc, h.len, h.sum, h.tail_bits >> 3)) frame_trailer(&x);
+  }
+  return MD_OK;
+}
+}  // namespace
+
+extern "C" {
+
+md_inf_batch *md_inf_batch_open(md_ctx *ctx, int format, size_t n) {
+  if (!ctx || n == 0 || n > 0x7fffffffu) return nullptr;
+  if (format != MD_FORMAT_DEFLATE && format != MD_FORMAT_ZLIB && format != MD_FORMAT_GZIP) return nullptr;
+  md_inf_batch *b = new md_inf_batch();
+  b->ctx = ctx;
+  b->format = format;
+  b->n = n;
+  b->d.resize(n);
+  for (auto &x : b->d) inf_slot_clear(&x, format);
+  return b;
+}
+void md_inf_batch_close(md_inf_batch *b) {
+  if (!b) return;
+  DevGuard guard(md_i_device(b->ctx));
+  hipStreamSynchronize(md_i_stream(b->ctx));
+  void *bufs[] = {b->d_in[0], b->d_in[1], b->d_out[0], b->d_out[1], b->d_fresh, b->d_desc, b->d_pack};
+  for (void *p : bufs)
+    if (p) hipFree(p);
+  if (b->h_stage) hipHostFree(b->h_stage);
+  if (b->h_pack) hipHostFree(b->h_pack);
+  delete b;
+}
+int md_inf_batch_src(md_inf_batch *b, size_t i, const uint8_t *buf, size_t len) {
+  if (!b || i >= b->n || (!buf && len)) return MD_E_INVALID_ARGUMENT;
+  md_inf_batch::Dec &x = b->d[i];
+  if (x.eoi || x.finished) return MD_E_INVALID_ARGUMENT;  // (after the end of the input, or of the stream)
+  if (len == 0) {
+    x.eoi = true;
+    return MD_OK;
+  }
+  if (x.round_in + len > kSrcMax) return MD_E_INVALID_ARGUMENT;  // (what one round takes: call md_inf_batch_decode in between)
+  x.in.insert(x.in.end(), buf, buf + len);
+  x.round_in += len;
+  return MD_OK;
+}
+// One round: the decoders that have input (or its end) beyond what their last attempt saw - md_inf_*'s need rule - take
+// their next step, the ones whose body goes on in one launch of the inflate kernel; those whose output room ran out go
+// through one more launch with 4x the room, in this call.  Everything else sits the round out; no work, no launch.
+int md_inf_batch_decode(md_inf_batch *b) {
+  if (!b) return MD_E_INVALID_ARGUMENT;
+  std::vector<size_t> rows;
+  for (size_t i = 0; i < b->n; i++) {
+    md_inf_batch::Dec &x = b->d[i];
+    if (x.finished || (!x.eoi && x.in.size() < x.need)) continue;
+    x.attempts++;
+    if (!frame_head(&x)) continue;
+    if (x.body_done) {
+      frame_trailer(&x);
+      continue;
+    }
+    if (x.in.size() > MD_MAX_INFLATE_IN) {  // (md_de_inf_continue_host's refusal: bit positions are 32-bit)
+      frame_fail(&x, MD_E_INVALID_ARGUMENT);
+      x.dev_tail = 0;
+      x.win_len = 0;
+      continue;
+    }
+    rows.push_back(i);
+  }
+  for (auto &x : b->d) x.round_in = 0;
+  if (rows.empty()) return MD_OK;
+  DevGuard guard(md_i_device(b->ctx));
+  const int old = b->cur, nxt = old ^ 1;
+  uint64_t opos = 0;
+  std::vector<size_t> grown;
+  int rc = inf_batch_launch(b, rows, true, old, nxt, &opos, &grown);
+  if (rc != MD_OK) return rc;  // (nothing was committed: the decoders try again in the next call)
+  b->cur = nxt;
+  while (!grown.empty()) {
+    std::vector<size_t> again;
+    again.swap(grown);
+    rc = inf_batch_launch(b, again, false, old, nxt, &opos, &grown);
+    if (rc != MD_OK) {  // (the round's other decoders have gone on: these cannot go back)
+      for (size_t i : again) {
+        frame_fail(&b->d[i], rc);
+        b->d[i].dev_tail = 0;
+        b->d[i].win_len = 0;
+      }
+      return rc;
+    }
+  }
+  return MD_OK;
+}
+size_t md_inf_batch_pending(const md_inf_batch *b, size_t i) {
+  if (!b || i >= b->n) return 0;
+  return b->d[i].held.size() - b->d[i].held_pos;
+}
+size_t md_inf_batch_out(md_inf_batch *b, size_t i, uint8_t *dst, size_t cap) {
+  if (!b || i >= b->n || (!dst && cap)) return 0;
+  md_inf_batch::Dec &x = b->d[i];
+  const size_t left = x.held.size() - x.held_pos, k = left < cap ? left : cap;
+  if (k) memcpy(dst, x.held.data() + x.held_pos, k);
+  x.held_pos += k;
+  if (x.held_pos == x.held.size()) {
+    x.held.clear();
+    x.held_pos = 0;
+  } else if (x.held_pos > (1u << 20) && x.held_pos * 2 > x.held.size()) {
+    x.held.erase(x.held.begin(), x.held.begin() + x.held_pos);
+    x.held_pos = 0;
+  }
+  return k;
+}
+int md_inf_batch_status(const md_inf_batch *b, size_t i) {  // the signal md_inf_decode would give once the output is fetched
+  if (!b || i >= b->n) return MD_MALFORMED;
+  const md_inf_batch::Dec &x = b->d[i];
+  if (x.finished) return x.status == MD_OK ? MD_END : MD_MALFORMED;
+  return MD_AWAIT;
+}
+int md_inf_batch_error(const md_inf_batch *b, size_t i) { return b && i < b->n ? b->d[i].status : MD_E_INVALID_ARGUMENT; }
+const char *md_inf_batch_message(const md_inf_batch *b, size_t i) {
+  if (!b || i >= b->n) return "Invalid argument";
+  const md_inf_batch::Dec &x = b->d[i];
+  return x.message.empty() ? md_status_string(x.status) : x.message.c_str();
+}
+uint32_t md_inf_batch_checksum(const md_inf_batch *b, size_t i) { return b && i < b->n ? b->d[i].checksum : 0; }
+size_t md_inf_batch_src_rem(const md_inf_batch *b, size_t i) { return b && i < b->n && b->d[i].finished ? b->d[i].in.size() : 0; }
+void md_inf_batch_reset(md_inf_batch *b, size_t i) {
+  if (b && i < b->n) inf_slot_clear(&b->d[i], b->format);
+}
+// test hooks (not in mdeflate.h): inflate launches so far; rounds decoder i took part in
+long long md_i_inf_batch_launches(const md_inf_batch *b) { return b ? (long long)b->launches : -1; }
+long long md_i_inf_batch_attempts(const md_inf_batch *b, size_t i) { return b && i < b->n ? (long long)b->d[i].attempts : -1; }
 
 }  // extern "C"

@@ -134,6 +134,55 @@ class Inf:
         finally:
             lib.md_inf_free(d)
 
+    @staticmethod
+    def decode_many(streams, fmt=_engine.FORMAT_DEFLATE, o_len=65536, device=0):
+        """many decoders of the same format at once (md_inf_batch_*): `streams` holds one iterable of chunks per stream;
+        each round gives every unfinished decoder its next chunk (or its end of input once its chunks are used up) and
+        decodes all of them in one launch.  -> [(verdict, bytes, message), ...] with the verdicts of decode_chunks.
+        o_len: bytes fetched per md_inf_batch_out call"""
+        eng = _engine.default_engine(device)
+        lib = eng.lib
+        its = [iter(s) for s in streams]
+        n = len(its)
+        if n == 0:
+            return []
+        b = lib.md_inf_batch_open(eng.ctx, fmt, n)
+        if not b:
+            raise ValueError("md_inf_batch_open: format %r, %d streams" % (fmt, n))
+        o = ctypes.create_string_buffer(o_len)
+        outs = [bytearray() for _ in range(n)]
+        fed_end = [False] * n
+        try:
+            live = set(range(n))
+            while live:
+                for i in live:
+                    if fed_end[i]:
+                        continue
+                    c = next(its[i], None)
+                    if c is None:
+                        fed_end[i] = True
+                        eng._check(lib.md_inf_batch_src(b, i, None, 0))
+                    elif len(c):
+                        c = bytes(c)
+                        eng._check(lib.md_inf_batch_src(b, i, c, len(c)))
+                eng._check(lib.md_inf_batch_decode(b))
+                for i in list(live):
+                    while lib.md_inf_batch_pending(b, i):
+                        k = lib.md_inf_batch_out(b, i, o, o_len)
+                        outs[i] += o.raw[:k]
+                    if lib.md_inf_batch_status(b, i) != AWAIT:
+                        live.discard(i)
+            res = []
+            for i in range(n):
+                st = lib.md_inf_batch_error(b, i)
+                if st < 0:
+                    eng._check(st)
+                verdict = "Ok" if lib.md_inf_batch_status(b, i) == END else _engine.STATUS_NAMES[st]
+                res.append((verdict, bytes(outs[i]), lib.md_inf_batch_message(b, i).decode()))
+            return res
+        finally:
+            lib.md_inf_batch_close(b)
+
     class Ns:
         """De.Inf.Ns — whole-buffer inflate (lib/de.ml:1534-1823)."""
 

@@ -465,6 +465,37 @@ int md_def_batch_error(const md_def_batch *b, size_t i);
 uint32_t md_def_batch_checksum(const md_def_batch *b, size_t i);
 void md_def_batch_close(md_def_batch *b);
 
+/* ---- many streaming decoders at once ----
+ * n independent De.Inf / Zl.Inf / Gz.Inf decoders (format MD_FORMAT_DEFLATE, _ZLIB or _GZIP; NULL on misuse), advanced
+ * TOGETHER: md_inf_batch_src hands input to decoder i (host memory, copied; length 0 = the end of its input, as in the
+ * reference), md_inf_batch_decode is ONE launch of the inflate kernel over every decoder that received input or its end
+ * since the last round - whatever n is; decoders with nothing new sit the round out, and a round without work launches
+ * nothing.  (A decoder whose output room ran out gets 4x the room and one more launch in the same call.)  Each round
+ * decodes a decoder's undecoded input up to the last complete block boundary and hands that output out; the round that
+ * ends a stream - or fails it - hands out everything decoded.  md_inf_batch_pending / md_inf_batch_out: output waits on
+ * the host side until fetched, across rounds.  md_inf_batch_status: MD_AWAIT (more input wanted), MD_END or MD_MALFORMED
+ * (md_inf_batch_error: the MD_* status; md_inf_batch_message: the reference's `Malformed string, as md_inf_message).
+ * md_inf_batch_checksum: Adler-32 (DEFLATE, ZLIB) or CRC-32 (GZIP) once the stream ended; md_inf_batch_src_rem: input
+ * after the stream's end; md_inf_batch_reset: De.Inf.reset for slot i.  Every decoder's results - bytes, status, message,
+ * checksum, src_rem - are those of md_inf_* with md_inf_chunk_bytes(1) handed the same pieces.  A decoder that found no
+ * block end takes part again only once its buffered input has doubled (or at its end of input), as md_inf_* does.  The
+ * undecoded tail and the window (the last <= 32 KiB of output) stay in device memory between rounds; a round costs one
+ * copy of the fresh bytes in, and two copies back.  md_inf_batch_src refuses (MD_E_INVALID_ARGUMENT) input after the end of
+ * input, on a finished slot, and more than 1 GiB per decoder and round. */
+typedef struct md_inf_batch md_inf_batch;
+md_inf_batch *md_inf_batch_open(md_ctx *ctx, int format, size_t n);
+int md_inf_batch_src(md_inf_batch *b, size_t i, const uint8_t *buf, size_t len);
+int md_inf_batch_decode(md_inf_batch *b);
+size_t md_inf_batch_pending(const md_inf_batch *b, size_t i);
+size_t md_inf_batch_out(md_inf_batch *b, size_t i, uint8_t *dst, size_t cap);
+int md_inf_batch_status(const md_inf_batch *b, size_t i);
+int md_inf_batch_error(const md_inf_batch *b, size_t i);
+const char *md_inf_batch_message(const md_inf_batch *b, size_t i);
+uint32_t md_inf_batch_checksum(const md_inf_batch *b, size_t i);
+size_t md_inf_batch_src_rem(const md_inf_batch *b, size_t i);
+void md_inf_batch_reset(md_inf_batch *b, size_t i);
+void md_inf_batch_close(md_inf_batch *b);
+
 /* ---- GZip (lib/gz.ml) ---- */
 
 /* What Gz.Inf.filename / comment / os / extra report (lib/gz.ml:612-633): offsets into src. */
