@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""bench.py — headline benchmark: batched zlib inflate (and the deflate leg) on MI355X.
+"""bench.py — headline benchmark: batched zlib inflate (and, with --full, the deflate leg) on MI355X.
 
 A "step" is one pass of the hot path (Zl.Inf.Ns semantics, one stream per workgroup of two wavefronts) over one
 batch of BASELINE.json config[1]:
@@ -12,8 +12,13 @@ Inputs are resident in HBM before the timed region.  Weak scaling: every rank in
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
     python bench.py --dump-outputs DIR  # also writes what the last timed step returned, DIR/<name>.npy (dump_outputs)
+    python bench.py --full              # also the checks against libz and every leg marked [full] below
 
-Prints ONE JSON line (rank 0); `ms_per_step` = wall milliseconds of one of the --steps timed steps.
+Prints ONE JSON line (rank 0); `ms_per_step` = wall milliseconds of one of the --steps timed steps.  A plain run does only
+what the headline needs: it generates the inputs, warms up, times the steps, writes --dump-outputs if asked and prints the
+line.  Its `parity_ok` covers what the device returned: every stream Ok, out_len = the stream's size, consumed = its
+compressed size.  --full also compares every output byte and every Adler-32 with libz's and adds the legs marked [full],
+all outside the timed region (`full` in the line says which kind of run it was; --no-* options leave parts out):
   roofline      the hot path's one kernel, md::wv::inflate_wave_kernel: algorithmic bytes = compressed bytes
                 read + uncompressed bytes written per launch, over the launch duration
                 measured with HIP events on the stream the kernel runs on; peak = 8 TB/s HBM3E
@@ -21,23 +26,24 @@ Prints ONE JSON line (rank 0); `ms_per_step` = wall milliseconds of one of the -
                 committed rocprofv3 --pmc passes of this same command (PMC_DIR below: profiles/<round>_final/pmc_summary.json,
                 gfx950 correction of the guide applied; `traffic_source` names the file and the commit it was
                 collected at), null when the configuration differs.
-  cpu_baseline  the repo's C restatement of lib/de.ml (oracle/, kind "port") on the host cores of this box,
+  cpu_baseline [full] the repo's C restatement of lib/de.ml (oracle/, kind "port") on the host cores of this box,
                 bounded sample of the same streams.
-  deflate       BASELINE.json config[2] on the same GPU(s), outside the inflate timed region: 4096 x 1 MiB
+  deflate [full] BASELINE.json config[2] on the same GPU(s), outside the inflate timed region: 4096 x 1 MiB
                 printable-ASCII buffers, De.Lz77 + De.Def level 6, queue 4096, Zl driver — its own value,
                 ms_per_step, roofline and cpu_baseline (BASELINE's metric is "inflate+deflate").  One step = the
                 three kernels of the path (hash chains, longest_match ahead, parse + encode).
-  r01_workload  the same kernel on round 1's input (every stream seeded word text), N = 1 only.
-  gzip          BASELINE.json config[3], STRONG scaling (outside `value`): one batch of 32768 gzip members = the
+  r01_workload [full] the same kernel on round 1's input (every stream seeded word text), N = 1 only.
+  gzip [full]   BASELINE.json config[3], STRONG scaling (outside `value`): one batch of 32768 gzip members = the
                 reference's corpus files cycled, sharded over the N ranks by bytes; Gz.Def level 4 then Gz.Inf on
                 every shard; the compressed members are then gathered to rank 0 (sizes by all_gather, bytes by
                 exact-size send/recv) — `results_gathered`, `gather_ms`.
-  lzo           BASELINE.json config[4] (N = 1 only): 8192 x 128 KiB buffers through Lzo.compress then
+  lzo [full]    BASELINE.json config[4] (N = 1 only): 8192 x 128 KiB buffers through Lzo.compress then
                 Lzo.uncompress — MiB/s, ms and HBM fraction per direction, round trip and oracle bytes checked.
-  long_stream   ONE zlib stream of 64 MiB through Zl.Higher.uncompress (N = 1 only): decoded in pieces by the whole device
+  long_stream [full] ONE zlib stream of 64 MiB through Zl.Higher.uncompress (N = 1 only): decoded in pieces by the whole device
                 (DESIGN 3b), host to host, beside the one-pair-of-wavefronts path the call took before round 6.
-  def_ns        SURVEY 8(f) row 4 (N = 1 only): De.Def.Ns.deflate level 4 over 1024 x 256 KiB buffers, inflated back,
+  def_ns [full] SURVEY 8(f) row 4 (N = 1 only): De.Def.Ns.deflate level 4 over 1024 x 256 KiB buffers, inflated back,
                 oracle bytes checked on a sample.
+  host_path [full] the same batch from pinned host buffers through md_inflate_batch_host, beside the copies alone (N = 1).
   ranks_seen    an all_reduce over the process group: how many ranks really took part.
 For N > 1 the per-stream results of every rank (sizes and Adler-32 from the kernel) are gathered with
 decompress_amd.shard.gather_varlen — the path's only exchange (RCCL over xGMI).
@@ -118,13 +124,16 @@ def parse(argv=None):
     ap.add_argument("--stream-kib", type=int, default=256)
     ap.add_argument("--unique", type=int, default=0, help="distinct streams to generate (0 = all)")
     ap.add_argument("--level", type=int, default=6)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: compare the outputs with libz's, and run the CPU baselines, the host-buffer, "
+                         "round 1 workload, deflate, gzip, LZO, Def.Ns and long-stream legs (the --no-* options below leave some out)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="budget of each CPU baseline leg")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-verify", action="store_true")
-    ap.add_argument("--no-deflate", action="store_true", help="skip the deflate leg (config 3)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the gzip (config 4) and LZO (config 5) legs")
-    ap.add_argument("--no-host-path", action="store_true", help="skip the host-buffer legs (md_*_batch_host end to end, H2D / D2H alone)")
-    ap.add_argument("--no-text-leg", action="store_true", help="skip the extra inflate measurement on round 1's workload")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-verify", action="store_true", help="with --full: skip the comparisons with libz and the oracle")
+    ap.add_argument("--no-deflate", action="store_true", help="with --full: skip the deflate leg (config 3)")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the gzip (config 4), LZO (config 5), Def.Ns and long-stream legs")
+    ap.add_argument("--no-host-path", action="store_true", help="with --full: skip the host-buffer legs (md_*_batch_host end to end, H2D / D2H alone)")
+    ap.add_argument("--no-text-leg", action="store_true", help="with --full: skip the extra inflate measurement on round 1's workload")
     ap.add_argument("--deflate-streams", type=int, default=4096)
     ap.add_argument("--deflate-kib", type=int, default=1024)
     ap.add_argument("--deflate-steps", type=int, default=3)
@@ -792,10 +801,11 @@ def main():
     n = args.streams
     nbytes = args.stream_kib * 1024
     unique = args.unique or n
-    # every rank owns different streams (seed offset by rank): weak scaling
+    # every rank owns different streams (seed offset by rank): weak scaling.  One worker per host core this process may
+    # use (os.cpu_count() counts the whole machine, and more workers than cores only slow each other down)
     t_gen = time.perf_counter()
     streams = workloads.c2_streams(n, nbytes=nbytes, level=args.level, first=rank * n,
-                                   unique=unique, workers=max(1, min(32, (os.cpu_count() or 8) // max(1, world))))
+                                   unique=unique, workers=max(1, min(32, host_cores()[0] // max(1, world))))
     t_gen = time.perf_counter() - t_gen
     assert all(((s[2] >> 1) & 3) == 2 for s in streams[:64]), "first block must be dynamic Huffman"
     blob, in_off, in_len = workloads.pack(streams, align=16)
@@ -846,11 +856,11 @@ def main():
         # outside the timed region, before anything else writes d_out (the r01_workload leg reuses it)
         dump_outputs(args.dump_outputs, results, d_out, out_off, nbytes)
 
-    # ---- verification (outside the timed region): every stream Ok, bytes exact
+    # ---- verification (outside the timed region): every stream Ok and whole; with --full, bytes exact
     out_len, consumed, status, checksum = results
     ok = bool((status == 0).all().item()) and bool((out_len == nbytes).all().item())
     ok = ok and bool((consumed == d_in_len).all().item())
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         # every output byte of every stream, compared on the device with libz's plaintexts; every Adler-32 the kernel
         # reports with libz's
         host_sum = checksum.cpu().numpy().view(np.uint32)
@@ -894,6 +904,7 @@ def main():
             "dtype": "u8",
             "data": "synthetic",
             "parity_ok": ok,
+            "full": args.full,
             "config": {
                 "workload": "C2: %d x %d KiB zlib streams per GPU, dynamic Huffman (libz level %d; even streams = "
                             "slices of the reference's test/corpus, odd = order-2 Markov ASCII text, 64 symbols, seed 0xC2 + i, SURVEY 8(d)), "
@@ -911,15 +922,15 @@ def main():
                 "algorithmic_bytes_per_launch": algo_bytes,
             },
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline_inflate(streams, nbytes, args.cpu_seconds)
-    if world == 1 and not args.no_host_path:
+    if args.full and world == 1 and not args.no_host_path:
         # the same batch from HOST buffers (outside the timed region of `value`, which stays the resident-buffer figure)
         try:
             line["host_path"] = host_path_inflate(eng, dev, blob, in_off, in_len, out_off, out_cap, n * nbytes, d_out, kernel_ms)
         except (MemoryError, RuntimeError) as e:
             line["host_path"] = {"error": str(e)[:200]}
-    if not args.no_text_leg and world == 1 and (n, nbytes) == (4096, 262144):
+    if args.full and not args.no_text_leg and world == 1 and (n, nbytes) == (4096, 262144):
         # the same kernel on round 1's stand-in workload (every stream seeded word text, 512 distinct), so that
         # BENCH_r01's 10.99 ms/step has a like-for-like successor; outside the timed region of `value`
         ts = [workloads._c2_text_one((0xC2 + i, nbytes, args.level)) for i in range(512)]
@@ -938,11 +949,11 @@ def main():
         del td_in
     del d_in, d_out
     torch.cuda.empty_cache()
-    if not args.no_deflate:
+    if args.full and not args.no_deflate:
         leg = deflate_leg(args, eng, dev, rank, world, dist, fence)
         if rank == 0:
             line["deflate"] = leg
-    if not args.no_secondary:  # configs 4 (one batch sharded over the ranks, outputs gathered) and 5 (not part of `value`)
+    if args.full and not args.no_secondary:  # configs 4 (one batch sharded over the ranks, outputs gathered) and 5 (not part of `value`)
         torch.cuda.empty_cache()
         leg = gzip_leg(args, eng, dev, rank, world, dist)
         torch.cuda.empty_cache()

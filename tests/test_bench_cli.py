@@ -1,5 +1,6 @@
 """bench.py's launcher logic on CPU: `--gpus N` without a launcher re-executes under torch.distributed.run with N ranks
-(`--gpus N` used to be ignored), and asks for more GPUs than the box has fail loudly."""
+(`--gpus N` used to be ignored), and asks for more GPUs than the box has fail loudly.  With a GPU
+(`pytest -m gpu`): what a plain run's line holds next to a --full one."""
 import os
 import sys
 
@@ -42,6 +43,38 @@ def test_steps_must_be_at_least_one():
         bench.parse(["--steps", "0"])
     assert bench.parse(["--steps", "3"]).steps == 3 and bench.parse([]).dump_outputs is None
     assert bench.parse(["--dump-outputs", "d"]).dump_outputs == "d"
+
+
+def test_extra_legs_are_opt_in():
+    """a plain run measures the headline only; --full adds the other legs and checks, and the --no-* options still apply"""
+    assert bench.parse([]).full is False and bench.parse(["--gpus", "1", "--steps", "3", "--warmup", "1"]).full is False
+    a = bench.parse(["--full", "--no-deflate"])
+    assert a.full is True and a.no_deflate is True and a.no_secondary is False
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("full", [False, True])
+def test_plain_and_full_lines(tmp_path, full):
+    """a plain run prints the headline with no extra legs; --full adds them (here the host path and the libz byte check)"""
+    import json
+    import subprocess
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--streams", "64",
+           "--stream-kib", "64", "--dump-outputs", str(tmp_path)]
+    if full:
+        cmd += ["--full", "--no-cpu-baseline", "--no-deflate", "--no-secondary"]
+    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["unit"] == "MiB/s" and d["higher_is_better"] is True and d["dtype"] == "u8" and d["value"] > 0
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["parity_ok"] is True and d["full"] is full
+    assert d["roofline"]["kernel_ms"] > 0 and os.path.exists(os.path.join(str(tmp_path), "out_len.npy"))
+    for leg in ("cpu_baseline", "deflate", "gzip", "lzo", "def_ns", "long_stream"):
+        assert leg not in d, leg
+    assert ("host_path" in d) is full
+    if full:
+        assert d["host_path"]["parity_ok"] is True
 
 
 @pytest.mark.parametrize("n,nbytes", [(64, 64 * 1024), (2, 4 << 20)])

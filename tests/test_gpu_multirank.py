@@ -20,7 +20,7 @@ def test_two_ranks_on_one_device():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     n, members = 192, 600
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--streams", str(n),
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--streams", str(n),
            "--stream-kib", "64", "--deflate-streams", "64", "--deflate-kib", "64", "--deflate-steps", "1", "--gzip-members", str(members),
            "--no-cpu-baseline", "--no-host-path", "--no-text-leg"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)

@@ -3,7 +3,7 @@
 cd "$(dirname "$0")/../.."
 for v in "$@"; do
   cp gpurun_variants/$v.so decompress_amd/libmdeflate.so
-  a=$(timeout 200 python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-secondary --no-deflate --no-verify 2>/dev/null | python -c "
+  a=$(timeout 200 python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-secondary --no-deflate --no-verify 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['roofline']['kernel_ms'], d['r01_workload']['kernel_ms'], d['parity_ok'])")
   b=$(timeout 200 python tools/dbg/deflate_slices.py 0 2>&1 | tail -1 | cut -c1-30)

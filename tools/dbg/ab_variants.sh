@@ -4,7 +4,7 @@ for v in "$@"; do
   cp gpurun_variants/$v.so decompress_amd/libmdeflate.so
   echo "== $v"
   timeout 200 python tools/dbg/deflate_slices.py 0 2>&1 | tail -1
-  timeout 400 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-text-leg --no-deflate --no-verify 2>/dev/null | python -c "
+  timeout 400 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-text-leg --no-deflate --no-verify 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 g = [l for l in d.get('secondary', d.get('legs', [])) if 'C4' in str(l)] if isinstance(d.get('secondary', d.get('legs', None)), list) else None

@@ -4,7 +4,7 @@ cd "$(dirname "$0")/../.." && REPO=$PWD
 OUT=$REPO/gpurun_out/variants; mkdir -p $OUT
 for so in decompress_amd/libmdeflate.so decompress_amd/libmdeflate_v*.so; do
   name=$(basename $so .so)
-  MD_LIBMDEFLATE=$REPO/$so timeout 600 python bench.py --no-deflate --no-secondary --no-cpu-baseline --no-host-path ${BENCH_ARGS} > $OUT/$name.json 2> $OUT/$name.err
+  MD_LIBMDEFLATE=$REPO/$so timeout 600 python bench.py --full --no-deflate --no-secondary --no-cpu-baseline --no-host-path ${BENCH_ARGS} > $OUT/$name.json 2> $OUT/$name.err
   python - "$name" <<'PY'
 import json,sys
 n=sys.argv[1]

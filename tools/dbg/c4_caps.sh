@@ -2,7 +2,7 @@
 cd "$(dirname "$0")/../.."
 for cap in "--deflate-cap-mib 40800" "--deflate-cap-mib 36000"; do
   echo "== cap '$cap'"
-  timeout 400 python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-text-leg --no-deflate --no-verify $cap 2>/dev/null | python -c "
+  timeout 400 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-text-leg --no-deflate --no-verify $cap 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 def find(o):

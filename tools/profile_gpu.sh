@@ -3,12 +3,14 @@
 # usage: tools/profile_gpu.sh <tag> [bench args...]
 # Summaries land in gpurun_out/prof_<tag>/ ; copy what you want judged to profiles/.
 set -u
+[ "${1:-}" = --out-dir ] && { shift; ONLY_DIR=1; }  # only print the folder this script writes to
 TAG=${1:-r04}; shift || true
 REPO=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$REPO/gpurun_out/prof_$TAG
+[ -n "${ONLY_DIR:-}" ] && { echo "$OUT"; exit 0; }
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-BENCH="python $REPO/bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-text-leg --no-secondary --no-host-path --no-verify $*"
+BENCH="python $REPO/bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-text-leg --no-secondary --no-host-path --no-verify $*"
 echo "== kernel trace: $BENCH"
 rocprofv3 --kernel-trace --stats -f csv -d "$OUT/trace" -o trace -- $BENCH > "$OUT/bench_under_rocprof.json" 2> "$OUT/trace.log"
 tail -1 "$OUT/bench_under_rocprof.json" | cut -c1-400
