@@ -12,91 +12,19 @@
 #include <string>
 #include <vector>
 
+#include "host_util.hpp"
+#include "internal.hpp"
 #include "mdeflate.h"
 
-extern "C" int md_launch_inflate_wave(int format, uint32_t n, const uint8_t *in, const uint64_t *in_off,
-                                      const uint64_t *in_len, uint8_t *out, const uint64_t *out_off,
-                                      const uint64_t *out_cap, uint64_t *out_len, uint64_t *consumed,
-                                      int32_t *status, uint32_t *checksum, uint64_t *dbg, uint32_t *order,
-                                      int waves, const void *cont_ptrs, hipStream_t stream);
-
-// deflate: the front workspace (deflate_common.hpp) is opaque here
-struct md_front {
-  const void *p_end, *slot, *chunk0, *tail, *flags;
-  void *link, *flg, *m, *mq;
-};
-extern "C" size_t md_deflate_queue_bytes(uint32_t n, int qcap);
-// a stream's slot in the per-position workspace: its length + 64, rounded up to the match kernel's chunk; the chunk and
-// the size of a stream's state slot are the kernels' constants (deflate_common.hpp), asked for, not copied
-extern "C" uint32_t md_front_chunk();
-extern "C" uint32_t md_piece_state_bytes();
-static const unsigned long long kChunkPositions = md_front_chunk();
-static const unsigned long long kSlotPad = 64 + kChunkPositions - 1;
-extern "C" size_t md_front_small_bytes(uint32_t n);
-extern "C" size_t md_front_big_bytes(uint64_t positions);
-extern "C" void md_front_carve(void *small_ws, void *big_ws, uint32_t n, uint64_t positions, md_front *f);
-extern "C" int md_launch_deflate_plan(uint32_t n, const uint64_t *in_len, int driver, int matcher, int level,
-                                      uint64_t cap_positions, uint32_t cap_chunks, const md_front *f, hipStream_t stream);
-extern "C" int md_launch_deflate_front(uint32_t n, uint32_t nchunks_max, const uint8_t *in, const uint64_t *in_off,
-                                       const uint64_t *in_len, int matcher, uint32_t max_chain, uint32_t nice,
-                                       const md_front *f, const uint32_t *order, uint32_t match_skip, hipStream_t stream);
-extern "C" int md_launch_deflate_match(uint32_t n, uint32_t nchunks_max, const uint8_t *in, const uint64_t *in_off,
-                                       const uint64_t *in_len, uint32_t max_chain, uint32_t nice, const md_front *f,
-                                       uint32_t match_skip, hipStream_t stream);
-extern "C" int md_launch_link_chunked(const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len, uint32_t p_end,
-                                      uint32_t seg, uint32_t cus, const md_front *f, hipStream_t stream);
-extern "C" int md_i_debug_inflate_lds_pad(uint32_t bytes);
-extern "C" int md_i_debug_known_bounds(int mode, uint32_t nstreams);
-extern "C" int md_launch_stream_order(uint32_t n, const uint64_t *in_len, uint32_t *order, hipStream_t stream);
-extern "C" void md_deflate_level_params(int driver, int matcher, int level, uint32_t *max_chain, uint32_t *nice);
-extern "C" int md_launch_def_ns(int format, int level, uint32_t n, uint32_t nchunks_max, const uint8_t *in, const uint64_t *in_off,
-                                const uint64_t *in_len, uint8_t *out, const uint64_t *out_off, const uint64_t *out_cap,
-                                uint64_t *out_len, int32_t *status, uint32_t *checksum, const md_front *f, hipStream_t stream);
-extern "C" int md_launch_deflate(int format, int level, int qcap, int driver, int dynamic, uint32_t n,
-                                 const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len,
-                                 uint8_t *out, const uint64_t *out_off, const uint64_t *out_cap,
-                                 uint64_t *out_len, int32_t *status, uint32_t *checksum, const md_front *fr, void *queue_ws,
-                                 uint64_t *dbg, const uint8_t *gz_hdr, uint32_t gz_hdr_len,
-                                 const uint32_t *gz_crc, int matcher, uint32_t *hist, const uint32_t *order, const void *piece_ptrs,
-                                 hipStream_t stream);
-
-extern "C" int md_launch_gz_header(uint32_t n, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len,
-                                   uint64_t *body_off, uint64_t *body_len, int32_t *hstatus, hipStream_t stream);
-extern "C" int md_launch_crc32(uint32_t n, const uint8_t *data, const uint64_t *off, const uint64_t *len,
-                               uint32_t *crc_out, hipStream_t stream);
-extern "C" int md_launch_gz_finish(uint32_t n, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len,
-                                   const uint64_t *body_off, const int32_t *hstatus, const uint8_t *out,
-                                   const uint64_t *out_off, uint64_t *out_len, uint64_t *consumed, int32_t *status,
-                                   uint32_t *checksum, hipStream_t stream);
-
-extern "C" int md_launch_lzo_uncompress(uint32_t n, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len,
-                                        uint8_t *out, const uint64_t *out_off, const uint64_t *out_cap,
-                                        uint64_t *out_len, int32_t *status, uint32_t *counter, uint32_t slots, hipStream_t stream);
-extern "C" int md_launch_lzo_compress(uint32_t n, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len,
-                                      uint8_t *out, const uint64_t *out_off, const uint64_t *out_cap,
-                                      uint64_t *out_len, int32_t *status, uint16_t *ws_dict, uint32_t *counter, uint32_t slots,
-                                      hipStream_t stream);
-extern "C" uint32_t md_lzo_slots(int compress, uint32_t cus);
-// inflate_chunked.hip
-extern "C" int md_launch_find_blocks(const uint8_t *body, uint64_t nbytes, uint64_t K, uint32_t nchunks_behind_first, uint64_t *cand,
-                                     hipStream_t stream);
-extern "C" int md_launch_fill_windows(uint32_t n, uint8_t *out, const uint64_t *out_off, const uint8_t *variant, hipStream_t stream);
-extern "C" int md_launch_window_chain(uint32_t npieces, const uint8_t *dst, const uint8_t *scratch, const uint64_t *offa,
-                                      const uint64_t *offb, const uint64_t *u, uint8_t *wins, uint32_t *flag, hipStream_t stream);
-extern "C" size_t md_windows_work_bytes(uint32_t npieces, uint32_t group);
-extern "C" int md_launch_windows_parallel(uint32_t npieces, uint32_t group, const uint8_t *dst, uint64_t u0, const uint8_t *scratch, const uint64_t *offa,
-                                          const uint64_t *offb, const uint64_t *u, const uint64_t *pos, uint8_t *wins, uint32_t *work, uint32_t *flag,
-                                          hipStream_t stream);
-extern "C" int md_launch_resolve(uint32_t npieces, uint8_t *dst, const uint8_t *scratch, const uint64_t *offa, const uint64_t *offb,
-                                 const uint64_t *u, const uint64_t *pos, const uint8_t *wins, uint32_t *flag, hipStream_t stream);
-extern "C" int md_launch_adler_segments(const uint8_t *data, uint64_t n, uint32_t seg, uint32_t *sums, hipStream_t stream);
+// a stream's slot in the per-position workspace: its length + 64, rounded up to the match kernel's chunk
+constexpr uint64_t kSlotPad = 64 + md::defl::kChunk - 1;
 
 struct md_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
   bool own_stream = false;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  // GZip: per-stream scratch (body offsets/lengths, header status, CRCs) and the header to write
+  // GZip: per-stream scratch (body_off[n], body_len[n] u64, hstatus[n] i32, crc[n] u32), grow-only, and the header to write
   void *gz_tmp = nullptr;
   size_t gz_tmp_bytes = 0;
   uint8_t *gz_hdr_dev = nullptr;  // device copy of gz_hdr (530 bytes max)
@@ -122,8 +50,8 @@ struct md_ctx {
   // a deflate batch in slices of positions: descriptors of the slice and the streams' states between the slices, grow-only
   void *slice_desc = nullptr, *slice_state = nullptr;
   size_t slice_desc_bytes = 0, slice_state_bytes = 0;
-  uint32_t *order = nullptr;  // inflate: launch order of a large batch (n words)
-  size_t order_words = 0;
+  uint32_t *order = nullptr;  // launch order of a large batch (4 bytes per stream)
+  size_t order_bytes = 0;
   // the host-buffer entry points (md_*_batch_host): device copies of the caller's blobs and descriptors, grow-only, and
   // the two copy streams that run next to the context's stream (copy-in of slice k + 1 and copy-out of slice k - 1 under
   // the kernels of slice k)
@@ -167,21 +95,8 @@ int fail(md_ctx *ctx, int code, const char *what, hipError_t e = hipSuccess) {
     if (e_ != hipSuccess) return fail(ctx, MD_E_HIP, #expr, e_); \
   } while (0)
 
-// every entry point works on the context's device and leaves the caller's current device as it found it
-struct DeviceGuard {
-  int prev = -1;
-  bool ok = true;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) ok = hipSetDevice(dev) == hipSuccess;
-    if (!ok) (void)hipGetLastError();  // (the call reports the failure itself: no stale error for whoever asks next)
-  }
-  ~DeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
 #define MD_ON_DEVICE(ctx)                 \
-  DeviceGuard guard_((ctx)->device);      \
+  md::DeviceGuard guard_((ctx)->device);  \
   if (!guard_.ok) return fail(ctx, MD_E_HIP, "hipSetDevice")
 
 constexpr size_t kOrderFrom = 2049;  // 256 CUs x 8 resident wavefronts: smaller batches start all at once
@@ -274,7 +189,7 @@ md_ctx *md_create(int device, void *hip_stream) {
   }
   md_ctx *ctx = new md_ctx();
   ctx->device = device;
-  DeviceGuard guard(device);
+  md::DeviceGuard guard(device);
   if (!guard.ok) {
     delete ctx;
     fail(nullptr, MD_E_HIP, "hipSetDevice");
@@ -315,7 +230,7 @@ md_ctx *md_create(int device, void *hip_stream) {
 
 void md_destroy(md_ctx *ctx) {
   if (!ctx) return;
-  DeviceGuard guard(ctx->device);
+  md::DeviceGuard guard(ctx->device);
   if (ctx->ev0) hipEventDestroy(ctx->ev0);
   if (ctx->ev1) hipEventDestroy(ctx->ev1);
   if (ctx->ws) hipFree(ctx->ws);
@@ -368,7 +283,7 @@ int md_timing_end(md_ctx *ctx, float *ms) {
 
 void *md_host_alloc(md_ctx *ctx, size_t bytes) {
   if (!ctx) return nullptr;
-  DeviceGuard guard(ctx->device);
+  md::DeviceGuard guard(ctx->device);
   void *p = nullptr;
   if (!guard.ok || hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocDefault) != hipSuccess) {
     fail(ctx, MD_E_OUT_OF_MEMORY, "hipHostMalloc");
@@ -414,7 +329,7 @@ int md_set_option(md_ctx *ctx, const char *key, int value) {
     void **bufs[] = {&ctx->ws, &ctx->fsmall, &ctx->fbig, (void **)&ctx->order, &ctx->cont_in, &ctx->cont_out, &ctx->cont_desc,
                      &ctx->slice_desc, &ctx->slice_state, &ctx->host_in, &ctx->host_out, &ctx->host_desc,
                      &ctx->par_in, &ctx->par_out, &ctx->par_win, &ctx->par_desc};
-    size_t *sizes[] = {&ctx->ws_bytes, &ctx->fsmall_bytes, &ctx->fbig_bytes, &ctx->order_words, &ctx->cont_in_bytes,
+    size_t *sizes[] = {&ctx->ws_bytes, &ctx->fsmall_bytes, &ctx->fbig_bytes, &ctx->order_bytes, &ctx->cont_in_bytes,
                        &ctx->cont_out_bytes, &ctx->cont_desc_bytes, &ctx->slice_desc_bytes, &ctx->slice_state_bytes,
                        &ctx->host_in_bytes, &ctx->host_out_bytes, &ctx->host_desc_bytes,
                        &ctx->par_in_bytes, &ctx->par_out_bytes, &ctx->par_win_bytes, &ctx->par_desc_bytes};
@@ -479,34 +394,17 @@ int md_get_profile(md_ctx *ctx, uint64_t *out32) {
   return MD_OK;
 }
 
-// per-stream GZip scratch: body_off[n] u64, body_len[n] u64, hstatus[n] i32, crc[n] u32
-static int gz_scratch(md_ctx *ctx, size_t n) {
-  const size_t need = n * 24;
-  if (need > ctx->gz_tmp_bytes) {
-    if (ctx->gz_tmp) {
-      HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-      HIP_TRY(ctx, hipFree(ctx->gz_tmp));
-      ctx->gz_tmp = nullptr;
-      ctx->gz_tmp_bytes = 0;
-    }
-    if (hipMalloc(&ctx->gz_tmp, need) != hipSuccess) return fail(ctx, MD_E_OUT_OF_MEMORY, "hipMalloc(gzip scratch)");
-    ctx->gz_tmp_bytes = need;
-  }
-  return MD_OK;
-}
-
-// the scratch for the launch order of a large batch (4 bytes per stream): kept by the context, only ever grows — the
-// one allocation a batch call can make, on its first large batch
-static int order_scratch(md_ctx *ctx, size_t n) {
-  if (n <= ctx->order_words) return MD_OK;
-  if (ctx->order) {
+// a grow-only device buffer of the context
+static int grow(md_ctx *ctx, void **buf, size_t *have, size_t need, const char *what) {
+  if (need <= *have) return MD_OK;
+  if (*buf) {
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    HIP_TRY(ctx, hipFree(ctx->order));
-    ctx->order = nullptr;
-    ctx->order_words = 0;
+    HIP_TRY(ctx, hipFree(*buf));
+    *buf = nullptr;
+    *have = 0;
   }
-  if (hipMalloc((void **)&ctx->order, n * 4) != hipSuccess) return fail(ctx, MD_E_OUT_OF_MEMORY, "hipMalloc(launch order)");
-  ctx->order_words = n;
+  if (hipMalloc(buf, need) != hipSuccess) return fail(ctx, MD_E_OUT_OF_MEMORY, what);
+  *have = need;
   return MD_OK;
 }
 
@@ -525,7 +423,7 @@ int md_inflate_batch_device(md_ctx *ctx, int format, size_t n, const uint8_t *d_
   MD_ON_DEVICE(ctx);
   if (format == MD_FORMAT_GZIP) {
     // Gz.Inf = header, De.Inf on the body, checksum (lib/gz.ml:463-531, :344-356)
-    int rc = gz_scratch(ctx, n);
+    int rc = grow(ctx, &ctx->gz_tmp, &ctx->gz_tmp_bytes, n * 24, "hipMalloc(gzip scratch)");
     if (rc != MD_OK) return rc;
     uint64_t *body_off = (uint64_t *)ctx->gz_tmp, *body_len = body_off + n;
     int32_t *hstatus = (int32_t *)(body_len + n);
@@ -543,7 +441,7 @@ int md_inflate_batch_device(md_ctx *ctx, int format, size_t n, const uint8_t *d_
   // order is kept and only ever grows (the one allocation a batch call can make, on its first large batch)
   uint32_t *order = nullptr;
   if (n >= kOrderFrom) {
-    const int orc = order_scratch(ctx, n);
+    const int orc = grow(ctx, (void **)&ctx->order, &ctx->order_bytes, n * 4, "hipMalloc(launch order)");
     if (orc != MD_OK) return orc;
     order = ctx->order;
   }
@@ -571,7 +469,6 @@ struct DevBuf {
 // are).  With pinned host buffers (hipHostMalloc / hipHostRegister) the copies are DMA transfers and really overlap;
 // pageable buffers go through the runtime's staging and mostly do not.  The device copies of the blobs are the context's,
 // grow-only (md_set_option "release_workspace" gives them back).
-static int grow(md_ctx *ctx, void **buf, size_t *have, size_t need, const char *what);
 extern "C++" {
 namespace {
 struct HostSlice {
@@ -763,7 +660,7 @@ int md_inflate_batch_host(md_ctx *ctx, int format, size_t n, const uint8_t *h_in
         uint32_t sum = 0;
         const int prc = inflate_parallel(ctx, format, h_in + in_off[i], (size_t)in_len[i], h_out + out_off[i], (size_t)out_cap[i], &used, &wrote,
                                          checksum ? &sum : nullptr);
-        if (prc == 1000 /* kNotHandled: not a well-formed stream that fits - the batch path says what it is */) {
+        if (prc == MD_NOT_HANDLED) {  // (not a well-formed stream that fits: the batch path says what it is)
           const int rc = sub(std::vector<size_t>{i});
           if (rc != MD_OK) return rc;
           continue;
@@ -827,13 +724,13 @@ int md_inflate_continue_batch_device(md_ctx *ctx, size_t n, const uint8_t *d_in,
   MD_ON_DEVICE(ctx);
   uint32_t *order = nullptr;
   if (n >= kOrderFrom) {
-    const int orc = order_scratch(ctx, n);
+    const int orc = grow(ctx, (void **)&ctx->order, &ctx->order_bytes, n * 4, "hipMalloc(launch order)");
     if (orc != MD_OK) return orc;
     order = ctx->order;
   }
-  const void *cont[7] = {d_start_bit, d_hist_len, d_adler_in, d_resume_bits, d_resume_out, d_resume_adler, d_resume_last};
+  const md::wv::Cont cont{d_start_bit, d_hist_len, d_adler_in, d_resume_bits, d_resume_out, d_resume_adler, d_resume_last};
   int rc = md_launch_inflate_wave(MD_FORMAT_DEFLATE, (uint32_t)n, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len,
-                                  d_consumed, d_status, d_checksum, ctx->dbg, order, ctx->inflate_waves, cont, ctx->stream);
+                                  d_consumed, d_status, d_checksum, ctx->dbg, order, ctx->inflate_waves, &cont, ctx->stream);
   if (rc != 0) return fail(ctx, MD_E_HIP, "inflate kernel launch", (hipError_t)rc);
   return MD_OK;
 }
@@ -855,7 +752,7 @@ int md_de_inf_continue_host(md_ctx *ctx, const uint8_t *src, size_t src_len, uns
   ctx->par_last_pieces = ctx->par_last_rounds = 0;
   if (ctx->par_min && src_len >= ctx->par_min) {  // a long piece: its complete blocks by the whole chip, the rest as before
     const int prc = continue_parallel(ctx, src, src_len, start_bit, dst, hist_len, dst_cap, adler_in, flags, dst_len, status, resume);
-    if (prc != 1000 /* kNotHandled */) return prc;
+    if (prc != MD_NOT_HANDLED) return prc;
     ctx->par_last_pieces = 0;
   }
   return continue_serial(ctx, src, src_len, start_bit, dst, hist_len, dst_cap, adler_in, flags, dst_len, status, resume);
@@ -883,10 +780,10 @@ static int continue_serial(md_ctx *ctx, const uint8_t *src, size_t src_len, unsi
   if (hist_len) HIP_TRY(ctx, hipMemcpyAsync(dout.p, dst, hist_len, hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipMemcpyAsync(d64, h64, sizeof h64, hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipMemcpyAsync(d32, h32, sizeof h32, hipMemcpyHostToDevice, st));
-  const void *cont[7] = {d32 + 2, d32 + 3, d32 + 4, d64 + 6, d64 + 7, d32 + 5, d32 + 6};
+  const md::wv::Cont cont{d32 + 2, d32 + 3, d32 + 4, d64 + 6, d64 + 7, d32 + 5, d32 + 6};
   int rc = md_launch_inflate_wave(MD_FORMAT_DEFLATE, 1, (const uint8_t *)din.p, d64 + 0, d64 + 1, (uint8_t *)dout.p, d64 + 2,
                                   d64 + 3, d64 + 4, d64 + 5, (int32_t *)d32, d32 + 1, nullptr, nullptr, ctx->inflate_waves,
-                                  cont, st);
+                                  &cont, st);
   if (rc != 0) return fail(ctx, MD_E_HIP, "inflate kernel launch", (hipError_t)rc);
   HIP_TRY(ctx, hipMemcpyAsync(h64, d64, sizeof h64, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipMemcpyAsync(h32, d32, sizeof h32, hipMemcpyDeviceToHost, st));
@@ -919,15 +816,6 @@ static int continue_serial(md_ctx *ctx, const uint8_t *src, size_t src_len, unsi
   return MD_OK;
 }
 
-// host-side CRC-32 of the few header bytes (the CRC16 of lib/gz.ml:771-789 is its upper half)
-static uint32_t host_crc32(const uint8_t *p, size_t n) {
-  uint32_t c = 0xffffffffu;
-  for (size_t i = 0; i < n; i++) {
-    c ^= p[i];
-    for (int k = 0; k < 8; k++) c = (c >> 1) ^ (0xedb88320u & (0u - (c & 1)));
-  }
-  return c ^ 0xffffffffu;
-}
 // The bytes Gz.Def writes in front of the body (lib/gz.ml:796-812) for the header fields of Gz.Def.encoder
 // (lib/gz.ml:859-918); returns the length, 0 when a field is out of range.
 static uint32_t gz_header_bytes(const md_gz_header *g, int level, uint8_t h[544]) {
@@ -957,7 +845,7 @@ static uint32_t gz_header_bytes(const md_gz_header *g, int level, uint8_t h[544]
     p += (uint32_t)cl + 1;
   }
   if (g->hcrc) {  // the upper half of the CRC-32 of what precedes, big-endian (H10, lib/gz.ml:771-789)
-    const uint32_t c16 = (host_crc32(h, p) & 0xffff0000u) >> 16;
+    const uint32_t c16 = (md::crc32_update(0, h, p) & 0xffff0000u) >> 16;
     h[p] = (uint8_t)(c16 >> 8);
     h[p + 1] = (uint8_t)c16;
     p += 2;
@@ -976,26 +864,11 @@ int md_crc32_batch_device(md_ctx *ctx, size_t n, const uint8_t *d_data, const ui
   return MD_OK;
 }
 
-// a grow-only device buffer of the context
-static int grow(md_ctx *ctx, void **buf, size_t *have, size_t need, const char *what) {
-  if (need <= *have) return MD_OK;
-  if (*buf) {
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    HIP_TRY(ctx, hipFree(*buf));
-    *buf = nullptr;
-    *have = 0;
-  }
-  if (hipMalloc(buf, need) != hipSuccess) return fail(ctx, MD_E_OUT_OF_MEMORY, what);
-  *have = need;
-  return MD_OK;
-}
-
-static const size_t kPieceStateBytes = md_piece_state_bytes();  // deflate_common.hpp kPieceState (checked against sizeof there)
 // One piece of one stream (md_i_piece_run below): device pointers of what differs from a batch of whole streams.
 struct PieceArgs {
   const uint64_t *d_front_len;  // length of the text the launch holds, n - w0 (d_in_len is the absolute length n)
   void *queue;                  // the stream's own command queue: it lives across launches
-  const void *ptrs[4];          // struct Piece of deflate_common.hpp: flags, state, pos, sum
+  md::defl::Piece piece;        // flags, state, pos, sum
   uint32_t match_skip;          // leading positions of the text no stream of the launch will take (the window brought along)
 };
 
@@ -1021,7 +894,7 @@ static int deflate_launch(md_ctx *ctx, int format, int level, int queue_len, int
   const uint64_t *d_front_len = pa ? pa->d_front_len : d_in_len;  // (a piece: the front kernels see [w0, n) as a stream)
   grc_ = grow(ctx, &ctx->fsmall, &ctx->fsmall_bytes, md_front_small_bytes((uint32_t)n), "hipMalloc(deflate plan)");
   if (grc_ != MD_OK) return grc_;
-  md_front fr;
+  md::defl::Front fr;
   uint64_t positions = 0;
   uint32_t chunks = 0;
   uint32_t max_chain = 0, nice = 0;
@@ -1030,7 +903,7 @@ static int deflate_launch(md_ctx *ctx, int format, int level, int queue_len, int
   if (matcher_runs && total_in != 0) {
     // slot <= len + 64 + (chunk - 1) positions and <= len / chunk + 2 chunks per stream
     positions = (uint64_t)total_in + kSlotPad * n;
-    const uint64_t c64 = (uint64_t)total_in / kChunkPositions + 2ull * n;
+    const uint64_t c64 = (uint64_t)total_in / md::defl::kChunk + 2ull * n;
     if (c64 > 0x7fffffffull) return fail(ctx, MD_E_INVALID_ARGUMENT, "batch too large for one launch");
     chunks = (uint32_t)c64;
     grc_ = grow(ctx, &ctx->fbig, &ctx->fbig_bytes, md_front_big_bytes(positions), "hipMalloc(deflate front workspace)");
@@ -1042,8 +915,8 @@ static int deflate_launch(md_ctx *ctx, int format, int level, int queue_len, int
   if (matcher_runs && total_in == 0) {
     uint64_t tot_pos = 0;
     uint32_t tot_chunks = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&tot_pos, (const uint64_t *)fr.slot + n, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(&tot_chunks, (const uint32_t *)fr.chunk0 + n, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&tot_pos, fr.slot + n, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&tot_chunks, fr.chunk0 + n, 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     positions = tot_pos;
     chunks = tot_chunks;
@@ -1058,7 +931,7 @@ static int deflate_launch(md_ctx *ctx, int format, int level, int queue_len, int
     uint8_t h[544];
     gz_hdr_len = gz_header_bytes(gz, level, h);
     if (!gz_hdr_len) return fail(ctx, MD_E_INVALID_ARGUMENT, "gzip header field out of range");
-    int grc = gz_scratch(ctx, n);
+    int grc = grow(ctx, &ctx->gz_tmp, &ctx->gz_tmp_bytes, n * 24, "hipMalloc(gzip scratch)");
     if (grc != MD_OK) return grc;
     gz_crc = (uint32_t *)((uint8_t *)ctx->gz_tmp + n * 20);
     if (!ctx->gz_hdr_dev && hipMalloc((void **)&ctx->gz_hdr_dev, sizeof h) != hipSuccess)
@@ -1078,7 +951,7 @@ static int deflate_launch(md_ctx *ctx, int format, int level, int queue_len, int
   // more streams than the link kernel (one per CU) or the sequential kernel (16 per CU) hold at once: longest first
   uint32_t *order = nullptr;
   if (n >= kOrderFromDeflate) {
-    const int orc = order_scratch(ctx, n);
+    const int orc = grow(ctx, (void **)&ctx->order, &ctx->order_bytes, n * 4, "hipMalloc(launch order)");
     if (orc != MD_OK) return orc;
     order = ctx->order;
     // (a slice of a batch: by what the slice brings, not by the absolute length so far - idle streams bring nothing)
@@ -1102,7 +975,7 @@ static int deflate_launch(md_ctx *ctx, int format, int level, int queue_len, int
   }
   int rc = md_launch_deflate(format, level, queue_len, driver, dynamic, (uint32_t)n, d_in, d_in_off, d_in_len, d_out,
                              d_out_off, d_out_cap, d_out_len, d_status, d_checksum, &fr, pa ? pa->queue : ctx->ws, ctx->dbg,
-                             gz_hdr, gz_hdr_len, gz_crc, matcher, d_hist, order, pa ? pa->ptrs : nullptr, ctx->stream);
+                             gz_hdr, gz_hdr_len, gz_crc, matcher, d_hist, order, pa ? &pa->piece : nullptr, ctx->stream);
   if (rc != 0) return fail(ctx, MD_E_HIP, "deflate kernel launch", (hipError_t)rc);
   return MD_OK;
 }
@@ -1114,13 +987,13 @@ static int def_ns_launch(md_ctx *ctx, int format, int level, size_t n, const uin
                          uint64_t *d_out_len, int32_t *d_status, uint32_t *d_checksum, size_t total_in) {
   int grc_ = grow(ctx, &ctx->fsmall, &ctx->fsmall_bytes, md_front_small_bytes((uint32_t)n), "hipMalloc(deflate plan)");
   if (grc_ != MD_OK) return grc_;
-  md_front fr;
+  md::defl::Front fr;
   uint64_t positions = 0;
   uint32_t chunks = 0;
   const bool matcher_runs = level >= 1 && level <= 4;
   if (matcher_runs && total_in != 0) {
     positions = (uint64_t)total_in + kSlotPad * n;
-    const uint64_t c64 = (uint64_t)total_in / kChunkPositions + 2ull * n;
+    const uint64_t c64 = (uint64_t)total_in / md::defl::kChunk + 2ull * n;
     if (c64 > 0x7fffffffull) return fail(ctx, MD_E_INVALID_ARGUMENT, "batch too large for one launch");
     chunks = (uint32_t)c64;
     grc_ = grow(ctx, &ctx->fbig, &ctx->fbig_bytes, md_front_big_bytes(positions), "hipMalloc(deflate front workspace)");
@@ -1132,8 +1005,8 @@ static int def_ns_launch(md_ctx *ctx, int format, int level, size_t n, const uin
   if (matcher_runs && total_in == 0) {
     uint64_t tot_pos = 0;
     uint32_t tot_chunks = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&tot_pos, (const uint64_t *)fr.slot + n, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(&tot_chunks, (const uint32_t *)fr.chunk0 + n, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&tot_pos, fr.slot + n, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&tot_chunks, fr.chunk0 + n, 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     positions = tot_pos;
     chunks = tot_chunks;
@@ -1281,7 +1154,7 @@ static int deflate_in_slices(md_ctx *ctx, int format, const md_deflate_params &q
     if (h_in_len[i] > S) slot[i] = n_long++;
     if (h_in_len[i] > longest) longest = h_in_len[i];
   }
-  int rc = grow(ctx, &ctx->slice_state, &ctx->slice_state_bytes, (n_long ? n_long : 1) * kPieceStateBytes, "hipMalloc(deflate slice states)");
+  int rc = grow(ctx, &ctx->slice_state, &ctx->slice_state_bytes, (n_long ? n_long : 1) * md::defl::kPieceState, "hipMalloc(deflate slice states)");
   if (rc != MD_OK) return rc;
   rc = grow(ctx, &ctx->ws, &ctx->ws_bytes, md_deflate_queue_bytes((uint32_t)n, q.queue_len), "hipMalloc(deflate command queues)");
   if (rc != MD_OK) return rc;
@@ -1328,7 +1201,7 @@ static int deflate_in_slices(md_ctx *ctx, int format, const md_deflate_params &q
     }
     HIP_TRY(ctx, hipMemcpyAsync(d64, h64, desc_bytes, hipMemcpyHostToDevice, ctx->stream));
     // (every stream of a later slice stopped less than 262 + 64 short of the slice before's end)
-    PieceArgs pa{d64 + n, ctx->ws, {d32 + 2 * n, ctx->slice_state, d64 + 6 * n, d32 + 3 * n}, k == 0 ? 0u : (uint32_t)kSliceKeep - 512u};
+    PieceArgs pa{d64 + n, ctx->ws, {d32 + 2 * n, (uint8_t *)ctx->slice_state, d64 + 6 * n, d32 + 3 * n}, k == 0 ? 0u : (uint32_t)kSliceKeep - 512u};
     rc = deflate_launch(ctx, format, q.level, q.queue_len, q.driver, q.dynamic, q.matcher, q.gz_header, n, d_in, d64, d64 + 2 * n,
                         d_out, d64 + 3 * n, d64 + 4 * n, d64 + 5 * n, (int32_t *)d32, d32 + n, nullptr, total ? total : 1, &pa);
     if (rc != MD_OK) return rc;
@@ -1341,7 +1214,7 @@ static int deflate_in_slices(md_ctx *ctx, int format, const md_deflate_params &q
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     for (size_t i = 0; i < n; i++) {
       if (flags[i] & 8) continue;
-      if ((int32_t)st[i] == 1000) {  // MD_PIECE_AWAIT: more of the stream to come
+      if ((int32_t)st[i] == MD_PIECE_AWAIT) {  // more of the stream to come
         used[i] += out_len[i];
         continue;
       }
@@ -1388,7 +1261,7 @@ static int deflate_capped(md_ctx *ctx, int format, const md_deflate_params &q, s
   std::vector<int32_t> r_st(n);
   std::vector<uint32_t> r_sum(n), crc;
   if (format == MD_FORMAT_GZIP) {  // the CRC-32 of every stream, once
-    int grc = gz_scratch(ctx, n);
+    int grc = grow(ctx, &ctx->gz_tmp, &ctx->gz_tmp_bytes, n * 24, "hipMalloc(gzip scratch)");
     if (grc != MD_OK) return grc;
     uint32_t *d_crc = (uint32_t *)((uint8_t *)ctx->gz_tmp + n * 20);
     int e = md_launch_crc32((uint32_t)n, d_in, d_in_off, d_in_len, d_crc, ctx->stream);
@@ -1502,9 +1375,9 @@ size_t md_i_piece_bytes(const md_ctx *ctx) { return ctx ? ctx->piece_bytes : 0; 
 int md_i_test_flags(const md_ctx *ctx) { return ctx ? ctx->test_flags : 0; }
 md_piece *md_i_piece_open(md_ctx *ctx, int queue_len) {
   if (!ctx || queue_len < 4) return nullptr;
-  DeviceGuard guard(ctx->device);
+  md::DeviceGuard guard(ctx->device);
   md_piece *p = new md_piece();
-  if (hipMalloc(&p->d_state, kPieceStateBytes) != hipSuccess || hipMalloc(&p->d_queue, (size_t)queue_len * 4) != hipSuccess ||
+  if (hipMalloc(&p->d_state, md::defl::kPieceState) != hipSuccess || hipMalloc(&p->d_queue, (size_t)queue_len * 4) != hipSuccess ||
       hipMalloc(&p->d_desc, 128) != hipSuccess) {
     hipFree(p->d_state);
     hipFree(p->d_queue);
@@ -1517,7 +1390,7 @@ md_piece *md_i_piece_open(md_ctx *ctx, int queue_len) {
 }
 void md_i_piece_close(md_ctx *ctx, md_piece *p) {
   if (!ctx || !p) return;
-  DeviceGuard guard(ctx->device);
+  md::DeviceGuard guard(ctx->device);
   hipStreamSynchronize(ctx->stream);
   hipFree(p->d_text);
   hipFree(p->d_out);
@@ -1530,7 +1403,7 @@ void md_i_piece_close(md_ctx *ctx, md_piece *p) {
 // before), of which the first `seen` went through the piece before already.  Positions count from an origin the caller moves up now and then so that they stay below MD_MAX_STREAM:
 // rebase is how far it moved since the piece before (a multiple of 65536, at least 65536 below w0 as that piece counted
 // it).  sum / isize: Adler-32 (CRC-32 for gzip) and length mod 2^32 of the whole input so far.  The piece's output
-// stays in device memory (md_i_piece_out reads it); *status is MD_PIECE_AWAIT (1000) when the encoder waits for more.
+// stays in device memory (md_i_piece_out reads it); *status is MD_PIECE_AWAIT when the encoder waits for more.
 int md_i_piece_run(md_ctx *ctx, md_piece *p, int format, const md_deflate_params *params, const uint8_t *text, size_t text_len,
                    size_t seen, uint64_t w0, uint64_t rebase, int first, int last, uint32_t sum, uint32_t isize, size_t out_cap,
                    size_t *out_len, int *status) {
@@ -1552,7 +1425,7 @@ int md_i_piece_run(md_ctx *ctx, md_piece *p, int format, const md_deflate_params
   uint32_t *d32 = (uint32_t *)(d64 + 10);
   HIP_TRY(ctx, hipMemcpyAsync(d64, h, sizeof h, hipMemcpyHostToDevice, ctx->stream));
   if (text_len) HIP_TRY(ctx, hipMemcpyAsync(p->d_text, text, text_len, hipMemcpyHostToDevice, ctx->stream));
-  PieceArgs pa{d64 + 1, p->d_queue, {d32 + 2, p->d_state, d64 + 6, d32 + 4}, seen > 512 ? (uint32_t)(seen - 512) : 0u};
+  PieceArgs pa{d64 + 1, p->d_queue, {d32 + 2, (uint8_t *)p->d_state, d64 + 6, d32 + 4}, seen > 512 ? (uint32_t)(seen - 512) : 0u};
   rc = deflate_launch(ctx, format, q.level, q.queue_len, q.driver, q.dynamic, q.matcher, q.gz_header, 1, (const uint8_t *)p->d_text,
                       d64 + 0, d64 + 2, (uint8_t *)p->d_out, d64 + 3, d64 + 4, d64 + 5, (int32_t *)d32, d32 + 1, nullptr,
                       text_len ? text_len : 1, &pa);
@@ -1569,12 +1442,6 @@ int md_i_piece_run(md_ctx *ctx, md_piece *p, int format, const md_deflate_params
 // One piece of each of n streams in ONE launch of the kernels (md_def_batch, stream_shim.cpp): texts, outputs, states
 // and queues are the caller's device buffers, the descriptors host arrays of n entries.  flags as struct Piece's (bit 3:
 // the stream takes no part in this launch).  Synchronous: the results are read back.
-struct md_pieces_io {
-  const uint64_t *text_off, *text_len, *abs_len, *out_off, *out_cap, *w0, *rebase;
-  const uint32_t *flags, *sum, *isize;
-  uint64_t *out_len;
-  int32_t *status;
-};
 int md_i_pieces_run(md_ctx *ctx, int format, const md_deflate_params *params, size_t n, const uint8_t *d_text, uint8_t *d_out,
                     void *d_state, void *d_queue, void **d_desc, size_t *d_desc_bytes, const md_pieces_io *io, uint32_t match_skip) {
   if (!ctx || !params || !io || n == 0) return MD_E_INVALID_ARGUMENT;
@@ -1615,7 +1482,7 @@ int md_i_pieces_run(md_ctx *ctx, int format, const md_deflate_params *params, si
   uint64_t *d64 = (uint64_t *)*d_desc;
   uint32_t *d32 = (uint32_t *)(d64 + 10 * n);
   HIP_TRY(ctx, hipMemcpyAsync(d64, h64, desc_bytes, hipMemcpyHostToDevice, ctx->stream));
-  PieceArgs pa{d64 + n, d_queue, {d32 + 2 * n, d_state, d64 + 6 * n, d32 + 3 * n}, match_skip};
+  PieceArgs pa{d64 + n, d_queue, {d32 + 2 * n, (uint8_t *)d_state, d64 + 6 * n, d32 + 3 * n}, match_skip};
   rc = deflate_launch(ctx, format, q.level, q.queue_len, q.driver, q.dynamic, q.matcher, q.gz_header, n, d_text, d64, d64 + 2 * n,
                       d_out, d64 + 3 * n, d64 + 4 * n, d64 + 5 * n, (int32_t *)d32, d32 + n, nullptr, total ? total : 1, &pa);
   if (rc != MD_OK) return rc;
@@ -1638,30 +1505,30 @@ int md_i_piece_out(md_ctx *ctx, const md_piece *p, size_t off, uint8_t *host, si
 // slices of positions (deflate_in_slices: the kernels go on from the state the slice before left, same bytes out) and the
 // copies ride along - the columns [k S, (k + 1) S) of every stream's input as ONE strided copy under the kernels of slice
 // k - 1, and every output column that is final for all streams as one strided copy under the kernels of the next slice.
-// Returns 1000 when the batch is not of that kind (GZip: the CRC-32 of a whole stream comes first; level 0; short or
+// Returns MD_NOT_HANDLED when the batch is not of that kind (GZip: the CRC-32 of a whole stream comes first; level 0; short or
 // irregular streams): the caller then pipelines slices of streams as before.
 extern "C++" {
 static int deflate_host_positions(md_ctx *ctx, int format, const md_deflate_params *params, size_t n, const uint8_t *h_in, size_t in_bytes,
                                   const uint64_t *in_off, const uint64_t *in_len, uint8_t *h_out, size_t out_bytes, const uint64_t *out_off,
                                   const uint64_t *out_cap, uint64_t *out_len, int32_t *status, uint32_t *checksum, uint8_t *din, uint8_t *dout) {
-  if (format == MD_FORMAT_GZIP || n < 2 || ctx->host_slices_max < 2) return 1000;
+  if (format == MD_FORMAT_GZIP || n < 2 || ctx->host_slices_max < 2) return MD_NOT_HANDLED;
   md_deflate_params q;
-  if (check_params(ctx, format, params, &q) != MD_OK) return 1000;  // (the usual path reports it)
+  if (check_params(ctx, format, params, &q) != MD_OK) return MD_NOT_HANDLED;  // (the usual path reports it)
   uint32_t max_chain = 0, nice = 0;
   md_deflate_level_params(q.driver, q.matcher, q.level, &max_chain, &nice);
-  if (max_chain == 0) return 1000;
+  if (max_chain == 0) return MD_NOT_HANDLED;
   const uint64_t ip = in_off[1] - in_off[0], op = out_off[1] - out_off[0];
   uint64_t longest = 0, cap_max = 0;
   for (size_t i = 0; i < n; i++) {
-    if (in_off[i] != in_off[0] + i * ip || out_off[i] != out_off[0] + i * op || in_len[i] > ip || out_cap[i] > op) return 1000;
+    if (in_off[i] != in_off[0] + i * ip || out_off[i] != out_off[0] + i * op || in_len[i] > ip || out_cap[i] > op) return MD_NOT_HANDLED;
     longest = in_len[i] > longest ? in_len[i] : longest;
     cap_max = out_cap[i] > cap_max ? out_cap[i] : cap_max;
   }
-  if (in_off[1] <= in_off[0] || out_off[1] <= out_off[0] || longest < 4 * kSliceMin || longest > MD_MAX_STREAM) return 1000;
+  if (in_off[1] <= in_off[0] || out_off[1] <= out_off[0] || longest < 4 * kSliceMin || longest > MD_MAX_STREAM) return MD_NOT_HANDLED;
   // four slices (more if the workspace cap asks for smaller ones), S a multiple of 32 KiB
   uint64_t S = ((longest + 3) / 4 + 32767) / 32768 * 32768;
   while (S > kSliceMin && ctx->front_cap_bytes && md_front_big_bytes(slice_positions(in_len, n, S)) > ctx->front_cap_bytes) S -= 32768;
-  if (ctx->front_cap_bytes && md_front_big_bytes(slice_positions(in_len, n, S)) > ctx->front_cap_bytes) return 1000;
+  if (ctx->front_cap_bytes && md_front_big_bytes(slice_positions(in_len, n, S)) > ctx->front_cap_bytes) return MD_NOT_HANDLED;
   const uint64_t nslices = (longest + S - 1) / S;
   if (!ctx->s_in && hipStreamCreateWithFlags(&ctx->s_in, hipStreamNonBlocking) != hipSuccess) return fail(ctx, MD_E_HIP, "hipStreamCreate");
   if (!ctx->s_out && hipStreamCreateWithFlags(&ctx->s_out, hipStreamNonBlocking) != hipSuccess) return fail(ctx, MD_E_HIP, "hipStreamCreate");
@@ -1797,7 +1664,7 @@ static int deflate_batch_host(md_ctx *ctx, int format, const md_deflate_params *
   {  // long streams in a regular layout: slices of POSITIONS, input arriving and output leaving under the kernels
     const int prc = deflate_host_positions(ctx, format, params, n, h_in, in_bytes, in_off, in_len, h_out, out_bytes, out_off, out_cap,
                                            out_len, status, checksum, din, dout);
-    if (prc != 1000 /* not this kind of batch: slices of streams below */) return prc;
+    if (prc != MD_NOT_HANDLED) return prc;  // (not this kind of batch: slices of streams below)
   }
   // the sequential kernel holds 16 streams per CU: a slice of fewer than 4 096 streams leaves the chip part empty for as
   // long as a stream takes, so a batch is only cut where every slice still has that many
@@ -1970,30 +1837,11 @@ int md_de_def_run(md_ctx *ctx, int queue_len, const uint32_t *ops, size_t nops, 
 
 // ---- one long stream on the whole chip (csrc/inflate_chunked.hip has the scheme and the kernels) --------------------
 // De.Higher.uncompress / Zl.Higher.uncompress / Gz on ONE big input (lib/de.ml:4555-4571, lib/zl.ml:650-666,
-// bin/decompress.ml:77-100).  Returns kNotHandled whenever anything is not exactly as a well-formed stream decoded in
+// bin/decompress.ml:77-100).  Returns MD_NOT_HANDLED whenever anything is not exactly as a well-formed stream decoded in
 // pieces should be - the caller then takes the serial path, whose statuses and counts are the reference's; MD_OK means
 // the whole stream is decoded, verified against its checksum, and copied out.
 extern "C++" {
 namespace {
-constexpr int kNotHandled = 1000;
-uint32_t par_gf_mul(uint32_t a, uint32_t b) {
-  uint32_t p = 0;
-  for (int k = 0; k < 32; k++) {
-    p ^= b & (0u - ((a >> 31) & 1));
-    a <<= 1;
-    b = (b >> 1) ^ (0xedb88320u & (0u - (b & 1)));
-  }
-  return p;
-}
-// crc(A || B) from crc(A), crc(B) and |B| (reflected CRC-32: bit 31 = x^0)
-uint32_t par_crc_concat(uint32_t crc_a, uint32_t crc_b, uint64_t len_b) {
-  uint32_t sq = 0x00800000u, r = 0x80000000u;  // x^8, x^0
-  for (uint64_t n = len_b; n; n >>= 1) {
-    if (n & 1) r = par_gf_mul(r, sq);
-    sq = par_gf_mul(sq, sq);
-  }
-  return par_gf_mul(crc_a, r) ^ crc_b;
-}
 struct ParPiece {
   uint64_t bit;      // first bit of the piece in the body (a block start)
   uint64_t u = 0;    // bytes it produces
@@ -2033,7 +1881,7 @@ static int par_decode(md_ctx *ctx, const ParIn &in, ParOut *out) {
   uint64_t K = ctx->par_chunk;
   if (in.body_len / 256 < K) K = (in.body_len / 256 + 4095) & ~(uint64_t)4095;
   if (K < 4096) K = 4096;
-  if (body_len < 4 * K || body_len > ((uint64_t)1 << 31) || hl + dst_cap > MD_MAX_STREAM) return kNotHandled;
+  if (body_len < 4 * K || body_len > ((uint64_t)1 << 31) || hl + dst_cap > MD_MAX_STREAM) return MD_NOT_HANDLED;
   const uint32_t nchunks = (uint32_t)((body_len + K - 1) / K);
   hipStream_t st = ctx->stream;
   // -- the body on the device, candidate block starts
@@ -2092,7 +1940,7 @@ static int par_decode(md_ctx *ctx, const ParIn &in, ParOut *out) {
     for (uint64_t c : cand)
       if (c != ~0ull && c > seeded && c > pc.back().bit) pc.push_back(ParPiece{c});
   }
-  if (pc.size() < 3) return kNotHandled;  // nothing to gain
+  if (pc.size() < 3) return MD_NOT_HANDLED;  // nothing to gain
   // -- decode, verify the chain of pieces, decode again without a candidate that proved false or with more room
   uint32_t capmul = 6;
   uint64_t total = 0, used_body = 0;
@@ -2100,7 +1948,7 @@ static int par_decode(md_ctx *ctx, const ParIn &in, ParOut *out) {
   out->resume_bits = 0;
   std::vector<uint64_t> offa, offb;
   for (int round = 1;; round++) {
-    if (round > 8) return kNotHandled;
+    if (round > 8) return MD_NOT_HANDLED;
     ctx->par_last_rounds = round;
     const size_t np = pc.size(), n = 2 * np - 1;  // piece 0 once (its window is real), the others with window A and window B
     // out blob: [the final output: dst_cap][scratch of piece 1 A, 1 B, 2 A, ...]: 32 KiB of window + room, 64-byte aligned
@@ -2133,7 +1981,7 @@ static int par_decode(md_ctx *ctx, const ParIn &in, ParOut *out) {
         }
       }
     }
-    if (at > ((uint64_t)64 << 30)) return kNotHandled;
+    if (at > ((uint64_t)64 << 30)) return MD_NOT_HANDLED;
     rc = grow(ctx, &ctx->par_out, &ctx->par_out_bytes, at + 64, "hipMalloc(parallel inflate output)");
     if (rc != MD_OK) return rc;
     // descriptors: u64 x n: in_off in_len out_off out_cap out_len consumed resume_bits resume_out; u32 x n: start_bit hist
@@ -2199,7 +2047,7 @@ static int par_decode(md_ctx *ctx, const ParIn &in, ParOut *out) {
       const size_t i = p ? 2 * p - 1 : 0;
       const uint64_t base_bits = (pc[p].bit >> 3) * 8;
       if (p && (r_st[i] != r_st[i + 1] || r_out[i] != r_out[i + 1] || r_bits[i] != r_bits[i + 1])) {
-        if (chain) return kNotHandled;  // (the two decodes of a piece of the real chain differ in more than the window's bytes)
+        if (chain) return MD_NOT_HANDLED;  // (the two decodes of a piece of the real chain differ in more than the window's bytes)
         if (p + 1 < np) kill.push_back({pc[p].bit, pc[p + 1].bit});
         again = true;
         continue;
@@ -2212,7 +2060,7 @@ static int par_decode(md_ctx *ctx, const ParIn &in, ParOut *out) {
         again = true;
         if (chain) {  // a piece of the real chain needs more room (the candidate behind it stays)
           capmul *= 6;
-          if (capmul > 1300) return kNotHandled;
+          if (capmul > 1300) return MD_NOT_HANDLED;
         } else if (p + 1 < np) kill.push_back({pc[p].bit, pc[p + 1].bit});  // (behind a false candidate: garbage that expands)
         chain = false;
       } else if (r_st[i] == MD_OK && chain) {  // the final block ended inside this piece: what follows is not the stream's
@@ -2235,7 +2083,7 @@ static int par_decode(md_ctx *ctx, const ParIn &in, ParOut *out) {
         // on the real chain: a piece that runs over the next candidate makes that candidate false; anything else is an
         // error of the stream itself (or a stream that ends inside its last block): the serial path's
         const bool ran_over = r_st[i] == MD_UNEXPECTED_END_OF_INPUT && p + 1 < np && base_bits + r_bits[i] < pc[p + 1].bit;
-        if (chain && !ran_over) return kNotHandled;
+        if (chain && !ran_over) return MD_NOT_HANDLED;
         if (ran_over) unlinked(p, base_bits + r_bits[i]);
         else if (p + 1 < np) kill.push_back({pc[p].bit, pc[p + 1].bit});
         again = true;
@@ -2253,15 +2101,15 @@ static int par_decode(md_ctx *ctx, const ParIn &in, ParOut *out) {
       std::sort(keep.begin(), keep.end(), [](const ParPiece &x, const ParPiece &y) { return x.bit < y.bit; });
       keep.erase(std::unique(keep.begin(), keep.end(), [](const ParPiece &x, const ParPiece &y) { return x.bit == y.bit; }), keep.end());
       pc.swap(keep);
-      if (pc.size() < 2) return kNotHandled;
+      if (pc.size() < 2) return MD_NOT_HANDLED;
       continue;
     }
-    if (last == np) return kNotHandled;
+    if (last == np) return MD_NOT_HANDLED;
     if (last + 1 < np) pc.resize(last + 1);  // (the scratch of the pieces behind it is simply not looked at)
     break;
   }
   const size_t np = pc.size();
-  if (total > dst_cap || np < 2) return kNotHandled;
+  if (total > dst_cap || np < 2) return MD_NOT_HANDLED;
   // -- windows, then every byte
   {
     std::vector<uint64_t> u(np), pos(np);
@@ -2307,7 +2155,7 @@ static int par_decode(md_ctx *ctx, const ParIn &in, ParOut *out) {
     HIP_TRY(ctx, hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     stamp("windows + resolve");
-    if (flag) return kNotHandled;  // a reference in front of the stream's start
+    if (flag) return MD_NOT_HANDLED;  // a reference in front of the stream's start
   }
   out->total = total;
   out->used_body = used_body;
@@ -2358,7 +2206,7 @@ static int par_crc(md_ctx *ctx, const uint8_t *d_base, uint64_t off, uint64_t n,
   HIP_TRY(ctx, hipMemcpyAsync(crcs.data(), d_crc, ncrc * 4, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   uint32_t crc = crcs[0];
-  for (size_t s = 1; s < ncrc; s++) crc = par_crc_concat(crc, crcs[s], cl[s]);
+  for (size_t s = 1; s < ncrc; s++) crc = md::crc32_concat(crc, crcs[s], cl[s]);
   *res = crc;
   return MD_OK;
 }
@@ -2411,8 +2259,8 @@ static int continue_parallel(md_ctx *ctx, const uint8_t *src, size_t src_len, un
   resume->checksum = t.checksum;
   if (flags & MD_CONT_CRC32) {
     const uint64_t n_out = t.out - hl2, n_end = t_len - hl2;
-    resume->crc_out = po.total ? (n_out ? par_crc_concat(crc, t.crc_out, n_out) : crc) : t.crc_out;
-    resume->crc_end = po.total ? (n_end ? par_crc_concat(crc, t.crc_end, n_end) : crc) : t.crc_end;
+    resume->crc_out = po.total ? (n_out ? md::crc32_concat(crc, t.crc_out, n_out) : crc) : t.crc_out;
+    resume->crc_end = po.total ? (n_end ? md::crc32_concat(crc, t.crc_end, n_end) : crc) : t.crc_end;
   } else resume->crc_out = resume->crc_end = 0;
   ctx->par_last_pieces = pieces;
   ctx->par_last_rounds = rounds;
@@ -2424,30 +2272,30 @@ static int inflate_parallel(md_ctx *ctx, int format, const uint8_t *src, size_t 
   // -- the frame: anything but a plain valid header is the serial path's (it knows the reference's answer)
   size_t hdr = 0, trailer = 0;
   if (format == MD_FORMAT_ZLIB) {
-    if (src_len < 6 || (((uint32_t)src[0] << 8) + src[1]) % 31 != 0 || (src[0] & 0xf) != 8) return kNotHandled;
+    if (src_len < 6 || (((uint32_t)src[0] << 8) + src[1]) % 31 != 0 || (src[0] & 0xf) != 8) return MD_NOT_HANDLED;
     hdr = 2;
     trailer = 4;
   } else if (format == MD_FORMAT_GZIP) {
-    if (src_len < 18 || src[0] != 0x1f || src[1] != 0x8b || (src[3] & 2)) return kNotHandled;  // (a header CRC: serial path)
+    if (src_len < 18 || src[0] != 0x1f || src[1] != 0x8b || (src[3] & 2)) return MD_NOT_HANDLED;  // (a header CRC: serial path)
     size_t p = 10;
     const uint32_t flg = src[3];
     if (flg & 4) {  // FEXTRA, big-endian length as the reference reads it (lib/gz.ml:455)
-      if (src_len - p < 2) return kNotHandled;
+      if (src_len - p < 2) return MD_NOT_HANDLED;
       const size_t xl = ((size_t)src[p] << 8) | src[p + 1];
       p += 2;
-      if (src_len - p < xl) return kNotHandled;
+      if (src_len - p < xl) return MD_NOT_HANDLED;
       p += xl;
     }
     for (int which = 0; which < 2; which++) {
       if (!(flg & (which == 0 ? 8u : 16u))) continue;
       while (p < src_len && src[p] != 0) p++;
-      if (p >= src_len) return kNotHandled;
+      if (p >= src_len) return MD_NOT_HANDLED;
       p++;
     }
     hdr = p;
     trailer = 8;
-  } else if (format != MD_FORMAT_DEFLATE) return kNotHandled;
-  if (src_len < hdr + trailer) return kNotHandled;
+  } else if (format != MD_FORMAT_DEFLATE) return MD_NOT_HANDLED;
+  if (src_len < hdr + trailer) return MD_NOT_HANDLED;
   ParIn in{src + hdr, src_len - hdr, 0, nullptr, 0, dst_cap, false};  // (the trailer's bytes included: where the stream ends is the decoder's to say)
   ParOut po;
   int rc = par_decode(ctx, in, &po);
@@ -2455,7 +2303,7 @@ static int inflate_parallel(md_ctx *ctx, int format, const uint8_t *src, size_t 
   const uint64_t total = po.total, used_body = po.used_body;
   if (src_len - hdr - used_body < trailer) {
     ctx->par_last_pieces = 0;
-    return kNotHandled;
+    return MD_NOT_HANDLED;
   }
   const uint8_t *d_out = (const uint8_t *)ctx->par_out;
   const uint8_t *t = src + hdr + used_body;
@@ -2483,7 +2331,7 @@ static int inflate_parallel(md_ctx *ctx, int format, const uint8_t *src, size_t 
   }
   if (!good) {  // the serial path reports it
     ctx->par_last_pieces = 0;
-    return kNotHandled;
+    return MD_NOT_HANDLED;
   }
   if (total) HIP_TRY(ctx, hipMemcpy(dst, d_out, total, hipMemcpyDeviceToHost));
   *consumed = hdr + (size_t)used_body + trailer;

@@ -14,7 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "mdeflate.h"
+#include "internal.hpp"  // struct Front, struct Piece, kChunk, kPieceState, MD_PIECE_AWAIT
 
 namespace md {
 namespace defl {
@@ -29,52 +29,11 @@ constexpr int WSIZE = 1 << 15, WMASK = WSIZE - 1, MAX_DIST = WSIZE - MIN_LOOKAHE
 // (full / quartered chain, (length << 16) | distance), 0 the matcher has to look for itself
 enum { FL_ENDED = 2, FL_MATCH = 4 };
 constexpr int KSPEC = 128;  // chain links walked ahead per position at most (min(max_chain, KSPEC))
-#ifndef MD_PGM
-#define MD_PGM 4
-#endif
 #ifndef MD_MATCH_WAVES
 #define MD_MATCH_WAVES 6
 #endif
 constexpr int PGM = MD_PGM;  // steps of 64 positions one wavefront of the match kernel keeps in flight
-constexpr uint32_t kChunk = PGM * kWave;
-
-// Position-indexed workspace of a batch.  Stream i owns positions [slot[i], slot[i + 1]) of link / flg / m / mq.
-struct Front {
-  const uint32_t *p_end;   // [n]     positions < p_end[i] are inserted ahead (and have a verdict)
-  const uint64_t *slot;    // [n + 1]
-  const uint32_t *chunk0;  // [n + 1] first kChunk-position chunk of stream i in the match kernel's grid
-  const uint32_t *tail;    // [2 n]   hash head of position len - 3 (De matcher): 4th byte 0 / the byte 32 KiB earlier (H7)
-  const uint32_t *flags;   // [1]     bit 0: the batch needs more workspace than the caller's size hint allowed
-  uint32_t *link;          // low 16 bits: distance to the previous position with the same hash, 0 = none within
-                           // 32767; high 16 bits: a fingerprint of the 3 bytes at the position (fp16)
-  uint8_t *flg;            // FL_*
-  uint32_t *m, *mq;        // longest_match ahead over the full / quartered chain, valid where flg == FL_MATCH
-};
-
-// A stream compressed IN PIECES (the encoder of `Def.encode` while input is still arriving, lib/de.ml:4294-4349,
-// lib/zl.ml:523-555): the sequential kernel's state - two LDS structs - is written out when the matcher wants input the
-// piece does not hold, and read back when the next piece begins.  Every pointer null: whole streams (the batch path).
-//   flags[i]  bit 0: the stream's first piece, bit 1: its last one (the end of the input has been signalled), bit 2: the
-//             Adler-32 is the kernel's own, carried in the state (else sum[2i] is the caller's running checksum), bit 3:
-//             nothing to do for this stream (it ended in an earlier launch of a batch in slices)
-//   state     kPieceState bytes per state slot
-//   pos[4i]   w0: position of the first byte the input buffer holds (in_off[i] points at it): the piece brings the
-//             32 KiB window (and a margin) along; in_len[i] is the length of the input so far, counted like w0
-//   pos[4i+1] rebase: positions are 32-bit, so a long stream's origin moves now and then - w0 and in_len count from the
-//             new origin, and this (a multiple of 64 KiB, at most the window base) is what the positions in the state
-//             the piece before left have to come down by
-//   pos[4i+2] the stream's state slot, pos[4i+3] its command queue's slot (whole streams: queue i)
-//   sum[2i]   the checksum of the whole input so far (Adler-32 / CRC-32; for gzip always the caller's), [2i+1] its length
-//             mod 2^32 (the trailer of the last piece)
-// status[i] = MD_PIECE_AWAIT when the piece ended with the matcher waiting for more input.
-struct Piece {
-  const uint32_t *flags;
-  uint8_t *state;
-  const uint64_t *pos;
-  const uint32_t *sum;
-};
-constexpr uint32_t kPieceState = 12288;
-constexpr int MD_PIECE_AWAIT = 1000;
+static_assert(kChunk == PGM * kWave, "kChunk (internal.hpp): PGM steps of a wavefront");
 
 // hash of the string at a, from its little-endian first 4 bytes:
 //   De.Lz77  hash4, lib/de.ml:4067-4071: 4 bytes multiplied by 0x9e3779b1, top 15 bits;

@@ -23,7 +23,6 @@
 // The window is the input buffer itself: w[rel] = in[base + rel]; bytes the
 // reference reads beyond the data (H7) follow its 64 KiB sliding buffer exactly
 // (zero before the first slide, the byte 32 KiB earlier after it).  See DESIGN.md 4.
-#include <string.h>
 #include "deflate_common.hpp"
 
 namespace md {
@@ -2134,12 +2133,11 @@ extern "C" int md_launch_deflate(int format, int level, int qcap, int driver, in
                                  uint8_t *out, const uint64_t *out_off, const uint64_t *out_cap,
                                  uint64_t *out_len, int32_t *status, uint32_t *checksum, const md::defl::Front *fr,
                                  void *queue_ws, uint64_t *dbg, const uint8_t *gz_hdr, uint32_t gz_hdr_len,
-                                 const uint32_t *gz_crc, int matcher, uint32_t *hist, const uint32_t *order, const void *piece_ptrs,
-                                 hipStream_t stream) {
+                                 const uint32_t *gz_crc, int matcher, uint32_t *hist, const uint32_t *order,
+                                 const md::defl::Piece *pieces, hipStream_t stream) {
   if (n == 0) return 0;
   if (dbg) order = nullptr;  // (the profile is stream 0's)
-  md::defl::Piece pcs{};  // (four device pointers in the order of struct Piece, or null: whole streams)
-  if (piece_ptrs) memcpy(&pcs, piece_ptrs, sizeof pcs);
+  const md::defl::Piece pcs = pieces ? *pieces : md::defl::Piece{};
   if (dbg)
     hipLaunchKernelGGL(md::defl::deflate_kernel<true>, dim3(n), dim3(md::defl::kWave), 0, stream, format, level,
                        qcap, driver, dynamic, n, in, in_off, in_len, out, out_off, out_cap, out_len, status,

@@ -865,9 +865,6 @@ __global__ __launch_bounds__(kWave) void ns_kernel(int format, int level, uint32
 }  // namespace ns
 }  // namespace md
 
-extern "C" int md_launch_link_ns(uint32_t n, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len, const md::defl::Front *f,
-                                 hipStream_t stream);
-
 // links (deflate_front.hip, NS variant), matches, then the sequential kernel.  max_depth / nice: lib/de.ml:3933-3936.
 extern "C" int md_launch_def_ns(int format, int level, uint32_t n, uint32_t nchunks_max, const uint8_t *in, const uint64_t *in_off,
                                 const uint64_t *in_len, uint8_t *out, const uint64_t *out_off, const uint64_t *out_cap,

@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #include "gz_crc.hpp"
+#include "internal.hpp"
 #include "mdeflate.h"
 
 namespace md {

@@ -1,0 +1,90 @@
+// host_util.hpp — small host-side helpers of capi.cpp and stream_shim.cpp: checksums of the few bytes the host
+// handles itself, and the device guard of the entry points.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+
+namespace md {
+
+// Adler-32 going on from `adler` (lib/de.ml:4217-4218 keeps it per fill; the sum is the same)
+inline uint32_t adler32_update(uint32_t adler, const uint8_t *p, size_t n) {
+  uint32_t a = adler & 0xffff, b = adler >> 16;
+  while (n) {
+    size_t k = n < 5552 ? n : 5552;
+    n -= k;
+    while (k--) {
+      a += *p++;
+      b += a;
+    }
+    a %= 65521u;
+    b %= 65521u;
+  }
+  return (b << 16) | a;
+}
+
+// CRC-32 going on from `crc` (a complete value: 0 for none yet), eight bytes a step
+struct Crc32Tables {
+  uint32_t t[8][256];
+  Crc32Tables() {
+    for (uint32_t i = 0; i < 256; i++) {
+      uint32_t c = i;
+      for (int k = 0; k < 8; k++) c = (c >> 1) ^ (0xedb88320u & (0u - (c & 1)));
+      t[0][i] = c;
+    }
+    for (uint32_t i = 0; i < 256; i++)
+      for (int j = 1; j < 8; j++) t[j][i] = (t[j - 1][i] >> 8) ^ t[0][t[j - 1][i] & 0xff];
+  }
+};
+inline uint32_t crc32_update(uint32_t crc, const uint8_t *p, size_t n) {
+  static const Crc32Tables T;
+  uint32_t c = ~crc;
+  while (n >= 8) {
+    uint32_t lo, hi;
+    memcpy(&lo, p, 4);
+    memcpy(&hi, p + 4, 4);
+    lo ^= c;
+    c = T.t[7][lo & 0xff] ^ T.t[6][(lo >> 8) & 0xff] ^ T.t[5][(lo >> 16) & 0xff] ^ T.t[4][lo >> 24] ^ T.t[3][hi & 0xff] ^
+        T.t[2][(hi >> 8) & 0xff] ^ T.t[1][(hi >> 16) & 0xff] ^ T.t[0][hi >> 24];
+    p += 8;
+    n -= 8;
+  }
+  while (n--) c = T.t[0][(c ^ *p++) & 0xff] ^ (c >> 8);
+  return ~c;
+}
+
+// crc(A || B) = crc(A) * x^(8|B|) mod P xor crc(B) in GF(2)[x] / P, reflected (bit 31 = x^0): the CRC-32 of output
+// whose pieces' CRCs came from the device
+inline uint32_t crc32_gf_mul(uint32_t a, uint32_t b) {
+  uint32_t p = 0;
+  for (int k = 0; k < 32; k++) {
+    p ^= b & (0u - ((a >> 31) & 1));
+    a <<= 1;
+    b = (b >> 1) ^ (0xedb88320u & (0u - (b & 1)));
+  }
+  return p;
+}
+inline uint32_t crc32_concat(uint32_t crc_a, uint32_t crc_b, uint64_t len_b) {
+  uint32_t sq = 0x00800000u, r = 0x80000000u;  // x^8, x^0
+  for (uint64_t n = len_b; n; n >>= 1) {
+    if (n & 1) r = crc32_gf_mul(r, sq);
+    sq = crc32_gf_mul(sq, sq);
+  }
+  return crc32_gf_mul(crc_a, r) ^ crc_b;
+}
+
+// every entry point works on the context's device and leaves the caller's current device as it found it
+struct DeviceGuard {
+  int prev = -1;
+  bool ok = true;
+  explicit DeviceGuard(int dev) {
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    if (prev != dev) ok = hipSetDevice(dev) == hipSuccess;
+    if (!ok) (void)hipGetLastError();  // (the call reports the failure itself: no stale error for whoever asks next)
+  }
+  ~DeviceGuard() {
+    if (prev >= 0) (void)hipSetDevice(prev);
+  }
+};
+
+}  // namespace md

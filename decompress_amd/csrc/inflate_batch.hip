@@ -119,7 +119,6 @@ __global__ __launch_bounds__(kPackThreads) void inf_hand_pack_kernel(uint32_t m,
 }  // namespace ib
 }  // namespace md
 
-// m rows of one inflate launch: scan, then pack (res: m HandRow; pack: room for the padded ranges, see stream_shim.cpp)
 extern "C" int md_launch_inf_handout(uint32_t m, md::ib::HandIn in, const uint8_t *out, md::ib::HandRow *res, uint8_t *pack,
                                      int with_crc, hipStream_t stream) {
   using namespace md::ib;

@@ -28,6 +28,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "internal.hpp"
 #include "mdeflate.h"
 
 namespace md {

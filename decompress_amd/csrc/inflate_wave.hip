@@ -45,8 +45,8 @@
 // failing token in stream order decides the status and everything before it is written
 // (oracle/de_inflate.c).
 #include <stdlib.h>
-#include <string.h>
 #include "inflate_util.hpp"
+#include "internal.hpp"
 
 namespace md {
 namespace wv {
@@ -1441,18 +1441,8 @@ __device__ __forceinline__ void copier_main(lds_smem *sm, const uint8_t *__restr
   }
 }
 
-// A stream decoded in pieces (md_de_inf_continue_host: the `Flush steps of De.Inf.decode while input is still arriving,
-// lib/de.ml:1427-1474): the piece starts start_bit bits into its first byte, the output buffer begins with hist_len
-// bytes of what was decoded before (the window), the checksum goes on from adler_in; the kernel says where the last
-// block that was complete in this piece ended (bit position, output position, checksum state there) so that the next
-// piece can start at that block boundary.  All pointers null: a whole stream, nothing to report (the batch path).
-struct Cont {
-  const uint32_t *start_bit, *hist_len, *adler_in;
-  uint64_t *resume_bits, *resume_out;
-  uint32_t *resume_adler, *resume_last;
-};
-
 // PAIR = two wavefronts per stream (decoder + copier, see inflate_block); otherwise one wavefront does both in turn.
+// cont: a stream decoded in pieces (struct Cont, internal.hpp), all null for whole streams.
 template <bool PROF, bool PAIR>
 __global__ __launch_bounds__(PAIR ? 2 * kWave : kWave, PAIR ? MD_PAIR_OCC : 2) void inflate_wave_kernel(
     int format, uint32_t n, const uint8_t *__restrict__ in, const uint64_t *__restrict__ in_off,
@@ -1776,24 +1766,22 @@ extern "C" int md_i_debug_known_bounds(int mode, uint32_t nstreams) {
 #endif
 }
 
-// `order` = n words of device scratch, or null for index order; waves = wavefronts per stream (2, or 1)
 extern "C" int md_launch_inflate_wave(int format, uint32_t n, const uint8_t *in, const uint64_t *in_off,
                                       const uint64_t *in_len, uint8_t *out, const uint64_t *out_off,
                                       const uint64_t *out_cap, uint64_t *out_len, uint64_t *consumed,
                                       int32_t *status, uint32_t *checksum, uint64_t *dbg, uint32_t *order,
-                                      int waves, const void *cont_ptrs, hipStream_t stream) {
+                                      int waves, const md::wv::Cont *cont, hipStream_t stream) {
   if (n == 0) return 0;
   using namespace md::wv;
   const bool single = waves == 1;  // the one-wavefront form of the kernel: same results, kept for comparison
   dim3 grid(n), block(single ? kWave : 2 * kWave);
   if (order) hipLaunchKernelGGL(inflate_order_kernel, dim3(1), dim3(kOrderThreads), 0, stream, n, in_len, order);
   const uint32_t *ord = dbg ? nullptr : order;
-  Cont cont{};  // (seven device pointers in the order of struct Cont, or null)
-  if (cont_ptrs) memcpy(&cont, cont_ptrs, sizeof cont);
+  const Cont cn = cont ? *cont : Cont{};
   const uint32_t lds_pad = g_debug_lds_pad;
 #define MD_LAUNCH_INFLATE(P, Q)                                                                                          \
   hipLaunchKernelGGL((inflate_wave_kernel<P, Q>), grid, block, (P) ? 0u : lds_pad, stream, format, n, in, in_off, in_len, out, out_off, \
-                     out_cap, out_len, consumed, status, checksum, dbg, ord, cont)
+                     out_cap, out_len, consumed, status, checksum, dbg, ord, cn)
   if (dbg) {
     if (single) MD_LAUNCH_INFLATE(true, false);
     else MD_LAUNCH_INFLATE(true, true);

@@ -1,0 +1,181 @@
+// internal.hpp — the boundary between the library's translation units: every extern "C" function that one file
+// defines and another calls, the structs that cross, and the constants both sides size things by.  The defining file
+// and every caller include it, so a prototype that drifts from its definition does not compile.  Plain host C++.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "mdeflate.h"
+
+// statuses of the library's own, beside mdeflate.h's MD_* (none of which they equal)
+constexpr int MD_PIECE_AWAIT = 1000;  // a stream in pieces: the matcher waits for input the piece does not hold
+constexpr int MD_NOT_HANDLED = 1001;  // a special path does not take this input: the caller goes the general way
+
+namespace md {
+namespace defl {
+
+#ifndef MD_PGM
+#define MD_PGM 4
+#endif
+constexpr uint32_t kChunk = MD_PGM * 64;  // positions per wavefront of the match kernel (PGM steps of 64, deflate_common.hpp)
+
+// Position-indexed workspace of a batch.  Stream i owns positions [slot[i], slot[i + 1]) of link / flg / m / mq.
+struct Front {
+  const uint32_t *p_end;   // [n]     positions < p_end[i] are inserted ahead (and have a verdict)
+  const uint64_t *slot;    // [n + 1]
+  const uint32_t *chunk0;  // [n + 1] first kChunk-position chunk of stream i in the match kernel's grid
+  const uint32_t *tail;    // [2 n]   hash head of position len - 3 (De matcher): 4th byte 0 / the byte 32 KiB earlier (H7)
+  const uint32_t *flags;   // [1]     bit 0: the batch needs more workspace than the caller's size hint allowed
+  uint32_t *link;          // low 16 bits: distance to the previous position with the same hash, 0 = none within
+                           // 32767; high 16 bits: a fingerprint of the 3 bytes at the position (fp16)
+  uint8_t *flg;            // FL_*
+  uint32_t *m, *mq;        // longest_match ahead over the full / quartered chain, valid where flg == FL_MATCH
+};
+
+// A stream compressed IN PIECES (the encoder of `Def.encode` while input is still arriving, lib/de.ml:4294-4349,
+// lib/zl.ml:523-555): the sequential kernel's state - two LDS structs - is written out when the matcher wants input the
+// piece does not hold, and read back when the next piece begins.  Every pointer null: whole streams (the batch path).
+//   flags[i]  bit 0: the stream's first piece, bit 1: its last one (the end of the input has been signalled), bit 2: the
+//             Adler-32 is the kernel's own, carried in the state (else sum[2i] is the caller's running checksum), bit 3:
+//             nothing to do for this stream (it ended in an earlier launch of a batch in slices)
+//   state     kPieceState bytes per state slot
+//   pos[4i]   w0: position of the first byte the input buffer holds (in_off[i] points at it): the piece brings the
+//             32 KiB window (and a margin) along; in_len[i] is the length of the input so far, counted like w0
+//   pos[4i+1] rebase: positions are 32-bit, so a long stream's origin moves now and then - w0 and in_len count from the
+//             new origin, and this (a multiple of 64 KiB, at most the window base) is what the positions in the state
+//             the piece before left have to come down by
+//   pos[4i+2] the stream's state slot, pos[4i+3] its command queue's slot (whole streams: queue i)
+//   sum[2i]   the checksum of the whole input so far (Adler-32 / CRC-32; for gzip always the caller's), [2i+1] its length
+//             mod 2^32 (the trailer of the last piece)
+// status[i] = MD_PIECE_AWAIT when the piece ended with the matcher waiting for more input.
+struct Piece {
+  const uint32_t *flags;
+  uint8_t *state;
+  const uint64_t *pos;
+  const uint32_t *sum;
+};
+constexpr uint32_t kPieceState = 12288;
+
+}  // namespace defl
+
+namespace wv {
+
+// A stream decoded in pieces (md_de_inf_continue_host: the `Flush steps of De.Inf.decode while input is still arriving,
+// lib/de.ml:1427-1474): the piece starts start_bit bits into its first byte, the output buffer begins with hist_len
+// bytes of what was decoded before (the window), the checksum goes on from adler_in; the kernel says where the last
+// block that was complete in this piece ended (bit position, output position, checksum state there) so that the next
+// piece can start at that block boundary.  All pointers null: a whole stream, nothing to report (the batch path).
+struct Cont {
+  const uint32_t *start_bit, *hist_len, *adler_in;
+  uint64_t *resume_bits, *resume_out;
+  uint32_t *resume_adler, *resume_last;
+};
+
+}  // namespace wv
+}  // namespace md
+
+// The encoder takes its stream in pieces (capi.cpp, md_i_piece_*; stream_shim.cpp): the device goes on from the state the
+// piece before left, so neither side keeps more of the stream than the 64 KiB the matcher can reach back plus the piece.
+struct md_piece;
+// one piece of each of n streams, the descriptors host arrays of n entries (md_i_pieces_run)
+struct md_pieces_io {
+  const uint64_t *text_off, *text_len, *abs_len, *out_off, *out_cap, *w0, *rebase;
+  const uint32_t *flags, *sum, *isize;
+  uint64_t *out_len;
+  int32_t *status;
+};
+
+extern "C" {
+
+// ---- capi.cpp: what stream_shim.cpp needs of a context ----
+int md_validate_deflate_params(md_ctx *ctx, int format, const md_deflate_params *params);
+hipStream_t md_i_stream(md_ctx *ctx);
+int md_i_device(md_ctx *ctx);
+int md_i_test_flags(const md_ctx *ctx);
+size_t md_i_piece_bytes(const md_ctx *ctx);
+md_piece *md_i_piece_open(md_ctx *ctx, int queue_len);
+void md_i_piece_close(md_ctx *ctx, md_piece *p);
+int md_i_piece_run(md_ctx *ctx, md_piece *p, int format, const md_deflate_params *params, const uint8_t *text, size_t text_len,
+                   size_t seen, uint64_t w0, uint64_t rebase, int first, int last, uint32_t sum, uint32_t isize, size_t out_cap,
+                   size_t *out_len, int *status);
+int md_i_piece_out(md_ctx *ctx, const md_piece *p, size_t off, uint8_t *host, size_t len);
+int md_i_pieces_run(md_ctx *ctx, int format, const md_deflate_params *params, size_t n, const uint8_t *d_text, uint8_t *d_out,
+                    void *d_state, void *d_queue, void **d_desc, size_t *d_desc_bytes, const md_pieces_io *io, uint32_t match_skip);
+
+// ---- inflate_wave.hip ----
+// `order` = n words of device scratch, or null for index order; waves = wavefronts per stream (2, or 1); cont = null
+// for whole streams
+int md_launch_inflate_wave(int format, uint32_t n, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len, uint8_t *out,
+                           const uint64_t *out_off, const uint64_t *out_cap, uint64_t *out_len, uint64_t *consumed, int32_t *status,
+                           uint32_t *checksum, uint64_t *dbg, uint32_t *order, int waves, const md::wv::Cont *cont, hipStream_t stream);
+int md_launch_stream_order(uint32_t n, const uint64_t *in_len, uint32_t *order, hipStream_t stream);
+int md_i_debug_inflate_lds_pad(uint32_t bytes);
+int md_i_debug_known_bounds(int mode, uint32_t nstreams);
+
+// ---- inflate_chunked.hip ----
+int md_launch_find_blocks(const uint8_t *body, uint64_t nbytes, uint64_t K, uint32_t nchunks_behind_first, uint64_t *cand,
+                          hipStream_t stream);
+int md_launch_fill_windows(uint32_t n, uint8_t *out, const uint64_t *out_off, const uint8_t *variant, hipStream_t stream);
+int md_launch_window_chain(uint32_t npieces, const uint8_t *dst, const uint8_t *scratch, const uint64_t *offa, const uint64_t *offb,
+                           const uint64_t *u, uint8_t *wins, uint32_t *flag, hipStream_t stream);
+size_t md_windows_work_bytes(uint32_t npieces, uint32_t group);
+int md_launch_windows_parallel(uint32_t npieces, uint32_t group, const uint8_t *dst, uint64_t u0, const uint8_t *scratch,
+                               const uint64_t *offa, const uint64_t *offb, const uint64_t *u, const uint64_t *pos, uint8_t *wins,
+                               uint32_t *work, uint32_t *flag, hipStream_t stream);
+int md_launch_resolve(uint32_t npieces, uint8_t *dst, const uint8_t *scratch, const uint64_t *offa, const uint64_t *offb,
+                      const uint64_t *u, const uint64_t *pos, const uint8_t *wins, uint32_t *flag, hipStream_t stream);
+int md_launch_adler_segments(const uint8_t *data, uint64_t n, uint32_t seg, uint32_t *sums, hipStream_t stream);
+
+// ---- deflate_front.hip: the front workspace (struct Front) and the kernels that fill it ----
+size_t md_front_small_bytes(uint32_t n);
+size_t md_front_big_bytes(uint64_t positions);
+void md_front_carve(void *small_ws, void *big_ws, uint32_t n, uint64_t positions, md::defl::Front *f);
+int md_launch_deflate_plan(uint32_t n, const uint64_t *in_len, int driver, int matcher, int level, uint64_t cap_positions,
+                           uint32_t cap_chunks, const md::defl::Front *f, hipStream_t stream);
+int md_launch_deflate_match(uint32_t n, uint32_t nchunks_max, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len,
+                            uint32_t max_chain, uint32_t nice, const md::defl::Front *f, uint32_t match_skip, hipStream_t stream);
+int md_launch_deflate_front(uint32_t n, uint32_t nchunks_max, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len,
+                            int matcher, uint32_t max_chain, uint32_t nice, const md::defl::Front *f, const uint32_t *order,
+                            uint32_t match_skip, hipStream_t stream);
+int md_launch_link_ns(uint32_t n, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len, const md::defl::Front *f,
+                      hipStream_t stream);
+
+// ---- deflate_chunked.hip ----
+int md_launch_link_chunked(const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len, uint32_t p_end, uint32_t seg,
+                           uint32_t cus, const md::defl::Front *f, hipStream_t stream);
+
+// ---- deflate_kernel.hip ----
+size_t md_deflate_queue_bytes(uint32_t n, int qcap);
+void md_deflate_level_params(int driver, int matcher, int level, uint32_t *max_chain, uint32_t *nice);
+// pieces = null for whole streams
+int md_launch_deflate(int format, int level, int qcap, int driver, int dynamic, uint32_t n, const uint8_t *in, const uint64_t *in_off,
+                      const uint64_t *in_len, uint8_t *out, const uint64_t *out_off, const uint64_t *out_cap, uint64_t *out_len,
+                      int32_t *status, uint32_t *checksum, const md::defl::Front *fr, void *queue_ws, uint64_t *dbg,
+                      const uint8_t *gz_hdr, uint32_t gz_hdr_len, const uint32_t *gz_crc, int matcher, uint32_t *hist,
+                      const uint32_t *order, const md::defl::Piece *pieces, hipStream_t stream);
+
+// ---- deflate_ns.hip ----
+int md_launch_def_ns(int format, int level, uint32_t n, uint32_t nchunks_max, const uint8_t *in, const uint64_t *in_off,
+                     const uint64_t *in_len, uint8_t *out, const uint64_t *out_off, const uint64_t *out_cap, uint64_t *out_len,
+                     int32_t *status, uint32_t *checksum, const md::defl::Front *f, hipStream_t stream);
+
+// ---- gz_kernels.hip ----
+int md_launch_gz_header(uint32_t n, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len, uint64_t *body_off,
+                        uint64_t *body_len, int32_t *hstatus, hipStream_t stream);
+int md_launch_crc32(uint32_t n, const uint8_t *data, const uint64_t *off, const uint64_t *len, uint32_t *crc_out, hipStream_t stream);
+int md_launch_gz_finish(uint32_t n, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len, const uint64_t *body_off,
+                        const int32_t *hstatus, const uint8_t *out, const uint64_t *out_off, uint64_t *out_len, uint64_t *consumed,
+                        int32_t *status, uint32_t *checksum, hipStream_t stream);
+int md_launch_piece_gather(uint32_t n, const uint8_t *old_blob, const uint8_t *fresh, uint8_t *new_blob, const uint64_t *d,
+                           hipStream_t stream);
+
+// ---- lzo_kernels.hip ----
+uint32_t md_lzo_slots(int compress, uint32_t cus);
+int md_launch_lzo_uncompress(uint32_t n, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len, uint8_t *out,
+                             const uint64_t *out_off, const uint64_t *out_cap, uint64_t *out_len, int32_t *status, uint32_t *counter,
+                             uint32_t slots, hipStream_t stream);
+int md_launch_lzo_compress(uint32_t n, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len, uint8_t *out,
+                           const uint64_t *out_off, const uint64_t *out_cap, uint64_t *out_len, int32_t *status, uint16_t *ws_dict,
+                           uint32_t *counter, uint32_t slots, hipStream_t stream);
+
+}  // extern "C"

@@ -23,6 +23,7 @@
 #include <stdint.h>
 
 #include "inflate_util.hpp"
+#include "internal.hpp"
 #include "mdeflate.h"
 
 namespace md {

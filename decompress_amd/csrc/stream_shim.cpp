@@ -23,7 +23,9 @@
 #include <string>
 #include <vector>
 
+#include "host_util.hpp"
 #include "inflate_batch.hpp"
+#include "internal.hpp"
 #include "mdeflate.h"
 
 // The frame around the DEFLATE body of one stream that is decoded in pieces as it arrives, and the steps on it that
@@ -217,32 +219,6 @@ static void inf_run(md_inf_stream *s) {
   }
 }
 
-// ---- CRC-32 over pieces: crc(A || B) = crc(A) * x^(8|B|) mod P xor crc(B) in GF(2)[x] / P, reflected (bit 31 = x^0);
-// the pieces' CRCs come from the device (crc32_kernel), the few header bytes are done here
-static uint32_t crc_bytes(uint32_t c, const uint8_t *p, size_t n) {  // (running value, not complemented)
-  for (size_t i = 0; i < n; i++) {
-    c ^= p[i];
-    for (int k = 0; k < 8; k++) c = (c >> 1) ^ (0xedb88320u & (0u - (c & 1)));
-  }
-  return c;
-}
-static uint32_t gf_mul(uint32_t a, uint32_t b) {
-  uint32_t p = 0;
-  for (int k = 0; k < 32; k++) {
-    p ^= b & (0u - ((a >> 31) & 1));
-    a <<= 1;
-    b = (b >> 1) ^ (0xedb88320u & (0u - (b & 1)));
-  }
-  return p;
-}
-static uint32_t crc_concat(uint32_t crc_a, uint32_t crc_b, uint64_t len_b) {
-  uint32_t sq = 0x00800000u, r = 0x80000000u;  // x^8, x^0
-  for (uint64_t n = len_b; n; n >>= 1) {
-    if (n & 1) r = gf_mul(r, sq);
-    sq = gf_mul(sq, sq);
-  }
-  return gf_mul(crc_a, r) ^ crc_b;
-}
 // Gz.Inf's header walk with its checks (lib/gz.ml:463-491, as gz_header_kernel does it for the batch path): the offset
 // of the body, or 0 with *st = MD_OK when the header is not all there yet, or 0 with the status of a bad header
 static size_t gz_header_check(const std::vector<uint8_t> &in, int *st) {
@@ -257,11 +233,11 @@ static size_t gz_header_check(const std::vector<uint8_t> &in, int *st) {
   if (body == 0) return 0;
   const uint32_t flg = in[3];
   if (flg & 2) {  // FHCRC: the upper half of the CRC-32 of the fixed bytes + name + comment (FEXTRA excluded), big-endian
-    uint32_t c = crc_bytes(0xffffffffu, in.data(), 10);
+    uint32_t c = md::crc32_update(0, in.data(), 10);
     size_t p = 10;
     if (flg & 4) p += 2 + (((size_t)in[10] << 8) | in[11]);
-    c = crc_bytes(c, in.data() + p, body - 2 - p);
-    const uint32_t want = ((c ^ 0xffffffffu) & 0xffff0000u) >> 16, have = ((uint32_t)in[body - 2] << 8) | in[body - 1];
+    c = md::crc32_update(c, in.data() + p, body - 2 - p);
+    const uint32_t want = (c & 0xffff0000u) >> 16, have = ((uint32_t)in[body - 2] << 8) | in[body - 1];
     if (want != have) {
       *st = MD_INVALID_GZIP_HEADER_CHECKSUM;
       return 0;
@@ -307,7 +283,7 @@ static bool frame_head(InfFrame *f) {
 }
 // output that a piece hands out: the GZip CRC-32 goes on over it
 static void frame_took(InfFrame *f, uint32_t crc_piece, uint64_t len) {
-  f->crc = f->total_out ? crc_concat(f->crc, crc_piece, len) : crc_piece;
+  f->crc = f->total_out ? md::crc32_concat(f->crc, crc_piece, len) : crc_piece;
   f->total_out += len;
 }
 // the piece ended inside a block before the end of the input: what lies before that block went out, the input from the
@@ -453,78 +429,9 @@ int md_inf_decode(md_inf_stream *s) {
 // ---- the encoder side: Zl.Def.encoder / Gz.Def.encoder / De.Higher's loop with `Manual src and dst ----
 }  // extern "C"
 
-// The encoder takes its stream in pieces (capi.cpp, md_i_piece_*): the device goes on from the state the piece before
-// left, so neither side keeps more of the stream than the 64 KiB the matcher can reach back plus the piece in flight.
-struct md_piece;
-extern "C" {
-md_piece *md_i_piece_open(md_ctx *ctx, int queue_len);
-void md_i_piece_close(md_ctx *ctx, md_piece *p);
-int md_i_piece_run(md_ctx *ctx, md_piece *p, int format, const md_deflate_params *params, const uint8_t *text, size_t text_len,
-                   size_t seen, uint64_t w0, uint64_t rebase, int first, int last, uint32_t sum, uint32_t isize, size_t out_cap,
-                   size_t *out_len, int *status);
-int md_i_test_flags(const md_ctx *ctx);
-int md_i_piece_out(md_ctx *ctx, const md_piece *p, size_t off, uint8_t *host, size_t len);
-size_t md_i_piece_bytes(const md_ctx *ctx);
-struct md_pieces_io {
-  const uint64_t *text_off, *text_len, *abs_len, *out_off, *out_cap, *w0, *rebase;
-  const uint32_t *flags, *sum, *isize;
-  uint64_t *out_len;
-  int32_t *status;
-};
-int md_i_pieces_run(md_ctx *ctx, int format, const md_deflate_params *params, size_t n, const uint8_t *d_text, uint8_t *d_out,
-                    void *d_state, void *d_queue, void **d_desc, size_t *d_desc_bytes, const md_pieces_io *io, uint32_t match_skip);
-hipStream_t md_i_stream(md_ctx *ctx);
-int md_i_device(md_ctx *ctx);
-uint32_t md_piece_state_bytes();
-int md_launch_piece_gather(uint32_t n, const uint8_t *old_blob, const uint8_t *fresh, uint8_t *new_blob, const uint64_t *d, hipStream_t stream);
-}
 namespace {
 constexpr size_t kKeepBytes = 65536;             // text behind the end of a piece that the next launch sees again
 constexpr size_t kSrcMax = (size_t)1 << 30;      // most that one md_def_src hands over
-constexpr int kPieceAwait = 1000;                // MD_PIECE_AWAIT, deflate_common.hpp
-
-uint32_t adler32_update(uint32_t adler, const uint8_t *p, size_t n) {  // lib/de.ml:4217-4218 keeps it per fill; the sum is the same
-  uint32_t a = adler & 0xffff, b = adler >> 16;
-  while (n) {
-    size_t k = n < 5552 ? n : 5552;
-    n -= k;
-    while (k--) {
-      a += *p++;
-      b += a;
-    }
-    a %= 65521u;
-    b %= 65521u;
-  }
-  return (b << 16) | a;
-}
-struct Crc32Tables {
-  uint32_t t[8][256];
-  Crc32Tables() {
-    for (uint32_t i = 0; i < 256; i++) {
-      uint32_t c = i;
-      for (int k = 0; k < 8; k++) c = (c >> 1) ^ (0xedb88320u & (0u - (c & 1)));
-      t[0][i] = c;
-    }
-    for (uint32_t i = 0; i < 256; i++)
-      for (int j = 1; j < 8; j++) t[j][i] = (t[j - 1][i] >> 8) ^ t[0][t[j - 1][i] & 0xff];
-  }
-};
-uint32_t crc32_update(uint32_t crc, const uint8_t *p, size_t n) {  // eight bytes a step
-  static const Crc32Tables T;
-  uint32_t c = ~crc;
-  while (n >= 8) {
-    uint32_t lo, hi;
-    memcpy(&lo, p, 4);
-    memcpy(&hi, p + 4, 4);
-    lo ^= c;
-    c = T.t[7][lo & 0xff] ^ T.t[6][(lo >> 8) & 0xff] ^ T.t[5][(lo >> 16) & 0xff] ^ T.t[4][lo >> 24] ^ T.t[3][hi & 0xff] ^
-        T.t[2][(hi >> 8) & 0xff] ^ T.t[1][(hi >> 16) & 0xff] ^ T.t[0][hi >> 24];
-    p += 8;
-    n -= 8;
-  }
-  while (n--) c = T.t[0][(c ^ *p++) & 0xff] ^ (c >> 8);
-  return ~c;
-}
 }  // namespace
 
 struct md_def_stream {
@@ -546,8 +453,6 @@ struct md_def_stream {
 };
 
 extern "C" {
-
-extern "C" int md_validate_deflate_params(md_ctx *ctx, int format, const md_deflate_params *params);
 
 md_def_stream *md_def_encoder(md_ctx *ctx, int format, const md_deflate_params *params, uint8_t *o, size_t o_len) {
   if (!ctx || !params || !o || o_len == 0) return nullptr;
@@ -600,7 +505,7 @@ int md_def_src(md_def_stream *s, const uint8_t *buf, size_t off, size_t len) {
   // one launch can take (mdeflate.h: call md_def_encode between sources; it launches what has arrived)
   if ((s->w0 + s->text.size()) - s->launched + len > kSrcMax) return MD_E_INVALID_ARGUMENT;
   s->text.insert(s->text.end(), buf + off, buf + off + len);
-  s->checksum = s->format == MD_FORMAT_GZIP ? crc32_update(s->checksum, buf + off, len) : adler32_update(s->checksum, buf + off, len);
+  s->checksum = s->format == MD_FORMAT_GZIP ? md::crc32_update(s->checksum, buf + off, len) : md::adler32_update(s->checksum, buf + off, len);
   return MD_OK;
 }
 void md_def_dst(md_def_stream *s, uint8_t *o, size_t o_len) {  // Zl.Def.dst: a fresh output buffer
@@ -636,7 +541,7 @@ static void def_launch(md_def_stream *s) {
   s->first = false;
   s->served = 0;
   s->launched = end;
-  if (rc != MD_OK || (st != MD_OK && st != kPieceAwait)) {
+  if (rc != MD_OK || (st != MD_OK && st != MD_PIECE_AWAIT)) {
     s->status = rc != MD_OK ? rc : st;
     s->out_len = 0;
     s->done = true;
@@ -715,16 +620,6 @@ struct md_def_batch {
   size_t stage_cap = 0;
 };
 namespace {
-struct DevGuard {
-  int prev = -1;
-  explicit DevGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) hipSetDevice(dev);
-  }
-  ~DevGuard() {
-    if (prev >= 0) hipSetDevice(prev);
-  }
-};
 bool regrow(void **p, size_t *cap, size_t need) {
   if (need <= *cap) return true;
   if (*p) hipFree(*p);
@@ -740,7 +635,7 @@ bool regrow(void **p, size_t *cap, size_t need) {
 md_def_batch *md_def_batch_open(md_ctx *ctx, int format, const md_deflate_params *params, size_t n) {
   if (!ctx || !params || n == 0 || n > 0x7fffffffu) return nullptr;
   if (md_validate_deflate_params(ctx, format, params) != MD_OK) return nullptr;
-  DevGuard guard(md_i_device(ctx));
+  md::DeviceGuard guard(md_i_device(ctx));
   md_def_batch *b = new md_def_batch();
   b->ctx = ctx;
   b->format = format;
@@ -760,7 +655,7 @@ md_def_batch *md_def_batch_open(md_ctx *ctx, int format, const md_deflate_params
   b->n = n;
   b->e.resize(n);
   for (auto &x : b->e) x.checksum = format == MD_FORMAT_GZIP ? 0u : 1u;
-  if (hipMalloc(&b->d_state, n * (size_t)md_piece_state_bytes()) != hipSuccess ||
+  if (hipMalloc(&b->d_state, n * (size_t)md::defl::kPieceState) != hipSuccess ||
       hipMalloc(&b->d_queue, n * (size_t)params->queue_len * 4) != hipSuccess) {
     hipFree(b->d_state);
     hipFree(b->d_queue);
@@ -771,7 +666,7 @@ md_def_batch *md_def_batch_open(md_ctx *ctx, int format, const md_deflate_params
 }
 void md_def_batch_close(md_def_batch *b) {
   if (!b) return;
-  DevGuard guard(md_i_device(b->ctx));
+  md::DeviceGuard guard(md_i_device(b->ctx));
   hipStreamSynchronize(md_i_stream(b->ctx));
   void *bufs[] = {b->d_text[0], b->d_text[1], b->d_fresh, b->d_out, b->d_state, b->d_queue, b->d_desc, b->d_gdesc};
   for (void *p : bufs)
@@ -789,7 +684,7 @@ int md_def_batch_src(md_def_batch *b, size_t i, const uint8_t *buf, size_t len) 
   }
   if (x.fresh.size() + len > kSrcMax) return MD_E_INVALID_ARGUMENT;  // (what one launch takes: call md_def_batch_encode in between)
   x.fresh.insert(x.fresh.end(), buf, buf + len);
-  x.checksum = b->format == MD_FORMAT_GZIP ? crc32_update(x.checksum, buf, len) : adler32_update(x.checksum, buf, len);
+  x.checksum = b->format == MD_FORMAT_GZIP ? md::crc32_update(x.checksum, buf, len) : md::adler32_update(x.checksum, buf, len);
   return MD_OK;
 }
 size_t md_def_batch_pending(const md_def_batch *b, size_t i) {
@@ -819,7 +714,7 @@ size_t md_def_batch_out(md_def_batch *b, size_t i, uint8_t *dst, size_t cap) {
     got = k;
   }
   if (got < cap && x.served < x.out_len) {
-    DevGuard guard(md_i_device(b->ctx));
+    md::DeviceGuard guard(md_i_device(b->ctx));
     const size_t left = (size_t)(x.out_len - x.served), k = left < cap - got ? left : cap - got;
     if (hipMemcpy(dst + got, (const uint8_t *)b->d_out + x.out_off + x.served, k, hipMemcpyDeviceToHost) != hipSuccess) return got;
     x.served += k;
@@ -831,7 +726,7 @@ size_t md_def_batch_out(md_def_batch *b, size_t i, uint8_t *dst, size_t cap) {
 // input has not been signalled since) sit the launch out.  MD_OK, or the call-level error.
 int md_def_batch_encode(md_def_batch *b) {
   if (!b) return MD_E_INVALID_ARGUMENT;
-  DevGuard guard(md_i_device(b->ctx));
+  md::DeviceGuard guard(md_i_device(b->ctx));
   hipStream_t st = md_i_stream(b->ctx);
   const size_t n = b->n, ql = (size_t)b->params.queue_len;
   // output that was not fetched yet moves to the host: the launch writes a new output blob
@@ -926,7 +821,7 @@ int md_def_batch_encode(md_def_batch *b) {
     x.fresh.clear();
     x.first = false;
     if (x.eoi) x.launched_eoi = true;
-    if (status[i] != MD_OK && status[i] != kPieceAwait) {
+    if (status[i] != MD_OK && status[i] != MD_PIECE_AWAIT) {
       x.status = status[i];
       x.done = true;
       continue;
@@ -987,8 +882,6 @@ struct md_inf_batch {
   size_t stage_cap = 0, hpack_cap = 0;
   uint64_t launches = 0;      // inflate launches so far (md_i_inf_batch_launches)
 };
-extern "C" int md_launch_inf_handout(uint32_t m, md::ib::HandIn in, const uint8_t *out, md::ib::HandRow *res, uint8_t *pack,
-                                     int with_crc, hipStream_t stream);
 namespace {
 void inf_slot_clear(md_inf_batch::Dec *x, int format) {
   *x = md_inf_batch::Dec();
@@ -1210,7 +1103,7 @@ md_inf_batch *md_inf_batch_open(md_ctx *ctx, int format, size_t n) {
 }
 void md_inf_batch_close(md_inf_batch *b) {
   if (!b) return;
-  DevGuard guard(md_i_device(b->ctx));
+  md::DeviceGuard guard(md_i_device(b->ctx));
   hipStreamSynchronize(md_i_stream(b->ctx));
   void *bufs[] = {b->d_in[0], b->d_in[1], b->d_out[0], b->d_out[1], b->d_fresh, b->d_desc, b->d_pack};
   for (void *p : bufs)
@@ -1257,7 +1150,7 @@ int md_inf_batch_decode(md_inf_batch *b) {
   }
   for (auto &x : b->d) x.round_in = 0;
   if (rows.empty()) return MD_OK;
-  DevGuard guard(md_i_device(b->ctx));
+  md::DeviceGuard guard(md_i_device(b->ctx));
   const int old = b->cur, nxt = old ^ 1;
   uint64_t opos = 0;
   std::vector<size_t> grown;
