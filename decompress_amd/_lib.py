@@ -130,7 +130,16 @@ SYMBOLS = [
     ("md_lzo_compress_batch_device", ctypes.c_int, [c_vp, c_sz] + [c_vp] * 8),
     ("md_lzo_uncompress", ctypes.c_int, [c_vp, c_vp, c_sz, c_vp, c_sz, ctypes.POINTER(c_sz)]),
     ("md_lzo_compress", ctypes.c_int, [c_vp, c_vp, c_sz, c_vp, c_sz, ctypes.POINTER(c_sz)]),
+    ("md_gz_members_scan", ctypes.c_int, [c_vp, c_vp, c_sz, c_vp, c_vp, c_vp, c_sz]),
+    ("md_gz_members_uncompress", ctypes.c_int, [c_vp, c_vp, c_sz, c_vp, c_sz, c_vp]),
+    ("md_bgzf_compress_bound", c_sz, [c_sz, c_sz]),
+    ("md_bgzf_compress", ctypes.c_int, [c_vp, ctypes.c_int, c_sz, c_vp, c_sz, c_vp, c_sz, c_szp]),
 ]
+
+
+class GzMembersInfo(ctypes.Structure):
+    """md_gz_members_info of include/mdeflate.h"""
+    _fields_ = [("members", c_sz), ("consumed", c_sz), ("written", c_sz), ("indexed", ctypes.c_int)]
 
 
 class GzMeta(ctypes.Structure):

@@ -72,6 +72,11 @@ struct Cont {
 };
 
 }  // namespace wv
+
+namespace gzm {
+// input bytes one workgroup of the member scan looks at: it leaves one count per span (gz_members.hip)
+constexpr uint32_t kMarkSpanBytes = 16384;
+}  // namespace gzm
 }  // namespace md
 
 // The encoder takes its stream in pieces (capi.cpp, md_i_piece_*; stream_shim.cpp): the device goes on from the state the
@@ -168,6 +173,34 @@ int md_launch_gz_finish(uint32_t n, const uint8_t *in, const uint64_t *in_off, c
                         int32_t *status, uint32_t *checksum, hipStream_t stream);
 int md_launch_piece_gather(uint32_t n, const uint8_t *old_blob, const uint8_t *fresh, uint8_t *new_blob, const uint64_t *d,
                            hipStream_t stream);
+
+// ---- gz_members.hip: a GZip file of many members (md_gz_members_*, md_bgzf_compress) ----
+// the scan for members that carry a BC size field: bits = 1 bit per input byte, cnt = one word per kMarkSpanBytes
+int md_launch_gzm_mark(const uint8_t *src, uint64_t len, uint32_t *bits, uint32_t *cnt, uint64_t *last_nz, hipStream_t stream);
+// out[i] = in[0] + ... + in[i - 1], out[n] = the total
+int md_launch_gzm_scan32(const uint32_t *in, uint64_t n, uint64_t *out, hipStream_t stream);
+int md_launch_gzm_scan64(const uint64_t *in, uint64_t n, uint64_t *out, hipStream_t stream);
+int md_launch_gzm_compact(const uint8_t *src, uint64_t len, const uint32_t *bits, const uint64_t *base, uint64_t *cpos, uint64_t *cnext,
+                          hipStream_t stream);
+// C candidates; jump_a / jump_b / reach: C + 2 words each.  reach[i] = candidate i is a member of the file, reach[C] = the
+// chain from offset 0 ends at the end of the buffer (or at NUL bytes that reach it)
+int md_launch_gzm_chain(uint64_t C, const uint64_t *cpos, const uint64_t *cnext, const uint64_t *last_nz, uint32_t *jump_a,
+                        uint32_t *jump_b, uint32_t *reach, hipStream_t stream);
+int md_launch_gzm_select(uint64_t C, const uint32_t *reach, const uint64_t *ridx, const uint64_t *cpos, const uint64_t *cnext,
+                         uint64_t *mpos, uint64_t *mlen, hipStream_t stream);
+// body_off / body_len / hstatus as md_launch_gz_header leaves them, for RFC headers; isize from the members' trailers
+int md_launch_gzm_headers(uint64_t M, const uint8_t *src, const uint64_t *mpos, const uint64_t *mlen, uint64_t *body_off,
+                          uint64_t *body_len, uint64_t *isize, int32_t *hstatus, hipStream_t stream);
+// *first (preset to M) = the first member whose status is not MD_OK
+int md_launch_gzm_verdict(uint64_t M, const uint64_t *mlen, const uint64_t *consumed, int32_t *status, uint64_t *first, hipStream_t stream);
+int md_launch_bgzf_plan(uint64_t nb, uint64_t len, uint64_t block, uint64_t stride, uint64_t *in_off, uint64_t *in_len, uint64_t *out_off,
+                        uint64_t *out_cap, hipStream_t stream);
+int md_launch_bgzf_sizes(uint64_t nb, const uint64_t *in_len, const uint64_t *out_len, const int32_t *status, uint64_t *msize, int32_t *err,
+                         hipStream_t stream);
+// moff: nb + 1 member offsets in dst (the scan of msize); the EOF marker goes to moff[nb]
+int md_launch_bgzf_pack(uint64_t nb, const uint8_t *src, const uint64_t *in_off, const uint64_t *in_len, const uint8_t *slots,
+                        const uint64_t *slot_off, const uint64_t *out_len, const int32_t *status, const uint64_t *moff, const uint32_t *crc,
+                        uint8_t *dst, hipStream_t stream);
 
 // ---- lzo_kernels.hip ----
 uint32_t md_lzo_slots(int compress, uint32_t cus);

@@ -4,7 +4,8 @@
 import ctypes
 
 from . import engine as _engine
-from ._lib import GzMeta
+from ._lib import GzMembersInfo, GzMeta
+from ._lib import load as _load
 
 # Gz.os, lib/gz.ml:158-246 (RFC1952 numbering)
 OS = {"FAT": 0, "Amiga": 1, "VMS": 2, "Unix": 3, "VM": 4, "Atari": 5, "HPFS": 6, "Macintosh": 7, "Z": 8, "CPM": 9,
@@ -79,3 +80,80 @@ class Def:
         hdr.update(header)
         hdr["os"] = OS[hdr["os"]] if isinstance(hdr["os"], str) else int(hdr["os"])
         return _engine.default_engine(device).deflate_many(bufs, _engine.FORMAT_GZIP, level=level, queue=queue, header=hdr)
+
+
+def _raw(src):
+    """bytes-like -> (object ctypes passes by address without a copy of bytes, length)"""
+    src = src if isinstance(src, bytes) else bytes(src)
+    return src, len(src)
+
+
+class Members:
+    """A GZip FILE of many members (RFC 1952 2.2: `cat a.gz b.gz`, bgzip / BGZF), read as libz reads it - not `Gz.Inf`'s
+    reading, which `Higher.uncompress` keeps.  A file whose members all carry the BC size field is indexed: its members are
+    found on the device and decoded by one inflate launch; any other file goes member by member."""
+
+    @staticmethod
+    def scan(src, device=0):
+        """-> None when the file is not indexed, else a dict: members, size (uncompressed), c_off / u_off (per member:
+        its offset in src, the offset of its output) - the .gzi index, without decoding."""
+        eng = _engine.default_engine(device)
+        src, n = _raw(src)
+        info = GzMembersInfo()
+        eng._check(eng.lib.md_gz_members_scan(eng.ctx, src, n, ctypes.byref(info), None, None, 0))
+        if not info.indexed:
+            return None
+        c_off, u_off = (ctypes.c_uint64 * info.members)(), (ctypes.c_uint64 * info.members)()
+        eng._check(eng.lib.md_gz_members_scan(eng.ctx, src, n, ctypes.byref(info), c_off, u_off, info.members))
+        return {"members": info.members, "size": info.written, "c_off": list(c_off), "u_off": list(u_off)}
+
+    @staticmethod
+    def uncompress(src, dst_len=None, device=0):
+        """-> ("Ok", info, bytes) | ("Error", msg, info, bytes of the members in front of the failing one); info: members,
+        consumed, written, indexed.  dst_len None: the size an indexed file states, else room that grows until it fits."""
+        eng = _engine.default_engine(device)
+        src, n = _raw(src)
+        info = GzMembersInfo()
+        grow = dst_len is None
+        if grow:
+            idx = Members.scan(src, device)
+            dst_len = idx["size"] if idx else max(4 * n, 1 << 16)
+        while True:
+            dst = ctypes.create_string_buffer(max(dst_len, 1))
+            st = eng.lib.md_gz_members_uncompress(eng.ctx, src, n, dst, dst_len, ctypes.byref(info))
+            if st < 0:
+                eng._check(st)
+            if grow and st == _engine.STATUS_CODES["Unexpected_end_of_output"]:
+                dst_len = max(2 * dst_len, info.written, 1 << 16)
+                continue
+            d = {"members": info.members, "consumed": info.consumed, "written": info.written, "indexed": info.indexed}
+            if st != 0:
+                # (an indexed file without room: `written` is the room it needs, not what dst holds)
+                keep = 0 if st == _engine.STATUS_CODES["Unexpected_end_of_output"] and info.indexed else info.written
+                return "Error", _engine.STATUS_NAMES[st], d, dst.raw[:keep]
+            return "Ok", d, dst.raw[:info.written]
+
+
+class Bgzf:
+    @staticmethod
+    def compress_bound(n, block=0xff00):
+        """room that always suffices for `compress` of n bytes (host arithmetic, no device needed)"""
+        return _load().md_bgzf_compress_bound(n, block)
+
+    @staticmethod
+    def compress(src, level=4, block=0xff00, dst_len=None, device=0):
+        """Blocked gzip as bgzip writes it: members of at most `block` input bytes, each with its BC size field, then the
+        empty member that marks the end.  All blocks go through one deflate launch; the bytes depend on (src, level,
+        block) alone.  Raises `Error` with the status' name (dst_len too small: "Unexpected_end_of_output")."""
+        eng = _engine.default_engine(device)
+        src, n = _raw(src)
+        if dst_len is None:
+            dst_len = eng.lib.md_bgzf_compress_bound(n, block)
+        dst = ctypes.create_string_buffer(max(dst_len, 1))
+        wrote = ctypes.c_size_t()
+        st = eng.lib.md_bgzf_compress(eng.ctx, level, block, src, n, dst, dst_len, ctypes.byref(wrote))
+        if st < 0:
+            eng._check(st)
+        if st != 0:
+            raise _engine.Error(_engine.STATUS_NAMES[st])
+        return dst.raw[:wrote.value]

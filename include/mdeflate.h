@@ -540,6 +540,51 @@ int md_lzo_uncompress(md_ctx *ctx, const uint8_t *src, size_t src_len, uint8_t *
 int md_lzo_compress(md_ctx *ctx, const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap,
                     size_t *written);
 
+/* ---- A GZip FILE of many members (RFC 1952 2.2): `cat a.gz b.gz`, bgzip / BGZF (.bam, .vcf.gz), pigz -i -----------------
+ * These entry points read and write RFC 1952 as libz does - NOT Gz.Inf's reading, which MD_FORMAT_GZIP keeps (FEXTRA's
+ * length big-endian, its own header CRC, one member and stop): XLEN is little-endian, CM must be 8, the reserved flag
+ * bits must be clear, FHCRC is the low half of the CRC-32 of the whole header, members follow each other until the
+ * input ends, and NUL bytes behind a member are padding.  Host pointers: copy in, kernels, copy out, synchronise.
+ *
+ * A file is INDEXED when every member carries its own length - the extra subfield 'B' 'C' (SLEN 2, BSIZE = length - 1)
+ * that bgzip writes - and the chain of those lengths leads from offset 0 to the end of the file (or to NUL padding that
+ * reaches it).  The device finds the members of such a file without decoding (a scan of every byte position, pointer
+ * jumping over the candidates), parses their headers and decodes ALL of them in one inflate launch, each into a window of
+ * its own ISIZE bytes.  Workspace: 1 bit per input byte, 4 bytes per 16 KiB and O(members), grow-only.
+ * Any other file takes the GENERAL path: a host loop, member by member - header on the host, the body through the
+ * raw-DEFLATE path of md_de_inf_ns_inflate (a long member is decoded by the whole chip), CRC-32 and ISIZE checked on the
+ * host - so one round of launches PER MEMBER: right for any file, fast only for files of few, long members.  A member
+ * is bound by MD_MAX_INFLATE_IN / MD_MAX_STREAM; the file may be longer. */
+typedef struct md_gz_members_info {
+  size_t members;  /* members decoded (or found, for _scan) */
+  size_t consumed; /* bytes of src taken: src_len on success; on failure the offset of the failing member */
+  size_t written;  /* bytes in dst from the members before that; with MD_UNEXPECTED_END_OF_OUTPUT on an indexed file:
+                    * the room needed (the sum of the members' ISIZE fields; such a call goes member by member) */
+  int indexed;     /* 1: every member carried a BC size field - found on the device, decoded by one inflate launch */
+} md_gz_members_info;
+/* The .gzi index of an indexed file without decoding it: info->members, info->written = the uncompressed size (the sum of
+ * the members' ISIZE fields), and the first `cap` pairs (offset of member i in src, offset of its output).  c_off / u_off
+ * may be NULL when cap is 0.  A file that is not indexed: MD_OK, indexed = 0, nothing else filled. */
+int md_gz_members_scan(md_ctx *ctx, const uint8_t *src, size_t src_len, md_gz_members_info *info, uint64_t *c_off,
+                       uint64_t *u_off, size_t cap);
+/* Every member of src, in order, into dst.  Returns MD_OK or the status of the first member that failed (info says where):
+ * MD_INVALID_GZIP_HEADER (magic, CM, reserved flag bits, bytes other than NUL behind a member),
+ * MD_INVALID_GZIP_HEADER_CHECKSUM, MD_INVALID_CHECKSUM, MD_INVALID_SIZE, MD_UNEXPECTED_END_OF_INPUT (truncated),
+ * MD_UNEXPECTED_END_OF_OUTPUT (dst_cap), or what the inflate kernel says about the body.  Empty input: MD_OK, 0 members. */
+int md_gz_members_uncompress(md_ctx *ctx, const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap,
+                             md_gz_members_info *info);
+/* Blocked gzip, as bgzip writes it: src cut into blocks of `block` bytes (1..0xff00; 0 = 0xff00), each a member
+ * 1f 8b 08 04 | MTIME 0 | XFL 0 | OS ff | XLEN 6 | 'B' 'C' 02 00 BSIZE | body | CRC-32 | ISIZE, then the 28-byte empty
+ * member that marks the end.  All blocks are compressed by ONE deflate launch; a member's body is byte for byte what
+ * MD_FORMAT_GZIP writes for that block at `level` (Gz.Def: Zl driver, dynamic blocks, queue 4096) - unless one stored block
+ * (01 LEN NLEN + the bytes) is shorter (input that does not compress: the reference's body for 0xff00 random bytes would make
+ * a member of 65 898 bytes, and none may pass 65 536), then it is that stored block.  The output depends on (src, level,
+ * block) alone and is an indexed file for md_gz_members_*.  md_bgzf_compress_bound: room that always suffices (host
+ * arithmetic: 31 bytes per block, the stored form, + 28); 0 for a block size out of range. */
+size_t md_bgzf_compress_bound(size_t src_len, size_t block);
+int md_bgzf_compress(md_ctx *ctx, int level, size_t block, const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap,
+                     size_t *written);
+
 #ifdef __cplusplus
 }
 #endif
