@@ -1,0 +1,346 @@
+// capi_inflate.cpp — the decoder's entry points: batches on the device and from host buffers, a stream in pieces, and
+// the one-stream calls that mirror the reference's.
+#include <string.h>
+
+#include <vector>
+
+#include "ctx.hpp"
+#include "host_pipeline.hpp"
+
+constexpr size_t kOrderFrom = 2049;  // 256 CUs x 8 resident wavefronts: smaller batches start all at once
+
+int md_inflate_batch_device(md_ctx *ctx, int format, size_t n, const uint8_t *d_in,
+                            const uint64_t *d_in_off, const uint64_t *d_in_len, uint8_t *d_out,
+                            const uint64_t *d_out_off, const uint64_t *d_out_cap,
+                            uint64_t *d_out_len, uint64_t *d_consumed, int32_t *d_status,
+                            uint32_t *d_checksum) {
+  if (!ctx) return MD_E_INVALID_ARGUMENT;
+  if (format != MD_FORMAT_DEFLATE && format != MD_FORMAT_ZLIB && format != MD_FORMAT_GZIP)
+    return fail(ctx, MD_E_INVALID_ARGUMENT, "unknown format");
+  if (n == 0) return MD_OK;
+  if (n > 0x7fffffffull) return fail(ctx, MD_E_INVALID_ARGUMENT, "too many streams in one batch");
+  if (!d_in_off || !d_in_len || !d_out_off || !d_out_cap || !d_out_len || !d_consumed || !d_status)
+    return fail(ctx, MD_E_INVALID_ARGUMENT, "null descriptor array");
+  MD_ON_DEVICE(ctx);
+  if (format == MD_FORMAT_GZIP) {
+    // Gz.Inf = header, De.Inf on the body, checksum (lib/gz.ml:463-531, :344-356)
+    int rc = ctx->gz_tmp.reserve(ctx, n * 24, "hipMalloc(gzip scratch)");
+    if (rc != MD_OK) return rc;
+    uint64_t *body_off = (uint64_t *)ctx->gz_tmp.p, *body_len = body_off + n;
+    int32_t *hstatus = (int32_t *)(body_len + n);
+    int e = md_launch_gz_header((uint32_t)n, d_in, d_in_off, d_in_len, body_off, body_len, hstatus, ctx->stream);
+    if (e != 0) return fail(ctx, MD_E_HIP, "gz header kernel launch", (hipError_t)e);
+    rc = md_inflate_batch_device(ctx, MD_FORMAT_DEFLATE, n, d_in, body_off, body_len, d_out, d_out_off, d_out_cap,
+                                 d_out_len, d_consumed, d_status, nullptr);
+    if (rc != MD_OK) return rc;
+    e = md_launch_gz_finish((uint32_t)n, d_in, d_in_off, d_in_len, body_off, hstatus, d_out, d_out_off, d_out_len,
+                            d_consumed, d_status, d_checksum, ctx->stream);
+    if (e != 0) return fail(ctx, MD_E_HIP, "gz finish kernel launch", (hipError_t)e);
+    return MD_OK;
+  }
+  // a batch of more streams than are resident at once (8 per CU) is started longest stream first; the scratch for the
+  // order is kept and only ever grows (the one allocation a batch call can make, on its first large batch)
+  uint32_t *order = nullptr;
+  const int orc = launch_order(ctx, n, kOrderFrom, &order);
+  if (orc != MD_OK) return orc;
+  int rc = md_launch_inflate_wave(format, (uint32_t)n, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len,
+                                  d_consumed, d_status, d_checksum, ctx->dbg.as<uint64_t>(), order, ctx->inflate_waves, nullptr, ctx->stream);
+  if (rc != 0) return fail(ctx, MD_E_HIP, "inflate kernel launch", (hipError_t)rc);
+  return MD_OK;
+}
+
+int md_inflate_batch_host(md_ctx *ctx, int format, size_t n, const uint8_t *h_in, size_t in_bytes,
+                          const uint64_t *in_off, const uint64_t *in_len, uint8_t *h_out,
+                          size_t out_bytes, const uint64_t *out_off, const uint64_t *out_cap,
+                          uint64_t *out_len, uint64_t *consumed, int32_t *status,
+                          uint32_t *checksum) {
+  if (!ctx) return MD_E_INVALID_ARGUMENT;
+  if (n == 0) return MD_OK;
+  if (!in_off || !in_len || !out_off || !out_cap || !out_len || !consumed || !status)
+    return fail(ctx, MD_E_INVALID_ARGUMENT, "null descriptor array");
+  for (size_t i = 0; i < n; i++) {
+    if (in_off[i] > in_bytes || in_len[i] > in_bytes - in_off[i])
+      return fail(ctx, MD_E_INVALID_ARGUMENT, "input range out of bounds");  // invalid_bounds, lib/de.ml:146
+    if (in_len[i] > MD_MAX_INFLATE_IN) return fail(ctx, MD_E_INVALID_ARGUMENT, "stream longer than MD_MAX_INFLATE_IN");
+    if (out_off[i] > out_bytes || out_cap[i] > out_bytes - out_off[i])
+      return fail(ctx, MD_E_INVALID_ARGUMENT, "output range out of bounds");
+  }
+  MD_ON_DEVICE(ctx);
+  ctx->par_last_pieces = ctx->par_last_rounds = 0;
+  // A FEW LONG streams (a handful of big files): each of them in pieces, by the whole chip (inflate_parallel) - as streams
+  // of a batch they would get one pair of wavefronts each.  What that path does not take, and the short streams beside
+  // them, go through the batch as before.
+  if (ctx->par_min && n <= 64) {
+    std::vector<size_t> shorts, longs;
+    // (each long stream is a call of ~1 ms at least, one after the other, where the batch kernel takes all n at once at ~0.2
+    // GiB/s each: worth it from ~128 KiB of input per stream of the batch)
+    const uint64_t long_from = ctx->par_min > n * ((uint64_t)128 << 10) ? ctx->par_min : n * ((uint64_t)128 << 10);
+    for (size_t i = 0; i < n; i++) (in_len[i] >= long_from ? longs : shorts).push_back(i);
+    if (!longs.empty()) {
+      const size_t keep = ctx->par_min;
+      // a batch of picked streams through this same entry point, the long-stream path switched off
+      auto sub = [&](const std::vector<size_t> &pick) -> int {
+        const size_t m = pick.size();
+        std::vector<uint64_t> io(m), il(m), oo(m), oc(m), ol(m), cs(m);
+        std::vector<int32_t> st(m);
+        std::vector<uint32_t> ck(m);
+        for (size_t k = 0; k < m; k++) {
+          io[k] = in_off[pick[k]];
+          il[k] = in_len[pick[k]];
+          oo[k] = out_off[pick[k]];
+          oc[k] = out_cap[pick[k]];
+        }
+        ctx->par_min = 0;
+        const int rc = md_inflate_batch_host(ctx, format, m, h_in, in_bytes, io.data(), il.data(), h_out, out_bytes, oo.data(), oc.data(), ol.data(),
+                                             cs.data(), st.data(), checksum ? ck.data() : nullptr);
+        ctx->par_min = keep;
+        if (rc != MD_OK) return rc;
+        for (size_t k = 0; k < m; k++) {
+          out_len[pick[k]] = ol[k];
+          consumed[pick[k]] = cs[k];
+          status[pick[k]] = st[k];
+          if (checksum) checksum[pick[k]] = ck[k];
+        }
+        return MD_OK;
+      };
+      // the short ones first, as one batch (its copies take the span of the caller's blobs its streams lie in: what the long
+      // streams' places receive from that is overwritten below)
+      if (!shorts.empty()) {
+        const int rc = sub(shorts);
+        if (rc != MD_OK) return rc;
+      }
+      int pieces = 0, rounds = 0;
+      for (size_t i : longs) {
+        size_t used = 0, wrote = 0;
+        uint32_t sum = 0;
+        const int prc = inflate_parallel(ctx, format, h_in + in_off[i], (size_t)in_len[i], h_out + out_off[i], (size_t)out_cap[i], &used, &wrote,
+                                         checksum ? &sum : nullptr);
+        if (prc == MD_NOT_HANDLED) {  // (not a well-formed stream that fits: the batch path says what it is)
+          const int rc = sub(std::vector<size_t>{i});
+          if (rc != MD_OK) return rc;
+          continue;
+        }
+        if (prc != MD_OK) return prc;
+        out_len[i] = wrote;
+        consumed[i] = used;
+        status[i] = MD_OK;
+        if (checksum) checksum[i] = sum;
+        pieces += ctx->par_last_pieces;
+        rounds = ctx->par_last_rounds > rounds ? ctx->par_last_rounds : rounds;
+      }
+      ctx->par_last_pieces = pieces;
+      ctx->par_last_rounds = rounds;
+      return MD_OK;
+    }
+  }
+  const size_t desc_words = 6 * n;  // in_off in_len out_off out_cap out_len consumed
+  int grc_ = ctx->scratch[kHostIn].reserve(ctx, in_bytes + 64, "hipMalloc(host path input)");
+  if (grc_ == MD_OK) grc_ = ctx->scratch[kHostOut].reserve(ctx, out_bytes + 64, "hipMalloc(host path output)");
+  if (grc_ == MD_OK) grc_ = ctx->scratch[kHostDesc].reserve(ctx, desc_words * 8 + n * 8, "hipMalloc(host path descriptors)");
+  if (grc_ != MD_OK) return grc_;
+  uint8_t *din = (uint8_t *)ctx->scratch[kHostIn].p, *dout = (uint8_t *)ctx->scratch[kHostOut].p;
+  uint64_t *d64 = (uint64_t *)ctx->scratch[kHostDesc].p;
+  int32_t *dstatus = (int32_t *)(d64 + desc_words);
+  uint32_t *dsum = (uint32_t *)(dstatus + n);
+  hipStream_t st = ctx->stream;
+  HIP_TRY(ctx, hipMemcpyAsync(d64 + 0 * n, in_off, n * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d64 + 1 * n, in_len, n * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d64 + 2 * n, out_off, n * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d64 + 3 * n, out_cap, n * 8, hipMemcpyHostToDevice, st));
+  // a slice of 1 024 streams (4 per CU) runs at half the batch's rate per stream - still several times what the link to
+  // the host moves (57 GB/s each way measured), so the copies stay the longer leg and more slices hide more of the kernels
+  const std::vector<HostSlice> sl = host_slices(n, in_off, in_len, out_off, out_cap, 1024, (size_t)ctx->host_slices_max, in_bytes, out_bytes);
+  int rc = host_pipeline(ctx, sl, h_in, din, h_out, dout, [&](size_t i0, size_t cnt) {
+    return md_inflate_batch_device(ctx, format, cnt, din, d64 + i0, d64 + n + i0, dout, d64 + 2 * n + i0, d64 + 3 * n + i0,
+                                   d64 + 4 * n + i0, d64 + 5 * n + i0, dstatus + i0, dsum + i0);
+  });
+  if (rc != MD_OK) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(out_len, d64 + 4 * n, n * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipMemcpyAsync(consumed, d64 + 5 * n, n * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipMemcpyAsync(status, dstatus, n * 4, hipMemcpyDeviceToHost, st));
+  if (checksum) HIP_TRY(ctx, hipMemcpyAsync(checksum, dsum, n * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  return MD_OK;
+}
+
+// Pieces of n streams at once (mdeflate.h): the inflate kernel with its continuation arguments, descriptors in HBM.
+int md_inflate_continue_batch_device(md_ctx *ctx, size_t n, const uint8_t *d_in, const uint64_t *d_in_off,
+                                     const uint64_t *d_in_len, uint8_t *d_out, const uint64_t *d_out_off,
+                                     const uint64_t *d_out_cap, const uint32_t *d_start_bit, const uint32_t *d_hist_len,
+                                     const uint32_t *d_adler_in, uint64_t *d_out_len, uint64_t *d_consumed,
+                                     int32_t *d_status, uint32_t *d_checksum, uint64_t *d_resume_bits,
+                                     uint64_t *d_resume_out, uint32_t *d_resume_adler, uint32_t *d_resume_last) {
+  if (!ctx) return MD_E_INVALID_ARGUMENT;
+  if (n == 0) return MD_OK;
+  if (n > 0xffffffffull) return fail(ctx, MD_E_INVALID_ARGUMENT, "too many streams");
+  if (!d_in || !d_in_off || !d_in_len || !d_out || !d_out_off || !d_out_cap || !d_start_bit || !d_hist_len || !d_adler_in ||
+      !d_out_len || !d_consumed || !d_status || !d_resume_bits || !d_resume_out || !d_resume_adler || !d_resume_last)
+    return fail(ctx, MD_E_INVALID_ARGUMENT, "null device pointer");
+  MD_ON_DEVICE(ctx);
+  uint32_t *order = nullptr;
+  const int orc = launch_order(ctx, n, kOrderFrom, &order);
+  if (orc != MD_OK) return orc;
+  const md::wv::Cont cont{d_start_bit, d_hist_len, d_adler_in, d_resume_bits, d_resume_out, d_resume_adler, d_resume_last};
+  int rc = md_launch_inflate_wave(MD_FORMAT_DEFLATE, (uint32_t)n, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len,
+                                  d_consumed, d_status, d_checksum, ctx->dbg.as<uint64_t>(), order, ctx->inflate_waves, &cont, ctx->stream);
+  if (rc != 0) return fail(ctx, MD_E_HIP, "inflate kernel launch", (hipError_t)rc);
+  return MD_OK;
+}
+
+// One piece of a raw DEFLATE stream that is decoded as it arrives (mdeflate.h): the inflate kernel on one stream with
+// a starting bit, the window in front of the output buffer and the checksum state handed in, and the last block
+// boundary inside the piece handed back.
+int md_de_inf_continue_host(md_ctx *ctx, const uint8_t *src, size_t src_len, unsigned start_bit, uint8_t *dst, size_t hist_len,
+                            size_t dst_cap, uint32_t adler_in, unsigned flags, size_t *dst_len, int *status,
+                            md_inf_resume *resume) {
+  if (!ctx || (!src && src_len) || !dst || !dst_len || !status || !resume) return MD_E_INVALID_ARGUMENT;
+  if (start_bit > 7 || hist_len > 32768 || hist_len > dst_cap || dst_cap > MD_MAX_STREAM || src_len > MD_MAX_INFLATE_IN)
+    return fail(ctx, MD_E_INVALID_ARGUMENT, "md_de_inf_continue_host: start_bit <= 7, hist_len <= 32768 and <= dst_cap");
+  MD_ON_DEVICE(ctx);
+  ctx->par_last_pieces = ctx->par_last_rounds = 0;
+  if (ctx->par_min && src_len >= ctx->par_min) {  // a long piece: its complete blocks by the whole chip, the rest as before
+    const int prc = continue_parallel(ctx, src, src_len, start_bit, dst, hist_len, dst_cap, adler_in, flags, dst_len, status, resume);
+    if (prc != MD_NOT_HANDLED) return prc;
+    ctx->par_last_pieces = 0;
+  }
+  return continue_serial(ctx, src, src_len, start_bit, dst, hist_len, dst_cap, adler_in, flags, dst_len, status, resume);
+}
+int continue_serial(md_ctx *ctx, const uint8_t *src, size_t src_len, unsigned start_bit, uint8_t *dst, size_t hist_len,
+                    size_t dst_cap, uint32_t adler_in, unsigned flags, size_t *dst_len, int *status, md_inf_resume *resume) {
+  // the context's scratch, grow-only: a long stream comes in many pieces, and three hipMalloc / hipFree per piece
+  // cost more than a short piece's kernel
+  // descriptors: in_off in_len out_off out_cap out_len consumed resume_bits resume_out (u64); status, checksum,
+  // start_bit, hist_len, adler_in, resume_adler, resume_last (u32)
+  md::DevBuf &din = ctx->scratch[kContIn], &dout = ctx->scratch[kContOut], &ddesc = ctx->scratch[kContDesc];
+  int grc_ = din.reserve(ctx, src_len + 16, "hipMalloc(decoder piece input)");
+  if (grc_ == MD_OK) grc_ = dout.reserve(ctx, dst_cap + 16, "hipMalloc(decoder piece output)");
+  if (grc_ == MD_OK) grc_ = ddesc.reserve(ctx, 8 * 8 + 8 * 4 + 4 * 8 + 2 * 4, "hipMalloc(decoder piece descriptors)");
+  if (grc_ != MD_OK) return grc_;
+  uint64_t h64[8] = {0, (uint64_t)src_len, 0, (uint64_t)dst_cap, 0, 0, 0, 0};
+  uint32_t h32[7] = {0, 0, start_bit, (uint32_t)hist_len, adler_in, 0, 0};
+  uint64_t *d64 = (uint64_t *)ddesc.p;
+  uint32_t *d32 = (uint32_t *)(d64 + 8);
+  hipStream_t st = ctx->stream;
+  if (src_len) HIP_TRY(ctx, hipMemcpyAsync(din.p, src, src_len, hipMemcpyHostToDevice, st));
+  if (hist_len) HIP_TRY(ctx, hipMemcpyAsync(dout.p, dst, hist_len, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d64, h64, sizeof h64, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d32, h32, sizeof h32, hipMemcpyHostToDevice, st));
+  const md::wv::Cont cont{d32 + 2, d32 + 3, d32 + 4, d64 + 6, d64 + 7, d32 + 5, d32 + 6};
+  int rc = md_launch_inflate_wave(MD_FORMAT_DEFLATE, 1, (const uint8_t *)din.p, d64 + 0, d64 + 1, (uint8_t *)dout.p, d64 + 2,
+                                  d64 + 3, d64 + 4, d64 + 5, (int32_t *)d32, d32 + 1, nullptr, nullptr, ctx->inflate_waves,
+                                  &cont, st);
+  if (rc != 0) return fail(ctx, MD_E_HIP, "inflate kernel launch", (hipError_t)rc);
+  HIP_TRY(ctx, hipMemcpyAsync(h64, d64, sizeof h64, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipMemcpyAsync(h32, d32, sizeof h32, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  const size_t produced = (size_t)h64[4];
+  if (produced > hist_len) HIP_TRY(ctx, hipMemcpy(dst + hist_len, (const uint8_t *)dout.p + hist_len, produced - hist_len, hipMemcpyDeviceToHost));
+  *dst_len = produced;
+  *status = (int32_t)h32[0];
+  resume->bits = h64[6];
+  resume->out = h64[7];
+  resume->adler = h32[5];
+  resume->last = h32[6];
+  resume->consumed = h64[5];
+  resume->checksum = h32[1];
+  resume->crc_out = resume->crc_end = 0;
+  if (flags & MD_CONT_CRC32) {  // CRC-32 of the new output up to the block boundary, and up to where decoding got
+    uint64_t *c64 = (uint64_t *)(d32 + 8);
+    uint32_t *c32 = (uint32_t *)(c64 + 4);
+    const uint64_t to_out = resume->out > hist_len ? resume->out - hist_len : 0, to_end = produced > hist_len ? produced - hist_len : 0;
+    const uint64_t hc[4] = {(uint64_t)hist_len, (uint64_t)hist_len, to_out, to_end};
+    uint32_t crc[2] = {0, 0};
+    HIP_TRY(ctx, hipMemcpyAsync(c64, hc, sizeof hc, hipMemcpyHostToDevice, st));
+    int e = md_launch_crc32(2, (const uint8_t *)dout.p, c64, c64 + 2, c32, st);
+    if (e != 0) return fail(ctx, MD_E_HIP, "crc32 kernel launch", (hipError_t)e);
+    HIP_TRY(ctx, hipMemcpyAsync(crc, c32, sizeof crc, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    resume->crc_out = crc[0];
+    resume->crc_end = crc[1];
+  }
+  return MD_OK;
+}
+
+static int inflate_one(md_ctx *ctx, int format, const uint8_t *src, size_t src_len, uint8_t *dst,
+                       size_t dst_cap, size_t *consumed, size_t *written) {
+  if (!ctx || !consumed || !written || (!src && src_len) || (!dst && dst_cap))
+    return MD_E_INVALID_ARGUMENT;
+  uint64_t in_off = 0, in_len = src_len, out_off = 0, out_cap = dst_cap, out_len = 0, used = 0;
+  int32_t status = 0;
+  int rc = md_inflate_batch_host(ctx, format, 1, src, src_len, &in_off, &in_len, dst, dst_cap,
+                                 &out_off, &out_cap, &out_len, &used, &status, nullptr);
+  if (rc != MD_OK) return rc;
+  *consumed = (size_t)used;
+  *written = (size_t)out_len;
+  return status;
+}
+
+int md_de_inf_ns_inflate(md_ctx *ctx, const uint8_t *src, size_t src_len, uint8_t *dst,
+                         size_t dst_cap, size_t *consumed, size_t *written) {
+  return inflate_one(ctx, MD_FORMAT_DEFLATE, src, src_len, dst, dst_cap, consumed, written);
+}
+
+int md_zl_inf_ns_inflate(md_ctx *ctx, const uint8_t *src, size_t src_len, uint8_t *dst,
+                         size_t dst_cap, size_t *consumed, size_t *written) {
+  return inflate_one(ctx, MD_FORMAT_ZLIB, src, src_len, dst, dst_cap, consumed, written);
+}
+
+
+// De.Higher.uncompress / Zl.Higher.uncompress (lib/de.ml:4555-4571, lib/zl.ml:650-666): the whole stream in, the
+// whole output out; the reference's `Error (`Msg s)` is md_status_string of the status returned
+int md_de_higher_uncompress(md_ctx *ctx, const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap, size_t *written) {
+  size_t used = 0;
+  return inflate_one(ctx, MD_FORMAT_DEFLATE, src, src_len, dst, dst_cap, &used, written);
+}
+int md_zl_higher_uncompress(md_ctx *ctx, const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap, size_t *written) {
+  size_t used = 0;
+  return inflate_one(ctx, MD_FORMAT_ZLIB, src, src_len, dst, dst_cap, &used, written);
+}
+
+// The accessors of a finished Gz.Inf decoder (filename / comment / os / extra, lib/gz.ml:612-633):
+// where the header fields sit in src.  Framing only — the kernels have validated the header.
+static void gz_meta_of(const uint8_t *s, size_t n, md_gz_meta *m) {
+  memset(m, 0, sizeof *m);
+  if (n < 10) return;
+  m->flg = s[3];
+  m->mtime = ((uint32_t)s[4] << 24) | ((uint32_t)s[5] << 16) | ((uint32_t)s[6] << 8) | s[7];
+  m->xfl = s[8];
+  m->os = s[9];
+  size_t p = 10;
+  if (m->flg & 4) {
+    if (n - p < 2) return;
+    const size_t xl = ((size_t)s[p] << 8) | s[p + 1];
+    p += 2;
+    if (n - p < xl) return;
+    m->has_extra = 1;
+    m->extra_off = p;
+    m->extra_len = xl;
+    p += xl;
+  }
+  for (int which = 0; which < 2; which++) {
+    if (!(m->flg & (which == 0 ? 8u : 16u))) continue;
+    size_t q = p;
+    while (q < n && s[q] != 0) q++;
+    if (q >= n) return;
+    if (which == 0) {
+      m->has_name = 1;
+      m->name_off = p;
+      m->name_len = q - p;
+    } else {
+      m->has_comment = 1;
+      m->comment_off = p;
+      m->comment_len = q - p;
+    }
+    p = q + 1;
+  }
+}
+
+int md_gz_higher_uncompress(md_ctx *ctx, const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap,
+                            size_t *consumed, size_t *written, md_gz_meta *meta) {
+  int st = inflate_one(ctx, MD_FORMAT_GZIP, src, src_len, dst, dst_cap, consumed, written);
+  if (meta) {
+    memset(meta, 0, sizeof *meta);
+    if (st == MD_OK) gz_meta_of(src, src_len, meta);
+  }
+  return st;
+}

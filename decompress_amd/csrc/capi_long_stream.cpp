@@ -1,0 +1,512 @@
+// capi_long_stream.cpp — ONE long stream decoded by the whole chip (csrc/inflate_chunked.hip has the scheme and the
+// kernels).
+#include <stdio.h>
+#include <stdlib.h>
+
+#include <algorithm>
+#include <chrono>
+#include <vector>
+
+#include "ctx.hpp"
+
+// De.Higher.uncompress / Zl.Higher.uncompress / Gz on ONE big input (lib/de.ml:4555-4571, lib/zl.ml:650-666,
+// bin/decompress.ml:77-100).  Returns MD_NOT_HANDLED whenever anything is not exactly as a well-formed stream decoded in
+// pieces should be - the caller then takes the serial path, whose statuses and counts are the reference's; MD_OK means
+// the whole stream is decoded, verified against its checksum, and copied out.
+namespace {
+struct ParPiece {
+  uint64_t bit;      // first bit of the piece in the body (a block start)
+  uint64_t u = 0;    // bytes it produces
+};
+}  // namespace
+
+// What par_decode works on: a raw DEFLATE body in host memory that starts start_bit bits into body[0], the (at most 32 KiB
+// of) output in front of it, room for dst_cap new bytes.  partial_ok: the body may end inside a block (a piece of a stream
+// that is still arriving) - the complete blocks are decoded, the rest is the caller's.
+struct ParIn {
+  const uint8_t *body;
+  uint64_t body_len;
+  uint32_t start_bit;
+  const uint8_t *hist;
+  uint32_t hist_len;
+  uint64_t dst_cap;
+  bool partial_ok;
+};
+struct ParOut {
+  int status;            // MD_OK: the final block ended; MD_UNEXPECTED_END_OF_INPUT (partial_ok): the body ended inside a block
+  uint64_t total;        // new bytes, final, at ctx->scratch[kParOut].p + hist_len
+  uint64_t used_body;    // MD_OK: bytes of the body the stream used
+  uint64_t resume_bits;  // bit of the body behind the last complete block
+};
+static int par_decode(md_ctx *ctx, const ParIn &in, ParOut *out) {
+  ctx->par_last_pieces = ctx->par_last_rounds = 0;
+  const bool dbg_t = getenv("MD_DEBUG_HOSTPATH") != nullptr;
+  const auto t_start = std::chrono::steady_clock::now();
+  auto stamp = [&](const char *what) {
+    if (dbg_t) fprintf(stderr, "[par_decode] %-22s at %.2f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count());
+  };
+  const uint8_t *body = in.body;
+  const uint64_t body_len = in.body_len, dst_cap = in.dst_cap;
+  const uint32_t hl = in.hist_len;
+  // pieces of "inflate_parallel_chunk" (64 KiB) of input - smaller ones for a smaller stream, so that it still comes in a few
+  // hundred pieces (a piece is a serial decode: 880 KB of 40-byte flush units in 14 pieces took 36 ms), never under 4 KiB
+  uint64_t K = ctx->par_chunk;
+  if (in.body_len / 256 < K) K = (in.body_len / 256 + 4095) & ~(uint64_t)4095;
+  if (K < 4096) K = 4096;
+  if (body_len < 4 * K || body_len > ((uint64_t)1 << 31) || hl + dst_cap > MD_MAX_STREAM) return MD_NOT_HANDLED;
+  const uint32_t nchunks = (uint32_t)((body_len + K - 1) / K);
+  hipStream_t st = ctx->stream;
+  // -- the body on the device, candidate block starts
+  int rc = ctx->scratch[kParIn].reserve(ctx, body_len + 64, "hipMalloc(parallel inflate input)");
+  if (rc != MD_OK) return rc;
+  const size_t desc_bytes = (size_t)nchunks * 2 * 160 + 4096;
+  rc = ctx->scratch[kParDesc].reserve(ctx, desc_bytes, "hipMalloc(parallel inflate descriptors)");
+  if (rc != MD_OK) return rc;
+  uint8_t *d_body = (uint8_t *)ctx->scratch[kParIn].p;
+  HIP_TRY(ctx, hipMemcpyAsync(d_body, body, body_len, hipMemcpyHostToDevice, st));
+  uint64_t *d_cand = (uint64_t *)ctx->scratch[kParDesc].p;
+  if (dbg_t) {
+    hipStreamSynchronize(st);
+    stamp("body on the device");
+  }
+  int e = md_launch_find_blocks(d_body, body_len, K, nchunks - 1, d_cand, st);
+  if (e != 0) return fail(ctx, MD_E_HIP, "find_blocks launch", (hipError_t)e);
+  std::vector<uint64_t> cand(nchunks - 1);
+  HIP_TRY(ctx, hipMemcpyAsync(cand.data(), d_cand, (nchunks - 1) * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  stamp("candidates found");
+  // A run of STORED blocks from bit `pos` on is followed on the host, a read per block (lib/de.ml:1613-1627: header, padding,
+  // LEN, NLEN): -> the bit behind the run (`pos` itself when the block there is not a stored, non-final one); *mid receives
+  // block starts inside the run at least K bytes apart - stored data is the one kind whose block starts need no decoding to
+  // be found, and a long run of it (incompressible input, level 0, compressed files inside a tar) should not be one piece.
+  auto hop_stored = [&](uint64_t pos, std::vector<uint64_t> *mid) -> uint64_t {
+    uint64_t last_mid = pos;
+    for (int hops = 0; hops < (1 << 22); hops++) {
+      const uint64_t by = pos >> 3;
+      if (by + 5 > body_len) break;
+      const uint32_t h = ((uint32_t)body[by] | ((uint32_t)body[by + 1] << 8)) >> (pos & 7);
+      if ((h & 6) != 0 || (h & 1)) break;  // not stored, or the final block
+      const uint64_t at = (pos + 3 + 7) >> 3;
+      if (at + 4 > body_len) break;
+      const uint32_t len = body[at] | ((uint32_t)body[at + 1] << 8), nlen = body[at + 2] | ((uint32_t)body[at + 3] << 8);
+      if ((len ^ nlen) != 0xffffu || at + 4 + len > body_len) break;
+      if (mid && pos >= last_mid + K * 8) {
+        mid->push_back(pos);
+        last_mid = pos;
+      }
+      pos = (at + 4 + len) * 8;
+    }
+    return pos;
+  };
+  std::vector<ParPiece> pc;
+  pc.push_back(ParPiece{in.start_bit});
+  {  // a stream that BEGINS with stored blocks: their starts are candidates the finder cannot see
+    std::vector<uint64_t> mid;
+    const uint64_t x = hop_stored(in.start_bit, &mid);
+    if (x > in.start_bit && x < body_len * 8) mid.push_back(x);
+    for (uint64_t c : mid)
+      if (c > pc.back().bit) pc.push_back(ParPiece{c});
+  }
+  {
+    const uint64_t seeded = pc.back().bit;
+    for (uint64_t c : cand)
+      if (c != ~0ull && c > seeded && c > pc.back().bit) pc.push_back(ParPiece{c});
+  }
+  if (pc.size() < 3) return MD_NOT_HANDLED;  // nothing to gain
+  // -- decode, verify the chain of pieces, decode again without a candidate that proved false or with more room
+  uint32_t capmul = 6;
+  uint64_t total = 0, used_body = 0;
+  out->status = MD_OK;
+  out->resume_bits = 0;
+  std::vector<uint64_t> offa, offb;
+  for (int round = 1;; round++) {
+    if (round > 8) return MD_NOT_HANDLED;
+    ctx->par_last_rounds = round;
+    const size_t np = pc.size(), n = 2 * np - 1;  // piece 0 once (its window is real), the others with window A and window B
+    // out blob: [the final output: dst_cap][scratch of piece 1 A, 1 B, 2 A, ...]: 32 KiB of window + room, 64-byte aligned
+    std::vector<uint64_t> in_off(n), in_len(n), out_off(n), out_cap(n);
+    std::vector<uint32_t> start_bit(n), hist(n), adler_in(n, 1);
+    std::vector<uint8_t> variant(n);
+    offa.assign(np, 0);
+    offb.assign(np, 0);
+    uint64_t at = ((uint64_t)hl + dst_cap + 63) & ~(uint64_t)63;
+    for (size_t p = 0; p < np; p++) {
+      const uint64_t b0 = pc[p].bit >> 3, b1 = p + 1 < np ? (pc[p + 1].bit + 7) >> 3 : body_len;
+      for (int v = 0; v < (p ? 2 : 1); v++) {
+        const size_t i = p ? 2 * p - 1 + v : 0;
+        in_off[i] = b0;
+        in_len[i] = b1 - b0;
+        start_bit[i] = (uint32_t)(pc[p].bit & 7);
+        if (p == 0) {
+          out_off[i] = 0;
+          out_cap[i] = hl + dst_cap;
+          hist[i] = hl;  // (the caller's window lies in front of the output)
+          variant[i] = 0;
+        } else {
+          const uint64_t room = (uint64_t)capmul * (b1 - b0) + 65536;
+          out_off[i] = at;
+          out_cap[i] = 32768 + room;
+          hist[i] = 32768;
+          variant[i] = (uint8_t)(1 + v);
+          (v ? offb : offa)[p] = at + 32768;
+          at += (32768 + room + 64 + 63) & ~(uint64_t)63;
+        }
+      }
+    }
+    if (at > ((uint64_t)64 << 30)) return MD_NOT_HANDLED;
+    rc = ctx->scratch[kParOut].reserve(ctx, at + 64, "hipMalloc(parallel inflate output)");
+    if (rc != MD_OK) return rc;
+    // descriptors: u64 x n: in_off in_len out_off out_cap out_len consumed resume_bits resume_out; u32 x n: start_bit hist
+    // adler_in status checksum resume_adler resume_last; u8 x n: variant
+    const size_t need = n * (8 * 8 + 7 * 4 + 1) + 256;
+    rc = ctx->scratch[kParDesc].reserve(ctx, need, "hipMalloc(parallel inflate descriptors)");
+    if (rc != MD_OK) return rc;
+    uint64_t *d64 = (uint64_t *)ctx->scratch[kParDesc].p;
+    uint32_t *d32 = (uint32_t *)(d64 + 8 * n);
+    uint8_t *d8 = (uint8_t *)(d32 + 7 * n);
+    uint8_t *d_out = (uint8_t *)ctx->scratch[kParOut].p;
+    if (hl) HIP_TRY(ctx, hipMemcpyAsync(d_out, in.hist, hl, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d64 + 0 * n, in_off.data(), n * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d64 + 1 * n, in_len.data(), n * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d64 + 2 * n, out_off.data(), n * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d64 + 3 * n, out_cap.data(), n * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d32 + 0 * n, start_bit.data(), n * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d32 + 1 * n, hist.data(), n * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d32 + 2 * n, adler_in.data(), n * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d8, variant.data(), n, hipMemcpyHostToDevice, st));
+    e = md_launch_fill_windows((uint32_t)n, d_out, d64 + 2 * n, d8, st);
+    if (e != 0) return fail(ctx, MD_E_HIP, "fill_windows launch", (hipError_t)e);
+    rc = md_inflate_continue_batch_device(ctx, n, d_body, d64 + 0 * n, d64 + 1 * n, d_out, d64 + 2 * n, d64 + 3 * n, d32 + 0 * n,
+                                          d32 + 1 * n, d32 + 2 * n, d64 + 4 * n, d64 + 5 * n, (int32_t *)(d32 + 3 * n), d32 + 4 * n,
+                                          d64 + 6 * n, d64 + 7 * n, d32 + 5 * n, d32 + 6 * n);
+    if (rc != MD_OK) return rc;
+    std::vector<uint64_t> r_used(n), r_bits(n), r_out(n);
+    std::vector<int32_t> r_st(n);
+    std::vector<uint32_t> r_last(n);
+    HIP_TRY(ctx, hipMemcpyAsync(r_used.data(), d64 + 5 * n, n * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(r_bits.data(), d64 + 6 * n, n * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(r_out.data(), d64 + 7 * n, n * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(r_st.data(), d32 + 3 * n, n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(r_last.data(), d32 + 6 * n, n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    stamp("pieces decoded");
+    // The pieces in order: piece p must end - its last complete block - exactly where piece p + 1 starts ("links").  From
+    // piece 0, the true start of the stream, an unbroken chain of links IS the stream's chain of blocks.  A candidate its
+    // predecessor does not link to goes (all of them in one round: behind a false candidate the verdicts say little, and a
+    // true block start dropped by mistake only costs a split), and everything is decoded again.
+    bool again = false, chain = true;
+    size_t last = np;  // index of the piece that holds the stream's final block
+    std::vector<std::pair<uint64_t, uint64_t>> kill;  // candidates at bits (lo, hi] go
+    std::vector<uint64_t> add;                        // block starts found by hopping over stored blocks
+    // piece p ended its last complete block at bit e, in front of the next candidate: that candidate is no block start.  If
+    // the block at e is STORED, so are all candidates inside it and the stored blocks behind it (compressed data inside the
+    // plaintext - a tar of .gz files - is stored, and full of real block headers that are not this stream's): hop over
+    // them on the host, a read per block, and the block start behind the run is a candidate the finder could not see.
+    auto unlinked = [&](size_t p, uint64_t e) {
+      uint64_t hi = p + 1 < np ? pc[p + 1].bit : ~0ull;
+      std::vector<uint64_t> mid;
+      const uint64_t pos = hop_stored(e, &mid);
+      if (pos > e) {
+        if (pos > hi) hi = pos;
+        for (uint64_t c : mid)
+          if (c > pc[p].bit) add.push_back(c);
+        if (pos < body_len * 8) add.push_back(pos);
+      }
+      kill.push_back({pc[p].bit, hi == ~0ull ? pc[p].bit : hi});
+    };
+    total = 0;
+    for (size_t p = 0; p < np; p++) {
+      const size_t i = p ? 2 * p - 1 : 0;
+      const uint64_t base_bits = (pc[p].bit >> 3) * 8;
+      if (p && (r_st[i] != r_st[i + 1] || r_out[i] != r_out[i + 1] || r_bits[i] != r_bits[i + 1])) {
+        if (chain) return MD_NOT_HANDLED;  // (the two decodes of a piece of the real chain differ in more than the window's bytes)
+        if (p + 1 < np) kill.push_back({pc[p].bit, pc[p + 1].bit});
+        again = true;
+        continue;
+      }
+      const bool linked = r_st[i] == MD_UNEXPECTED_END_OF_INPUT && p + 1 < np && base_bits + r_bits[i] == pc[p + 1].bit && r_last[i] == 0;
+      if (linked) {
+        pc[p].u = r_out[i] - hist[i];
+        total += pc[p].u;
+      } else if (r_st[i] == MD_UNEXPECTED_END_OF_OUTPUT && p) {  // (piece 0 writes into the caller's room: the serial path's error)
+        again = true;
+        if (chain) {  // a piece of the real chain needs more room (the candidate behind it stays)
+          capmul *= 6;
+          if (capmul > 1300) return MD_NOT_HANDLED;
+        } else if (p + 1 < np) kill.push_back({pc[p].bit, pc[p + 1].bit});  // (behind a false candidate: garbage that expands)
+        chain = false;
+      } else if (r_st[i] == MD_OK && chain) {  // the final block ended inside this piece: what follows is not the stream's
+        pc[p].u = r_out[i] - hist[i];
+        total += pc[p].u;
+        used_body = (pc[p].bit >> 3) + r_used[i];
+        out->resume_bits = base_bits + r_bits[i];
+        out->status = MD_OK;
+        last = p;
+        break;
+      } else if (chain && in.partial_ok && p + 1 == np && r_st[i] == MD_UNEXPECTED_END_OF_INPUT) {
+        // the input ends inside the last piece: its complete blocks count, the caller goes on from the last block boundary
+        pc[p].u = r_out[i] - hist[i];
+        total += pc[p].u;
+        out->resume_bits = base_bits + r_bits[i];
+        out->status = MD_UNEXPECTED_END_OF_INPUT;
+        last = p;
+        break;
+      } else {
+        // on the real chain: a piece that runs over the next candidate makes that candidate false; anything else is an
+        // error of the stream itself (or a stream that ends inside its last block): the serial path's
+        const bool ran_over = r_st[i] == MD_UNEXPECTED_END_OF_INPUT && p + 1 < np && base_bits + r_bits[i] < pc[p + 1].bit;
+        if (chain && !ran_over) return MD_NOT_HANDLED;
+        if (ran_over) unlinked(p, base_bits + r_bits[i]);
+        else if (p + 1 < np) kill.push_back({pc[p].bit, pc[p + 1].bit});
+        again = true;
+        chain = false;
+      }
+    }
+    if (again) {
+      std::vector<ParPiece> keep;
+      for (size_t p = 0; p < np; p++) {
+        bool dead = false;
+        for (const auto &k : kill) dead = dead || (pc[p].bit > k.first && pc[p].bit <= k.second);
+        if (!dead) keep.push_back(pc[p]);
+      }
+      for (uint64_t x : add) keep.push_back(ParPiece{x});  // (block starts read off the stream itself)
+      std::sort(keep.begin(), keep.end(), [](const ParPiece &x, const ParPiece &y) { return x.bit < y.bit; });
+      keep.erase(std::unique(keep.begin(), keep.end(), [](const ParPiece &x, const ParPiece &y) { return x.bit == y.bit; }), keep.end());
+      pc.swap(keep);
+      if (pc.size() < 2) return MD_NOT_HANDLED;
+      continue;
+    }
+    if (last == np) return MD_NOT_HANDLED;
+    if (last + 1 < np) pc.resize(last + 1);  // (the scratch of the pieces behind it is simply not looked at)
+    break;
+  }
+  const size_t np = pc.size();
+  if (total > dst_cap || np < 2) return MD_NOT_HANDLED;
+  // -- windows, then every byte
+  {
+    std::vector<uint64_t> u(np), pos(np);
+    uint64_t acc = 0;
+    for (size_t p = 0; p < np; p++) {  // (the window the caller handed in counts as output in front of piece 0)
+      u[p] = pc[p].u + (p ? 0 : hl);
+      pos[p] = acc;
+      acc += u[p];
+    }
+    // the windows: by pointer jumping over the whole chip (a table of 128 KiB per piece, twice, in groups of 1 023 pieces), or -
+    // a handful of pieces - by the one-workgroup chain
+    const uint32_t kGroup = 1023;
+    const bool jumping = np >= 24;
+    const size_t win_bytes = ((np * (size_t)32768 + 255) & ~(size_t)255);
+    rc = ctx->scratch[kParWin].reserve(ctx, win_bytes + (jumping ? md_windows_work_bytes((uint32_t)np, kGroup) : 0) + 64,
+              "hipMalloc(parallel inflate windows)");
+    if (rc != MD_OK) return rc;
+    const size_t need = np * 32 + 256;
+    rc = ctx->scratch[kParDesc].reserve(ctx, need, "hipMalloc(parallel inflate descriptors)");
+    if (rc != MD_OK) return rc;
+    uint64_t *d64 = (uint64_t *)ctx->scratch[kParDesc].p;  // offa offb u pos | flag
+    uint32_t *d_flag = (uint32_t *)(d64 + 4 * np);
+    uint8_t *d_out = (uint8_t *)ctx->scratch[kParOut].p;
+    HIP_TRY(ctx, hipMemcpyAsync(d64 + 0 * np, offa.data(), np * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d64 + 1 * np, offb.data(), np * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d64 + 2 * np, u.data(), np * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d64 + 3 * np, pos.data(), np * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemsetAsync(d_flag, 0, 64, st));
+    if (jumping)
+      e = md_launch_windows_parallel((uint32_t)np, kGroup, d_out, u[0], d_out, d64 + 0 * np, d64 + 1 * np, d64 + 2 * np, d64 + 3 * np,
+                                     (uint8_t *)ctx->scratch[kParWin].p, (uint32_t *)((uint8_t *)ctx->scratch[kParWin].p + win_bytes), d_flag, st);
+    else e = md_launch_window_chain((uint32_t)np, d_out, d_out, d64 + 0 * np, d64 + 1 * np, d64 + 2 * np, (uint8_t *)ctx->scratch[kParWin].p, d_flag, st);
+    if (e != 0) return fail(ctx, MD_E_HIP, "window_chain launch", (hipError_t)e);
+    if (dbg_t) {
+      hipStreamSynchronize(st);
+      stamp("window chain");
+    }
+    e = md_launch_resolve((uint32_t)np, d_out, d_out, d64 + 0 * np, d64 + 1 * np, d64 + 2 * np, d64 + 3 * np,
+                          (const uint8_t *)ctx->scratch[kParWin].p, d_flag, st);
+    if (e != 0) return fail(ctx, MD_E_HIP, "resolve launch", (hipError_t)e);
+    // (the flag is read by the caller together with what it needs next)
+    uint32_t flag = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    stamp("windows + resolve");
+    if (flag) return MD_NOT_HANDLED;  // a reference in front of the stream's start
+  }
+  out->total = total;
+  out->used_body = used_body;
+  ctx->par_last_pieces = (int)np;
+  return MD_OK;
+}
+
+// Adler-32 of n bytes at d (device) going on from `adler`; CRC-32 of the same bytes (complete value)
+static int par_adler(md_ctx *ctx, const uint8_t *d, uint64_t n, uint32_t adler, uint32_t *res) {
+  *res = adler;
+  if (n == 0) return MD_OK;
+  const size_t nseg = (size_t)((n + 65535) / 65536);
+  int rc = ctx->scratch[kParDesc].reserve(ctx, nseg * 8 + 64, "hipMalloc(parallel inflate descriptors)");
+  if (rc != MD_OK) return rc;
+  uint32_t *d_sums = (uint32_t *)ctx->scratch[kParDesc].p;
+  int e = md_launch_adler_segments(d, n, 65536, d_sums, ctx->stream);
+  if (e != 0) return fail(ctx, MD_E_HIP, "adler_segments launch", (hipError_t)e);
+  std::vector<uint32_t> sums(2 * nseg);
+  HIP_TRY(ctx, hipMemcpyAsync(sums.data(), d_sums, nseg * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  uint64_t a = adler & 0xffffu, b = adler >> 16;
+  for (size_t s = 0; s < nseg; s++) {
+    const uint64_t len = s + 1 < nseg ? 65536 : n - (uint64_t)s * 65536;
+    b = (b + (len % 65521) * a + sums[2 * s + 1]) % 65521;
+    a = (a + sums[2 * s]) % 65521;
+  }
+  *res = (uint32_t)((b << 16) | a);
+  return MD_OK;
+}
+static int par_crc(md_ctx *ctx, const uint8_t *d_base, uint64_t off, uint64_t n, uint32_t *res) {
+  *res = 0;
+  if (n == 0) return MD_OK;
+  const size_t ncrc = (size_t)((n + ((1u << 20) - 1)) >> 20);
+  int rc = ctx->scratch[kParDesc].reserve(ctx, ncrc * 24 + 64, "hipMalloc(parallel inflate descriptors)");
+  if (rc != MD_OK) return rc;
+  uint64_t *d_off = (uint64_t *)ctx->scratch[kParDesc].p, *d_len = d_off + ncrc;
+  uint32_t *d_crc = (uint32_t *)(d_len + ncrc);
+  std::vector<uint64_t> co(ncrc), cl(ncrc);
+  for (size_t s = 0; s < ncrc; s++) {
+    co[s] = off + ((uint64_t)s << 20);
+    cl[s] = s + 1 < ncrc ? (uint64_t)1 << 20 : n - ((uint64_t)s << 20);
+  }
+  HIP_TRY(ctx, hipMemcpyAsync(d_off, co.data(), ncrc * 8, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(d_len, cl.data(), ncrc * 8, hipMemcpyHostToDevice, ctx->stream));
+  int e = md_launch_crc32((uint32_t)ncrc, d_base, d_off, d_len, d_crc, ctx->stream);
+  if (e != 0) return fail(ctx, MD_E_HIP, "crc32 launch", (hipError_t)e);
+  std::vector<uint32_t> crcs(ncrc);
+  HIP_TRY(ctx, hipMemcpyAsync(crcs.data(), d_crc, ncrc * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  uint32_t crc = crcs[0];
+  for (size_t s = 1; s < ncrc; s++) crc = md::crc32_concat(crc, crcs[s], cl[s]);
+  *res = crc;
+  return MD_OK;
+}
+
+// md_de_inf_continue_host on a long piece: the blocks that are complete in it by par_decode; if the piece ends inside a
+// block, that tail goes through the serial path from the block boundary on (window = the bytes just decoded), so what the
+// caller sees - status, the output reached inside the incomplete block, the resume point, the checksums there - is what
+// the serial path alone would have said.
+int continue_parallel(md_ctx *ctx, const uint8_t *src, size_t src_len, unsigned start_bit, uint8_t *dst, size_t hist_len,
+                      size_t dst_cap, uint32_t adler_in, unsigned flags, size_t *dst_len, int *status, md_inf_resume *resume) {
+  ParIn in{src, src_len, start_bit, dst, (uint32_t)hist_len, dst_cap - hist_len, true};
+  ParOut po;
+  int rc = par_decode(ctx, in, &po);
+  if (rc != MD_OK) return rc;
+  const uint8_t *d_out = (const uint8_t *)ctx->scratch[kParOut].p;
+  const int pieces = ctx->par_last_pieces, rounds = ctx->par_last_rounds;
+  uint32_t adler = adler_in, crc = 0;
+  rc = par_adler(ctx, d_out + hist_len, po.total, adler_in, &adler);
+  if (rc == MD_OK && (flags & MD_CONT_CRC32)) rc = par_crc(ctx, d_out, hist_len, po.total, &crc);
+  if (rc != MD_OK) return rc;
+  if (po.total) HIP_TRY(ctx, hipMemcpy(dst + hist_len, d_out + hist_len, po.total, hipMemcpyDeviceToHost));
+  const uint64_t O = hist_len + po.total;  // output position behind the last complete block
+  if (po.status == MD_OK) {
+    *dst_len = (size_t)O;
+    *status = MD_OK;
+    resume->bits = po.resume_bits;
+    resume->out = O;
+    resume->adler = adler;
+    resume->last = 1;
+    resume->consumed = po.used_body;
+    resume->checksum = adler;
+    resume->crc_out = resume->crc_end = crc;
+    return MD_OK;
+  }
+  // the tail, serially: from bit B on, with the last 32 KiB in front of it as its window - in place
+  const uint64_t B = po.resume_bits, hl2 = O < 32768 ? O : 32768, shift = O - hl2;
+  size_t t_len = 0;
+  int t_st = 0;
+  md_inf_resume t;
+  rc = continue_serial(ctx, src + (B >> 3), src_len - (size_t)(B >> 3), (unsigned)(B & 7), dst + shift, (size_t)hl2, dst_cap - (size_t)shift, adler,
+                       flags, &t_len, &t_st, &t);
+  if (rc != MD_OK) return rc;
+  *dst_len = (size_t)shift + t_len;
+  *status = t_st;
+  resume->bits = (B >> 3) * 8 + t.bits;
+  resume->out = shift + t.out;
+  resume->adler = t.adler;
+  resume->last = t.last;
+  resume->consumed = (B >> 3) + t.consumed;
+  resume->checksum = t.checksum;
+  if (flags & MD_CONT_CRC32) {
+    const uint64_t n_out = t.out - hl2, n_end = t_len - hl2;
+    resume->crc_out = po.total ? (n_out ? md::crc32_concat(crc, t.crc_out, n_out) : crc) : t.crc_out;
+    resume->crc_end = po.total ? (n_end ? md::crc32_concat(crc, t.crc_end, n_end) : crc) : t.crc_end;
+  } else resume->crc_out = resume->crc_end = 0;
+  ctx->par_last_pieces = pieces;
+  ctx->par_last_rounds = rounds;
+  return MD_OK;
+}
+
+int inflate_parallel(md_ctx *ctx, int format, const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap,
+                     size_t *consumed, size_t *written, uint32_t *checksum) {
+  // -- the frame: anything but a plain valid header is the serial path's (it knows the reference's answer)
+  size_t hdr = 0, trailer = 0;
+  if (format == MD_FORMAT_ZLIB) {
+    if (src_len < 6 || (((uint32_t)src[0] << 8) + src[1]) % 31 != 0 || (src[0] & 0xf) != 8) return MD_NOT_HANDLED;
+    hdr = 2;
+    trailer = 4;
+  } else if (format == MD_FORMAT_GZIP) {
+    if (src_len < 18 || src[0] != 0x1f || src[1] != 0x8b || (src[3] & 2)) return MD_NOT_HANDLED;  // (a header CRC: serial path)
+    size_t p = 10;
+    const uint32_t flg = src[3];
+    if (flg & 4) {  // FEXTRA, big-endian length as the reference reads it (lib/gz.ml:455)
+      if (src_len - p < 2) return MD_NOT_HANDLED;
+      const size_t xl = ((size_t)src[p] << 8) | src[p + 1];
+      p += 2;
+      if (src_len - p < xl) return MD_NOT_HANDLED;
+      p += xl;
+    }
+    for (int which = 0; which < 2; which++) {
+      if (!(flg & (which == 0 ? 8u : 16u))) continue;
+      while (p < src_len && src[p] != 0) p++;
+      if (p >= src_len) return MD_NOT_HANDLED;
+      p++;
+    }
+    hdr = p;
+    trailer = 8;
+  } else if (format != MD_FORMAT_DEFLATE) return MD_NOT_HANDLED;
+  if (src_len < hdr + trailer) return MD_NOT_HANDLED;
+  ParIn in{src + hdr, src_len - hdr, 0, nullptr, 0, dst_cap, false};  // (the trailer's bytes included: where the stream ends is the decoder's to say)
+  ParOut po;
+  int rc = par_decode(ctx, in, &po);
+  if (rc != MD_OK) return rc;
+  const uint64_t total = po.total, used_body = po.used_body;
+  if (src_len - hdr - used_body < trailer) {
+    ctx->par_last_pieces = 0;
+    return MD_NOT_HANDLED;
+  }
+  const uint8_t *d_out = (const uint8_t *)ctx->scratch[kParOut].p;
+  const uint8_t *t = src + hdr + used_body;
+  bool good = true;
+  if (format == MD_FORMAT_ZLIB || (format == MD_FORMAT_DEFLATE && checksum)) {
+    uint32_t adler = 1;
+    rc = par_adler(ctx, d_out, total, 1u, &adler);
+    if (rc != MD_OK) return rc;
+    if (format == MD_FORMAT_ZLIB) {
+      const uint32_t want = ((uint32_t)t[0] << 24) | ((uint32_t)t[1] << 16) | ((uint32_t)t[2] << 8) | t[3];
+      good = want == adler;
+    }
+    if (checksum) *checksum = adler;
+  } else if (format == MD_FORMAT_GZIP) {
+    uint32_t crc = 0;
+    rc = par_crc(ctx, d_out, 0, total, &crc);
+    if (rc != MD_OK) return rc;
+    uint32_t want = 0, isize = 0;
+    for (int k = 0; k < 4; k++) {
+      want |= (uint32_t)t[k] << (8 * k);
+      isize |= (uint32_t)t[4 + k] << (8 * k);
+    }
+    good = want == crc && isize == (uint32_t)total;
+    if (checksum) *checksum = crc;
+  }
+  if (!good) {  // the serial path reports it
+    ctx->par_last_pieces = 0;
+    return MD_NOT_HANDLED;
+  }
+  if (total) HIP_TRY(ctx, hipMemcpy(dst, d_out, total, hipMemcpyDeviceToHost));
+  *consumed = hdr + (size_t)used_body + trailer;
+  *written = (size_t)total;
+  return MD_OK;
+}

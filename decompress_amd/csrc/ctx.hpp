@@ -1,0 +1,255 @@
+// ctx.hpp — what the host translation units (capi*.cpp, stream_shim.cpp) share and no kernel sees: the context, the one
+// type that owns device or pinned memory, the error helpers, and every function that one of those files defines and
+// another calls.  The defining file and every caller include it, as with internal.hpp.  Plain host C++.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <string>
+#include <utility>
+
+#include "host_util.hpp"
+#include "internal.hpp"
+#include "mdeflate.h"
+
+// nothing here is exported but the extern "C" functions below
+#pragma GCC visibility push(hidden)
+
+// records `what` (and HIP's text for e) as the last error of ctx and of the calling thread, returns code.  ONE definition
+// (capi.cpp, beside the thread's string that md_last_error_string(NULL) reads).
+int fail(md_ctx *ctx, int code, const char *what, hipError_t e = hipSuccess);
+
+#define HIP_TRY(ctx, expr)                                   \
+  do {                                                       \
+    hipError_t e_ = (expr);                                  \
+    if (e_ != hipSuccess) return fail(ctx, MD_E_HIP, #expr, e_); \
+  } while (0)
+
+#define MD_ON_DEVICE(ctx)                 \
+  md::DeviceGuard guard_((ctx)->device);  \
+  if (!guard_.ok) return fail(ctx, MD_E_HIP, "hipSetDevice")
+
+namespace md {
+
+// what the batch shims ask of the allocator for a blob of `need` bytes: a quarter and 4 KiB of headroom
+inline size_t blob_room(size_t need) { return need + need / 4 + 4096; }
+
+// One allocation of device (or pinned host) memory and its capacity.  It frees itself when its owner goes: whoever
+// deletes the owner sets the device and waits for the context's stream first.  Grow-only, and growing does not keep the
+// contents (reserve_keep does).
+template <bool kPinned>
+struct Buffer {
+  void *p = nullptr;
+  size_t cap = 0;
+  Buffer() = default;
+  Buffer(const Buffer &) = delete;
+  Buffer &operator=(const Buffer &) = delete;
+  Buffer(Buffer &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
+  Buffer &operator=(Buffer &&o) noexcept {
+    if (this != &o) {
+      release();
+      std::swap(p, o.p);
+      std::swap(cap, o.cap);
+    }
+    return *this;
+  }
+  ~Buffer() { release(); }
+  void release() {
+    if (p) (void)(kPinned ? hipHostFree(p) : hipFree(p));
+    p = nullptr;
+    cap = 0;
+  }
+  template <class T>
+  T *as() const {
+    return (T *)p;
+  }
+  // Nothing when `need` bytes are there.  Otherwise the context's stream is waited for, the block is freed and `room`
+  // bytes are allocated (`need` itself unless the caller asks for headroom); no room: MD_E_OUT_OF_MEMORY, with `what` as
+  // the context's error text unless it is null (the batch shims report the status alone).
+  int reserve(md_ctx *ctx, size_t need, const char *what, size_t room = 0);
+  int reserve_blob(md_ctx *ctx, size_t need) { return reserve(ctx, need, nullptr, blob_room(need)); }
+  // a blob (device) that keeps its first `keep` bytes when it grows
+  int reserve_keep(md_ctx *ctx, size_t need, size_t keep);
+};
+using DevBuf = Buffer<false>;
+using PinnedBuf = Buffer<true>;
+
+}  // namespace md
+
+// The context's grow-only scratch.  md_set_option "release_workspace" gives back exactly these, in this order (they grow
+// again on demand); gz_tmp, lzo_ws, counters, dbg and gz_hdr_dev below are not among them and live as long as the context.
+enum Scratch {
+  // deflate: command queues (n x queue_len), the per-stream part of the front workspace (slots, chunk starts: n-sized)
+  // and its per-position part (hash-chain links, look-ahead verdicts: 13 bytes per input byte)
+  kWs, kFsmall, kFbig,
+  kOrder,  // launch order of a large batch (4 bytes per stream)
+  // the decoder in pieces (md_de_inf_continue_host): input, output and descriptors
+  kContIn, kContOut, kContDesc,
+  // a deflate batch in slices of positions: descriptors of the slice and the streams' states between the slices
+  kSliceDesc, kSliceState,
+  // the host-buffer entry points (md_*_batch_host): device copies of the caller's blobs and descriptors
+  kHostIn, kHostOut, kHostDesc,
+  // one long stream decoded by the whole chip (inflate_parallel): input, output + the pieces' scratch decodes, windows
+  // and descriptors
+  kParIn, kParOut, kParWin, kParDesc,
+  // a GZip file of many members (md_gz_members_*, md_bgzf_compress): the member scan's bitmap and counts, its candidate
+  // lists, the members' descriptors, and the writer's packed file
+  kGzmWs, kGzmCand, kGzmDesc, kGzmOut,
+  kScratchCount
+};
+
+struct md_ctx {
+  int device = 0;
+  hipStream_t stream = nullptr;
+  bool own_stream = false;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  md::DevBuf scratch[kScratchCount];
+  // GZip: per-stream scratch (body_off[n], body_len[n] u64, hstatus[n] i32, crc[n] u32), grow-only, and the header to write
+  md::DevBuf gz_tmp;
+  md::DevBuf gz_hdr_dev;           // device copy of gz_hdr (530 bytes max)
+  uint8_t gz_hdr_sent[544] = {0};  // what gz_hdr_dev holds
+  bool gz_hdr_valid = false;
+  md::DevBuf lzo_ws;    // Lzo.compress dictionaries
+  md::DevBuf counters;  // work counters of the kernels with persistent workgroups (zeroed in front of a launch)
+  int cus = 256;        // compute units of the device
+  int inflate_waves = 2;    // wavefronts per stream of the inflate kernel (md_set_option "inflate_waves": 1 = the one-wavefront form)
+  size_t piece_bytes = (size_t)1 << 20;  // md_set_option "encoder_piece_bytes": input the md_def_* encoder gathers before a launch
+  size_t front_cap_bytes = 0;  // md_set_option "deflate_workspace_cap_mib" (md_create: a sixth of the device's memory; 0 = none):
+                               // batches whose per-position workspace would be larger go in slices of positions
+  int test_flags = 0;  // md_set_option "deflate_test_flags": bit 4 = the md_def_* encoder moves its origin every 128 KiB (tests)
+  md::DevBuf dbg;      // device buffer of the optional in-kernel profile (32 x u64)
+  // the two copy streams of the host-buffer entry points, next to the context's stream (copy-in of slice k + 1 and
+  // copy-out of slice k - 1 under the kernels of slice k)
+  hipStream_t s_in = nullptr, s_out = nullptr;
+  // one long stream by the whole chip: md_set_option "inflate_parallel_min" (compressed bytes from which a single stream
+  // goes this way, 0 = never) and "inflate_parallel_chunk" (compressed bytes per piece)
+  size_t par_min = (size_t)96 << 10, par_chunk = (size_t)64 << 10;  // (measured: the pieces pay from ~100 KB of input, ~1 ms flat up to 4 MiB of text)
+  int par_last_pieces = 0, par_last_rounds = 0;  // of the last stream that went this way (md_get_option, tests)
+  int host_slices_max = 16;  // md_set_option "host_pipeline_slices": 1 = copy-in / kernels / copy-out one after the other
+  // ONE long stream's hash chains in segments on the whole chip (link_segments): md_set_option
+  // "deflate_link_segment_min" (input bytes from which a single stream of md_deflate_batch_host goes this way, 0 = never)
+  // and "deflate_link_segment" (positions per segment, 0 = by the stream's length); link_last_segments: the segments
+  // the last deflate batch call built its chains in (0 = one workgroup per stream; md_i_link_segments, tests)
+  size_t link_seg_min = (size_t)128 << 10, link_seg = 0;
+  uint32_t link_last_segments = 0;
+  std::string err;
+};
+
+namespace md {
+
+template <bool kPinned>
+int Buffer<kPinned>::reserve(md_ctx *ctx, size_t need, const char *what, size_t room) {
+  if (need <= cap) return MD_OK;
+  if (p) {
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, kPinned ? hipHostFree(p) : hipFree(p));
+    p = nullptr;
+    cap = 0;
+  }
+  if (room < need) room = need;
+  if ((kPinned ? hipHostMalloc(&p, room, hipHostMallocDefault) : hipMalloc(&p, room)) != hipSuccess) {
+    p = nullptr;
+    return what ? fail(ctx, MD_E_OUT_OF_MEMORY, what) : MD_E_OUT_OF_MEMORY;
+  }
+  cap = room;
+  return MD_OK;
+}
+
+template <bool kPinned>
+int Buffer<kPinned>::reserve_keep(md_ctx *ctx, size_t need, size_t keep) {
+  static_assert(!kPinned, "device blobs only");
+  if (need <= cap) return MD_OK;
+  Buffer q;
+  if (hipMalloc(&q.p, blob_room(need)) != hipSuccess) {
+    q.p = nullptr;
+    return MD_E_OUT_OF_MEMORY;
+  }
+  q.cap = blob_room(need);
+  if (keep) HIP_TRY(ctx, hipMemcpyAsync(q.p, p, keep, hipMemcpyDeviceToDevice, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  *this = std::move(q);
+  return MD_OK;
+}
+
+}  // namespace md
+
+// the launch-order scratch of a batch of n streams: null (index order) below `from` streams
+inline int launch_order(md_ctx *ctx, size_t n, size_t from, uint32_t **order) {
+  *order = nullptr;
+  if (n < from) return MD_OK;
+  const int rc = ctx->scratch[kOrder].reserve(ctx, n * 4, "hipMalloc(launch order)");
+  if (rc == MD_OK) *order = ctx->scratch[kOrder].as<uint32_t>();
+  return rc;
+}
+
+// One host buffer through a batch of one: input, output (16 bytes of slack each: Lzo's compressor over-copies into it)
+// and the descriptor (in_off in_len out_off out_cap out_len, status) live for the call; `launch(d_in, d64, d_out,
+// d_status, d_extra)` enqueues the batch entry point with n = 1 on the context's stream.  extra_bytes of device memory
+// go to the launch as a further result and come back in `extra` when that is not null.  Returns the stream's status.
+template <class Launch>
+int one_through_batch(md_ctx *ctx, const void *src, size_t src_len, void *dst, size_t dst_cap, size_t *written, Launch launch,
+                      size_t extra_bytes = 0, void *extra = nullptr) {
+  md::DevBuf din, dout, ddesc, dextra;
+  int rc = din.reserve(ctx, src_len + 16, "hipMalloc");
+  if (rc == MD_OK) rc = dout.reserve(ctx, dst_cap + 16, "hipMalloc");
+  if (rc == MD_OK) rc = ddesc.reserve(ctx, 6 * 8 + 16, "hipMalloc");
+  if (rc == MD_OK) rc = dextra.reserve(ctx, extra_bytes, "hipMalloc");
+  if (rc != MD_OK) return rc;
+  const uint64_t desc[5] = {0, src_len, 0, dst_cap, 0};
+  uint64_t *d64 = ddesc.as<uint64_t>();
+  int32_t *dstatus = (int32_t *)(d64 + 5);
+  hipStream_t st = ctx->stream;
+  if (src_len) HIP_TRY(ctx, hipMemcpyAsync(din.p, src, src_len, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d64, desc, sizeof desc, hipMemcpyHostToDevice, st));
+  rc = launch(din.as<const uint8_t>(), d64, dout.as<uint8_t>(), dstatus, dextra.as<uint32_t>());
+  if (rc != MD_OK) return rc;
+  uint64_t out_len = 0;
+  int32_t status = 0;
+  HIP_TRY(ctx, hipMemcpyAsync(&out_len, d64 + 4, 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipMemcpyAsync(&status, dstatus, 4, hipMemcpyDeviceToHost, st));
+  if (extra) HIP_TRY(ctx, hipMemcpyAsync(extra, dextra.p, extra_bytes, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  if (status == MD_OK && out_len) HIP_TRY(ctx, hipMemcpy(dst, dout.p, (size_t)out_len, hipMemcpyDeviceToHost));
+  *written = (size_t)out_len;
+  return status;
+}
+
+// ---- capi_deflate.cpp: the encoder in pieces, as stream_shim.cpp drives it (not part of the public ABI) ----
+// The device goes on from the state the piece before left, so neither side keeps more of the stream than the 64 KiB the
+// matcher can reach back plus the piece.
+struct md_piece;
+// one piece of each of n streams, the descriptors host arrays of n entries (md_i_pieces_run)
+struct md_pieces_io {
+  const uint64_t *text_off, *text_len, *abs_len, *out_off, *out_cap, *w0, *rebase;
+  const uint32_t *flags, *sum, *isize;
+  uint64_t *out_len;
+  int32_t *status;
+};
+
+#pragma GCC visibility pop
+extern "C" {
+int md_validate_deflate_params(md_ctx *ctx, int format, const md_deflate_params *params);
+md_piece *md_i_piece_open(md_ctx *ctx, int queue_len);
+void md_i_piece_close(md_ctx *ctx, md_piece *p);
+int md_i_piece_run(md_ctx *ctx, md_piece *p, int format, const md_deflate_params *params, const uint8_t *text, size_t text_len,
+                   size_t seen, uint64_t w0, uint64_t rebase, int first, int last, uint32_t sum, uint32_t isize, size_t out_cap,
+                   size_t *out_len, int *status);
+int md_i_piece_out(md_ctx *ctx, const md_piece *p, size_t off, uint8_t *host, size_t len);
+// d_desc: the caller's, grown here to the n streams' descriptors
+int md_i_pieces_run(md_ctx *ctx, int format, const md_deflate_params *params, size_t n, const uint8_t *d_text, uint8_t *d_out,
+                    void *d_state, void *d_queue, md::DevBuf &d_desc, const md_pieces_io *io, uint32_t match_skip);
+// test hooks that Python binds, and the profile read-back beside md_set_option "profile"
+int md_i_link_segments(const md_ctx *ctx);
+int md_get_profile(md_ctx *ctx, uint64_t *out32);
+}
+
+#pragma GCC visibility push(hidden)
+// ---- capi_inflate.cpp ----
+int continue_serial(md_ctx *ctx, const uint8_t *src, size_t src_len, unsigned start_bit, uint8_t *dst, size_t hist_len,
+                    size_t dst_cap, uint32_t adler_in, unsigned flags, size_t *dst_len, int *status, md_inf_resume *resume);
+// ---- capi_long_stream.cpp: both return MD_NOT_HANDLED for what the serial path has to answer ----
+int continue_parallel(md_ctx *ctx, const uint8_t *src, size_t src_len, unsigned start_bit, uint8_t *dst, size_t hist_len,
+                      size_t dst_cap, uint32_t adler_in, unsigned flags, size_t *dst_len, int *status, md_inf_resume *resume);
+int inflate_parallel(md_ctx *ctx, int format, const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap, size_t *consumed,
+                     size_t *written, uint32_t *checksum);
+#pragma GCC visibility pop

@@ -1,4 +1,4 @@
-// host_util.hpp — small host-side helpers of capi.cpp and stream_shim.cpp: checksums of the few bytes the host
+// host_util.hpp — small host-side helpers of capi*.cpp and stream_shim.cpp: checksums of the few bytes the host
 // handles itself, and the device guard of the entry points.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,6 +1,7 @@
-// internal.hpp — the boundary between the library's translation units: every extern "C" function that one file
-// defines and another calls, the structs that cross, and the constants both sides size things by.  The defining file
+// internal.hpp — the boundary between the host code and the kernel files: every extern "C" function that a .hip file
+// defines and the host calls, the structs that cross, and the constants both sides size things by.  The defining file
 // and every caller include it, so a prototype that drifts from its definition does not compile.  Plain host C++.
+// (What the host files share among themselves is in ctx.hpp.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -79,33 +80,7 @@ constexpr uint32_t kMarkSpanBytes = 16384;
 }  // namespace gzm
 }  // namespace md
 
-// The encoder takes its stream in pieces (capi.cpp, md_i_piece_*; stream_shim.cpp): the device goes on from the state the
-// piece before left, so neither side keeps more of the stream than the 64 KiB the matcher can reach back plus the piece.
-struct md_piece;
-// one piece of each of n streams, the descriptors host arrays of n entries (md_i_pieces_run)
-struct md_pieces_io {
-  const uint64_t *text_off, *text_len, *abs_len, *out_off, *out_cap, *w0, *rebase;
-  const uint32_t *flags, *sum, *isize;
-  uint64_t *out_len;
-  int32_t *status;
-};
-
 extern "C" {
-
-// ---- capi.cpp: what stream_shim.cpp needs of a context ----
-int md_validate_deflate_params(md_ctx *ctx, int format, const md_deflate_params *params);
-hipStream_t md_i_stream(md_ctx *ctx);
-int md_i_device(md_ctx *ctx);
-int md_i_test_flags(const md_ctx *ctx);
-size_t md_i_piece_bytes(const md_ctx *ctx);
-md_piece *md_i_piece_open(md_ctx *ctx, int queue_len);
-void md_i_piece_close(md_ctx *ctx, md_piece *p);
-int md_i_piece_run(md_ctx *ctx, md_piece *p, int format, const md_deflate_params *params, const uint8_t *text, size_t text_len,
-                   size_t seen, uint64_t w0, uint64_t rebase, int first, int last, uint32_t sum, uint32_t isize, size_t out_cap,
-                   size_t *out_len, int *status);
-int md_i_piece_out(md_ctx *ctx, const md_piece *p, size_t off, uint8_t *host, size_t len);
-int md_i_pieces_run(md_ctx *ctx, int format, const md_deflate_params *params, size_t n, const uint8_t *d_text, uint8_t *d_out,
-                    void *d_state, void *d_queue, void **d_desc, size_t *d_desc_bytes, const md_pieces_io *io, uint32_t match_skip);
 
 // ---- inflate_wave.hip ----
 // `order` = n words of device scratch, or null for index order; waves = wavefronts per stream (2, or 1); cont = null

@@ -23,10 +23,8 @@
 #include <string>
 #include <vector>
 
-#include "host_util.hpp"
+#include "ctx.hpp"
 #include "inflate_batch.hpp"
-#include "internal.hpp"
-#include "mdeflate.h"
 
 // The frame around the DEFLATE body of one stream that is decoded in pieces as it arrives, and the steps on it that
 // md_inf_* and md_inf_batch_* share: the GZip / ZLIB header, the bookkeeping of a decoded piece, both trailers with
@@ -85,7 +83,7 @@ md_inf_stream *md_inf_decoder(md_ctx *ctx, int format, uint8_t *o, size_t o_len)
   s->format = format;
   s->o = o;
   s->o_len = o_len;
-  s->chunk = (size_t)8 << 20;  // (pieces this long are decoded by the whole chip: capi.cpp continue_parallel)
+  s->chunk = (size_t)8 << 20;  // (pieces this long are decoded by the whole chip: capi_long_stream.cpp continue_parallel)
   inf_clear(s);
   return s;
 }
@@ -528,7 +526,7 @@ static void def_launch(md_def_stream *s) {
   const size_t cap = 2048 + 6 * ql + 2 * fresh + blocks * per_block;
   // the device's positions are 32-bit: once the text is 2 GiB from their origin the origin moves up to 64 KiB below it
   // (deflate_test_flags bit 4: at 128 KiB already, so that a test of ordinary size goes through it)
-  const uint64_t far = (md_i_test_flags(s->ctx) & 16) ? (uint64_t)1 << 17 : (uint64_t)1 << 31;
+  const uint64_t far = (s->ctx->test_flags & 16) ? (uint64_t)1 << 17 : (uint64_t)1 << 31;
   uint64_t rebase = 0;
   if (s->w0 - s->origin >= far) {
     rebase = (s->w0 - s->origin - 65536) & ~(uint64_t)65535;
@@ -578,7 +576,7 @@ int md_def_encode(md_def_stream *s) {
     if (s->done) return s->status == MD_OK ? MD_END : MD_MALFORMED;
     const size_t fresh = (size_t)(s->w0 + s->text.size() - s->launched);
     // (a launch costs three kernels whatever it holds: input is gathered, 1 MiB unless md_set_option "encoder_piece_bytes")
-    if (!s->eoi && fresh < md_i_piece_bytes(s->ctx)) return MD_AWAIT;
+    if (!s->eoi && fresh < s->ctx->piece_bytes) return MD_AWAIT;
     def_launch(s);
   }
 }
@@ -611,31 +609,16 @@ struct md_def_batch {
     std::vector<uint8_t> held;    // output of earlier launches that was not fetched before the next one
   };
   std::vector<Enc> e;
-  void *d_text[2] = {nullptr, nullptr};
-  size_t text_cap[2] = {0, 0};
+  md::DevBuf d_text[2];
   int cur = 0;
-  void *d_fresh = nullptr, *d_out = nullptr, *d_state = nullptr, *d_queue = nullptr, *d_desc = nullptr, *d_gdesc = nullptr;
-  size_t fresh_cap = 0, out_cap = 0, desc_bytes = 0, gdesc_cap = 0;
-  uint8_t *h_stage = nullptr;     // pinned: the fresh bytes of a launch, packed
-  size_t stage_cap = 0;
+  md::DevBuf d_fresh, d_out, d_state, d_queue, d_desc, d_gdesc;
+  md::PinnedBuf h_stage;          // the fresh bytes of a launch, packed
 };
-namespace {
-bool regrow(void **p, size_t *cap, size_t need) {
-  if (need <= *cap) return true;
-  if (*p) hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  const size_t want = need + need / 4 + 4096;
-  if (hipMalloc(p, want) != hipSuccess) return false;
-  *cap = want;
-  return true;
-}
-}  // namespace
 
 md_def_batch *md_def_batch_open(md_ctx *ctx, int format, const md_deflate_params *params, size_t n) {
   if (!ctx || !params || n == 0 || n > 0x7fffffffu) return nullptr;
   if (md_validate_deflate_params(ctx, format, params) != MD_OK) return nullptr;
-  md::DeviceGuard guard(md_i_device(ctx));
+  md::DeviceGuard guard(ctx->device);
   md_def_batch *b = new md_def_batch();
   b->ctx = ctx;
   b->format = format;
@@ -655,10 +638,8 @@ md_def_batch *md_def_batch_open(md_ctx *ctx, int format, const md_deflate_params
   b->n = n;
   b->e.resize(n);
   for (auto &x : b->e) x.checksum = format == MD_FORMAT_GZIP ? 0u : 1u;
-  if (hipMalloc(&b->d_state, n * (size_t)md::defl::kPieceState) != hipSuccess ||
-      hipMalloc(&b->d_queue, n * (size_t)params->queue_len * 4) != hipSuccess) {
-    hipFree(b->d_state);
-    hipFree(b->d_queue);
+  if (b->d_state.reserve(ctx, n * (size_t)md::defl::kPieceState, nullptr) != MD_OK ||
+      b->d_queue.reserve(ctx, n * (size_t)params->queue_len * 4, nullptr) != MD_OK) {
     delete b;
     return nullptr;
   }
@@ -666,12 +647,8 @@ md_def_batch *md_def_batch_open(md_ctx *ctx, int format, const md_deflate_params
 }
 void md_def_batch_close(md_def_batch *b) {
   if (!b) return;
-  md::DeviceGuard guard(md_i_device(b->ctx));
-  hipStreamSynchronize(md_i_stream(b->ctx));
-  void *bufs[] = {b->d_text[0], b->d_text[1], b->d_fresh, b->d_out, b->d_state, b->d_queue, b->d_desc, b->d_gdesc};
-  for (void *p : bufs)
-    if (p) hipFree(p);
-  if (b->h_stage) hipHostFree(b->h_stage);
+  md::DeviceGuard guard(b->ctx->device);
+  hipStreamSynchronize(b->ctx->stream);
   delete b;
 }
 int md_def_batch_src(md_def_batch *b, size_t i, const uint8_t *buf, size_t len) {
@@ -714,9 +691,9 @@ size_t md_def_batch_out(md_def_batch *b, size_t i, uint8_t *dst, size_t cap) {
     got = k;
   }
   if (got < cap && x.served < x.out_len) {
-    md::DeviceGuard guard(md_i_device(b->ctx));
+    md::DeviceGuard guard(b->ctx->device);
     const size_t left = (size_t)(x.out_len - x.served), k = left < cap - got ? left : cap - got;
-    if (hipMemcpy(dst + got, (const uint8_t *)b->d_out + x.out_off + x.served, k, hipMemcpyDeviceToHost) != hipSuccess) return got;
+    if (hipMemcpy(dst + got, b->d_out.as<const uint8_t>() + x.out_off + x.served, k, hipMemcpyDeviceToHost) != hipSuccess) return got;
     x.served += k;
     got += k;
   }
@@ -726,8 +703,8 @@ size_t md_def_batch_out(md_def_batch *b, size_t i, uint8_t *dst, size_t cap) {
 // input has not been signalled since) sit the launch out.  MD_OK, or the call-level error.
 int md_def_batch_encode(md_def_batch *b) {
   if (!b) return MD_E_INVALID_ARGUMENT;
-  md::DeviceGuard guard(md_i_device(b->ctx));
-  hipStream_t st = md_i_stream(b->ctx);
+  md::DeviceGuard guard(b->ctx->device);
+  hipStream_t st = b->ctx->stream;
   const size_t n = b->n, ql = (size_t)b->params.queue_len;
   // output that was not fetched yet moves to the host: the launch writes a new output blob
   for (size_t i = 0; i < n; i++) {
@@ -735,14 +712,14 @@ int md_def_batch_encode(md_def_batch *b) {
     if (x.served < x.out_len) {
       const size_t k = (size_t)(x.out_len - x.served), at = x.held.size();
       x.held.resize(at + k);
-      if (hipMemcpy(x.held.data() + at, (const uint8_t *)b->d_out + x.out_off + x.served, k, hipMemcpyDeviceToHost) != hipSuccess) return MD_E_HIP;
+      if (hipMemcpy(x.held.data() + at, b->d_out.as<const uint8_t>() + x.out_off + x.served, k, hipMemcpyDeviceToHost) != hipSuccess) return MD_E_HIP;
     }
     x.out_len = x.served = 0;
   }
   std::vector<uint64_t> text_off(n), text_len(n), abs_len(n), out_off(n), out_cap(n), w0(n), rebase(n, 0), out_len(n, 0), g(6 * n);
   std::vector<uint32_t> flags(n), sum(n), isize(n);
   std::vector<int32_t> status(n, 0);
-  const uint64_t far = (md_i_test_flags(b->ctx) & 16) ? (uint64_t)1 << 17 : (uint64_t)1 << 31;
+  const uint64_t far = (b->ctx->test_flags & 16) ? (uint64_t)1 << 17 : (uint64_t)1 << 31;
   uint64_t tpos = 0, fpos = 0, opos = 0;
   uint32_t skip = 0xffffffffu;
   size_t active = 0;
@@ -788,28 +765,23 @@ int md_def_batch_encode(md_def_batch *b) {
   }
   if (active == 0) return MD_OK;
   const int nxt = b->cur ^ 1;
-  if (!regrow(&b->d_text[nxt], &b->text_cap[nxt], (size_t)tpos + 64) || !regrow(&b->d_fresh, &b->fresh_cap, (size_t)fpos + 64) ||
-      !regrow(&b->d_out, &b->out_cap, (size_t)opos + 64) || !regrow(&b->d_gdesc, &b->gdesc_cap, 6 * n * 8))
-    return MD_E_OUT_OF_MEMORY;
-  if (fpos + 64 > b->stage_cap) {
-    if (b->h_stage) hipHostFree(b->h_stage);
-    b->h_stage = nullptr;
-    b->stage_cap = 0;
-    const size_t want = (size_t)fpos + (size_t)fpos / 4 + 4096;
-    if (hipHostMalloc((void **)&b->h_stage, want, hipHostMallocDefault) != hipSuccess) return MD_E_OUT_OF_MEMORY;
-    b->stage_cap = want;
-  }
+  int grc = b->d_text[nxt].reserve_blob(b->ctx, (size_t)tpos + 64);
+  if (grc == MD_OK) grc = b->d_fresh.reserve_blob(b->ctx, (size_t)fpos + 64);
+  if (grc == MD_OK) grc = b->d_out.reserve_blob(b->ctx, (size_t)opos + 64);
+  if (grc == MD_OK) grc = b->d_gdesc.reserve_blob(b->ctx, 6 * n * 8);
+  if (grc == MD_OK) grc = b->h_stage.reserve(b->ctx, (size_t)fpos + 64, nullptr, md::blob_room((size_t)fpos));
+  if (grc != MD_OK) return grc;
   for (size_t i = 0; i < n; i++)
-    if (g[6 * i + 3]) memcpy(b->h_stage + g[6 * i + 2], b->e[i].fresh.data(), (size_t)g[6 * i + 3]);
-  if (fpos && hipMemcpyAsync(b->d_fresh, b->h_stage, (size_t)fpos, hipMemcpyHostToDevice, st) != hipSuccess) return MD_E_HIP;
-  if (hipMemcpyAsync(b->d_gdesc, g.data(), 6 * n * 8, hipMemcpyHostToDevice, st) != hipSuccess) return MD_E_HIP;
-  if (md_launch_piece_gather((uint32_t)n, (const uint8_t *)b->d_text[b->cur], (const uint8_t *)b->d_fresh, (uint8_t *)b->d_text[nxt],
-                             (const uint64_t *)b->d_gdesc, st) != 0)
+    if (g[6 * i + 3]) memcpy(b->h_stage.as<uint8_t>() + g[6 * i + 2], b->e[i].fresh.data(), (size_t)g[6 * i + 3]);
+  if (fpos && hipMemcpyAsync(b->d_fresh.p, b->h_stage.p, (size_t)fpos, hipMemcpyHostToDevice, st) != hipSuccess) return MD_E_HIP;
+  if (hipMemcpyAsync(b->d_gdesc.p, g.data(), 6 * n * 8, hipMemcpyHostToDevice, st) != hipSuccess) return MD_E_HIP;
+  if (md_launch_piece_gather((uint32_t)n, b->d_text[b->cur].as<const uint8_t>(), b->d_fresh.as<const uint8_t>(), b->d_text[nxt].as<uint8_t>(),
+                             b->d_gdesc.as<const uint64_t>(), st) != 0)
     return MD_E_HIP;
   md_pieces_io io{text_off.data(), text_len.data(), abs_len.data(), out_off.data(), out_cap.data(), w0.data(), rebase.data(),
                   flags.data(), sum.data(), isize.data(), out_len.data(), status.data()};
-  const int rc = md_i_pieces_run(b->ctx, b->format, &b->params, n, (const uint8_t *)b->d_text[nxt], (uint8_t *)b->d_out, b->d_state,
-                                 b->d_queue, &b->d_desc, &b->desc_bytes, &io, skip == 0xffffffffu ? 0u : skip);
+  const int rc = md_i_pieces_run(b->ctx, b->format, &b->params, n, b->d_text[nxt].as<const uint8_t>(), b->d_out.as<uint8_t>(), b->d_state.p,
+                                 b->d_queue.p, b->d_desc, &io, skip == 0xffffffffu ? 0u : skip);
   if (rc != MD_OK) return rc;
   b->cur = nxt;
   for (size_t i = 0; i < n; i++) {
@@ -873,13 +845,10 @@ struct md_inf_batch {
     uint64_t attempts = 0;      // rounds the decoder took part in (md_i_inf_batch_attempts)
   };
   std::vector<Dec> d;
-  void *d_in[2] = {nullptr, nullptr}, *d_out[2] = {nullptr, nullptr};
-  size_t in_cap[2] = {0, 0}, out_cap[2] = {0, 0};
+  md::DevBuf d_in[2], d_out[2];
   int cur = 0;
-  void *d_fresh = nullptr, *d_desc = nullptr, *d_pack = nullptr;
-  size_t fresh_cap = 0, desc_cap = 0, pack_cap = 0;
-  uint8_t *h_stage = nullptr, *h_pack = nullptr;  // pinned: the fresh bytes of a round, packed / the packed output
-  size_t stage_cap = 0, hpack_cap = 0;
+  md::DevBuf d_fresh, d_desc, d_pack;
+  md::PinnedBuf h_stage, h_pack;  // the fresh bytes of a round, packed / the packed output
   uint64_t launches = 0;      // inflate launches so far (md_i_inf_batch_launches)
 };
 namespace {
@@ -887,31 +856,6 @@ void inf_slot_clear(md_inf_batch::Dec *x, int format) {
   *x = md_inf_batch::Dec();
   x->format = format;
   x->need = 1;  // (md_inf_*'s rule with md_inf_chunk_bytes(1): a piece as soon as input has arrived)
-}
-bool regrow_pinned(uint8_t **p, size_t *cap, size_t need) {
-  if (need <= *cap) return true;
-  if (*p) hipHostFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  const size_t want = need + need / 4 + 4096;
-  if (hipHostMalloc((void **)p, want, hipHostMallocDefault) != hipSuccess) return false;
-  *cap = want;
-  return true;
-}
-// a device blob that must keep its first `keep` bytes when it grows
-bool regrow_keep(void **p, size_t *cap, size_t need, size_t keep, hipStream_t st) {
-  if (need <= *cap) return true;
-  void *q = nullptr;
-  const size_t want = need + need / 4 + 4096;
-  if (hipMalloc(&q, want) != hipSuccess) return false;
-  if (keep && (hipMemcpyAsync(q, *p, keep, hipMemcpyDeviceToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)) {
-    hipFree(q);
-    return false;
-  }
-  if (*p) hipFree(*p);
-  *p = q;
-  *cap = want;
-  return true;
 }
 uint64_t up(uint64_t x, uint64_t a) { return (x + a - 1) & ~(a - 1); }
 
@@ -923,7 +867,7 @@ uint64_t up(uint64_t x, uint64_t a) { return (x + a - 1) & ~(a - 1); }
 int inf_batch_launch(md_inf_batch *b, const std::vector<size_t> &rows, bool first, int old, int nxt, uint64_t *opos_io,
                      std::vector<size_t> *grown) {
   using md::ib::HandRow;
-  hipStream_t st = md_i_stream(b->ctx);
+  hipStream_t st = b->ctx->stream;
   const size_t m = rows.size();
   std::vector<char> is_row(first ? b->n : 0, 0);
   for (size_t i : rows)
@@ -1003,26 +947,29 @@ int inf_batch_launch(md_inf_batch *b, const std::vector<size_t> &rows, bool firs
       r64[1 * m + k] = b->d[rows[k]].in.size();
     }
   }
-  if ((first && !regrow(&b->d_in[nxt], &b->in_cap[nxt], (size_t)ipos + 64)) ||
-      !(first ? regrow(&b->d_out[nxt], &b->out_cap[nxt], (size_t)opos + 64)
-              : regrow_keep(&b->d_out[nxt], &b->out_cap[nxt], (size_t)opos + 64, (size_t)*opos_io, st)) ||
-      !regrow(&b->d_fresh, &b->fresh_cap, (size_t)fpos + 64) || !regrow(&b->d_desc, &b->desc_cap, all_w * 8 + 64) ||
-      !regrow(&b->d_pack, &b->pack_cap, (size_t)pack + 64) || !regrow_pinned(&b->h_stage, &b->stage_cap, (size_t)fpos + 64))
-    return MD_E_OUT_OF_MEMORY;
+  // (a launch again keeps the output regions the round has used)
+  int grc = first ? b->d_in[nxt].reserve_blob(b->ctx, (size_t)ipos + 64) : MD_OK;
+  if (grc == MD_OK)
+    grc = first ? b->d_out[nxt].reserve_blob(b->ctx, (size_t)opos + 64) : b->d_out[nxt].reserve_keep(b->ctx, (size_t)opos + 64, (size_t)*opos_io);
+  if (grc == MD_OK) grc = b->d_fresh.reserve_blob(b->ctx, (size_t)fpos + 64);
+  if (grc == MD_OK) grc = b->d_desc.reserve_blob(b->ctx, all_w * 8 + 64);
+  if (grc == MD_OK) grc = b->d_pack.reserve_blob(b->ctx, (size_t)pack + 64);
+  if (grc == MD_OK) grc = b->h_stage.reserve_blob(b->ctx, (size_t)fpos + 64);
+  if (grc != MD_OK) return grc;
   if (first) {
     for (size_t j = 0; j < L; j++) {
       const md_inf_batch::Dec &x = b->d[live[j]];
       const uint64_t *g = gin + 6 * j;
-      if (g[3]) memcpy(b->h_stage + g[2], x.in.data() + x.dev_tail, (size_t)g[3]);
+      if (g[3]) memcpy(b->h_stage.as<uint8_t>() + g[2], x.in.data() + x.dev_tail, (size_t)g[3]);
     }
-    if (fpos && hipMemcpyAsync(b->d_fresh, b->h_stage, (size_t)fpos, hipMemcpyHostToDevice, st) != hipSuccess) return MD_E_HIP;
+    if (fpos && hipMemcpyAsync(b->d_fresh.p, b->h_stage.p, (size_t)fpos, hipMemcpyHostToDevice, st) != hipSuccess) return MD_E_HIP;
   }
-  uint64_t *dd = (uint64_t *)b->d_desc;
+  uint64_t *dd = b->d_desc.as<uint64_t>();
   if (hipMemcpyAsync(dd, desc.data(), up_w * 8, hipMemcpyHostToDevice, st) != hipSuccess) return MD_E_HIP;
-  if (first && md_launch_piece_gather((uint32_t)L, (const uint8_t *)b->d_in[old], (const uint8_t *)b->d_fresh, (uint8_t *)b->d_in[nxt],
+  if (first && md_launch_piece_gather((uint32_t)L, b->d_in[old].as<const uint8_t>(), b->d_fresh.as<const uint8_t>(), b->d_in[nxt].as<uint8_t>(),
                                       dd, st) != 0)
     return MD_E_HIP;
-  if (md_launch_piece_gather((uint32_t)L, (const uint8_t *)b->d_out[old], (const uint8_t *)b->d_fresh, (uint8_t *)b->d_out[nxt],
+  if (md_launch_piece_gather((uint32_t)L, b->d_out[old].as<const uint8_t>(), b->d_fresh.as<const uint8_t>(), b->d_out[nxt].as<uint8_t>(),
                              dd + gin_w, st) != 0)
     return MD_E_HIP;
   uint64_t *d64 = dd + gin_w + 6 * L;
@@ -1030,14 +977,14 @@ int inf_batch_launch(md_inf_batch *b, const std::vector<size_t> &rows, bool firs
   uint64_t *o64 = d64 + 6 * m;
   uint32_t *o32 = (uint32_t *)(o64 + 4 * m);
   HandRow *dres = (HandRow *)(o64 + 6 * m);
-  const int rc = md_inflate_continue_batch_device(b->ctx, m, (const uint8_t *)b->d_in[nxt], d64, d64 + m, (uint8_t *)b->d_out[nxt],
+  const int rc = md_inflate_continue_batch_device(b->ctx, m, b->d_in[nxt].as<const uint8_t>(), d64, d64 + m, b->d_out[nxt].as<uint8_t>(),
                                                   d64 + 2 * m, d64 + 3 * m, d32, d32 + m, d32 + 2 * m, o64, o64 + m, (int32_t *)o32,
                                                   o32 + m, o64 + 2 * m, o64 + 3 * m, o32 + 2 * m, o32 + 3 * m);
   if (rc != MD_OK) return rc;
   b->launches++;
   const md::ib::HandIn hin{d64 + 2 * m, d64 + 3 * m, o64, o64 + m, o64 + 2 * m, o64 + 3 * m, d32 + m, d32 + 3 * m, o32 + m, o32 + 2 * m,
                            (const int32_t *)o32};
-  if (md_launch_inf_handout((uint32_t)m, hin, (const uint8_t *)b->d_out[nxt], dres, (uint8_t *)b->d_pack,
+  if (md_launch_inf_handout((uint32_t)m, hin, b->d_out[nxt].as<const uint8_t>(), dres, b->d_pack.as<uint8_t>(),
                             b->format == MD_FORMAT_GZIP, st) != 0)
     return MD_E_HIP;
   std::vector<HandRow> res(m);
@@ -1047,8 +994,8 @@ int inf_batch_launch(md_inf_batch *b, const std::vector<size_t> &rows, bool firs
   const uint64_t total = m ? res[m - 1].pack_off + res[m - 1].len : 0;
   if (total > pack) return MD_E_HIP;  // (cannot happen: every range lies inside its row's room)
   if (total) {
-    if (!regrow_pinned(&b->h_pack, &b->hpack_cap, (size_t)total)) return MD_E_OUT_OF_MEMORY;
-    if (hipMemcpyAsync(b->h_pack, b->d_pack, (size_t)total, hipMemcpyDeviceToHost, st) != hipSuccess ||
+    if (b->h_pack.reserve_blob(b->ctx, (size_t)total) != MD_OK) return MD_E_OUT_OF_MEMORY;
+    if (hipMemcpyAsync(b->h_pack.p, b->d_pack.p, (size_t)total, hipMemcpyDeviceToHost, st) != hipSuccess ||
         hipStreamSynchronize(st) != hipSuccess)
       return MD_E_HIP;
   }
@@ -1070,7 +1017,7 @@ int inf_batch_launch(md_inf_batch *b, const std::vector<size_t> &rows, bool firs
       grown->push_back(rows[k]);
       continue;
     }
-    if (h.len) x.held.insert(x.held.end(), b->h_pack + h.pack_off, b->h_pack + h.pack_off + h.len);
+    if (h.len) x.held.insert(x.held.end(), b->h_pack.as<uint8_t>() + h.pack_off, b->h_pack.as<uint8_t>() + h.pack_off + h.len);
     if (h.kind == md::ib::kKindContinue) {
       const uint64_t skip = h.tail_bits >> 3, keep = h.end < 32768 ? h.end : 32768;
       frame_continue(&x, h.tail_bits, h.crc, h.len, h.sum, 1);
@@ -1103,13 +1050,8 @@ md_inf_batch *md_inf_batch_open(md_ctx *ctx, int format, size_t n) {
 }
 void md_inf_batch_close(md_inf_batch *b) {
   if (!b) return;
-  md::DeviceGuard guard(md_i_device(b->ctx));
-  hipStreamSynchronize(md_i_stream(b->ctx));
-  void *bufs[] = {b->d_in[0], b->d_in[1], b->d_out[0], b->d_out[1], b->d_fresh, b->d_desc, b->d_pack};
-  for (void *p : bufs)
-    if (p) hipFree(p);
-  if (b->h_stage) hipHostFree(b->h_stage);
-  if (b->h_pack) hipHostFree(b->h_pack);
+  md::DeviceGuard guard(b->ctx->device);
+  hipStreamSynchronize(b->ctx->stream);
   delete b;
 }
 int md_inf_batch_src(md_inf_batch *b, size_t i, const uint8_t *buf, size_t len) {
@@ -1150,7 +1092,7 @@ int md_inf_batch_decode(md_inf_batch *b) {
   }
   for (auto &x : b->d) x.round_in = 0;
   if (rows.empty()) return MD_OK;
-  md::DeviceGuard guard(md_i_device(b->ctx));
+  md::DeviceGuard guard(b->ctx->device);
   const int old = b->cur, nxt = old ^ 1;
   uint64_t opos = 0;
   std::vector<size_t> grown;

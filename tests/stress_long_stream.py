@@ -1,4 +1,4 @@
-"""randomized stress of the whole-chip path for ONE long stream (capi.cpp inflate_parallel) against libz and the serial
+"""randomized stress of the whole-chip path for ONE long stream (capi_long_stream.cpp inflate_parallel) against libz and the serial
 path (test infrastructure; run on the GPU box):
     python tests/stress_long_stream.py [streams] [seed]
 Long streams made of stretches of every kind (text, noise in stored blocks, runs, compressed data inside the plaintext),

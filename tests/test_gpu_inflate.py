@@ -336,7 +336,7 @@ def test_one_long_stream_by_the_whole_chip(eng):
 def test_long_pieces_of_the_decode_protocol(eng):
     """De.Inf.decode on a long stream (lib/de.ml:1427-1474, the tool's loop bin/decompress.ml:77-100): a piece of the
     protocol that is long enough is decoded by the whole chip up to its last block boundary, the incomplete block behind
-    it by the serial path (capi.cpp continue_parallel) - same bytes, same signals at the end, Adler-32 and CRC-32 carried
+    it by the serial path (capi_long_stream.cpp continue_parallel) - same bytes, same signals at the end, Adler-32 and CRC-32 carried
     across the pieces; a stream cut inside a block still ends in the serial path's `Malformed"""
     import decompress_amd
     from decompress_amd import de, engine, workloads
@@ -965,7 +965,7 @@ def test_host_entry_points_in_slices(eng, pinned):
 @pytest.mark.parametrize("pinned", [True, False], ids=["pinned", "pageable"])
 def test_deflate_host_entry_point_in_slices_of_positions(eng, oracle, pinned):
     """md_deflate_batch_host on LONG buffers at equal distances (C3's shape): the batch goes through the kernels in slices
-    of positions with its input arriving and its finished output leaving as strided copies under them (capi.cpp
+    of positions with its input arriving and its finished output leaving as strided copies under them (capi_deflate.cpp
     deflate_host_positions) - bytes, lengths, statuses and Adler-32 equal the one-after-the-other form's and the oracle's;
     ragged lengths, an empty buffer, one buffer too small for its output"""
     import decompress_amd

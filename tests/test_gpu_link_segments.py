@@ -1,4 +1,4 @@
-"""ONE long stream's hash chains built in segments by many workgroups instead of by one (capi.cpp link_segments,
+"""ONE long stream's hash chains built in segments by many workgroups instead of by one (capi_deflate.cpp link_segments,
 csrc/deflate_chunked.hip).  The bytes must be the oracle's and the one-workgroup path's in every case, and the
 segments must have run (Engine.link_segments).  Small "deflate_link_segment_min" and segment sizes make moderate inputs
 take it, with many segment boundaries.  Needs an MI355X: `pytest -m gpu`."""

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Run ON THE GPU BOX: one long stream through the Higher.uncompress entry points (round 6: decoded in pieces by the
-whole chip, capi.cpp inflate_parallel) - bytes against libz, host-to-host rate, what the path did."""
+whole chip, capi_long_stream.cpp inflate_parallel) - bytes against libz, host-to-host rate, what the path did."""
 import ctypes, sys, time, zlib, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import decompress_amd

@@ -1,4 +1,4 @@
-"""Run ON THE GPU BOX with MD_DEBUG_HOSTPATH=1: the phases of the whole-chip path for one long stream (capi.cpp par_decode
+"""Run ON THE GPU BOX with MD_DEBUG_HOSTPATH=1: the phases of the whole-chip path for one long stream (capi_long_stream.cpp par_decode
 prints them): body on the device, candidates found, pieces decoded, windows + resolve."""
 import ctypes, sys, time, zlib, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
