@@ -1,5 +1,5 @@
 // capi_deflate.cpp — the encoder's entry points: the launch of the deflate kernels over a batch, Def.Ns, batches in
-// slices of positions, the stream in pieces of stream_shim.cpp, host buffers, and the partial drivers.
+// slices of positions, the stream in pieces of stream_def.cpp, host buffers, and the partial drivers.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -251,7 +251,7 @@ static int check_params(md_ctx *ctx, int format, const md_deflate_params *p, md_
   return MD_OK;
 }
 
-// what md_def_encoder checks before it keeps the parameters (stream_shim.cpp); not part of the public header
+// what md_def_encoder checks before it keeps the parameters (stream_def.cpp); not part of the public header
 int md_validate_deflate_params(md_ctx *ctx, int format, const md_deflate_params *params) {
   if (!ctx) return MD_E_INVALID_ARGUMENT;
   md_deflate_params q;
@@ -516,7 +516,7 @@ int md_deflate_batch_device(md_ctx *ctx, int format, const md_deflate_params *pa
                               d_checksum, nullptr);
 }
 
-// ---- the encoder shim's stream in pieces (stream_shim.cpp): not part of the public ABI ------------------------------
+// ---- the encoder shim's stream in pieces (stream_def.cpp): not part of the public ABI ------------------------------
 // A launch takes the text [w0, n) of ONE stream - the last 64 KiB the launch before already saw plus what arrived since -
 // and goes on from the state that launch left in device memory (the two structs of the sequential kernel, 12 KiB, and
 // the stream's command queue): the matcher answers `Await at the end of the piece exactly where the reference's would
@@ -583,7 +583,7 @@ int md_i_piece_run(md_ctx *ctx, md_piece *p, int format, const md_deflate_params
   *status = st;
   return MD_OK;
 }
-// One piece of each of n streams in ONE launch of the kernels (md_def_batch, stream_shim.cpp): texts, outputs, states
+// One piece of each of n streams in ONE launch of the kernels (md_def_batch, stream_def.cpp): texts, outputs, states
 // and queues are the caller's device buffers, the descriptors host arrays of n entries.  flags as struct Piece's (bit 3:
 // the stream takes no part in this launch).  Synchronous: the results are read back.
 int md_i_pieces_run(md_ctx *ctx, int format, const md_deflate_params *params, size_t n, const uint8_t *d_text, uint8_t *d_out,

@@ -1,4 +1,4 @@
-// ctx.hpp — what the host translation units (capi*.cpp, stream_shim.cpp) share and no kernel sees: the context, the one
+// ctx.hpp — what the host translation units (capi*.cpp, stream_*.cpp) share and no kernel sees: the context, the one
 // type that owns device or pinned memory, the error helpers, and every function that one of those files defines and
 // another calls.  The defining file and every caller include it, as with internal.hpp.  Plain host C++.
 #pragma once
@@ -30,6 +30,10 @@ int fail(md_ctx *ctx, int code, const char *what, hipError_t e = hipSuccess);
   if (!guard_.ok) return fail(ctx, MD_E_HIP, "hipSetDevice")
 
 namespace md {
+
+// most input that one src call of a streaming encoder, or one round of a decoder of a batch, hands over: positions
+// within a launch are 32-bit
+constexpr size_t kSrcMax = (size_t)1 << 30;
 
 // what the batch shims ask of the allocator for a blob of `need` bytes: a quarter and 4 KiB of headroom
 inline size_t blob_room(size_t need) { return need + need / 4 + 4096; }
@@ -214,7 +218,7 @@ int one_through_batch(md_ctx *ctx, const void *src, size_t src_len, void *dst, s
   return status;
 }
 
-// ---- capi_deflate.cpp: the encoder in pieces, as stream_shim.cpp drives it (not part of the public ABI) ----
+// ---- capi_deflate.cpp: the encoder in pieces, as stream_def.cpp drives it (not part of the public ABI) ----
 // The device goes on from the state the piece before left, so neither side keeps more of the stream than the 64 KiB the
 // matcher can reach back plus the piece.
 struct md_piece;

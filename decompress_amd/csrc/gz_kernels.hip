@@ -135,12 +135,12 @@ __global__ __launch_bounds__(kWave) void gz_finish_kernel(
 }
 
 
-// The text of n streaming encoders for their next launch (md_def_batch, stream_shim.cpp): stream i's region of the new
+// The text of n streaming encoders for their next launch (md_def_batch, stream_def.cpp): stream i's region of the new
 // blob is the tail of its region in the old one (the window the matcher can still reach) followed by the bytes that
-// arrived since (packed in `fresh`).  d[6 i ..]: old offset of the tail, its length, offset in `fresh`, fresh length,
-// new offset (unused).  Grid = (chunks of 64 KiB, stream): a thread copies 16 destination-aligned bytes per step (the
-// source is read with unaligned 16-byte loads), the few bytes in front of the first and behind the last aligned chunk of a
-// part one by one (it was one byte per thread and step, one workgroup per stream).
+// arrived since (packed in `fresh`).  d[i]: md::GatherRow (internal.hpp).  Grid = (chunks of 64 KiB, stream): a thread
+// copies 16 destination-aligned bytes per step (the source is read with unaligned 16-byte loads), the few bytes in front of
+// the first and behind the last aligned chunk of a part one by one (it was one byte per thread and step, one
+// workgroup per stream).
 constexpr uint32_t kGatherChunk = 65536;
 __device__ __forceinline__ void gather_part(uint8_t *__restrict__ o, const uint8_t *__restrict__ a, uint64_t len, uint64_t c0, uint64_t c1) {
   // bytes [c0, c1) of the part (c0, c1 within [0, len]); 16-byte steps on o's alignment
@@ -158,9 +158,13 @@ __device__ __forceinline__ void gather_part(uint8_t *__restrict__ o, const uint8
   (void)len;
 }
 __global__ __launch_bounds__(256) void piece_gather_kernel(uint32_t n, const uint8_t *__restrict__ old_blob, const uint8_t *__restrict__ fresh,
-                                                           uint8_t *__restrict__ new_blob, const uint64_t *__restrict__ d) {
+                                                           uint8_t *__restrict__ new_blob, const GatherRow *__restrict__ d) {
   for (uint32_t i = blockIdx.y; i < n; i += gridDim.y) {
-    const uint64_t toff = d[6 * i], tlen = d[6 * i + 1], foff = d[6 * i + 2], flen = d[6 * i + 3], noff = d[6 * i + 4];
+    // (the row's words, indexed in 32 bits as they always were: the kernel's code does not depend on how the row is declared)
+    const auto word = [&](size_t off) { return (&d->old_off)[(uint32_t)(sizeof(GatherRow) / 8) * i + (uint32_t)(off / 8)]; };
+    const uint64_t toff = word(offsetof(GatherRow, old_off)), tlen = word(offsetof(GatherRow, old_len)),
+                   foff = word(offsetof(GatherRow, fresh_off)), flen = word(offsetof(GatherRow, fresh_len)),
+                   noff = word(offsetof(GatherRow, new_off));
     uint8_t *o = new_blob + noff;
     // the stream's new text is [0, tlen) from the old blob, then [tlen, tlen + flen) from `fresh`; this workgroup takes the
     // chunks blockIdx.x, blockIdx.x + gridDim.x, ... of it
@@ -197,7 +201,7 @@ extern "C" int md_launch_gz_finish(uint32_t n, const uint8_t *in, const uint64_t
                      body_off, hstatus, out, out_off, out_len, consumed, status, checksum);
   return (int)hipGetLastError();
 }
-extern "C" int md_launch_piece_gather(uint32_t n, const uint8_t *old_blob, const uint8_t *fresh, uint8_t *new_blob, const uint64_t *d,
+extern "C" int md_launch_piece_gather(uint32_t n, const uint8_t *old_blob, const uint8_t *fresh, uint8_t *new_blob, const md::GatherRow *d,
                                       hipStream_t stream) {
   if (n == 0) return 0;
   hipLaunchKernelGGL(md::gz::piece_gather_kernel, dim3(16, n < 65535u ? n : 65535u), dim3(256), 0, stream, n, old_blob, fresh, new_blob, d);

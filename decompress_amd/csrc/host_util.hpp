@@ -1,11 +1,15 @@
-// host_util.hpp — small host-side helpers of capi*.cpp and stream_shim.cpp: checksums of the few bytes the host
-// handles itself, and the device guard of the entry points.
+// host_util.hpp — small host-side helpers of capi*.cpp and stream_*.cpp: checksums of the few bytes the host
+// handles itself, 32-bit reads of header and trailer fields, and the device guard of the entry points.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
 
 namespace md {
+
+// a 32-bit field of a frame: little-endian (GZip's trailer) / big-endian (ZLIB's)
+inline uint32_t le32(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
+inline uint32_t be32(const uint8_t *p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
 
 // Adler-32 going on from `adler` (lib/de.ml:4217-4218 keeps it per fill; the sum is the same)
 inline uint32_t adler32_update(uint32_t adler, const uint8_t *p, size_t n) {

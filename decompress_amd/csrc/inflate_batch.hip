@@ -1,4 +1,4 @@
-// inflate_batch.hip — the hand-out step of many streaming decoders (md_inf_batch_*, stream_shim.cpp), for gfx950.
+// inflate_batch.hip — the hand-out step of many streaming decoders (md_inf_batch_*, stream_inf.cpp), for gfx950.
 //
 // A round of md_inf_batch_decode is one launch of the inflate kernel over the pieces of every decoder that has new input
 // (md_inflate_continue_batch_device: start bit, window and Adler state in, the last block boundary out).  These kernels

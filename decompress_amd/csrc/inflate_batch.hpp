@@ -1,5 +1,5 @@
 // inflate_batch.hpp — what the hand-out kernels of inflate_batch.hip read and write for one row of a launch of
-// md_inflate_continue_batch_device (md_inf_batch, stream_shim.cpp).  Shared by the kernels and the host.
+// md_inflate_continue_batch_device (md_inf_batch, stream_inf.cpp).  Shared by the kernels and the host.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -40,6 +40,6 @@ static_assert(sizeof(HandRow) == 48, "HandRow is copied to the host as is");
 }  // namespace ib
 }  // namespace md
 
-// m rows of one inflate launch: scan, then pack (res: m HandRow; pack: room for the padded ranges, see stream_shim.cpp)
+// m rows of one inflate launch: scan, then pack (res: m HandRow; pack: room for the padded ranges, see stream_inf.cpp)
 extern "C" int md_launch_inf_handout(uint32_t m, md::ib::HandIn in, const uint8_t *out, md::ib::HandRow *res, uint8_t *pack,
                                      int with_crc, hipStream_t stream);

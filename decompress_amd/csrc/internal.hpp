@@ -74,6 +74,13 @@ struct Cont {
 
 }  // namespace wv
 
+// One stream's row of piece_gather_kernel (gz_kernels.hip): its region of the new blob, at new_off, is old_len bytes
+// from old_off of the old blob followed by fresh_len bytes from fresh_off of the packed fresh bytes.
+struct GatherRow {
+  uint64_t old_off, old_len, fresh_off, fresh_len, new_off, reserved;
+};
+static_assert(sizeof(GatherRow) == 48, "GatherRow is uploaded as is: six u64 words");
+
 namespace gzm {
 // input bytes one workgroup of the member scan looks at: it leaves one count per span (gz_members.hip)
 constexpr uint32_t kMarkSpanBytes = 16384;
@@ -146,7 +153,7 @@ int md_launch_crc32(uint32_t n, const uint8_t *data, const uint64_t *off, const 
 int md_launch_gz_finish(uint32_t n, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len, const uint64_t *body_off,
                         const int32_t *hstatus, const uint8_t *out, const uint64_t *out_off, uint64_t *out_len, uint64_t *consumed,
                         int32_t *status, uint32_t *checksum, hipStream_t stream);
-int md_launch_piece_gather(uint32_t n, const uint8_t *old_blob, const uint8_t *fresh, uint8_t *new_blob, const uint64_t *d,
+int md_launch_piece_gather(uint32_t n, const uint8_t *old_blob, const uint8_t *fresh, uint8_t *new_blob, const md::GatherRow *d,
                            hipStream_t stream);
 
 // ---- gz_members.hip: a GZip file of many members (md_gz_members_*, md_bgzf_compress) ----
