@@ -132,6 +132,7 @@ SYMBOLS = [
     ("md_lzo_compress", ctypes.c_int, [c_vp, c_vp, c_sz, c_vp, c_sz, ctypes.POINTER(c_sz)]),
     ("md_gz_members_scan", ctypes.c_int, [c_vp, c_vp, c_sz, c_vp, c_vp, c_vp, c_sz]),
     ("md_gz_members_uncompress", ctypes.c_int, [c_vp, c_vp, c_sz, c_vp, c_sz, c_vp]),
+    ("md_gz_members_last", ctypes.c_int, [c_vp, c_vp]),
     ("md_bgzf_compress_bound", c_sz, [c_sz, c_sz]),
     ("md_bgzf_compress", ctypes.c_int, [c_vp, ctypes.c_int, c_sz, c_vp, c_sz, c_vp, c_sz, c_szp]),
 ]
@@ -140,6 +141,12 @@ SYMBOLS = [
 class GzMembersInfo(ctypes.Structure):
     """md_gz_members_info of include/mdeflate.h"""
     _fields_ = [("members", c_sz), ("consumed", c_sz), ("written", c_sz), ("indexed", ctypes.c_int)]
+
+
+class GzMembersStats(ctypes.Structure):
+    """md_gz_members_stats of include/mdeflate.h"""
+    _fields_ = [("path", ctypes.c_int)] + [(k, c_sz) for k in ("candidates", "spans_decoded", "members_device", "members_host",
+                                                                "spans_long", "spans_no_room", "spans_implausible")]
 
 
 class GzMeta(ctypes.Structure):

@@ -253,6 +253,11 @@ int md_set_option(md_ctx *ctx, const char *key, int value) {
     ctx->link_seg = (size_t)value << 10;
     return MD_OK;
   }
+  if (!strcmp(key, "gz_members_speculate")) {  // md_gz_members_uncompress, a file without size fields: 1 = members found by speculation, one batch
+    if (value != 0 && value != 1) return fail(ctx, MD_E_INVALID_ARGUMENT, "gz_members_speculate is 0 or 1");
+    ctx->gzm_speculate = value != 0;
+    return MD_OK;
+  }
   if (!strcmp(key, "host_pipeline_slices")) {  // md_*_batch_host: slices of streams in flight (1 = no overlap of copies and kernels)
     if (value < 1 || value > 64) return fail(ctx, MD_E_INVALID_ARGUMENT, "host_pipeline_slices is 1 .. 64");
     ctx->host_slices_max = value;

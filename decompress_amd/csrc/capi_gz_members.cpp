@@ -1,6 +1,8 @@
 // capi_gz_members.cpp — a GZip file of many members (mdeflate.h: md_gz_members_*, md_bgzf_*).
 #include <string.h>
 
+#include <vector>
+
 #include "ctx.hpp"
 #include "gz_rfc.hpp"
 
@@ -110,6 +112,37 @@ int md_gz_members_scan(md_ctx *ctx, const uint8_t *src, size_t src_len, md_gz_me
   return MD_OK;
 }
 
+// One member at *pos, as libz reads it: header on the host, the body through md_de_inf_ns_inflate straight into dst behind
+// the *written bytes it holds, CRC-32 and ISIZE.  MD_OK: *pos is the byte behind its trailer and *written counts its
+// bytes.  Anything else (negative: the library's own errors) leaves both alone.
+static int gzm_member(md_ctx *ctx, const uint8_t *src, size_t len, uint8_t *dst, size_t cap, size_t *pos, size_t *written) {
+  uint64_t hdr = 0;
+  int st = md::gz::rfc_header(src + *pos, len - *pos, &hdr);
+  if (st != MD_OK) return st;
+  const size_t body = *pos + (size_t)hdr, rest = len - body < MD_MAX_INFLATE_IN ? len - body : (size_t)MD_MAX_INFLATE_IN;
+  // where the member ends is the decoder's to say: it gets a window of the file that grows while it runs out of input
+  // (a file of many small members is not copied to the device once per member)
+  size_t used = 0, wrote = 0;
+  for (size_t win = (size_t)256 << 10;; win *= 4) {
+    const size_t in = rest < win ? rest : win;
+    st = md_de_inf_ns_inflate(ctx, src + body, in, dst ? dst + *written : dst, cap - *written, &used, &wrote);
+    if (st != MD_UNEXPECTED_END_OF_INPUT || in == rest) break;
+  }
+  if (st != MD_OK) return st;
+  if (len - body - used < 8) return MD_UNEXPECTED_END_OF_INPUT;
+  const uint8_t *t = src + body + used;
+  uint32_t want = 0, isize = 0;
+  for (int k = 0; k < 4; k++) {
+    want |= (uint32_t)t[k] << (8 * k);
+    isize |= (uint32_t)t[4 + k] << (8 * k);
+  }
+  if (want != md::crc32_update(0, dst + *written, wrote)) return MD_INVALID_CHECKSUM;
+  if (isize != (uint32_t)wrote) return MD_INVALID_SIZE;
+  *pos = body + used + 8;
+  *written += wrote;
+  return MD_OK;
+}
+
 // The general path: member by member from offset `pos` on, `written` bytes and `members` members already in dst.
 static int gzm_general(md_ctx *ctx, const uint8_t *src, size_t len, uint8_t *dst, size_t cap, size_t pos, size_t written, size_t members,
                        md_gz_members_info *info) {
@@ -119,35 +152,9 @@ static int gzm_general(md_ctx *ctx, const uint8_t *src, size_t len, uint8_t *dst
       while (pos < len && src[pos] == 0) pos++;
     }
     if (pos == len) break;
-    uint64_t hdr = 0;
-    st = md::gz::rfc_header(src + pos, len - pos, &hdr);
-    if (st != MD_OK) break;
-    const size_t body = pos + (size_t)hdr, rest = len - body < MD_MAX_INFLATE_IN ? len - body : (size_t)MD_MAX_INFLATE_IN;
-    // where the member ends is the decoder's to say: it gets a window of the file that grows while it runs out of input
-    // (a file of many small members is not copied to the device once per member)
-    size_t used = 0, wrote = 0;
-    for (size_t win = (size_t)256 << 10;; win *= 4) {
-      const size_t in = rest < win ? rest : win;
-      st = md_de_inf_ns_inflate(ctx, src + body, in, dst ? dst + written : dst, cap - written, &used, &wrote);
-      if (st != MD_UNEXPECTED_END_OF_INPUT || in == rest) break;
-    }
+    st = gzm_member(ctx, src, len, dst, cap, &pos, &written);
     if (st < 0) return st;  // (the library's own errors)
     if (st != MD_OK) break;
-    if (len - body - used < 8) {
-      st = MD_UNEXPECTED_END_OF_INPUT;
-      break;
-    }
-    const uint8_t *t = src + body + used;
-    uint32_t want = 0, isize = 0;
-    for (int k = 0; k < 4; k++) {
-      want |= (uint32_t)t[k] << (8 * k);
-      isize |= (uint32_t)t[4 + k] << (8 * k);
-    }
-    if (want != md::crc32_update(0, dst + written, wrote)) st = MD_INVALID_CHECKSUM;
-    else if (isize != (uint32_t)wrote) st = MD_INVALID_SIZE;
-    if (st != MD_OK) break;
-    pos = body + used + 8;
-    written += wrote;
     members++;
   }
   info->members = members;
@@ -156,10 +163,152 @@ static int gzm_general(md_ctx *ctx, const uint8_t *src, size_t len, uint8_t *dst
   return st;
 }
 
+// ---- a file that does not state its members' lengths: speculation and verification (gz_spec.hip) ----
+namespace {
+constexpr uint64_t kSpecMinCandidates = 2;  // fewer: one member (or none that starts at offset 0), the host loop's case
+// what the walk needs of the batch: per candidate its position, the size it promised if the batch let it in, and its flag
+struct SpecBatch {
+  std::vector<uint64_t> cpos, pass;
+  std::vector<uint8_t> flag;
+  const uint8_t *d_out = nullptr;  // the batch's output: span k's bytes at the sum of pass[0 .. k)
+};
+}  // namespace
+
+// (no error text: whatever fails here, the caller clears HIP's error and the host loop reads the file)
+#define SPEC_TRY(expr)                        \
+  do {                                        \
+    if ((int)(expr) != 0) return MD_E_HIP;    \
+  } while (0)
+
+// Mark, compact, spans, classify, the inflate launch over every admitted span, gz_finish, verify.  MD_NOT_HANDLED: fewer
+// than two candidates or none at offset 0.  Three read-backs: the candidate count, the sum of the admitted guesses (it
+// sizes the output), the candidates' 17 bytes each.
+static int gzm_spec_batch(md_ctx *ctx, const uint8_t *d_src, uint64_t len, uint64_t dst_cap, SpecBatch *b) {
+  hipStream_t st = ctx->stream;
+  const uint64_t nspans = (len + md::gzm::kMarkSpanBytes - 1) / md::gzm::kMarkSpanBytes, nwords = (len + 31) / 32;
+  const size_t words_bytes = (size_t)((nwords + nspans + 1) / 2 * 8);  // bitmap and counts, rounded to 8 (as gzm_index)
+  int rc = ctx->scratch[kGzmWs].reserve(ctx, words_bytes + (nspans + 2) * 8, nullptr);
+  if (rc != MD_OK) return rc;
+  uint32_t *bits = (uint32_t *)ctx->scratch[kGzmWs].p, *cnt = bits + nwords;
+  uint64_t *base = (uint64_t *)((uint8_t *)ctx->scratch[kGzmWs].p + words_bytes);
+  SPEC_TRY(md_launch_gzs_mark(d_src, len, bits, cnt, st));
+  SPEC_TRY(md_launch_gzm_scan32(cnt, nspans, base, st));
+  uint64_t C = 0;
+  uint32_t word0 = 0;
+  SPEC_TRY(hipMemcpyAsync(&C, base + nspans, 8, hipMemcpyDeviceToHost, st));
+  SPEC_TRY(hipMemcpyAsync(&word0, bits, 4, hipMemcpyDeviceToHost, st));
+  SPEC_TRY(hipStreamSynchronize(st));
+  if (C < kSpecMinCandidates || !(word0 & 1) || C > 0x7ffffff0ull) return MD_NOT_HANDLED;
+  rc = ctx->scratch[kGzmCand].reserve(ctx, (size_t)C * 8, nullptr);
+  if (rc == MD_OK) rc = ctx->scratch[kGzmDesc].reserve(ctx, (size_t)((10 * C + 1) * 8 + 2 * C * 4 + C), nullptr);
+  if (rc != MD_OK) return rc;
+  uint64_t *cpos = (uint64_t *)ctx->scratch[kGzmCand].p;
+  uint64_t *mlen = (uint64_t *)ctx->scratch[kGzmDesc].p, *body_off = mlen + C, *body_len = body_off + C, *guess = body_len + C, *pass = guess + C,
+           *dec_len = pass + C, *out_cap = dec_len + C, *out_len = out_cap + C, *consumed = out_len + C, *out_off = consumed + C;  // out_off: C + 1
+  int32_t *hstatus = (int32_t *)(out_off + C + 1), *status = hstatus + C;
+  uint8_t *flag = (uint8_t *)(status + C);
+  SPEC_TRY(md_launch_gzs_compact(len, bits, base, cpos, st));
+  SPEC_TRY(md_launch_gzs_spans(C, cpos, len, mlen, st));
+  SPEC_TRY(md_launch_gzm_headers(C, d_src, cpos, mlen, body_off, body_len, guess, hstatus, st));
+  SPEC_TRY(md_launch_gzm_scan64(body_len, C, out_off, st));  // (out_off[C]: the sum of all bodies, for rule (c))
+  SPEC_TRY(md_launch_gzs_classify(C, hstatus, body_len, guess, out_off + C, ctx->par_min, pass, flag, st));
+  SPEC_TRY(md_launch_gzm_scan64(pass, C, out_off, st));
+  uint64_t total = 0;
+  SPEC_TRY(hipMemcpyAsync(&total, out_off + C, 8, hipMemcpyDeviceToHost, st));
+  SPEC_TRY(md_launch_gzs_room(C, body_len, pass, dst_cap, out_off, dec_len, out_cap, flag, st));
+  SPEC_TRY(hipStreamSynchronize(st));
+  // no admitted span ends behind dst_cap (rule (d)), and none behind the sum
+  rc = ctx->scratch[kGzmOut].reserve(ctx, (size_t)(total < dst_cap ? total : dst_cap) + 64, nullptr);
+  if (rc != MD_OK) return rc;
+  uint8_t *d_out = (uint8_t *)ctx->scratch[kGzmOut].p;
+  rc = md_inflate_batch_device(ctx, MD_FORMAT_DEFLATE, (size_t)C, d_src, body_off, dec_len, d_out, out_off, out_cap, out_len, consumed, status, nullptr);
+  if (rc != MD_OK) return rc;
+  SPEC_TRY(md_launch_gz_finish((uint32_t)C, d_src, cpos, mlen, body_off, hstatus, d_out, out_off, out_len, consumed, status, nullptr, st));
+  SPEC_TRY(md_launch_gzs_verify(C, mlen, hstatus, status, consumed, out_len, pass, flag, st));
+  b->cpos.resize((size_t)C);
+  b->pass.resize((size_t)C);
+  b->flag.resize((size_t)C);
+  SPEC_TRY(hipMemcpyAsync(b->cpos.data(), cpos, (size_t)C * 8, hipMemcpyDeviceToHost, st));
+  SPEC_TRY(hipMemcpyAsync(b->pass.data(), pass, (size_t)C * 8, hipMemcpyDeviceToHost, st));
+  SPEC_TRY(hipMemcpyAsync(b->flag.data(), flag, (size_t)C, hipMemcpyDeviceToHost, st));
+  SPEC_TRY(hipStreamSynchronize(st));
+  b->d_out = d_out;
+  return MD_OK;
+}
+
+// The file as libz reads it, from offset 0: a member whose start is a verified span comes from the batch, any other is one
+// step of the host loop.  MD_NOT_HANDLED: nothing of this path stands (info and dst are the caller's to fill again).
+static int gzm_speculative(md_ctx *ctx, const uint8_t *d_src, const uint8_t *src, size_t len, uint8_t *dst, size_t cap, md_gz_members_info *info) {
+  SpecBatch b;
+  int rc = gzm_spec_batch(ctx, d_src, len, cap, &b);
+  if (rc != MD_OK) return MD_NOT_HANDLED;
+  md_gz_members_stats &stats = ctx->gzm_last;
+  const size_t C = b.cpos.size();
+  stats.path = 2;
+  stats.candidates = C;
+  for (size_t k = 0; k < C; k++) {
+    const uint32_t why = b.flag[k] >> 1;
+    stats.spans_decoded += why == md::gzs::kSpanAdmitted;
+    stats.spans_implausible += why == md::gzs::kSpanImplausible;
+    stats.spans_long += why == md::gzs::kSpanLong;
+    stats.spans_no_room += why == md::gzs::kSpanNoRoom;
+  }
+  size_t pos = 0, written = 0, members = 0, k = 0;
+  uint64_t off = 0;                 // where span k's bytes begin in the batch's output: the sum of pass[0 .. k)
+  size_t run_off = 0, run_len = 0;  // accepted members not yet in dst: consecutive spans, so one piece of the batch's output
+  const auto flush = [&]() {
+    const bool ok = run_len == 0 || hipMemcpy(dst + written - run_len, b.d_out + run_off, run_len, hipMemcpyDeviceToHost) == hipSuccess;
+    run_len = 0;
+    return ok;
+  };
+  int st = MD_OK;
+  for (;;) {
+    if (members) {  // (as gzm_general)
+      while (pos < len && src[pos] == 0) pos++;
+    }
+    if (pos == len) break;
+    while (k < C && b.cpos[k] < pos) off += b.pass[k++];
+    if (k < C && b.cpos[k] == pos && (b.flag[k] & md::gzs::kSpanVerified)) {
+      const size_t size = (size_t)b.pass[k];
+      if (size > cap - written) {  // (what the decoder of the host step says of a valid member without room)
+        st = MD_UNEXPECTED_END_OF_OUTPUT;
+        break;
+      }
+      if (run_len == 0) run_off = (size_t)off;
+      run_len += size;
+      written += size;
+      members++;
+      stats.members_device++;
+      pos = k + 1 < C ? (size_t)b.cpos[k + 1] : len;
+      continue;
+    }
+    if (!flush()) return MD_NOT_HANDLED;
+    st = gzm_member(ctx, src, len, dst, cap, &pos, &written);
+    if (st < 0) return st;
+    if (st != MD_OK) break;
+    members++;
+    stats.members_host++;
+  }
+  if (!flush()) return MD_NOT_HANDLED;
+  info->members = members;
+  info->consumed = pos;
+  info->written = written;
+  return st;
+}
+#undef SPEC_TRY
+
+int md_gz_members_last(const md_ctx *ctx, md_gz_members_stats *out) {
+  if (!ctx || !out) return MD_E_INVALID_ARGUMENT;
+  *out = ctx->gzm_last;
+  return MD_OK;
+}
+
 int md_gz_members_uncompress(md_ctx *ctx, const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap, md_gz_members_info *info) {
   if (!ctx) return MD_E_INVALID_ARGUMENT;
   if (!info || (!src && src_len) || (!dst && dst_cap)) return fail(ctx, MD_E_INVALID_ARGUMENT, "null pointer");
   memset(info, 0, sizeof *info);
+  md_gz_members_stats &stats = ctx->gzm_last;
+  stats = md_gz_members_stats{};
   if (src_len == 0) return MD_OK;
   MD_ON_DEVICE(ctx);
   int rc = gzm_upload(ctx, src, src_len);
@@ -169,12 +318,26 @@ int md_gz_members_uncompress(md_ctx *ctx, const uint8_t *src, size_t src_len, ui
   GzmIndex ix;
   rc = gzm_index(ctx, d_src, src_len, &indexed, &ix);
   if (rc != MD_OK) return rc;
-  if (!indexed) return gzm_general(ctx, src, src_len, dst, dst_cap, 0, 0, 0, info);
+  if (!indexed) {
+    if (ctx->gzm_speculate) {
+      rc = gzm_speculative(ctx, d_src, src, src_len, dst, dst_cap, info);
+      if (rc != MD_NOT_HANDLED) return rc;
+      // an allocation, a launch or a copy failed, or the file is no case for it: a valid file must not fail where the host
+      // loop reads it
+      (void)hipGetLastError();
+      stats = md_gz_members_stats{};
+    }
+    rc = gzm_general(ctx, src, src_len, dst, dst_cap, 0, 0, 0, info);
+    stats.members_host = info->members;
+    return rc;
+  }
   info->indexed = 1;
+  stats.path = 1;
   if (ix.total > dst_cap) {
     // The sizes the members state do not fit.  They may lie (a damaged ISIZE), so the host loop decides: it fails where a
     // member really does not fit, or at the member that is wrong - and only in the first case is the answer "more room".
     rc = gzm_general(ctx, src, src_len, dst, dst_cap, 0, 0, 0, info);
+    stats.members_host = info->members;
     if (rc == MD_UNEXPECTED_END_OF_OUTPUT) info->written = (size_t)ix.total;
     return rc;
   }
@@ -199,6 +362,7 @@ int md_gz_members_uncompress(md_ctx *ctx, const uint8_t *src, size_t src_len, ui
     info->members = (size_t)ix.M;
     info->consumed = src_len;
     info->written = (size_t)ix.total;
+    stats.members_device = (size_t)ix.M;
     return MD_OK;
   }
   // a member failed: the members in front of it are good and go out; from the failing one on the host loop speaks, so the
@@ -208,7 +372,10 @@ int md_gz_members_uncompress(md_ctx *ctx, const uint8_t *src, size_t src_len, ui
   HIP_TRY(ctx, hipMemcpyAsync(&at[1], ix.out_off + first, 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
   if (at[1]) HIP_TRY(ctx, hipMemcpy(dst, d_out, (size_t)at[1], hipMemcpyDeviceToHost));
-  return gzm_general(ctx, src, src_len, dst, dst_cap, (size_t)at[0], (size_t)at[1], (size_t)first, info);
+  rc = gzm_general(ctx, src, src_len, dst, dst_cap, (size_t)at[0], (size_t)at[1], (size_t)first, info);
+  stats.members_device = (size_t)first;
+  stats.members_host = info->members - (size_t)first;
+  return rc;
 }
 
 static const size_t kBgzfBlockMax = 0xff00;  // htslib's block: 64 KiB less room for a member that does not compress

@@ -97,7 +97,8 @@ enum Scratch {
   // and descriptors
   kParIn, kParOut, kParWin, kParDesc,
   // a GZip file of many members (md_gz_members_*, md_bgzf_compress): the member scan's bitmap and counts, its candidate
-  // lists, the members' descriptors, and the writer's packed file
+  // lists, the members' descriptors, and the writer's packed file (the reader of a file without size fields decodes its
+  // batch into that one: its host steps go through kHostIn / kHostOut)
   kGzmWs, kGzmCand, kGzmDesc, kGzmOut,
   kScratchCount
 };
@@ -136,6 +137,10 @@ struct md_ctx {
   // the last deflate batch call built its chains in (0 = one workgroup per stream; md_i_link_segments, tests)
   size_t link_seg_min = (size_t)128 << 10, link_seg = 0;
   uint32_t link_last_segments = 0;
+  // a GZip file of many members without size fields: md_set_option "gz_members_speculate" (0 = member by member on the
+  // host, as before there was a speculative path), and which way the last md_gz_members_uncompress went (md_gz_members_last)
+  bool gzm_speculate = true;
+  md_gz_members_stats gzm_last = {};
   std::string err;
 };
 

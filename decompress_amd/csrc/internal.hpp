@@ -85,6 +85,17 @@ namespace gzm {
 // input bytes one workgroup of the member scan looks at: it leaves one count per span (gz_members.hip)
 constexpr uint32_t kMarkSpanBytes = 16384;
 }  // namespace gzm
+
+namespace gzs {
+// a file whose members do not state their lengths (gz_spec.hip): a candidate needs this many bytes in front of the end
+constexpr uint64_t kCandidateMin = 18;
+// rule (c): a span whose body is this share of all bodies (1 / kLongShare) or more is not a stream of the batch.  One
+// stream runs at 0.13-0.22 GiB/s, the full batch at about 233 GiB/s of output: a ratio of roughly a thousand.
+constexpr uint64_t kLongShare = 1024;
+// flag[k] of a span: bit 0 = verified, the bits above it = why the batch left it out
+constexpr uint32_t kSpanVerified = 1;
+constexpr uint32_t kSpanAdmitted = 0, kSpanImplausible = 1, kSpanLong = 2, kSpanNoRoom = 3;
+}  // namespace gzs
 }  // namespace md
 
 extern "C" {
@@ -183,6 +194,22 @@ int md_launch_bgzf_sizes(uint64_t nb, const uint64_t *in_len, const uint64_t *ou
 int md_launch_bgzf_pack(uint64_t nb, const uint8_t *src, const uint64_t *in_off, const uint64_t *in_len, const uint8_t *slots,
                         const uint64_t *slot_off, const uint64_t *out_len, const int32_t *status, const uint64_t *moff, const uint32_t *crc,
                         uint8_t *dst, hipStream_t stream);
+
+// ---- gz_spec.hip: the members of a file without size fields, by speculation (md_gz_members_uncompress) ----
+// bits / cnt as md_launch_gzm_mark's; the counts go through md_launch_gzm_scan32
+int md_launch_gzs_mark(const uint8_t *src, uint64_t len, uint32_t *bits, uint32_t *cnt, hipStream_t stream);
+int md_launch_gzs_compact(uint64_t len, const uint32_t *bits, const uint64_t *base, uint64_t *cpos, hipStream_t stream);
+// mlen[k] = cpos[k + 1] - cpos[k], the last span ends at len; md_launch_gzm_headers takes (cpos, mlen) from here
+int md_launch_gzs_spans(uint64_t C, const uint64_t *cpos, uint64_t len, uint64_t *mlen, hipStream_t stream);
+// *sum_body = the sum of body_len[]; long_min = bytes of body from which rule (c) applies.  pass[k] = guess[k] or 0
+int md_launch_gzs_classify(uint64_t C, const int32_t *hstatus, const uint64_t *body_len, const uint64_t *guess, const uint64_t *sum_body,
+                           uint64_t long_min, uint64_t *pass, uint8_t *flag, hipStream_t stream);
+// out_off = the scan of pass[] (C + 1); leaves in_len (dec_len) / out_off / out_cap of the inflate launch
+int md_launch_gzs_room(uint64_t C, const uint64_t *body_len, const uint64_t *pass, uint64_t dst_cap, uint64_t *out_off, uint64_t *dec_len,
+                       uint64_t *out_cap, uint8_t *flag, hipStream_t stream);
+// behind md_launch_gz_finish
+int md_launch_gzs_verify(uint64_t C, const uint64_t *mlen, const int32_t *hstatus, const int32_t *status, const uint64_t *consumed,
+                         const uint64_t *out_len, const uint64_t *pass, uint8_t *flag, hipStream_t stream);
 
 // ---- lzo_kernels.hip ----
 uint32_t md_lzo_slots(int compress, uint32_t cus);

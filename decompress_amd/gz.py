@@ -4,7 +4,7 @@
 import ctypes
 
 from . import engine as _engine
-from ._lib import GzMembersInfo, GzMeta
+from ._lib import GzMembersInfo, GzMembersStats, GzMeta
 from ._lib import load as _load
 
 # Gz.os, lib/gz.ml:158-246 (RFC1952 numbering)
@@ -91,7 +91,9 @@ def _raw(src):
 class Members:
     """A GZip FILE of many members (RFC 1952 2.2: `cat a.gz b.gz`, bgzip / BGZF), read as libz reads it - not `Gz.Inf`'s
     reading, which `Higher.uncompress` keeps.  A file whose members all carry the BC size field is indexed: its members are
-    found on the device and decoded by one inflate launch; any other file goes member by member."""
+    found on the device and decoded by one inflate launch.  In any other file the device takes every position that looks
+    like a member's start, decodes the spans between them as one batch and keeps those that end in a matching trailer
+    where the next begins; the host walks the file over them and decodes the rest itself (`last_stats` says how it went)."""
 
     @staticmethod
     def scan(src, device=0):
@@ -132,6 +134,16 @@ class Members:
                 keep = 0 if st == _engine.STATUS_CODES["Unexpected_end_of_output"] and info.indexed else info.written
                 return "Error", _engine.STATUS_NAMES[st], d, dst.raw[:keep]
             return "Ok", d, dst.raw[:info.written]
+
+    @staticmethod
+    def last_stats(device=0):
+        """md_gz_members_last: which way the last `uncompress` of this device's engine went -> dict: path (0 general, 1
+        indexed, 2 speculative), candidates, spans_decoded, members_device, members_host, spans_long, spans_no_room,
+        spans_implausible."""
+        eng = _engine.default_engine(device)
+        s = GzMembersStats()
+        eng._check(eng.lib.md_gz_members_last(eng.ctx, ctypes.byref(s)))
+        return {k: getattr(s, k) for k, _ in GzMembersStats._fields_}
 
 
 class Bgzf:

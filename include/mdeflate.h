@@ -175,6 +175,9 @@ int md_synchronize(md_ctx *ctx);
  *                                device, in segments (csrc/deflate_chunked.hip), instead of from one workgroup.  The chains
  *                                are the same, so every status, byte and checksum is the same.
  *   "deflate_link_segment"       KiB of input per segment (0 = default: the stream spread over the CUs, at least 64 KiB).
+ *   "gz_members_speculate"       0 or 1 (default): md_gz_members_uncompress of a file whose members do not all state their
+ *                                lengths.  1: the device finds the members by speculation and decodes them as one batch;
+ *                                0: the host loop, member by member.  Status, info and bytes are the same either way.
  *   "debug_inflate_lds_pad", "debug_known_bounds"   measurement aids of tools/dbg (occupancy curve, known-boundaries floor).
  *   "profile"                    0 / 1: in-kernel phase profile of stream 0 (md_get_profile, a debugging aid).
  * Unknown keys and values out of range: MD_E_INVALID_ARGUMENT. */
@@ -551,10 +554,21 @@ int md_lzo_compress(md_ctx *ctx, const uint8_t *src, size_t src_len, uint8_t *ds
  * reaches it).  The device finds the members of such a file without decoding (a scan of every byte position, pointer
  * jumping over the candidates), parses their headers and decodes ALL of them in one inflate launch, each into a window of
  * its own ISIZE bytes.  Workspace: 1 bit per input byte, 4 bytes per 16 KiB and O(members), grow-only.
- * Any other file takes the GENERAL path: a host loop, member by member - header on the host, the body through the
- * raw-DEFLATE path of md_de_inf_ns_inflate (a long member is decoded by the whole chip), CRC-32 and ISIZE checked on the
- * host - so one round of launches PER MEMBER: right for any file, fast only for files of few, long members.  A member
- * is bound by MD_MAX_INFLATE_IN / MD_MAX_STREAM; the file may be longer. */
+ * Any other file (cat *.gz, WARC / ARC, rotated logs, mgzip, a BGZF file with one damaged BSIZE) is read by SPECULATION:
+ * every position that looks like a member's start (1f 8b 08, no reserved flag bit) is a candidate, the bytes between two
+ * candidates are a span, and every plausible span is decoded as if it were a member, all of them in ONE inflate launch,
+ * each into the size the four bytes at its end promise.  A span is VERIFIED when that decode ends exactly where the next
+ * candidate begins and the CRC-32 and ISIZE found there match.  The host then walks the file as libz does: where it stands
+ * on a verified span it takes the member from the batch (consecutive ones leave by one copy); anywhere else - a candidate
+ * that was none (magic bytes inside a body or a header field), NUL padding behind a member, a member long enough to set
+ * the batch's time (it goes to the whole chip), a member without room, a damaged member - it takes ONE step of the
+ * GENERAL path: header on the host, the body through the raw-DEFLATE path of md_de_inf_ns_inflate, CRC-32 and ISIZE
+ * checked on the host.  The walk only ever stands where libz's reading stands, a verified span is the same header, body
+ * and trailer check that step would make there, and everything else IS that step: status, members, consumed, written and
+ * the bytes are those of the general path for valid and damaged files alike.  A file with fewer than two candidates, or
+ * md_set_option "gz_members_speculate" = 0, takes the general path member by member - one round of launches per member.
+ * md_gz_members_last says which way the last call went.  A member is bound by MD_MAX_INFLATE_IN / MD_MAX_STREAM; the file
+ * may be longer. */
 typedef struct md_gz_members_info {
   size_t members;  /* members decoded (or found, for _scan) */
   size_t consumed; /* bytes of src taken: src_len on success; on failure the offset of the failing member */
@@ -573,6 +587,19 @@ int md_gz_members_scan(md_ctx *ctx, const uint8_t *src, size_t src_len, md_gz_me
  * MD_UNEXPECTED_END_OF_OUTPUT (dst_cap), or what the inflate kernel says about the body.  Empty input: MD_OK, 0 members. */
 int md_gz_members_uncompress(md_ctx *ctx, const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap,
                              md_gz_members_info *info);
+/* Which way the last md_gz_members_uncompress of this context went, and what the speculative path made of the file. */
+typedef struct md_gz_members_stats {
+  int path;              /* 0 general (the host loop alone), 1 indexed, 2 speculative */
+  size_t candidates;     /* path 2: positions that look like a member's start */
+  size_t spans_decoded;  /* path 2: spans the batch launch decoded */
+  size_t members_device; /* members accepted from a batch launch */
+  size_t members_host;   /* members the host step decoded */
+  size_t spans_long, spans_no_room, spans_implausible; /* path 2: spans the batch left out - a body of a 1 024th of all
+                          * bodies or more (and "inflate_parallel_min"); a promised size that ends behind dst_cap; no
+                          * member's header, or a promised size above 1 032 x body + 8, which DEFLATE cannot reach */
+} md_gz_members_stats;
+/* MD_OK, or MD_E_INVALID_ARGUMENT for a NULL pointer.  All zero before the first md_gz_members_uncompress. */
+int md_gz_members_last(const md_ctx *ctx, md_gz_members_stats *out);
 /* Blocked gzip, as bgzip writes it: src cut into blocks of `block` bytes (1..0xff00; 0 = 0xff00), each a member
  * 1f 8b 08 04 | MTIME 0 | XFL 0 | OS ff | XLEN 6 | 'B' 'C' 02 00 BSIZE | body | CRC-32 | ISIZE, then the 28-byte empty
  * member that marks the end.  All blocks are compressed by ONE deflate launch; a member's body is byte for byte what
