@@ -2,13 +2,15 @@
     python tests/stress_lzo.py [batches] [seed]
 Streams of every kind and length, compressed by the GPU (bytes = the oracle's), by minilzo and by hand-damaged copies;
 uncompressed by the GPU into exact, short and generous room: status and bytes = the oracle's (round 6: the decoder works
-in batches of instructions with a slow path - this is what keeps the two honest)."""
+in batches of instructions with a slow path - this is what keeps the two honest).  A share of each batch's streams is not
+a compressor's: random instruction lists of every form from tests/lzo_writer.py, whole, cut and into short room."""
 import os, random, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import decompress_amd
 from decompress_amd import lzo
 from tests import oracle_lib
+from tests.lzo_writer import random_instructions
 from tests.stress_inflate import plain
 
 
@@ -38,6 +40,11 @@ def run(batches, seed, verbose=True):
                 k = rng.randrange(len(src)); src = src[:k] + bytes([rng.getrandbits(8)]) + src[k + 1:]
             cap = len(d) + rng.choice((0, 0, 0, 1, 3, 70, 5000)) if rng.random() < 0.8 else max(0, len(d) - rng.choice((1, 2, 3, 30, 1000)))
             srcs.append(src); caps.append(cap)
+        for _ in range(len(datas) // 3 + 1):  # writer-made: M1, opcodes below 16 in both states, lengths and offsets at their edges
+            _, w = random_instructions(rng, compatible=False)
+            src, r = bytes(w.stream), rng.random()
+            if r < 0.15: src = src[:rng.randrange(len(src))]
+            srcs.append(src); caps.append(max(0, len(w.out) + rng.choice((0, 0, 0, 1, 70, -1, -2, -300))))
         # the compressor again into room that is (mostly) too small: status and bytes = the oracle's
         small = [max(0, len(z) - rng.choice((0, 1, 2, 3, 4, 17, 300))) if rng.random() < 0.7 else rng.randrange(0, len(z) + 1) for _, z in zs]
         for d, cap, got in zip(datas, small, eng.lzo_many(True, datas, small)):
