@@ -77,6 +77,9 @@ SYMBOLS = [
      [c_vp, ctypes.c_int, c_sz] + [c_vp] * 10),
     ("md_inflate_batch_host", ctypes.c_int,
      [c_vp, ctypes.c_int, c_sz, c_vp, c_sz, c_vp, c_vp, c_vp, c_sz, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    ("md_inflate_sizes_batch_device", ctypes.c_int, [c_vp, ctypes.c_int, c_sz] + [c_vp] * 6),
+    ("md_inflate_sizes_batch_host", ctypes.c_int, [c_vp, ctypes.c_int, c_sz, c_vp, c_sz] + [c_vp] * 5),
+    ("md_inflate_plan_device", ctypes.c_int, [c_vp, c_sz, c_vp, c_sz, c_vp, c_vp, c_vp]),
     ("md_deflate_batch_device", ctypes.c_int, [c_vp, ctypes.c_int, c_pp, c_sz] + [c_vp] * 9),
     ("md_deflate_batch_host", ctypes.c_int,
      [c_vp, ctypes.c_int, c_pp, c_sz, c_vp, c_sz, c_vp, c_vp, c_vp, c_sz, c_vp, c_vp, c_vp, c_vp, c_vp]),

@@ -107,6 +107,16 @@ int md_launch_inflate_wave(int format, uint32_t n, const uint8_t *in, const uint
                            const uint64_t *out_off, const uint64_t *out_cap, uint64_t *out_len, uint64_t *consumed, int32_t *status,
                            uint32_t *checksum, uint64_t *dbg, uint32_t *order, int waves, const md::wv::Cont *cont, hipStream_t stream);
 int md_launch_stream_order(uint32_t n, const uint64_t *in_len, uint32_t *order, hipStream_t stream);
+// the size query (md_inflate_sizes_batch_device): the count kernel, `order` as above; dbg = null, or three u64 counters the
+// streams add to (rounds, passes, rounds that needed the checking walk)
+int md_launch_inflate_count(int format, uint32_t n, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len, uint64_t *out_len,
+                            uint64_t *consumed, int32_t *status, uint64_t *dbg, uint32_t *order, hipStream_t stream);
+// GZIP behind it: body_off / hstatus as md_launch_gz_header leaves them; trailer present, ISIZE, consumed
+int md_launch_sizes_gz_finish(uint32_t n, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len, const uint64_t *body_off,
+                              const int32_t *hstatus, uint64_t *out_len, uint64_t *consumed, int32_t *status, hipStream_t stream);
+// out_cap = out_len, out_off = the exclusive sum of the caps rounded up to align (a power of two), *total = the whole
+int md_launch_inflate_plan(uint64_t n, const uint64_t *out_len, uint64_t align, uint64_t *out_off, uint64_t *out_cap, uint64_t *total,
+                           hipStream_t stream);
 int md_i_debug_inflate_lds_pad(uint32_t bytes);
 int md_i_debug_known_bounds(int mode, uint32_t nstreams);
 

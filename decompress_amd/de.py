@@ -225,3 +225,12 @@ class Higher:
         if st < 0:
             eng._check(st)
         return dst.raw[:n.value] if st == 0 else ("Error", eng.lib.md_status_string(st).decode())
+
+
+def inflated_size(src, device=0):
+    """The inflated size of a raw DEFLATE stream (md_inflate_sizes_batch_host):
+    ("Ok", (consumed, size)) without decoding, or ("Error", name)."""
+    st, used, size = _engine.default_engine(device).inflate_sizes_host(_engine.FORMAT_DEFLATE, [src])[0]
+    if st == 0:
+        return "Ok", (used, size)
+    return "Error", _engine.STATUS_NAMES[st]

@@ -254,8 +254,51 @@ class Engine:
             status.ctypes.data, checksum.ctypes.data))
         return out_len, status, checksum
 
-    def inflate_many(self, streams, caps, fmt=FORMAT_DEFLATE):
-        """Convenience for tests: list of bytes -> list of (status, consumed, bytes, adler)."""
+    def inflate_sizes(self, fmt, d_in, in_off, in_len, results=None):
+        """md_inflate_sizes_batch_device: every stream's inflated size without decoding it.  CUDA tensors as
+        inflate_batch; returns (out_len, consumed, status) CUDA tensors (async)."""
+        torch = self.torch
+        n = in_off.numel()
+        if results is None:
+            results = (torch.empty(n, dtype=torch.int64, device=self.device),
+                       torch.empty(n, dtype=torch.int64, device=self.device),
+                       torch.empty(n, dtype=torch.int32, device=self.device))
+        out_len, consumed, status = results
+        self._check(self.lib.md_inflate_sizes_batch_device(
+            self.ctx, fmt, n, _ptr(d_in), _ptr(in_off), _ptr(in_len), _ptr(out_len), _ptr(consumed), _ptr(status)))
+        return results
+
+    def inflate_plan(self, out_len, align=256):
+        """md_inflate_plan_device: (out_off, out_cap, total) for inflate_batch from the sizes; `total` is a one-element
+        CUDA tensor, the bytes to allocate (async)."""
+        torch = self.torch
+        n = out_len.numel()
+        out_off = torch.empty(n, dtype=torch.int64, device=self.device)
+        out_cap = torch.empty(n, dtype=torch.int64, device=self.device)
+        total = torch.empty(1, dtype=torch.int64, device=self.device)
+        self._check(self.lib.md_inflate_plan_device(self.ctx, n, _ptr(out_len), int(align), _ptr(out_off), _ptr(out_cap), _ptr(total)))
+        return out_off, out_cap, total
+
+    def inflate_sizes_host(self, fmt, streams):
+        """md_inflate_sizes_batch_host on a list of bytes: [(status, consumed, out_len)].  Synchronous."""
+        import numpy as np
+
+        n = len(streams)
+        if n == 0:
+            return []
+        in_len = np.array([len(s) for s in streams], dtype=np.uint64)
+        in_off = np.zeros(n, dtype=np.uint64)
+        np.cumsum(in_len[:-1], out=in_off[1:])
+        blob = np.frombuffer(b"".join(bytes(s) for s in streams) + bytes(16), dtype=np.uint8)
+        out_len, consumed, status = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.int32)
+        self._check(self.lib.md_inflate_sizes_batch_host(
+            self.ctx, fmt, n, blob.ctypes.data, blob.nbytes, in_off.ctypes.data, in_len.ctypes.data, out_len.ctypes.data,
+            consumed.ctypes.data, status.ctypes.data))
+        return [(int(status[i]), int(consumed[i]), int(out_len[i])) for i in range(n)]
+
+    def inflate_many(self, streams, caps=None, fmt=FORMAT_DEFLATE):
+        """Convenience for tests: list of bytes -> list of (status, consumed, bytes, adler).  caps=None: the room comes
+        from the streams themselves (inflate_sizes, inflate_plan, then the decode)."""
         import numpy as np
 
         torch = self.torch
@@ -265,6 +308,8 @@ class Engine:
         in_len = np.array([len(s) for s in streams], dtype=np.int64)
         in_off = np.zeros(n, dtype=np.int64)
         np.cumsum(((in_len + 15) // 16 * 16)[:-1], out=in_off[1:])
+        if caps is None:
+            return self._inflate_many_sized(streams, in_off, in_len, fmt)
         cap = np.array(caps, dtype=np.int64)
         out_off = np.zeros(n, dtype=np.int64)
         np.cumsum(((cap + 255) // 256 * 256)[:-1], out=out_off[1:])
@@ -287,6 +332,31 @@ class Engine:
                  out[out_off[i]:out_off[i] + out_len[i]].tobytes(), int(checksum[i]))
                 for i in range(n)]
 
+    def _inflate_many_sized(self, streams, in_off, in_len, fmt):
+        import numpy as np
+
+        torch, dev = self.torch, self.device
+        n = len(streams)
+        blob = np.zeros(int(in_off[-1] + in_len[-1]) + 16, dtype=np.uint8)
+        for s, o in zip(streams, in_off):
+            blob[o:o + len(s)] = np.frombuffer(bytes(s), dtype=np.uint8)
+        d_in = torch.from_numpy(blob).to(dev)
+        d_off, d_len = torch.from_numpy(in_off).to(dev), torch.from_numpy(in_len).to(dev)
+        if self.own_stream:
+            torch.cuda.synchronize(dev)
+        sizes, _, _ = self.inflate_sizes(fmt, d_in, d_off, d_len)
+        out_off, out_cap, total = self.inflate_plan(sizes, 256)
+        self.synchronize()
+        d_out = torch.zeros(int(total.item()) + 16, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)
+        out_len, consumed, status, checksum = self.inflate_batch(fmt, d_in, d_off, d_len, d_out, out_off, out_cap)
+        self.synchronize()
+        torch.cuda.synchronize(dev)
+        out, out_off = d_out.cpu().numpy(), out_off.cpu().numpy()
+        out_len, consumed, status = out_len.cpu().numpy(), consumed.cpu().numpy(), status.cpu().numpy()
+        checksum = checksum.cpu().numpy().view(np.uint32)
+        return [(int(status[i]), int(consumed[i]), out[out_off[i]:out_off[i] + out_len[i]].tobytes(), int(checksum[i]))
+                for i in range(n)]
 
     # ------------------------------------------------------------------ deflate
     def deflate_batch(self, fmt, d_in, in_off, in_len, d_out, out_off, out_cap, level=6, queue=4096,

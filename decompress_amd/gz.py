@@ -169,3 +169,12 @@ class Bgzf:
         if st != 0:
             raise _engine.Error(_engine.STATUS_NAMES[st])
         return dst.raw[:wrote.value]
+
+
+def inflated_size(src, device=0):
+    """The inflated size of a GZip member (md_inflate_sizes_batch_host; ISIZE is checked, the CRC-32 is not):
+    ("Ok", (consumed, size)) without decoding, or ("Error", name)."""
+    st, used, size = _engine.default_engine(device).inflate_sizes_host(_engine.FORMAT_GZIP, [src])[0]
+    if st == 0:
+        return "Ok", (used, size)
+    return "Error", _engine.STATUS_NAMES[st]

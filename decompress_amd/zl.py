@@ -57,3 +57,12 @@ class Higher:
         if st < 0:
             eng._check(st)
         return dst.raw[:n.value] if st == 0 else ("Error", eng.lib.md_status_string(st).decode())
+
+
+def inflated_size(src, device=0):
+    """The inflated size of a ZLIB stream (md_inflate_sizes_batch_host; the Adler-32 is not checked):
+    ("Ok", (consumed, size)) without decoding, or ("Error", name)."""
+    st, used, size = _engine.default_engine(device).inflate_sizes_host(_engine.FORMAT_ZLIB, [src])[0]
+    if st == 0:
+        return "Ok", (used, size)
+    return "Error", _engine.STATUS_NAMES[st]

@@ -223,6 +223,39 @@ int md_inflate_batch_host(md_ctx *ctx, int format, size_t n, const uint8_t *h_in
                           uint64_t *out_len, uint64_t *consumed, int32_t *status,
                           uint32_t *checksum);
 
+/* Every stream's inflated size WITHOUT decoding it: what a caller of md_inflate_batch_* needs to make room for raw
+ * DEFLATE and ZLIB streams, which do not say how large they are.  Streams as md_inflate_batch_device; results per
+ * stream (device arrays, none may be NULL).  Let R be what md_inflate_batch_device reports for the stream with room
+ * that never runs out:
+ *   R is MD_OK                 the same status, out_len and consumed.
+ *   R is MD_INVALID_CHECKSUM   the size call cannot see this: no byte is produced, so no checksum is compared.  It
+ *                              reports MD_OK (MD_INVALID_SIZE for MD_FORMAT_GZIP when ISIZE is wrong too), R's out_len
+ *                              and the consumed a correct checksum would have given.
+ *   R is any other status      the same status, consumed = 0, and R's out_len: the bytes in front of the failing token.
+ * out_len is 64-bit and exact: a stream whose output exceeds MD_MAX_STREAM reports its true size with MD_OK, although
+ * md_inflate_batch_device would refuse such a stream with MD_E_INVALID_ARGUMENT.  in_len > MD_MAX_INFLATE_IN is
+ * refused per stream, as the decoder refuses it.  MD_UNEXPECTED_END_OF_OUTPUT is not reported for any stream that has a
+ * size; the one stream that has none - an incomplete one-code block read at its unused code, which the reference
+ * decodes as literals that consume no input, without end - gets that status (what every finite room gives it) and
+ * the bytes in front of that point.
+ * Asynchronous on the context's stream.  Returns MD_OK or a call-level error (MD_E_INVALID_ARGUMENT: NULL context, a
+ * NULL array with n != 0, unknown format). */
+int md_inflate_sizes_batch_device(md_ctx *ctx, int format, size_t n, const uint8_t *d_in, const uint64_t *d_in_off,
+                                  const uint64_t *d_in_len, uint64_t *d_out_len, uint64_t *d_consumed, int32_t *d_status);
+/* The same with HOST pointers: copies the span of h_in the streams lie in, runs the device form, copies the 20 bytes
+ * per stream back and synchronises. */
+int md_inflate_sizes_batch_host(md_ctx *ctx, int format, size_t n, const uint8_t *h_in, size_t in_bytes, const uint64_t *in_off,
+                                const uint64_t *in_len, uint64_t *out_len, uint64_t *consumed, int32_t *status);
+/* The output plan for md_inflate_batch_device from the sizes, on the device: d_out_cap[i] = d_out_len[i], d_out_off =
+ * the exclusive sum of the capacities rounded up to `align` (a power of two >= 1), d_total[0] = the bytes to allocate.
+ * So sizes -> plan -> 8 bytes read back -> allocate -> decode needs no other round trip.  The plan takes no status: a
+ * stream that fails gets the bytes in front of its failure as room, and decoding with that room reports what unlimited
+ * room would (every other check of a token precedes the output check).  n is not limited.  Asynchronous on the
+ * context's stream.  MD_E_INVALID_ARGUMENT: NULL context, a NULL array with n != 0 (d_total never NULL), an align that
+ * is not a power of two. */
+int md_inflate_plan_device(md_ctx *ctx, size_t n, const uint64_t *d_out_len, size_t align, uint64_t *d_out_off,
+                           uint64_t *d_out_cap, uint64_t *d_total);
+
 /* Single-stream mirrors of the reference's whole-buffer entry points (host
  * pointers, batch of one):
  *   De.Inf.Ns.inflate : bigstring -> bigstring -> (int * int, error) result
