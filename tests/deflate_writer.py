@@ -7,7 +7,10 @@ put a match, a block end or an invalid symbol where a kernel's round limits are.
 
 A token is a literal (0..255), a match `(length, distance)`, or a `Match` from `match()`, which can also choose how it
 is coded: 258 as symbol 284 with extra 31, the symbols 286/287, the distance codes 30/31.  End-of-block is written at the
-end of every Huffman block.  `expand` replays the tokens byte by byte with forward-copy overlap and stops in front of the
+end of every Huffman block (unless the block or the call says eob=False).  A dynamic block's header can be spelled out
+too: the code-length code's lengths (cl_lens), how many of them are sent (hclen) and the exact run-length symbols
+(cl_syms), valid or not; `Bits(value, nbits)` in a token list (or in cl_syms) writes raw bits, e.g. the unused slot of a
+one-code table.  expand() refuses such blocks: what they decode to is for tests/deflate_header_model.py to say.  `expand` replays the tokens byte by byte with forward-copy overlap and stops in front of the
 first token that fails (the statuses of include/mdeflate.h): a literal or a whole match that does not fit `cap`, a
 distance beyond the output written so far or beyond 32 KiB, a distance code 30/31.  Everything before it is written."""
 from collections import namedtuple
@@ -22,6 +25,7 @@ FIXED_DIST = [5] * 32
 # lsym / dsym: the symbol to code (None: the usual one); lext / dext: the value of its extra bits (None: what the
 # length / distance needs).  Symbols 286/287 carry no extra bits; distance codes 30/31 carry none either.
 Match = namedtuple("Match", "length dist lsym lext dsym dext")
+Bits = namedtuple("Bits", "value nbits")  # raw bits in a block's token stream, least significant first
 
 
 def match(length, dist, lsym=None, lext=None, dsym=None, dext=None):
@@ -32,13 +36,23 @@ class Block:
     """kind: "stored", "fixed" or "dynamic".  Dynamic blocks: lit_lens / dist_lens give the code lengths (otherwise
     length-limited ones are built from the token counts), hlit / hdist send more lengths than the code needs (the extra
     ones are 0 unless lit_lens / dist_lens say otherwise), and `extra` lists symbols (286, 287, 1030 + d for distance
-    code d) that get a code although no token uses them.  last: None = only the last block of the list."""
+    code d) that get a code although no token uses them.  last: None = only the last block of the list.
+    Header spelled out (all optional, the stream is byte-identical without them): cl_lens = the 19 code-length code
+    lengths as given (incomplete, over-subscribed, all zero, one code); hclen = how many 3-bit fields are sent (4..19;
+    the lengths behind it must be 0); cl_syms = the exact `(symbol, extra value)` sequence (or `Bits`) that codes the
+    lengths, instead of the run-length coder - hlit and hdist are then sent exactly as given, and lit_lens / dist_lens
+    (what the sequence decodes to) only code the body.  Every symbol of cl_syms must have a code in cl_lens unless
+    cl_check=False (a symbol without one then writes its extra bits only).  eob: False leaves out the end-of-block code."""
 
-    def __init__(self, kind, tokens=(), lit_lens=None, dist_lens=None, hlit=None, hdist=None, extra=(), last=None):
+    def __init__(self, kind, tokens=(), lit_lens=None, dist_lens=None, hlit=None, hdist=None, extra=(), last=None,
+                 cl_lens=None, hclen=None, cl_syms=None, cl_check=True, eob=None):
         assert kind in ("stored", "fixed", "dynamic")
         self.kind, self.tokens = kind, list(tokens)
         self.lit_lens, self.dist_lens, self.hlit, self.hdist = lit_lens, dist_lens, hlit, hdist
         self.extra, self.last = tuple(extra), last
+        self.cl_lens, self.hclen, self.cl_syms, self.cl_check, self.eob = cl_lens, hclen, cl_syms, cl_check, eob
+        if cl_syms is not None:
+            assert hlit is not None and hdist is not None and lit_lens is not None and dist_lens is not None
         if kind == "stored":
             assert all(isinstance(t, int) for t in self.tokens) and len(self.tokens) <= 65535
 
@@ -46,7 +60,7 @@ class Block:
 def _norm(t):
     if isinstance(t, int):
         return t
-    if isinstance(t, Match):
+    if isinstance(t, (Match, Bits)):
         return t
     return Match(t[0], t[1], None, None, None, None)
 
@@ -171,7 +185,7 @@ def _tables(b, toks):
     for t in toks:
         if isinstance(t, int):
             lf[t] += 1
-        else:
+        elif not isinstance(t, Bits):
             ls, _, _ = length_code(t.length, t.lsym, t.lext)
             ds, _, _ = dist_code(t.dist, t.dsym, t.dext)
             lf[ls] += 1
@@ -192,33 +206,51 @@ def _tables(b, toks):
     return list(lit), list(dist)
 
 
-def _write_dynamic_header(w, lit, dist, hlit, hdist):
-    hlit = max(hlit or 0, 257, max(i + 1 for i, l in enumerate(lit) if l))
-    hdist = max(hdist or 0, 1, max((i + 1 for i, l in enumerate(dist) if l), default=1))
-    assert hlit <= 288 and hdist <= 32
-    lit = (lit + [0] * 288)[:hlit]
-    dist = (dist + [0] * 32)[:hdist]
-    syms = _rle(lit + dist)
-    cf = [0] * 19
-    for s, _, _ in syms:
-        cf[s] += 1
-    cl = limited_lengths(cf, 7)
-    if sum(1 for l in cl if l) == 1:  # a one-symbol code-length code: complete it
-        cl[next(i for i in range(19) if cl[i] == 0)] = 1
-    hclen = max(4, max(i + 1 for i, s in enumerate(CL_ORDER) if cl[s]))
+def _write_dynamic_header(w, lit, dist, hlit, hdist, b=None):
+    if b is not None and b.cl_syms is not None:  # the header spelled out: nothing is derived from the lengths
+        assert 257 <= hlit <= 288 and 1 <= hdist <= 32
+        syms = [s if isinstance(s, Bits) else (s[0], s[1], {16: 2, 17: 3, 18: 7}.get(s[0], 0)) for s in b.cl_syms]
+    else:
+        hlit = max(hlit or 0, 257, max((i + 1 for i, l in enumerate(lit) if l), default=257))
+        hdist = max(hdist or 0, 1, max((i + 1 for i, l in enumerate(dist) if l), default=1))
+        assert hlit <= 288 and hdist <= 32
+        lit = (lit + [0] * 288)[:hlit]
+        dist = (dist + [0] * 32)[:hdist]
+        syms = _rle(lit + dist)
+    if b is not None and b.cl_lens is not None:
+        cl = list(b.cl_lens)
+        assert len(cl) == 19 and all(0 <= l <= 7 for l in cl)
+        if b.cl_check:
+            assert all(cl[s[0]] for s in syms if not isinstance(s, Bits)), "a symbol of the header has no code"
+    else:
+        cf = [0] * 19
+        for s in syms:
+            if not isinstance(s, Bits):
+                cf[s[0]] += 1
+        cl = limited_lengths(cf, 7)
+        if sum(1 for l in cl if l) == 1:  # a one-symbol code-length code: complete it
+            cl[next(i for i in range(19) if cl[i] == 0)] = 1
+    hclen = max(4, max((i + 1 for i, s in enumerate(CL_ORDER) if cl[s]), default=4))
+    if b is not None and b.hclen is not None:
+        assert 4 <= b.hclen <= 19 and not any(cl[CL_ORDER[i]] for i in range(b.hclen, 19))
+        hclen = b.hclen
     w.bits(hlit - 257, 5)
     w.bits(hdist - 1, 5)
     w.bits(hclen - 4, 4)
     for i in range(hclen):
         w.bits(cl[CL_ORDER[i]], 3)
     cc = canonical(cl)
-    for s, v, n in syms:
-        w.huff(cc[s])
-        w.bits(v, n)
+    for s in syms:
+        if isinstance(s, Bits):
+            w.bits(s.value, s.nbits)
+            continue
+        if s[0] in cc:
+            w.huff(cc[s[0]])
+        w.bits(s[1], s[2])
 
 
-def write(blocks):
-    """the raw deflate stream of `blocks`"""
+def write(blocks, eob=True):
+    """the raw deflate stream of `blocks`; eob=False: no end-of-block codes (a block's own `eob` overrides it)"""
     w = BitWriter()
     for k, b in enumerate(blocks):
         last = b.last if b.last is not None else k == len(blocks) - 1
@@ -239,11 +271,14 @@ def write(blocks):
         else:
             w.bits(2, 2)
             lit, dist = _tables(b, toks)
-            _write_dynamic_header(w, lit, dist, b.hlit, b.hdist)
+            _write_dynamic_header(w, lit, dist, b.hlit, b.hdist, b)
         lc, dc = canonical(lit), canonical(dist)
         for t in toks:
             if isinstance(t, int):
                 w.huff(lc[t])
+                continue
+            if isinstance(t, Bits):
+                w.bits(t.value, t.nbits)
                 continue
             ls, lv, ln = length_code(t.length, t.lsym, t.lext)
             ds, dv, dn = dist_code(t.dist, t.dsym, t.dext)
@@ -251,7 +286,8 @@ def write(blocks):
             w.bits(lv, ln)
             w.huff(dc[ds])
             w.bits(dv, dn)
-        w.huff(lc[256])
+        if eob if b.eob is None else b.eob:
+            w.huff(lc[256])
     return w.getvalue()
 
 
@@ -260,6 +296,8 @@ def expand(blocks, cap=1 << 62):
     out = bytearray()
     for b in blocks:
         toks = [_norm(t) for t in b.tokens]
+        assert b.cl_lens is None and b.hclen is None and b.cl_syms is None and b.eob is None, "a spelled-out header"
+        assert not any(isinstance(t, Bits) for t in toks), "raw bits: expand() cannot say what they decode to"
         if b.kind == "stored":
             if len(toks) > cap - len(out):
                 return END_OF_OUTPUT, bytes(out)

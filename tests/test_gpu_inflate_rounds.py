@@ -377,11 +377,12 @@ def test_family_reaches_its_path(eng_ring, oracle, fam):
         assert prof[k] > 0, (name, k, {c: prof[c] for c in prof if not c.startswith("cyc_")})
 
 
-def _bounds_run(eng, oracle, cases, pattern=0xA5):
+def _bounds_run(eng, oracle, cases, pattern=0xA5, raw=None, check=None):
     """one batch with the streams' outputs back to back (no padding, unaligned offsets) in a buffer filled with a
-    pattern: nothing outside [out_off, out_off + out_len) may change"""
+    pattern: nothing outside [out_off, out_off + out_len) may change.  raw / check: for cases of another make than this
+    module's (tests/test_gpu_inflate_headers.py): how a case gives its stream and how the results are compared."""
     import torch
-    raws = [_raw(c[1]) for c in cases]
+    raws = [(raw or _raw)(c[1]) for c in cases]
     n = len(cases)
     in_len = np.array([len(r) for r in raws], dtype=np.int64)
     in_off = np.zeros(n, dtype=np.int64)
@@ -407,7 +408,7 @@ def _bounds_run(eng, oracle, cases, pattern=0xA5):
     assert outside.size == 0, ("written outside [out_off, out_off + out_len)", outside[:16])
     res = [(int(status[i]), int(consumed[i]), out[out_off[i]:out_off[i] + out_len[i]].tobytes(), zlib.adler32(
         out[out_off[i]:out_off[i] + out_len[i]].tobytes())) for i in range(n)]
-    _check(oracle, cases, res)
+    (check or _check)(oracle, cases, res)
 
 
 @pytest.mark.gpu
