@@ -133,6 +133,9 @@ SYMBOLS = [
     ("md_lzo_compress_batch_device", ctypes.c_int, [c_vp, c_sz] + [c_vp] * 8),
     ("md_lzo_uncompress", ctypes.c_int, [c_vp, c_vp, c_sz, c_vp, c_sz, ctypes.POINTER(c_sz)]),
     ("md_lzo_compress", ctypes.c_int, [c_vp, c_vp, c_sz, c_vp, c_sz, ctypes.POINTER(c_sz)]),
+    ("md_lzo_sizes_batch_device", ctypes.c_int, [c_vp, c_sz] + [c_vp] * 5),
+    ("md_lzo_sizes_batch_host", ctypes.c_int, [c_vp, c_sz, c_vp, c_sz] + [c_vp] * 4),
+    ("md_lzo_uncompress_with_buffer", ctypes.c_int, [c_vp, c_vp, c_sz, ctypes.POINTER(c_vp), c_szp]),
     ("md_gz_members_scan", ctypes.c_int, [c_vp, c_vp, c_sz, c_vp, c_vp, c_vp, c_sz]),
     ("md_gz_members_uncompress", ctypes.c_int, [c_vp, c_vp, c_sz, c_vp, c_sz, c_vp]),
     ("md_gz_members_last", ctypes.c_int, [c_vp, c_vp]),

@@ -73,6 +73,7 @@ const char *md_status_string(int s) {
   case MD_LZO_INVALID_INPUT: return "Invalid input";
   case MD_LZO_NO_DICTIONARY: return "No dictionary at offset 0 available";
   case MD_LZO_OUT_OF_BOUND: return "Input is malformed or output is not large enough";
+  case MD_LZO_MALFORMED_INPUT: return "Malformed input";
   case MD_E_INVALID_ARGUMENT: return "Invalid argument";
   case MD_E_NO_DEVICE: return "No gfx950 device";
   case MD_E_HIP: return "HIP runtime error";

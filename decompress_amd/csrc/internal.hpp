@@ -222,7 +222,11 @@ int md_launch_gzs_verify(uint64_t C, const uint64_t *mlen, const int32_t *hstatu
                          const uint64_t *out_len, const uint64_t *pass, uint8_t *flag, hipStream_t stream);
 
 // ---- lzo_kernels.hip ----
-uint32_t md_lzo_slots(int compress, uint32_t cus);
+// resident workgroups of kind 0: the decoder, 1: the compressor, 2: the count kernel
+uint32_t md_lzo_slots(int kind, uint32_t cus);
+// the size query (md_lzo_sizes_batch_device): out_len 64-bit and exact, status as mdeflate.h states it
+int md_launch_lzo_count(uint32_t n, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len, uint64_t *out_len, int32_t *status,
+                        uint32_t *counter, uint32_t slots, hipStream_t stream);
 int md_launch_lzo_uncompress(uint32_t n, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len, uint8_t *out,
                              const uint64_t *out_off, const uint64_t *out_cap, uint64_t *out_len, int32_t *status, uint32_t *counter,
                              uint32_t slots, hipStream_t stream);

@@ -606,6 +606,259 @@ __global__ __launch_bounds__(kWave) void lzo_uncompress_kernel(
   }
 }
 
+// ---- sizes without decoding (md_lzo_sizes_batch_*) -----------------------------------------------------------------
+// What a stream decodes to with room that never runs out - Lzo.uncompress_with_buffer's verdict (lib/lzo.ml:199-216,
+// :405-414) - and how many bytes that is, without producing one of them.  An instruction's output length is in its
+// opcode bytes, a run of literals is skipped without reading it, and an offset can only reach too far back while fewer
+// than 49 152 bytes have been produced: the count is the decoder's decode and walk of a window of 64 input bytes and a
+// sum over the marked lanes.  No staging, no records, no batch to fill - LDS is the input ring alone.
+// The position in the output is 64-bit: every zero byte of a length adds 255 bytes, 17 MB of input describe 4 GiB.
+struct Cnt {
+  Win in;
+  uint32_t i_pos, lane;
+  uint64_t o_pos;
+  int state;
+};
+struct NSmem {
+  alignas(16) uint8_t in[kInRing + 32];
+};
+
+// transmit_to_buffer (lib/lzo.ml:199-204): the literals have to be there; nothing is read
+__device__ __forceinline__ int transmit_n(Cnt &d, uint64_t len) {
+  if (d.i_pos > d.in.n || len > d.in.n - d.i_pos) return MD_LZO_MALFORMED_INPUT;
+  d.i_pos += (uint32_t)len;
+  d.o_pos += len;
+  return MD_OK;
+}
+// copy_to_buffer (lib/lzo.ml:206-216)
+__device__ __forceinline__ int copy_n(Cnt &d, uint32_t off, uint64_t len) {
+  if (off > d.o_pos) return MD_INVALID_DICTIONARY;
+  d.o_pos += len;
+  return MD_OK;
+}
+// count (lib/lzo.ml:218-236) over runs of zero bytes that are megabytes long in the reference's own vectors: whole
+// KiB of zeros 16 bytes a lane, then the 256 bytes of the register window at once
+__device__ __forceinline__ int count_n(Cnt &d, uint64_t *out) {
+  const uint32_t n = d.in.n, first = d.i_pos;
+  uint32_t idx = first;
+  while (idx < n && n - idx >= 1024u) {
+    uint4 v;
+    __builtin_memcpy(&v, d.in.src + idx + 16 * d.lane, 16);
+    if (__ballot((v.x | v.y | v.z | v.w) != 0)) break;
+    idx += 1024;
+  }
+  for (;;) {
+    if (idx >= n) return MD_LZO_INVALID_INPUT;
+    if (idx - d.in.wbase >= 256u) d.in.fill(idx);
+    // this lane's first byte at or behind idx that ends the run: it is not zero, or it is the input's end
+    const uint64_t a = (uint64_t)d.in.wbase + 4 * d.lane;
+    uint32_t k = 4;
+#pragma unroll
+    for (int j = 3; j >= 0; j--)
+      if (a + j >= idx && (a + j >= n || ((d.in.w >> (8 * j)) & 0xff) != 0)) k = (uint32_t)j;
+    const uint64_t m = __ballot(k < 4);
+    if (m) {
+      const uint32_t l = (uint32_t)__builtin_ctzll(m);
+      const uint64_t p = (uint64_t)d.in.wbase + 4 * l + rdl(k, l);
+      if (p >= n) return MD_LZO_INVALID_INPUT;
+      *out = (uint64_t)((uint32_t)p - first) * 255 + d.in.byte((uint32_t)p);
+      d.i_pos = (uint32_t)p + 1;
+      return MD_OK;
+    }
+    idx = d.in.wbase + 256;  // (below n: the window held no byte at or behind the input's end)
+  }
+}
+
+// fiber_step's twin: ONE instruction with the same checks in the same order, nothing written, a run of literals in
+// O(1).  The statuses are uncompress_with_buffer's: an offset beyond the bytes so far is `Invalid_dictionary, literals or
+// a two-byte operand over the input's end are "Malformed input" (the exception Out_of_bound, lib/lzo.ml:414).
+__device__ __forceinline__ int count_step(Cnt &d, bool *end) {
+  LZ_EOI()
+  uint32_t chr = d.in.byte(d.i_pos++);
+  const int st = d.state & 3;  // -1 land 3 = 3
+  uint32_t off;
+  uint64_t len, cnt;
+  int nstate;
+  if (chr < 16 && st == 0) {
+    if (chr == 0) {
+      LZ_EOI()
+      LZ_TRY(count_n(d, &cnt))
+      len = 3 + 15 + cnt;
+    } else len = chr + 3;
+    d.state = -1;
+    LZ_EOI()
+    LZ_TRY(transmit_n(d, len))
+    return MD_OK;
+  }
+  if (chr < 16) {
+    LZ_EOI()
+    const uint32_t h = d.in.byte(d.i_pos++);
+    off = (h << 2) + (chr >> 2) + 1;
+    len = 0;
+    nstate = (int)(chr & 3);
+  } else if (chr < 32) {
+    len = chr & 7;
+    if (len == 0) {
+      LZ_EOI()
+      LZ_TRY(count_n(d, &cnt))
+      len = 7 + cnt;
+    }
+    LZ_EOI()
+    if (d.i_pos + 2 > d.in.n) return MD_LZO_MALFORMED_INPUT;
+    const uint32_t s = d.in.byte(d.i_pos) | (d.in.byte(d.i_pos + 1) << 8);
+    d.i_pos += 2;
+    off = 16384 + (((chr & 8) >> 3) << 14) + (s >> 2);
+    nstate = (int)(s & 0xff);
+    if (off == 16384) {  // end_of_lzo
+      *end = true;
+      return MD_OK;
+    }
+  } else if (chr < 64) {
+    len = chr & 31;
+    if (len == 0) {
+      LZ_EOI()
+      LZ_TRY(count_n(d, &cnt))
+      len = 31 + cnt;
+    }
+    LZ_EOI()
+    if (d.i_pos + 2 > d.in.n) return MD_LZO_MALFORMED_INPUT;
+    const uint32_t s = d.in.byte(d.i_pos) | (d.in.byte(d.i_pos + 1) << 8);
+    d.i_pos += 2;
+    nstate = (int)(s & 0xff);
+    off = (s >> 2) + 1;
+  } else {
+    nstate = (int)chr;
+    len = (chr >> 5) - 1;
+    LZ_EOI()
+    const uint32_t h = d.in.byte(d.i_pos++);
+    off = (h << 3) + ((chr >> 2) & 7) + 1;
+  }
+  LZ_EOI()
+  d.state = nstate;
+  LZ_TRY(copy_n(d, off, len + 2))
+  LZ_TRY(transmit_n(d, (uint64_t)(nstate & 3)))
+  return MD_OK;
+}
+
+// Every pass of the loop takes at least one input byte or ends the stream: a window whose first instruction is not the
+// fast path's goes to count_step, which reads its opcode byte or fails; i_pos never passes n.
+__device__ __forceinline__ int count_stream(Cnt &d, NSmem MD_LDS *sm) {
+  LZ_EOI()
+  const uint32_t chr = d.in.byte(0);
+  if (chr == 16) return MD_LZO_NO_DICTIONARY;
+  if (chr >= 18) {  // the first byte, lib/lzo.ml:372-393
+    d.i_pos = 1;
+    d.state = 0;
+    LZ_EOI()
+    LZ_TRY(transmit_n(d, chr - 17))
+  }
+  const uint32_t lane = d.lane, n = d.in.n;
+  InRing ir;
+  ir.ring = (lds_u8 *)sm->in;
+  ir.src = d.in.src;
+  ir.n = n;
+  ir.lane = lane;
+  ir.lo = 0xfffffff0u;
+  ir.ahead = make_uint4(0, 0, 0, 0);
+  bool slow = false;
+  for (;;) {
+    if (slow) {
+      bool end = false;
+      LZ_TRY(count_step(d, &end))
+      if (end) return MD_OK;
+      slow = false;
+      continue;
+    }
+    // decode and walk: the decoder's (uncompress_stream), one window at a time
+    const uint32_t base = d.i_pos;
+    ir.ensure(base);
+    const uint32_t p = base + lane;
+    const uint32_t b = *reinterpret_cast<const MD_LDS wv::u32_u *>(ir.at(p));
+    const InsAll ia = decode_all(b);
+    const uint32_t kzz = ia.low ? ia.kz : ia.kc, lzz = ia.low ? ia.litz : ia.litc, knn = ia.low ? 2u : ia.kc, lnn = ia.low ? ia.litn : ia.litc;
+    const bool ezz = ia.low ? ia.exz : ia.exc, enn = !ia.low && ia.exc;
+    uint32_t wz, wn;
+    if ((uint64_t)base + 64u + 4u + 273u + 1u <= n) {
+      wz = walk_word<false>(kzz, lzz, !ia.low, ezz, p, n);
+      wn = walk_word<false>(knn, lnn, true, enn, p, n);
+    } else {
+      wz = walk_word<true>(kzz, lzz, !ia.low, ezz, p, n);
+      wn = walk_word<true>(knn, lnn, true, enn, p, n);
+    }
+    uint32_t cur = 0, zero = (d.state & 3) == 0 ? 1u : 0u, wd = 0;
+    uint64_t taken = 0, zmask = 0;
+    const uint32_t wboth = wn | (wz << 16);
+    do {
+      wd = rdl(wboth, cur) >> (zero << 4);
+      taken |= 1ull << cur;
+      zmask |= (uint64_t)zero << cur;
+      cur += wd & 1023;
+      zero = (wd >> kNextZeroBit) & 1;
+    } while (cur < 64);
+    if (wd & kExotic) {  // count_step's: the window ends in front of it
+      const uint32_t last = 63u - (uint32_t)__builtin_clzll(taken);
+      taken &= ~(1ull << last);
+      cur = last;
+      zero = (uint32_t)((zmask >> last) & 1);
+      slow = true;
+    }
+    // the marked lanes' bytes.  While an offset can still reach behind the stream's start every match needs its exact
+    // place: a prefix sum; from 49 152 bytes on (the format's offsets end at 49 151) the sum alone.
+    const bool mine = (taken >> lane) & 1, mz = (zmask >> lane) & 1;
+    const uint32_t off = ia.low ? (mz ? 0u : ia.offn) : ia.offc;
+    const uint32_t mlen = ia.low ? (mz ? 0u : 2u) : ia.mlenc, lit = ia.low ? (mz ? ia.litz : ia.litn) : ia.litc;
+    const uint32_t bytes = mine ? mlen + lit : 0u;
+    const uint32_t incl = wv::wave_incl_scan(bytes);
+    uint32_t wsum = rdl(incl, 63);
+    if (d.o_pos < 49152u) {
+      const uint32_t excl = incl - bytes;
+      const uint64_t bad = __ballot(mine && mlen != 0 && off > (uint32_t)d.o_pos + excl);
+      if (bad) {  // it fails in count_step, with the reference's error
+        const uint32_t fb = (uint32_t)__builtin_ctzll(bad);
+        wsum = rdl(excl, fb);
+        cur = fb;
+        zero = (uint32_t)((zmask >> fb) & 1);
+        slow = true;
+      }
+    }
+    d.o_pos += wsum;
+    d.i_pos = base + cur;
+    d.state = zero ? 0 : 1;
+  }
+}
+
+__global__ __launch_bounds__(kWave) void lzo_count_kernel(uint32_t n, const uint8_t *__restrict__ in, const uint64_t *__restrict__ in_off,
+                                                          const uint64_t *__restrict__ in_len, uint64_t *__restrict__ out_len,
+                                                          int32_t *__restrict__ status, uint32_t *counter) {
+  __shared__ NSmem smem;
+  const uint32_t lane = threadIdx.x;
+  for (;;) {
+    const uint32_t sid = next_stream(counter, lane);
+    if (sid >= n) return;
+    const uint64_t l64 = in_len[sid];
+    if (l64 > MD_MAX_STREAM) {  // 32-bit cursors in the input, as the decoder's
+      if (lane == 0) {
+        status[sid] = MD_E_INVALID_ARGUMENT;
+        out_len[sid] = 0;
+      }
+      continue;
+    }
+    Cnt d;
+    d.in.src = in + in_off[sid];
+    d.in.n = (uint32_t)l64;
+    d.in.lane = lane;
+    d.in.fill(0);
+    d.i_pos = 0;
+    d.o_pos = 0;
+    d.lane = lane;
+    d.state = 0;
+    const int st = count_stream(d, (NSmem MD_LDS *)&smem);
+    if (lane == 0) {
+      status[sid] = st;
+      out_len[sid] = st == MD_OK ? d.o_pos : 0;
+    }
+  }
+}
 
 // ---------------------------------------------------------------------------------------------
 // compress
@@ -1070,21 +1323,31 @@ __global__ __launch_bounds__(kWave, MD_LZO_C_WAVES) void lzo_compress_kernel(
 
 // grid: persistent workgroups, as many as the device holds at once (asked of the runtime: registers and LDS decide),
 // never more than there are streams
+#ifndef MD_LZO_N_SLOTS
+#define MD_LZO_N_SLOTS 16  // the count kernel's workgroups per CU (it could hold 32)
+#endif
 template <class K>
 static uint32_t resident_workgroups(K kernel, uint32_t cus) {
   int per_cu = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, md::lzo::kWave, 0) != hipSuccess || per_cu < 1) per_cu = 8;
   return cus * (uint32_t)per_cu;
 }
-extern "C" uint32_t md_lzo_slots(int compress, uint32_t cus) {
-  static uint32_t per_cu[2] = {0, 0};  // (per CU: the same on every device this library runs on)
-  uint32_t &v = per_cu[compress ? 1 : 0];
-  if (!v) v = compress ? resident_workgroups(md::lzo::lzo_compress_kernel, 1) : resident_workgroups(md::lzo::lzo_uncompress_kernel, 1);
+extern "C" uint32_t md_lzo_slots(int kind, uint32_t cus) {  // kind 0: the decoder, 1: the compressor, 2: the count kernel
+  static uint32_t per_cu[3] = {0, 0, 0};  // (per CU: the same on every device this library runs on)
+  const bool compress = kind == 1;
+  uint32_t &v = per_cu[kind == 2 ? 2 : compress ? 1 : 0];
+  if (!v)
+    v = kind == 2 ? resident_workgroups(md::lzo::lzo_count_kernel, 1)
+                  : compress ? resident_workgroups(md::lzo::lzo_compress_kernel, 1) : resident_workgroups(md::lzo::lzo_uncompress_kernel, 1);
   // The compressor is a chain of dependent memory round trips per stream: beyond four wavefronts per SIMD a CU gains
   // little (32 streams per CU: +12 % over 16) and a batch loses more at its end - the last streams run alone at the
   // slow rate, and in a mixed batch the CUs end up with unequal numbers of the expensive streams (C5: 14 to 20 text
   // streams per CU with 28 slots, 16 each with 16: 32.0 -> 26.8 ms).
   if (compress && v > 16) v = 16;
+  // The count kernel: with all of C5's 8 192 streams resident at once nothing is left for the counter to hand out, and
+  // the text streams - every other one - sit on every other XCD: 3.82 ms, as long as 8 192 text streams take (3.89).
+  // With 16 per CU the workgroups that drew noise draw again: 2.35 ms; text alone 3.97 (8 per CU: 3.10 / 6.01).
+  if (kind == 2 && v > MD_LZO_N_SLOTS) v = MD_LZO_N_SLOTS;
   return v * cus;
 }
 extern "C" int md_launch_lzo_uncompress(uint32_t n, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len,
@@ -1093,6 +1356,14 @@ extern "C" int md_launch_lzo_uncompress(uint32_t n, const uint8_t *in, const uin
   if (n == 0) return 0;
   hipLaunchKernelGGL(md::lzo::lzo_uncompress_kernel, dim3(n < slots ? n : slots), dim3(md::lzo::kWave), 0, stream, n, in, in_off, in_len,
                      out, out_off, out_cap, out_len, status, counter);
+  return (int)hipGetLastError();
+}
+
+extern "C" int md_launch_lzo_count(uint32_t n, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len, uint64_t *out_len,
+                                   int32_t *status, uint32_t *counter, uint32_t slots, hipStream_t stream) {
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(md::lzo::lzo_count_kernel, dim3(n < slots ? n : slots), dim3(md::lzo::kWave), 0, stream, n, in, in_off, in_len, out_len,
+                     status, counter);
   return (int)hipGetLastError();
 }
 

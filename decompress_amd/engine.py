@@ -20,7 +20,7 @@ STATUS_NAMES = {
     7: "Invalid_distance_code", 8: "Invalid_header", 9: "Invalid_checksum",
     10: "Invalid GZip header", 11: "Invalid GZip header checksum", 12: "Invalid input size",
     13: "Queue.Full", 14: "Invalid input", 15: "No dictionary at offset 0 available",
-    16: "Input is malformed or output is not large enough",
+    16: "Input is malformed or output is not large enough", 17: "Malformed input",
 }
 STATUS_CODES = {v: k for k, v in STATUS_NAMES.items()}
 
@@ -94,8 +94,37 @@ class Engine:
                        _ptr(results[0]), _ptr(results[1])))
         return results
 
+    def lzo_sizes(self, d_in, in_off, in_len, results=None):
+        """md_lzo_sizes_batch_device: every stream's uncompressed size without decoding it, with the statuses of
+        Lzo.uncompress_with_buffer.  CUDA tensors as lzo_batch; returns (out_len, status) CUDA tensors (async)."""
+        torch = self.torch
+        n = in_off.numel()
+        if results is None:
+            results = (torch.empty(n, dtype=torch.int64, device=self.device),
+                       torch.empty(n, dtype=torch.int32, device=self.device))
+        self._check(self.lib.md_lzo_sizes_batch_device(self.ctx, n, _ptr(d_in), _ptr(in_off), _ptr(in_len), _ptr(results[0]),
+                                                       _ptr(results[1])))
+        return results
+
+    def lzo_sizes_host(self, streams):
+        """md_lzo_sizes_batch_host on a list of bytes: [(status, out_len)].  Synchronous."""
+        import numpy as np
+
+        n = len(streams)
+        if n == 0:
+            return []
+        in_len = np.array([len(s) for s in streams], dtype=np.uint64)
+        in_off = np.zeros(n, dtype=np.uint64)
+        np.cumsum(in_len[:-1], out=in_off[1:])
+        blob = np.frombuffer(b"".join(bytes(s) for s in streams) + bytes(16), dtype=np.uint8)
+        out_len, status = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.int32)
+        self._check(self.lib.md_lzo_sizes_batch_host(self.ctx, n, blob.ctypes.data, blob.nbytes, in_off.ctypes.data,
+                                                     in_len.ctypes.data, out_len.ctypes.data, status.ctypes.data))
+        return [(int(status[i]), int(out_len[i])) for i in range(n)]
+
     def lzo_many(self, compress, bufs, caps):
-        """Convenience for tests: list of bytes -> list of (status, bytes)."""
+        """Convenience for tests: list of bytes -> list of (status, bytes).  Uncompress with caps=None: the room comes
+        from the streams themselves (lzo_sizes, inflate_plan, one read-back, then the decode)."""
         import numpy as np
 
         torch = self.torch
@@ -105,6 +134,10 @@ class Engine:
         in_len = np.array([len(s) for s in bufs], dtype=np.int64)
         in_off = np.zeros(n, dtype=np.int64)
         np.cumsum(((in_len + 31) // 16 * 16)[:-1], out=in_off[1:])
+        if caps is None:
+            if compress:
+                raise Error("Invalid argument: Lzo.compress needs the caller's room")
+            return self._lzo_many_sized(bufs, in_off, in_len)[0]
         cap = np.array(caps, dtype=np.int64)
         out_off = np.zeros(n, dtype=np.int64)
         np.cumsum(((cap + 255) // 256 * 256)[:-1], out=out_off[1:])
@@ -119,6 +152,38 @@ class Engine:
         out = d_out.cpu().numpy()
         out_len, status = out_len.cpu().numpy(), status.cpu().numpy()
         return [(int(status[i]), out[out_off[i]:out_off[i] + out_len[i]].tobytes()) for i in range(n)]
+
+    def _lzo_many_sized(self, bufs, in_off, in_len, align=256):
+        """-> ([(status, bytes)], out_off, total): a stream's status is the size call's; the decode of a stream the size
+        call called valid can only report Ok and the same length"""
+        import numpy as np
+
+        torch, dev = self.torch, self.device
+        n = len(bufs)
+        blob = np.zeros(int(in_off[-1] + in_len[-1]) + 32, dtype=np.uint8)
+        for s, o in zip(bufs, in_off):
+            blob[o:o + len(s)] = np.frombuffer(bytes(s), dtype=np.uint8)
+        d_in = torch.from_numpy(blob).to(dev)
+        d_off, d_len = torch.from_numpy(in_off).to(dev), torch.from_numpy(in_len).to(dev)
+        if self.own_stream:
+            torch.cuda.synchronize(dev)
+        sizes, s_status = self.lzo_sizes(d_in, d_off, d_len)
+        out_off, out_cap, total = self.inflate_plan(sizes, align)
+        self.synchronize()
+        total = int(total.item())
+        d_out = torch.zeros(total + 32, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)
+        out_len, status = self.lzo_batch(False, d_in, d_off, d_len, d_out, out_off, out_cap)
+        self.synchronize()
+        torch.cuda.synchronize(dev)
+        out, out_off = d_out.cpu().numpy(), out_off.cpu().numpy()
+        sizes, s_status = sizes.cpu().numpy(), s_status.cpu().numpy()
+        out_len, status = out_len.cpu().numpy(), status.cpu().numpy()
+        ok = s_status == 0
+        if not ((status[ok] == 0).all() and (out_len[ok] == sizes[ok]).all()):
+            raise Error("lzo: the decode disagrees with the size call")
+        res = [(int(s_status[i]), out[out_off[i]:out_off[i] + sizes[i]].tobytes() if ok[i] else b"") for i in range(n)]
+        return res, out_off, total
 
     def set_matcher(self, matcher):
         """Default matcher of this Engine object's later deflate calls: 0 = De.Lz77, 1 = Lz (lib/lz.ml).  Kept on the

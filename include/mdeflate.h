@@ -60,8 +60,9 @@ enum {
   /* Lzo.error, lib/lzo.ml:4-12 (LZO entry points below) */
   MD_LZO_INVALID_INPUT = 14, /* `Malformed "Invalid input" (count, lib/lzo.ml:236) */
   MD_LZO_NO_DICTIONARY = 15, /* `Malformed "No dictionary at offset 0 available" (lib/lzo.ml:376) */
-  MD_LZO_OUT_OF_BOUND = 16   /* `Invalid_argument "Input is malformed or output is not large enough"
+  MD_LZO_OUT_OF_BOUND = 16,  /* `Invalid_argument "Input is malformed or output is not large enough"
                               * (lib/lzo.ml:401-402); compress: "lzo: output is not large enough" (:655) */
+  MD_LZO_MALFORMED_INPUT = 17 /* `Malformed "Malformed input" (Lzo.uncompress_with_buffer, lib/lzo.ml:414) */
 };
 
 /* Call-level errors (negative): misuse raises Invalid_argument in the
@@ -252,7 +253,9 @@ int md_inflate_sizes_batch_host(md_ctx *ctx, int format, size_t n, const uint8_t
  * stream that fails gets the bytes in front of its failure as room, and decoding with that room reports what unlimited
  * room would (every other check of a token precedes the output check).  n is not limited.  Asynchronous on the
  * context's stream.  MD_E_INVALID_ARGUMENT: NULL context, a NULL array with n != 0 (d_total never NULL), an align that
- * is not a power of two. */
+ * is not a power of two.
+ * The plan is format-blind: it is also the plan step behind md_lzo_sizes_batch_device (a failing LZO stream has size 0,
+ * so its room is 0). */
 int md_inflate_plan_device(md_ctx *ctx, size_t n, const uint64_t *d_out_len, size_t align, uint64_t *d_out_off,
                            uint64_t *d_out_cap, uint64_t *d_total);
 
@@ -570,11 +573,45 @@ int md_lzo_uncompress_batch_device(md_ctx *ctx, size_t n, const uint8_t *d_in, c
 int md_lzo_compress_batch_device(md_ctx *ctx, size_t n, const uint8_t *d_in, const uint64_t *d_in_off,
                                  const uint64_t *d_in_len, uint8_t *d_out, const uint64_t *d_out_off,
                                  const uint64_t *d_out_cap, uint64_t *d_out_len, int32_t *d_status);
+/* Every LZO stream's uncompressed size WITHOUT decoding it: an LZO1X stream does not say how large its output is.
+ * Streams as md_lzo_uncompress_batch_device; results per stream (device arrays, none may be NULL).  The statuses are
+ * those of Lzo.uncompress_with_buffer (lib/lzo.ml:199-216, :405-414), whose buffer grows.  Let U be what
+ * md_lzo_uncompress_batch_device reports for the stream with room that never runs out:
+ *   U is MD_OK                      MD_OK and U's out_len.  It is 64-bit and exact, also beyond MD_MAX_STREAM (every zero
+ *                                   byte of a length adds 255 bytes: 17 MB of input can describe more than 4 GiB), although
+ *                                   the decoder writes at most MD_MAX_STREAM.
+ *   U is MD_UNEXPECTED_END_OF_INPUT, MD_LZO_INVALID_INPUT or MD_LZO_NO_DICTIONARY
+ *                                   the same status, out_len 0.
+ *   U is MD_LZO_OUT_OF_BOUND        because a match's offset reaches back beyond the output so far: MD_INVALID_DICTIONARY
+ *                                   (`Invalid_dictionary, lib/lzo.ml:216); because literals or a two-byte operand run over
+ *                                   the input's end: MD_LZO_MALFORMED_INPUT (lib/lzo.ml:414).  out_len 0.
+ * "Output not large enough" does not exist here, and the size call never reports MD_LZO_OUT_OF_BOUND.  Inside one
+ * instruction the checks come in the reference's order: operand bytes, the dictionary check of the copy, the literals
+ * behind it.  An empty input is MD_UNEXPECTED_END_OF_INPUT; in_len > MD_MAX_STREAM gets MD_E_INVALID_ARGUMENT for that
+ * stream with nothing read, as the decoder does.
+ * sizes -> md_inflate_plan_device -> 8 bytes read back -> allocate -> md_lzo_uncompress_batch_device needs no other round
+ * trip.  On that path a stream's status is the size call's; of a stream it called valid the decode reports MD_OK and the
+ * same out_len.
+ * Asynchronous on the context's stream.  Returns MD_OK or a call-level error (MD_E_INVALID_ARGUMENT: NULL context, a NULL
+ * array with n != 0, more than 2^31 - 1 streams). */
+int md_lzo_sizes_batch_device(md_ctx *ctx, size_t n, const uint8_t *d_in, const uint64_t *d_in_off, const uint64_t *d_in_len,
+                              uint64_t *d_out_len, int32_t *d_status);
+/* The same with HOST pointers: checks the ranges against in_bytes (and MD_MAX_STREAM), copies the span of h_in the streams
+ * lie in, runs the device form, copies the 12 bytes per stream back and synchronises. */
+int md_lzo_sizes_batch_host(md_ctx *ctx, size_t n, const uint8_t *h_in, size_t in_bytes, const uint64_t *in_off,
+                            const uint64_t *in_len, uint64_t *out_len, int32_t *status);
 /* Single-buffer mirrors (host pointers, batch of one): Lzo.uncompress / Lzo.compress. */
 int md_lzo_uncompress(md_ctx *ctx, const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap,
                       size_t *written);
 int md_lzo_compress(md_ctx *ctx, const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap,
                     size_t *written);
+/* Lzo.uncompress_with_buffer ?chunk input (lib/lzo.ml:405-414): the library makes the room.  One upload, the size call,
+ * 12 bytes back, *dst = md_host_alloc(size), a decode into exactly that room from the input already on the device, one
+ * copy back.  Returns the stream's status as md_lzo_sizes_batch_device states it, or a negative call error; a size beyond
+ * MD_MAX_STREAM is MD_E_INVALID_ARGUMENT.  On MD_OK the caller frees *dst with md_host_free (an empty result is a valid
+ * block too); on anything else *dst = NULL and *dst_len = 0.  (?chunk is only the initial size of the reference's
+ * buffer: there is nothing to pass.) */
+int md_lzo_uncompress_with_buffer(md_ctx *ctx, const uint8_t *src, size_t src_len, uint8_t **dst, size_t *dst_len);
 
 /* ---- A GZip FILE of many members (RFC 1952 2.2): `cat a.gz b.gz`, bgzip / BGZF (.bam, .vcf.gz), pigz -i -----------------
  * These entry points read and write RFC 1952 as libz does - NOT Gz.Inf's reading, which MD_FORMAT_GZIP keeps (FEXTRA's
