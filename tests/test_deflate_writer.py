@@ -82,15 +82,19 @@ def test_empty_and_stored_blocks(oracle):
 
 
 def test_fifteen_bit_codes(oracle):
-    """Fibonacci-like symbol counts make the unlimited Huffman code deeper than 15 bits: the lengths are limited"""
+    """Tie-free symbol counts (1, 2, 4, 7, 12, ..: each the two before it and one more) make the unlimited Huffman code
+    deeper than 15 bits: the lengths are limited.  (Plain Fibonacci counts do not: their ties are broken towards the
+    shallow subtree and 20 of them come out 11-12 bits deep.)"""
+    from tests import huffman_tree_model
     rng = random.Random(5)
-    fib = [1, 1]
-    while len(fib) < 30:
-        fib.append(fib[-1] + fib[-2])
+    counts = [1, 2]
+    while len(counts) < 17:
+        counts.append(counts[-1] + counts[-2] + 1)
     toks = []
-    for i, f in enumerate(fib[1:21]):  # 1, 2, 3, 5, ... (with end-of-block's 1: an unlimited code 20 bits deep)
+    for i, f in enumerate(counts):  # (with end-of-block's 1: an unlimited code 17 bits deep)
         toks += [i + 65] * f
     rng.shuffle(toks)
+    assert huffman_tree_model.plain_depth([toks.count(i) for i in range(256)] + [1]) > 15
     b = Block("dynamic", toks)
     lens = limited_lengths([toks.count(i) for i in range(256)] + [1], 15)
     assert max(lens) == 15
