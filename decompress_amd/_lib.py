@@ -141,7 +141,36 @@ SYMBOLS = [
     ("md_gz_members_last", ctypes.c_int, [c_vp, c_vp]),
     ("md_bgzf_compress_bound", c_sz, [c_sz, c_sz]),
     ("md_bgzf_compress", ctypes.c_int, [c_vp, ctypes.c_int, c_sz, c_vp, c_sz, c_vp, c_sz, c_szp]),
+    ("md_zip_directory", ctypes.c_int, [c_vp, c_sz, c_vp, c_vp, c_sz]),
+    ("md_zip_uncompress", ctypes.c_int, [c_vp, c_vp, c_sz, c_vp, c_sz, c_vp, c_sz, c_vp, c_vp, c_vp]),
+    ("md_zip_compress_bound", c_sz, [c_sz, c_vp]),
+    ("md_zip_compress", ctypes.c_int, [c_vp, ctypes.c_int, c_sz, c_vp, c_vp, c_sz, c_vp, c_sz, c_szp]),
 ]
+
+
+class ZipEntry(ctypes.Structure):
+    """md_zip_entry of include/mdeflate.h"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("header_off", "csize", "usize", "name_off")] + \
+               [(k, ctypes.c_uint32) for k in ("crc32", "external_attr")] + \
+               [(k, ctypes.c_uint16) for k in ("name_len", "method", "flags", "dos_time", "dos_date")] + \
+               [("reserved", ctypes.c_uint16 * 3)]
+
+
+class ZipInfo(ctypes.Structure):
+    """md_zip_info of include/mdeflate.h"""
+    _fields_ = [("entries", c_sz)] + [(k, ctypes.c_uint64) for k in ("total_usize", "dir_off", "dir_size", "prefix", "comment_off")] + \
+               [("comment_len", ctypes.c_uint32), ("zip64", ctypes.c_int)]
+
+
+class ZipResult(ctypes.Structure):
+    """md_zip_result of include/mdeflate.h"""
+    _fields_ = [("entries", c_sz), ("failed", c_sz), ("written", ctypes.c_uint64)]
+
+
+class ZipSource(ctypes.Structure):
+    """md_zip_source of include/mdeflate.h"""
+    _fields_ = [("name", ctypes.c_char_p), ("name_len", c_sz), ("off", ctypes.c_uint64), ("len", ctypes.c_uint64),
+                ("external_attr", ctypes.c_uint32), ("dos_time", ctypes.c_uint16), ("dos_date", ctypes.c_uint16)]
 
 
 class GzMembersInfo(ctypes.Structure):

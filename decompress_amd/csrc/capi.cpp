@@ -74,6 +74,9 @@ const char *md_status_string(int s) {
   case MD_LZO_NO_DICTIONARY: return "No dictionary at offset 0 available";
   case MD_LZO_OUT_OF_BOUND: return "Input is malformed or output is not large enough";
   case MD_LZO_MALFORMED_INPUT: return "Malformed input";
+  case MD_INVALID_ZIP_DIRECTORY: return "Invalid ZIP directory";
+  case MD_INVALID_ZIP_HEADER: return "Invalid ZIP local header";
+  case MD_ZIP_UNSUPPORTED: return "Unsupported ZIP entry";
   case MD_E_INVALID_ARGUMENT: return "Invalid argument";
   case MD_E_NO_DEVICE: return "No gfx950 device";
   case MD_E_HIP: return "HIP runtime error";
@@ -257,6 +260,11 @@ int md_set_option(md_ctx *ctx, const char *key, int value) {
   if (!strcmp(key, "gz_members_speculate")) {  // md_gz_members_uncompress, a file without size fields: 1 = members found by speculation, one batch
     if (value != 0 && value != 1) return fail(ctx, MD_E_INVALID_ARGUMENT, "gz_members_speculate is 0 or 1");
     ctx->gzm_speculate = value != 0;
+    return MD_OK;
+  }
+  if (!strcmp(key, "zip_crc_segment")) {  // KiB of an entry's output per wavefront of md_zip_*'s copy-and-checksum kernel; 0 = the default
+    if (value != 0 && (value < 4 || value > (1 << 20))) return fail(ctx, MD_E_INVALID_ARGUMENT, "zip_crc_segment is 0 or 4 .. 2^20 (KiB)");
+    ctx->zip_segment = value ? (size_t)value << 10 : md::kZipSegmentDefault;
     return MD_OK;
   }
   if (!strcmp(key, "host_pipeline_slices")) {  // md_*_batch_host: slices of streams in flight (1 = no overlap of copies and kernels)

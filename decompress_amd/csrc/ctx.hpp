@@ -38,6 +38,10 @@ constexpr size_t kSrcMax = (size_t)1 << 30;
 // what the batch shims ask of the allocator for a blob of `need` bytes: a quarter and 4 KiB of headroom
 inline size_t blob_room(size_t need) { return need + need / 4 + 4096; }
 
+// md_set_option "zip_crc_segment" = 0: the lowest median of 64 KiB .. 1 MiB for one stored entry of 1 GiB, alone and beside
+// 2 464 deflated ones (all five within 1 % of each other) - 4 096 wavefronts for 1 GiB, 16 a CU
+constexpr size_t kZipSegmentDefault = (size_t)256 << 10;
+
 // One allocation of device (or pinned host) memory and its capacity.  It frees itself when its owner goes: whoever
 // deletes the owner sets the device and waits for the context's stream first.  Grow-only, and growing does not keep the
 // contents (reserve_keep does).
@@ -100,6 +104,9 @@ enum Scratch {
   // lists, the members' descriptors, and the writer's packed file (the reader of a file without size fields decodes its
   // batch into that one: its host steps go through kHostIn / kHostOut)
   kGzmWs, kGzmCand, kGzmDesc, kGzmOut,
+  // a ZIP archive (md_zip_*): rows, names, descriptors and the segment table; the writer's file image (archive bytes and
+  // decoded entries / encoder slots go through kHostIn / kHostOut)
+  kZipDesc, kZipOut,
   kScratchCount
 };
 
@@ -141,6 +148,8 @@ struct md_ctx {
   // host, as before there was a speculative path), and which way the last md_gz_members_uncompress went (md_gz_members_last)
   bool gzm_speculate = true;
   md_gz_members_stats gzm_last = {};
+  // ZIP archives: md_set_option "zip_crc_segment", bytes of an entry's output per wavefront of the copy-and-checksum kernel
+  size_t zip_segment = md::kZipSegmentDefault;
   std::string err;
 };
 

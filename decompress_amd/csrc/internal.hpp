@@ -96,6 +96,19 @@ constexpr uint64_t kLongShare = 1024;
 constexpr uint32_t kSpanVerified = 1;
 constexpr uint32_t kSpanAdmitted = 0, kSpanImplausible = 1, kSpanLong = 2, kSpanNoRoom = 3;
 }  // namespace gzs
+
+namespace zip {
+// One selected entry of a ZIP archive as the host hands it to zip_kernels.hip: the directory's word on it.  name_pos: its
+// name in the blob of names that goes along.
+struct Row {
+  uint64_t header_off, csize, usize, name_pos;
+  uint32_t crc;
+  uint16_t name_len, method, flags, reserved;
+};
+static_assert(sizeof(Row) == 48, "Row is uploaded as is");
+// kind[e] of segment_kernel: where an entry's bytes are (and whether they are copied)
+constexpr uint8_t kSkip = 0, kStored = 1, kDeflated = 2;
+}  // namespace zip
 }  // namespace md
 
 extern "C" {
@@ -220,6 +233,30 @@ int md_launch_gzs_room(uint64_t C, const uint64_t *body_len, const uint64_t *pas
 // behind md_launch_gz_finish
 int md_launch_gzs_verify(uint64_t C, const uint64_t *mlen, const int32_t *hstatus, const int32_t *status, const uint64_t *consumed,
                          const uint64_t *out_len, const uint64_t *pass, uint8_t *flag, hipStream_t stream);
+
+// ---- zip_kernels.hip: ZIP archives (md_zip_uncompress, md_zip_compress) ----
+// src holds bytes [base, limit) of the archive; in_off / body_off count from base.  kind: md::zip::kSkip / kStored / kDeflated
+int md_launch_zip_local(uint64_t k, const md::zip::Row *rows, const uint8_t *src, uint64_t base, uint64_t limit, const uint8_t *names,
+                        uint64_t *in_off, uint64_t *in_len, uint64_t *out_cap, uint64_t *body_off, int32_t *hstatus, uint8_t *kind,
+                        hipStream_t stream);
+// segment s belongs to entry seg_entry[s] and begins (s - first[entry]) * seg bytes into its len[entry] bytes; out may be
+// null when every kind is kStored (checksums alone)
+int md_launch_zip_segments(uint64_t nseg, uint64_t seg, const uint32_t *seg_entry, const uint64_t *first, const uint64_t *len,
+                           const uint8_t *kind, const uint8_t *src, const uint64_t *src_off, uint8_t *out, const uint64_t *out_off,
+                           uint32_t *crc, hipStream_t stream);
+// status: the inflate launch's on entry, the entries' final ones on return; *failed (preset to 0) counts those not MD_OK
+int md_launch_zip_verdict(uint64_t k, const md::zip::Row *rows, const uint64_t *first, uint64_t seg, const uint32_t *crc,
+                          const int32_t *hstatus, const uint64_t *out_len, const uint64_t *consumed, int32_t *status, uint64_t *failed,
+                          hipStream_t stream);
+// the writer.  rec: four words a file (CRC-32, body size, method, offset of the local header); lsize[i] = bytes of local
+// header and body; *err (preset to 0) = a status of the encoder that is neither MD_OK nor "no room"
+int md_launch_zip_sizes(uint64_t n, int level, const uint64_t *in_len, const uint32_t *name_len, const uint64_t *out_len,
+                        const int32_t *status, const uint64_t *first, uint64_t seg, const uint32_t *crc, uint64_t *lsize, uint32_t *rec,
+                        int32_t *err, hipStream_t stream);
+// loff: n + 1 (the scan of lsize); longest: the longest file, it sizes the grid; dos[i] = time | date << 16
+int md_launch_zip_pack(uint64_t n, uint64_t longest, const uint8_t *src, const uint64_t *in_off, const uint64_t *in_len,
+                       const uint8_t *slots, const uint64_t *slot_off, const uint8_t *names, const uint64_t *name_pos,
+                       const uint32_t *name_len, const uint32_t *dos, const uint64_t *loff, uint32_t *rec, uint8_t *dst, hipStream_t stream);
 
 // ---- lzo_kernels.hip ----
 // resident workgroups of kind 0: the decoder, 1: the compressor, 2: the count kernel

@@ -21,6 +21,7 @@ STATUS_NAMES = {
     10: "Invalid GZip header", 11: "Invalid GZip header checksum", 12: "Invalid input size",
     13: "Queue.Full", 14: "Invalid input", 15: "No dictionary at offset 0 available",
     16: "Input is malformed or output is not large enough", 17: "Malformed input",
+    18: "Invalid ZIP directory", 19: "Invalid ZIP local header", 20: "Unsupported ZIP entry",
 }
 STATUS_CODES = {v: k for k, v in STATUS_NAMES.items()}
 

@@ -62,7 +62,11 @@ enum {
   MD_LZO_NO_DICTIONARY = 15, /* `Malformed "No dictionary at offset 0 available" (lib/lzo.ml:376) */
   MD_LZO_OUT_OF_BOUND = 16,  /* `Invalid_argument "Input is malformed or output is not large enough"
                               * (lib/lzo.ml:401-402); compress: "lzo: output is not large enough" (:655) */
-  MD_LZO_MALFORMED_INPUT = 17 /* `Malformed "Malformed input" (Lzo.uncompress_with_buffer, lib/lzo.ml:414) */
+  MD_LZO_MALFORMED_INPUT = 17, /* `Malformed "Malformed input" (Lzo.uncompress_with_buffer, lib/lzo.ml:414) */
+  /* ZIP archives (md_zip_* below; PKWARE APPNOTE) */
+  MD_INVALID_ZIP_DIRECTORY = 18, /* "Invalid ZIP directory": end record(s) or central directory */
+  MD_INVALID_ZIP_HEADER = 19,    /* "Invalid ZIP local header": an entry's local header or where its body lies */
+  MD_ZIP_UNSUPPORTED = 20        /* "Unsupported ZIP entry": encrypted, or a method other than 0 and 8 */
 };
 
 /* Call-level errors (negative): misuse raises Invalid_argument in the
@@ -179,6 +183,8 @@ int md_synchronize(md_ctx *ctx);
  *   "gz_members_speculate"       0 or 1 (default): md_gz_members_uncompress of a file whose members do not all state their
  *                                lengths.  1: the device finds the members by speculation and decodes them as one batch;
  *                                0: the host loop, member by member.  Status, info and bytes are the same either way.
+ *   "zip_crc_segment"            KiB (4 .. 2^20; 0 = the default, 256): bytes of an entry's output that one wavefront of
+ *                                md_zip_uncompress / md_zip_compress copies and checksums.  Results do not depend on it.
  *   "debug_inflate_lds_pad", "debug_known_bounds"   measurement aids of tools/dbg (occupancy curve, known-boundaries floor).
  *   "profile"                    0 / 1: in-kernel phase profile of stream 0 (md_get_profile, a debugging aid).
  * Unknown keys and values out of range: MD_E_INVALID_ARGUMENT. */
@@ -681,6 +687,107 @@ int md_gz_members_last(const md_ctx *ctx, md_gz_members_stats *out);
 size_t md_bgzf_compress_bound(size_t src_len, size_t block);
 int md_bgzf_compress(md_ctx *ctx, int level, size_t block, const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap,
                      size_t *written);
+
+/* ---- ZIP archives (PKWARE APPNOTE; .zip .jar .whl .npz .docx .apk .epub): every entry in one batch ----------------------
+ * An entry is a raw RFC 1951 stream (method 8) or plain bytes (method 0), and the central directory states every entry's
+ * offset, sizes and CRC-32: nothing is scanned for, guessed or sized by a pass of its own.
+ *
+ * md_zip_directory reads the directory of the archive src[0, src_len) on the HOST: it takes no context and touches no
+ * device (like md_bgzf_compress_bound and md_shard_plan).  It fills the first `cap` entries; info->entries says how many
+ * there are, so a caller calls it twice (entries may be NULL when cap is 0).  Returns MD_OK, MD_E_INVALID_ARGUMENT (a NULL
+ * src or info, NULL entries with cap != 0) or MD_INVALID_ZIP_DIRECTORY.  Every read is checked against src_len.  Rules:
+ *  - the end record is the LAST position p within the final 65 557 bytes that holds 50 4b 05 06 and whose comment ends
+ *    exactly at the end (p + 22 + comment length == src_len): a comment that contains a record's signature is not taken
+ *    for one, and an archive with bytes behind its comment is refused;
+ *  - a ZIP64 locator (50 4b 06 07) at p - 20 demands the 56-byte ZIP64 end record (50 4b 06 06, no extensible data) at
+ *    p - 76; its counts, directory size and offset are then the archive's.  A locator without that record is refused;
+ *  - prefix = (start of the ZIP64 end record if present, else p) - directory size - directory offset must be >= 0: the
+ *    directory ends where the end record begins, and bytes in front of the archive (a self-extracting stub) move every
+ *    offset by `prefix`;
+ *  - disk numbers are 0 (or all-ones where ZIP64 replaces them), the entry counts of "this disk" and "all disks" agree;
+ *  - every central header has its signature and lies, with name, extra field and comment, inside the directory; the ZIP64
+ *    extra field 0x0001 gives usize, csize, offset and disk - in that order, only for those fixed fields that are
+ *    all-ones - and a missing or short one is refused; the headers are as many as the end record says and fill the
+ *    directory exactly; the sum of usize fits 64 bits.
+ * Local headers and bodies are NOT looked at here. */
+typedef struct md_zip_entry { /* fixed-width fields only */
+  uint64_t header_off;        /* the local header in src (prefix added) */
+  uint64_t csize, usize;      /* as the directory states them */
+  uint64_t name_off;          /* the directory's copy of the name, in src */
+  uint32_t crc32, external_attr;
+  uint16_t name_len, method, flags, dos_time, dos_date;
+  uint16_t reserved[3];
+} md_zip_entry;
+typedef struct md_zip_info {
+  size_t entries;
+  uint64_t total_usize;       /* the sum of usize */
+  uint64_t dir_off, dir_size; /* as the end record states them: the directory begins at prefix + dir_off in src */
+  uint64_t prefix, comment_off;
+  uint32_t comment_len;
+  int zip64;                  /* 1: a ZIP64 end record was read */
+} md_zip_info;
+int md_zip_directory(const uint8_t *src, size_t src_len, md_zip_info *info, md_zip_entry *entries, size_t cap);
+
+/* Entries of the archive, decoded, checked and packed back to back into dst: host pointers (copy in, kernels, copy out,
+ * synchronise).  select == NULL: every entry in directory order (k = entries); otherwise the nselect directory indices in
+ * select, repeats allowed (an index out of range: MD_E_INVALID_ARGUMENT).  out_off (k + 1 words) and status (k words) are
+ * the caller's; out_off[j + 1] - out_off[j] is the directory's usize of selected entry j whatever its status, out_off[k] =
+ * res->written.  If that sum exceeds dst_cap the call returns MD_UNEXPECTED_END_OF_OUTPUT with res->written = the room
+ * needed; nothing is launched and dst is untouched (so dst_cap also bounds what a lying directory can make the call
+ * allocate).  Entries are independent files: the call returns MD_OK once the directory was read and every selected entry
+ * has a status, and res->failed counts those that are not MD_OK; a damaged entry touches neither the bytes nor the status
+ * of another.  A directory failure returns MD_INVALID_ZIP_DIRECTORY; an empty archive is MD_OK with 0 entries.
+ * Only the span of src from the first selected local header to where the last selected body can end goes to the device.
+ * On the device: one thread per entry checks the local header (it lies in front of the directory, signature 50 4b 03 04,
+ * the name has the directory's length and bytes - the one comparison Python's zipfile makes; the local sizes, CRC and
+ * extra field are not trusted or compared, a data descriptor makes them zero anyway - and the body ends in front of the
+ * directory); ONE inflate launch over the method-8 entries, each into exactly its usize bytes; then the outputs are cut
+ * into segments of md_set_option "zip_crc_segment" bytes (the table segment -> entry is built on the host, from the
+ * directory) and one wavefront per segment copies a stored entry's bytes and computes the segment's CRC-32, so one entry
+ * of 1 GiB is copied and checked by the whole chip; a last kernel joins each entry's segment CRCs.  status[j], the first
+ * that applies:
+ *   MD_INVALID_ZIP_HEADER        a check of the local header above failed
+ *   MD_ZIP_UNSUPPORTED           flag bit 0 (encrypted), 6 or 13, or a method other than 0 and 8
+ *   MD_INVALID_SIZE              a stored entry with csize != usize
+ *   the decoder's status         if not MD_OK.  A directory whose usize is too SMALL shows here, as the decoder's
+ *                                MD_UNEXPECTED_END_OF_OUTPUT; csize > MD_MAX_INFLATE_IN or usize > MD_MAX_STREAM of a
+ *                                method-8 entry is MD_E_INVALID_ARGUMENT, as with device descriptors (stored entries
+ *                                have no such limit)
+ *   MD_INVALID_SIZE              the stream ended before csize bytes were consumed or usize bytes written
+ *   MD_INVALID_CHECKSUM          the CRC-32 is not the directory's
+ * Out of scope: an entry long enough to set the batch's time is not taken out of the batch to the whole-chip decoder;
+ * encrypted entries and methods 9 / 12 / 14 / 93 (MD_ZIP_UNSUPPORTED); archives of several disks (refused by the
+ * directory); entries that share or overlap bodies are decoded independently (dst_cap bounds the total). */
+typedef struct md_zip_result {
+  size_t entries, failed; /* selected entries; those whose status is not MD_OK */
+  uint64_t written;       /* bytes of dst the entries take (or, with MD_UNEXPECTED_END_OF_OUTPUT, would take) */
+} md_zip_result;
+int md_zip_uncompress(md_ctx *ctx, const uint8_t *src, size_t src_len, const uint64_t *select, size_t nselect, uint8_t *dst,
+                      size_t dst_cap, uint64_t *out_off, int32_t *status, md_zip_result *res);
+
+/* The writer.  File i is src[off, off + len) under `name` (name_len bytes, not NUL-terminated).  ONE deflate launch over
+ * all files - raw DEFLATE with the parameters of MD_FORMAT_GZIP's body (Zl driver, dynamic blocks, queue 4096, De's
+ * matcher) at `level` - each into a slot of len bytes; a file whose body does not come out shorter than the file is
+ * written stored (method 0), as is every file at level 0 and every empty file.  The CRC-32 of the inputs comes from the
+ * segmented kernel of the reader, one launch packs local headers and bodies into the file image, and the host writes the
+ * central directory and the end record(s).  Local headers carry no extra field and no data descriptor, version needed is
+ * 20 (deflated) or 10 (stored), flag 0x0800 (UTF-8) is set exactly when the name has a byte >= 0x80; the ZIP64 end record
+ * and locator appear exactly when n > 0xfffe.  The bytes depend on (files, src, level) alone.
+ * md_zip_compress_bound: room that always suffices, the sum of (76 + 2 name_len + len) + 98 (host arithmetic); 0 when the
+ * arguments are refused (NULL files with n != 0, a name_len of 0 or above 0xffff, a sum that does not fit).
+ * MD_E_INVALID_ARGUMENT: a file beyond src_len, len > MD_MAX_STREAM, a NULL name, name_len 0 or > 0xffff, level outside
+ * 0..9, or an archive whose bound reaches 4 GiB: the writer has no 64-bit offset fields (the reader has no such limit).
+ * MD_UNEXPECTED_END_OF_OUTPUT: dst_cap is less than the archive takes. */
+typedef struct md_zip_source {
+  const char *name;
+  size_t name_len;
+  uint64_t off, len;
+  uint32_t external_attr;
+  uint16_t dos_time, dos_date;
+} md_zip_source;
+size_t md_zip_compress_bound(size_t n, const md_zip_source *files);
+int md_zip_compress(md_ctx *ctx, int level, size_t n, const md_zip_source *files, const uint8_t *src, size_t src_len,
+                    uint8_t *dst, size_t dst_cap, size_t *written);
 
 #ifdef __cplusplus
 }
