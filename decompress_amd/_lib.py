@@ -145,7 +145,27 @@ SYMBOLS = [
     ("md_zip_uncompress", ctypes.c_int, [c_vp, c_vp, c_sz, c_vp, c_sz, c_vp, c_sz, c_vp, c_vp, c_vp]),
     ("md_zip_compress_bound", c_sz, [c_sz, c_vp]),
     ("md_zip_compress", ctypes.c_int, [c_vp, ctypes.c_int, c_sz, c_vp, c_vp, c_sz, c_vp, c_sz, c_szp]),
+    ("md_inflate_index_build", ctypes.c_int, [c_vp, ctypes.c_int, c_vp, c_sz, ctypes.c_uint64, c_vp, c_sz, ctypes.POINTER(c_vp), c_vp]),
+    ("md_inflate_index_get", ctypes.c_int, [c_vp, c_vp]),
+    ("md_inflate_index_points", ctypes.c_int, [c_vp, c_vp, c_vp, c_sz]),
+    ("md_inflate_index_save_size", c_sz, [c_vp]),
+    ("md_inflate_index_save", ctypes.c_int, [c_vp, c_vp, c_sz, c_szp]),
+    ("md_inflate_index_load", ctypes.c_int, [c_vp, c_sz, ctypes.POINTER(c_vp)]),
+    ("md_inflate_index_free", None, [c_vp]),
+    ("md_inflate_index_read", ctypes.c_int, [c_vp, c_vp, c_vp, c_sz, c_sz, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    ("md_inflate_index_last", ctypes.c_int, [c_vp, c_vp]),
 ]
+
+
+class InflateIndexInfo(ctypes.Structure):
+    """md_inflate_index_info of include/mdeflate.h"""
+    _fields_ = [("format", ctypes.c_int32), ("checksum", ctypes.c_uint32)] + \
+               [(k, ctypes.c_uint64) for k in ("src_len", "header_len", "consumed", "size", "span", "points")]
+
+
+class InflateIndexStats(ctypes.Structure):
+    """md_inflate_index_stats of include/mdeflate.h"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("pieces", "launches", "bytes_in", "bytes_windows", "bytes_scratch")]
 
 
 class ZipEntry(ctypes.Structure):

@@ -1,5 +1,5 @@
 // capi.cpp — host side of the C ABI declared in include/mdeflate.h: contexts, options, timing, status strings.  The
-// entry points of each area are in capi_inflate / capi_long_stream / capi_deflate / capi_gz_members / capi_lzo.cpp.
+// entry points of each area are in capi_inflate / capi_long_stream / capi_deflate / capi_gz_members / capi_zip / capi_zindex / capi_lzo.cpp.
 // Plain HIP runtime calls; no torch types anywhere in this library.
 #include <string.h>
 
@@ -77,6 +77,7 @@ const char *md_status_string(int s) {
   case MD_INVALID_ZIP_DIRECTORY: return "Invalid ZIP directory";
   case MD_INVALID_ZIP_HEADER: return "Invalid ZIP local header";
   case MD_ZIP_UNSUPPORTED: return "Unsupported ZIP entry";
+  case MD_INVALID_INDEX: return "Invalid index";
   case MD_E_INVALID_ARGUMENT: return "Invalid argument";
   case MD_E_NO_DEVICE: return "No gfx950 device";
   case MD_E_HIP: return "HIP runtime error";
@@ -265,6 +266,11 @@ int md_set_option(md_ctx *ctx, const char *key, int value) {
   if (!strcmp(key, "zip_crc_segment")) {  // KiB of an entry's output per wavefront of md_zip_*'s copy-and-checksum kernel; 0 = the default
     if (value != 0 && (value < 4 || value > (1 << 20))) return fail(ctx, MD_E_INVALID_ARGUMENT, "zip_crc_segment is 0 or 4 .. 2^20 (KiB)");
     ctx->zip_segment = value ? (size_t)value << 10 : md::kZipSegmentDefault;
+    return MD_OK;
+  }
+  if (!strcmp(key, "index_read_workspace")) {  // MiB of piece scratch per round of md_inflate_index_read; 0 = one piece a round
+    if (value < 0 || value > (1 << 20)) return fail(ctx, MD_E_INVALID_ARGUMENT, "index_read_workspace is 0 .. 2^20 (MiB)");
+    ctx->zix_workspace = (size_t)value << 20;
     return MD_OK;
   }
   if (!strcmp(key, "host_pipeline_slices")) {  // md_*_batch_host: slices of streams in flight (1 = no overlap of copies and kernels)

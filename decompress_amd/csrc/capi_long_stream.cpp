@@ -38,7 +38,8 @@ struct ParOut {
   uint64_t used_body;    // MD_OK: bytes of the body the stream used
   uint64_t resume_bits;  // bit of the body behind the last complete block
 };
-static int par_decode(md_ctx *ctx, const ParIn &in, ParOut *out) {
+// starts (may be null): the starts of pieces 1 .. of the verified chain, as ParStart states them
+static int par_decode(md_ctx *ctx, const ParIn &in, ParOut *out, std::vector<ParStart> *starts = nullptr) {
   ctx->par_last_pieces = ctx->par_last_rounds = 0;
   const bool dbg_t = getenv("MD_DEBUG_HOSTPATH") != nullptr;
   const auto t_start = std::chrono::steady_clock::now();
@@ -332,11 +333,34 @@ static int par_decode(md_ctx *ctx, const ParIn &in, ParOut *out) {
   out->total = total;
   out->used_body = used_body;
   ctx->par_last_pieces = (int)np;
+  if (starts) {
+    starts->clear();
+    uint64_t acc = 0;
+    for (size_t p = 1; p < np; p++) {
+      acc += pc[p - 1].u;
+      starts->push_back(ParStart{pc[p].bit, acc});
+    }
+  }
   return MD_OK;
 }
 
-// Adler-32 of n bytes at d (device) going on from `adler`; CRC-32 of the same bytes (complete value)
-static int par_adler(md_ctx *ctx, const uint8_t *d, uint64_t n, uint32_t adler, uint32_t *res) {
+int continue_parallel_device(md_ctx *ctx, const uint8_t *src, size_t src_len, unsigned start_bit, const uint8_t *hist, size_t hist_len,
+                             uint64_t room, const uint8_t **d_out, int *status, uint64_t *total, uint64_t *used, uint64_t *resume_bits,
+                             std::vector<ParStart> *starts) {
+  ParIn in{src, src_len, start_bit, hist, (uint32_t)hist_len, room, true};
+  ParOut po;
+  const int rc = par_decode(ctx, in, &po, starts);
+  if (rc != MD_OK) return rc;
+  *d_out = (const uint8_t *)ctx->scratch[kParOut].p + hist_len;
+  *status = po.status;
+  *total = po.total;
+  *used = po.used_body;
+  *resume_bits = po.resume_bits;
+  return MD_OK;
+}
+
+// Adler-32 of n bytes at d (device) going on from `adler`; CRC-32 of the same bytes (complete value): ctx.hpp
+int par_adler(md_ctx *ctx, const uint8_t *d, uint64_t n, uint32_t adler, uint32_t *res) {
   *res = adler;
   if (n == 0) return MD_OK;
   const size_t nseg = (size_t)((n + 65535) / 65536);
@@ -357,7 +381,7 @@ static int par_adler(md_ctx *ctx, const uint8_t *d, uint64_t n, uint32_t adler, 
   *res = (uint32_t)((b << 16) | a);
   return MD_OK;
 }
-static int par_crc(md_ctx *ctx, const uint8_t *d_base, uint64_t off, uint64_t n, uint32_t *res) {
+int par_crc(md_ctx *ctx, const uint8_t *d_base, uint64_t off, uint64_t n, uint32_t *res) {
   *res = 0;
   if (n == 0) return MD_OK;
   const size_t ncrc = (size_t)((n + ((1u << 20) - 1)) >> 20);

@@ -7,6 +7,7 @@
 
 #include <string>
 #include <utility>
+#include <vector>
 
 #include "host_util.hpp"
 #include "internal.hpp"
@@ -107,6 +108,9 @@ enum Scratch {
   // a ZIP archive (md_zip_*): rows, names, descriptors and the segment table; the writer's file image (archive bytes and
   // decoded entries / encoder slots go through kHostIn / kHostOut)
   kZipDesc, kZipOut,
+  // the index of a long stream (md_inflate_index_*): compressed bytes of the pieces of a round, the pieces' slots (window +
+  // output), windows on their way in (read) or out (build), tables and descriptors, the ranges' bytes
+  kZixIn, kZixSlots, kZixWin, kZixDesc, kZixOut,
   kScratchCount
 };
 
@@ -150,6 +154,10 @@ struct md_ctx {
   md_gz_members_stats gzm_last = {};
   // ZIP archives: md_set_option "zip_crc_segment", bytes of an entry's output per wavefront of the copy-and-checksum kernel
   size_t zip_segment = md::kZipSegmentDefault;
+  // the index of a long stream: md_set_option "index_read_workspace" (bytes of piece scratch per round of a read; 0 = one
+  // piece a round) and the counts of the last md_inflate_index_read (md_inflate_index_last)
+  size_t zix_workspace = (size_t)256 << 20;
+  md_inflate_index_stats zix_last = {};
   std::string err;
 };
 
@@ -270,4 +278,19 @@ int continue_parallel(md_ctx *ctx, const uint8_t *src, size_t src_len, unsigned 
                       size_t dst_cap, uint32_t adler_in, unsigned flags, size_t *dst_len, int *status, md_inf_resume *resume);
 int inflate_parallel(md_ctx *ctx, int format, const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap, size_t *consumed,
                      size_t *written, uint32_t *checksum);
+// The complete blocks of a piece decoded by the whole chip and LEFT ON THE DEVICE (md_inflate_index_build): the piece
+// src[0, src_len) starts start_bit bits into src[0], hist[0, hist_len) is the output in front of it, `room` bounds the new
+// output.  MD_OK: the new bytes are at *d_out (hist_len bytes of window lie in front of them), *status is MD_OK (the final
+// block ended; *used bytes of src) or MD_UNEXPECTED_END_OF_INPUT (src ended inside a block), *resume_bits is the bit
+// behind the last complete block, and starts receives every block start the verified chain of pieces went through, in
+// order, as (bit from src[0], bytes of new output in front of it).
+struct ParStart {
+  uint64_t bit, out;
+};
+int continue_parallel_device(md_ctx *ctx, const uint8_t *src, size_t src_len, unsigned start_bit, const uint8_t *hist, size_t hist_len,
+                             uint64_t room, const uint8_t **d_out, int *status, uint64_t *total, uint64_t *used, uint64_t *resume_bits,
+                             std::vector<ParStart> *starts);
+// Adler-32 of n bytes at d (device) going on from `adler`; CRC-32 of the n bytes at d_base + off (complete value)
+int par_adler(md_ctx *ctx, const uint8_t *d, uint64_t n, uint32_t adler, uint32_t *res);
+int par_crc(md_ctx *ctx, const uint8_t *d_base, uint64_t off, uint64_t n, uint32_t *res);
 #pragma GCC visibility pop

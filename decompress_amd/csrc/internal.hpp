@@ -109,6 +109,35 @@ static_assert(sizeof(Row) == 48, "Row is uploaded as is");
 // kind[e] of segment_kernel: where an entry's bytes are (and whether they are copied)
 constexpr uint8_t kSkip = 0, kStored = 1, kDeflated = 2;
 }  // namespace zip
+
+namespace zix {
+// The index of a long stream (zindex_kernels.hip).  A round of a read lays its pieces end to end: piece j's compressed
+// bytes take in_stride(in_len) of the input blob, its slot - window, then output - slot_stride(out_cap) of the scratch.
+// The host copies the compressed bytes to where the plan put them, by the same arithmetic.
+constexpr uint64_t kWin = 32768;  // a window (zindex.hpp has the host's kWindow)
+constexpr uint64_t in_stride(uint64_t in_len) { return ((in_len + 15) & ~(uint64_t)15) + 16; }
+constexpr uint64_t slot_stride(uint64_t out_cap) { return ((out_cap + 63) & ~(uint64_t)63) + 64; }
+// what a round's plan leaves for the host (u64 words)
+constexpr int kPlanCount = 0, kPlanScratch = 1, kPlanIn = 2, kPlanNext = 3, kPlanWords = 4;
+// bytes of a range that one wavefront of the gather copies at a time
+constexpr uint64_t kGatherSegment = 16384;
+// The tables of a read in device memory.  P points: bit / out (the index's), marked (1 bit per piece: a range touches
+// it), round_of (the round a piece was decoded in), verdict (0 = good, else the status its ranges get), place (where its
+// new output begins in the slots of that round).
+struct Tables {
+  uint64_t points, size, body_end;  // body_end: the byte of src behind the DEFLATE body (consumed minus the trailer)
+  const uint64_t *bit, *out;
+  uint32_t *marked, *round_of;
+  int32_t *verdict;
+  uint64_t *place;
+};
+// The descriptors of a round, as md_inflate_continue_batch_device takes them, and piece[j] = which piece stream j is.
+struct Round {
+  uint64_t *in_off, *in_len, *out_off, *out_cap, *out_len, *consumed, *resume_bits, *resume_out;
+  uint32_t *start_bit, *hist_len, *adler_in, *checksum, *resume_adler, *resume_last, *piece;
+  int32_t *status;
+};
+}  // namespace zix
 }  // namespace md
 
 extern "C" {
@@ -257,6 +286,22 @@ int md_launch_zip_sizes(uint64_t n, int level, const uint64_t *in_len, const uin
 int md_launch_zip_pack(uint64_t n, uint64_t longest, const uint8_t *src, const uint64_t *in_off, const uint64_t *in_len,
                        const uint8_t *slots, const uint64_t *slot_off, const uint8_t *names, const uint64_t *name_pos,
                        const uint32_t *name_len, const uint32_t *dos, const uint64_t *loff, uint32_t *rec, uint8_t *dst, hipStream_t stream);
+
+// ---- zindex_kernels.hip: the index of a long stream (md_inflate_index_build, md_inflate_index_read) ----
+// build: window p = the wlen[p] bytes at out + src_off[p] -> wins + p * 32768
+int md_launch_zix_windows_take(uint32_t n, const uint8_t *out, const uint64_t *src_off, const uint32_t *wlen, uint8_t *wins,
+                               hipStream_t stream);
+// read, one round: pieces from `first` on that a range touches (mark != 0: the ranges are marked first; marked[] zeroed by
+// the caller), as many as `budget` bytes of slots hold (the first always); plan[kPlan*] and the descriptors
+int md_launch_zix_plan(const md::zix::Tables *t, uint64_t n, const uint64_t *off, const uint64_t *len, int mark, uint64_t first,
+                       uint64_t budget, uint32_t round, const md::zix::Round *r, uint64_t *plan, hipStream_t stream);
+// window j = wins + j * 32768 (hist_len[j] bytes) -> in front of slot j
+int md_launch_zix_windows_put(uint32_t count, const uint8_t *wins, const md::zix::Round *r, uint8_t *slots, hipStream_t stream);
+int md_launch_zix_verdict(uint32_t count, const md::zix::Tables *t, const md::zix::Round *r, hipStream_t stream);
+// the bytes of this round's good pieces into dst + dst_off[i]; status[i] (preset to 0) = the first failing piece's verdict
+int md_launch_zix_gather(const md::zix::Tables *t, uint64_t n, uint64_t longest, const uint64_t *off, const uint64_t *len,
+                         uint32_t round, const uint8_t *slots, uint8_t *dst, const uint64_t *dst_off, int32_t *status,
+                         hipStream_t stream);
 
 // ---- lzo_kernels.hip ----
 // resident workgroups of kind 0: the decoder, 1: the compressor, 2: the count kernel

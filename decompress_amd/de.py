@@ -234,3 +234,9 @@ def inflated_size(src, device=0):
     if st == 0:
         return "Ok", (used, size)
     return "Error", _engine.STATUS_NAMES[st]
+
+
+def index(src, span=1 << 20, device=0):
+    """The index of a long raw DEFLATE stream (decompress_amd.index.Index.build): any byte range of its output as one batch."""
+    from .index import Index
+    return Index.build(src, _engine.FORMAT_DEFLATE, span=span, device=device)

@@ -66,7 +66,10 @@ enum {
   /* ZIP archives (md_zip_* below; PKWARE APPNOTE) */
   MD_INVALID_ZIP_DIRECTORY = 18, /* "Invalid ZIP directory": end record(s) or central directory */
   MD_INVALID_ZIP_HEADER = 19,    /* "Invalid ZIP local header": an entry's local header or where its body lies */
-  MD_ZIP_UNSUPPORTED = 20        /* "Unsupported ZIP entry": encrypted, or a method other than 0 and 8 */
+  MD_ZIP_UNSUPPORTED = 20,       /* "Unsupported ZIP entry": encrypted, or a method other than 0 and 8 */
+  /* the index of a long stream (md_inflate_index_* below) */
+  MD_INVALID_INDEX = 21          /* "Invalid index": a serialised index that breaks a rule of its layout, an index used with
+                                  * another src than it was built from, a piece that does not end on the next point */
 };
 
 /* Call-level errors (negative): misuse raises Invalid_argument in the
@@ -185,6 +188,10 @@ int md_synchronize(md_ctx *ctx);
  *                                0: the host loop, member by member.  Status, info and bytes are the same either way.
  *   "zip_crc_segment"            KiB (4 .. 2^20; 0 = the default, 256): bytes of an entry's output that one wavefront of
  *                                md_zip_uncompress / md_zip_compress copies and checksums.  Results do not depend on it.
+ *   "index_read_workspace"       MiB (0 .. 2^20; default 256): device memory for the pieces that ONE round of
+ *                                md_inflate_index_read decodes - every piece's window and output, laid end to end.  A read
+ *                                whose pieces need more goes in several rounds, one inflate launch each; a piece larger
+ *                                than the value gets a round to itself.  0 is the minimum: one piece a round.
  *   "debug_inflate_lds_pad", "debug_known_bounds"   measurement aids of tools/dbg (occupancy curve, known-boundaries floor).
  *   "profile"                    0 / 1: in-kernel phase profile of stream 0 (md_get_profile, a debugging aid).
  * Unknown keys and values out of range: MD_E_INVALID_ARGUMENT. */
@@ -788,6 +795,82 @@ typedef struct md_zip_source {
 size_t md_zip_compress_bound(size_t n, const md_zip_source *files);
 int md_zip_compress(md_ctx *ctx, int level, size_t n, const md_zip_source *files, const uint8_t *src, size_t src_len,
                     uint8_t *dst, size_t dst_cap, size_t *written);
+
+/* ---- The index of ONE long stream: read any byte range without decoding what lies in front of it ------------------------
+ * An index in the zran / gztool / indexed_gzip sense over a raw DEFLATE, ZLIB or GZip stream (the first member, as
+ * md_gz_higher_uncompress reads it): P >= 1 access points.  Point k is the START OF A DEFLATE BLOCK: `bit` counts from
+ * src[0] (the frame's header included), `out` is the offset of the block's first byte in the inflated output, and the
+ * point carries the min(32768, out) bytes of output in front of it - the window a decoder needs to start there.  Point 0
+ * is the first block (out 0, no window); bits and outs increase strictly; no two points are closer than `span` bytes of
+ * output.  Piece k is what lies between point k and point k + 1 (the last piece runs to the end of the stream).
+ *
+ * md_inflate_index_build decodes the stream ONCE (pieces that go to one pair of wavefronts may be decoded again: one that
+ * held no complete block with half as much input again, the one that holds the stream's end cut by bisection), in pieces of bounded size (as md_inf_decode does: a long piece by the
+ * whole device, "inflate_parallel_min", any other by one pair of wavefronts), so a stream of any length needs a piece's
+ * worth of device memory; MD_MAX_INFLATE_IN does not bound src_len here.  The return value is the stream's status as
+ * md_de_higher_uncompress / md_zl_higher_uncompress / md_gz_higher_uncompress report it (header, body, trailer); any
+ * status but MD_OK leaves *idx = NULL.  dst == NULL: the output is not wanted and is not copied to the host (only the
+ * windows are); otherwise dst receives it and MD_UNEXPECTED_END_OF_OUTPUT applies when dst_cap is short.  span = 0 means
+ * 1 MiB; span < 4096 is MD_E_INVALID_ARGUMENT.  Every block start the decode learns is considered in order and kept when
+ * it lies at least `span` bytes of output behind the last one kept.  info may be NULL.  The index is the caller's
+ * (md_inflate_index_free) and does not refer to the context or to src.
+ *
+ * The serialised form (md_inflate_index_save / _load; _load takes no context and touches no device), little-endian:
+ *   offset  0  8 bytes  "MDZINDEX"
+ *           8  u32      version, 1
+ *          12  u32      format (MD_FORMAT_*)
+ *          16  u64      src_len      bytes of the src the index was built from
+ *          24  u64      header_len   bytes in front of the DEFLATE body (0 raw, 2 ZLIB, >= 10 GZip)
+ *          32  u64      consumed     bytes of src the stream used, trailer included
+ *          40  u64      size         inflated bytes
+ *          48  u64      span
+ *          56  u64      points       P
+ *          64  u32      checksum     Adler-32 of the output (raw, ZLIB) or its CRC-32 (GZip)
+ *          68  u32      0
+ *          72  P records of 24 bytes: u64 bit, u64 out, u32 win_len, u32 0
+ *   72 + 24 P  the windows back to back, win_len bytes each; the blob ends with the last one.
+ * md_inflate_index_load returns MD_INVALID_INDEX unless: magic, version and both zero words are as above; format is one of
+ * the three; consumed <= src_len < 2^60, header_len + trailer (0 / 4 / 8) <= consumed, header_len fits the format;
+ * span >= 4096; P >= 1; point 0 is (8 header_len, 0); bits and outs increase strictly; win_len == min(32768, out);
+ * 8 header_len <= bit < 8 (consumed - trailer): inside the body; out < size, or out == size for the last point (an empty block at the very end);
+ * and the blob is exactly 72 + 24 P + the sum of win_len bytes long.
+ *
+ * md_inflate_index_read: n ranges [off[i], off[i] + len[i]) of the inflated output into dst + dst_off[i] (host pointers;
+ * copy in, kernels, copy out, synchronise).  src_len other than the index's: MD_INVALID_INDEX as the call's return value;
+ * a range with off + len > size: MD_E_INVALID_ARGUMENT; len 0 is fine.  Otherwise MD_OK and status[i] per range.  The call
+ * works in rounds bounded by md_set_option "index_read_workspace", each round ONE inflate launch
+ * (md_inflate_continue_batch_device): the device marks the pieces any range touches - every piece is decoded once, however
+ * many ranges touch it - and writes the launch's descriptors; only the compressed bytes of those pieces and their windows
+ * are copied to the device; a piece is GOOD only if its last complete block ends exactly on the next point (bit and output
+ * offset), or, for the last piece, the final block ended and the output is exactly size - out; the good pieces' bytes are
+ * gathered into the ranges.  status[i] is MD_OK when every piece of range i is good, otherwise the first failing piece's
+ * inflate status, or MD_INVALID_INDEX where the decode itself found nothing wrong.  A failing range leaves its dst bytes
+ * unspecified (as it stands nothing is written to them); other ranges are not affected.  The bytes are not checked against a checksum: a src that differs from the
+ * indexed one in a way that moves no block boundary is not noticed.
+ * md_inflate_index_last: the counts of the context's last md_inflate_index_read - pieces decoded, inflate launches, bytes
+ * of src and of windows copied to the device, bytes of piece scratch (summed over the rounds). */
+typedef struct md_inflate_index md_inflate_index;
+typedef struct md_inflate_index_info {
+  int32_t format;
+  uint32_t checksum;
+  uint64_t src_len, header_len, consumed, size, span, points;
+} md_inflate_index_info;
+typedef struct md_inflate_index_stats {
+  uint64_t pieces, launches, bytes_in, bytes_windows, bytes_scratch;
+} md_inflate_index_stats;
+int md_inflate_index_build(md_ctx *ctx, int format, const uint8_t *src, size_t src_len, uint64_t span, uint8_t *dst,
+                           size_t dst_cap, md_inflate_index **idx, md_inflate_index_info *info);
+int md_inflate_index_get(const md_inflate_index *idx, md_inflate_index_info *info);
+/* the first `cap` points; bit / out may be NULL when cap is 0 */
+int md_inflate_index_points(const md_inflate_index *idx, uint64_t *bit, uint64_t *out, size_t cap);
+size_t md_inflate_index_save_size(const md_inflate_index *idx); /* 0 for NULL */
+/* MD_UNEXPECTED_END_OF_OUTPUT when cap is short; *len = the bytes written (or needed) */
+int md_inflate_index_save(const md_inflate_index *idx, uint8_t *buf, size_t cap, size_t *len);
+int md_inflate_index_load(const uint8_t *buf, size_t len, md_inflate_index **idx);
+void md_inflate_index_free(md_inflate_index *idx);
+int md_inflate_index_read(md_ctx *ctx, const md_inflate_index *idx, const uint8_t *src, size_t src_len, size_t n,
+                          const uint64_t *off, const uint64_t *len, uint8_t *dst, const uint64_t *dst_off, int32_t *status);
+int md_inflate_index_last(const md_ctx *ctx, md_inflate_index_stats *stats);
 
 #ifdef __cplusplus
 }
