@@ -451,7 +451,7 @@ int continue_parallel(md_ctx *ctx, const uint8_t *src, size_t src_len, unsigned 
   resume->out = shift + t.out;
   resume->adler = t.adler;
   resume->last = t.last;
-  resume->consumed = (B >> 3) + t.consumed;
+  resume->consumed = t_st == MD_OK ? (B >> 3) + t.consumed : t.consumed;  // (0 unless the stream ended: no offset then)
   resume->checksum = t.checksum;
   if (flags & MD_CONT_CRC32) {
     const uint64_t n_out = t.out - hl2, n_end = t_len - hl2;

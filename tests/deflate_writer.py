@@ -249,11 +249,14 @@ def _write_dynamic_header(w, lit, dist, hlit, hdist, b=None):
         w.bits(s[1], s[2])
 
 
-def write(blocks, eob=True):
-    """the raw deflate stream of `blocks`; eob=False: no end-of-block codes (a block's own `eob` overrides it)"""
+def write(blocks, eob=True, starts=None):
+    """the raw deflate stream of `blocks`; eob=False: no end-of-block codes (a block's own `eob` overrides it);
+    starts: a list that receives the bit position of every block's header"""
     w = BitWriter()
     for k, b in enumerate(blocks):
         last = b.last if b.last is not None else k == len(blocks) - 1
+        if starts is not None:
+            starts.append(8 * len(w.buf) + w.n)
         toks = [_norm(t) for t in b.tokens]
         w.bits(1 if last else 0, 1)
         if b.kind == "stored":
@@ -295,9 +298,9 @@ def expand(blocks, cap=1 << 62):
     """(status, output) of decoding `blocks` into a buffer of `cap` bytes: the tokens replayed byte by byte"""
     out = bytearray()
     for b in blocks:
-        toks = [_norm(t) for t in b.tokens]
+        toks = b.tokens if b.kind == "stored" else [_norm(t) for t in b.tokens]  # (a stored block's are bytes: Block checks)
         assert b.cl_lens is None and b.hclen is None and b.cl_syms is None and b.eob is None, "a spelled-out header"
-        assert not any(isinstance(t, Bits) for t in toks), "raw bits: expand() cannot say what they decode to"
+        assert b.kind == "stored" or not any(isinstance(t, Bits) for t in toks), "raw bits: expand() cannot say what they decode to"
         if b.kind == "stored":
             if len(toks) > cap - len(out):
                 return END_OF_OUTPUT, bytes(out)

@@ -450,10 +450,8 @@ def test_long_stream_kinds_and_false_candidates(eng):
         parts.append(co.flush())
         st, _, out = _higher(eng, "zl", b"".join(parts), len(small))
         assert st == 0 and out == small and _par_last(eng)[0] > 20
-        # a reference in front of the start of the stream, far behind a block boundary: Invalid distance from the serial path
-        # (raw stream: [stored 40000 zeros][dynamic blocks of text whose matches are fine]...) - the corrupted case: drop
-        # the first 100 KiB of plaintext from a stream by decoding from a later block start is not expressible with libz;
-        # the device-side check is exercised by the fuzz tests' short streams instead.
+        # (a reference in front of the start of the stream, behind a block boundary, is not expressible with libz: family R of
+        # tests/long_stream_cases.py writes it token by token, tests/test_gpu_long_stream.py holds the path to refusing it)
     finally:
         eng.set_option("inflate_parallel_chunk", 64)
 
