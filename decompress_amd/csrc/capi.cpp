@@ -306,7 +306,6 @@ int md_crc32_batch_device(md_ctx *ctx, size_t n, const uint8_t *d_data, const ui
   if (n == 0) return MD_OK;
   if (n > 0x7fffffffull || !d_off || !d_len || !d_crc) return fail(ctx, MD_E_INVALID_ARGUMENT, "bad crc32 batch");
   MD_ON_DEVICE(ctx);
-  int e = md_launch_crc32((uint32_t)n, d_data, d_off, d_len, d_crc, ctx->stream);
-  if (e != 0) return fail(ctx, MD_E_HIP, "crc32 kernel launch", (hipError_t)e);
+  MD_LAUNCH_TRY(ctx, md_launch_crc32((uint32_t)n, d_data, d_off, d_len, d_crc, ctx->stream));
   return MD_OK;
 }

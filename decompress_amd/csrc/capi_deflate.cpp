@@ -87,8 +87,7 @@ static int front_workspace(md_ctx *ctx, size_t n, const uint64_t *d_len, int dri
     if (rc != MD_OK) return rc;
   }
   md_front_carve(fsmall.p, fbig.p, (uint32_t)n, positions, fr);
-  int prc = md_launch_deflate_plan((uint32_t)n, d_len, driver, matcher, level, positions, *chunks, fr, ctx->stream);
-  if (prc != 0) return fail(ctx, MD_E_HIP, "deflate plan kernel launch", (hipError_t)prc);
+  MD_LAUNCH_TRY(ctx, md_launch_deflate_plan((uint32_t)n, d_len, driver, matcher, level, positions, *chunks, fr, ctx->stream));
   if (matcher_runs && total_in == 0) {
     uint64_t tot_pos = 0;
     HIP_TRY(ctx, hipMemcpyAsync(&tot_pos, fr->slot + n, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -139,20 +138,15 @@ static int deflate_launch(md_ctx *ctx, int format, int level, int queue_len, int
       ctx->gz_hdr_valid = true;
     }
     gz_hdr = ctx->gz_hdr_dev.as<const uint8_t>();
-    if (!pa) {  // (in pieces the CRC-32 is the caller's running one)
-      int e = md_launch_crc32((uint32_t)n, d_in, d_in_off, d_in_len, gz_crc, ctx->stream);
-      if (e != 0) return fail(ctx, MD_E_HIP, "crc32 kernel launch", (hipError_t)e);
-    }
+    // (in pieces the CRC-32 is the caller's running one)
+    if (!pa) MD_LAUNCH_TRY(ctx, md_launch_crc32((uint32_t)n, d_in, d_in_off, d_in_len, gz_crc, ctx->stream));
   }
   // more streams than the link kernel (one per CU) or the sequential kernel (16 per CU) hold at once: longest first
   uint32_t *order = nullptr;
   const int orc = launch_order(ctx, n, kOrderFromDeflate, &order);
   if (orc != MD_OK) return orc;
-  if (order) {
-    // (a slice of a batch: by what the slice brings, not by the absolute length so far - idle streams bring nothing)
-    int oe = md_launch_stream_order((uint32_t)n, d_front_len, order, ctx->stream);
-    if (oe != 0) return fail(ctx, MD_E_HIP, "launch order kernel", (hipError_t)oe);
-  }
+  // (a slice of a batch: by what the slice brings, not by the absolute length so far - idle streams bring nothing)
+  if (order) MD_LAUNCH_TRY(ctx, md_launch_stream_order((uint32_t)n, d_front_len, order, ctx->stream));
   if (matcher_runs && chunks != 0) {
     bool linked = false;
     if (ls && n == 1 && !pa && matcher == MD_MATCHER_DE) {
@@ -164,14 +158,13 @@ static int deflate_launch(md_ctx *ctx, int format, int level, int queue_len, int
         (void)hipGetLastError();  // a launch that failed: the one-workgroup link kernel instead
       }
     }
-    int frc = linked ? md_launch_deflate_match((uint32_t)n, chunks, d_in, d_in_off, d_front_len, max_chain, nice, &fr, 0u, ctx->stream)
-                     : md_launch_deflate_front((uint32_t)n, chunks, d_in, d_in_off, d_front_len, matcher, max_chain, nice, &fr, order, pa ? pa->match_skip : 0u, ctx->stream);
-    if (frc != 0) return fail(ctx, MD_E_HIP, "deflate front kernel launch", (hipError_t)frc);
+    MD_LAUNCH_TRY(ctx, linked ? md_launch_deflate_match((uint32_t)n, chunks, d_in, d_in_off, d_front_len, max_chain, nice, &fr, 0u, ctx->stream)
+                              : md_launch_deflate_front((uint32_t)n, chunks, d_in, d_in_off, d_front_len, matcher, max_chain, nice, &fr, order,
+                                                        pa ? pa->match_skip : 0u, ctx->stream));
   }
-  int rc = md_launch_deflate(format, level, queue_len, driver, dynamic, (uint32_t)n, d_in, d_in_off, d_in_len, d_out,
-                             d_out_off, d_out_cap, d_out_len, d_status, d_checksum, &fr, pa ? pa->queue : ctx->scratch[kWs].p, ctx->dbg.as<uint64_t>(),
-                             gz_hdr, gz_hdr_len, gz_crc, matcher, d_hist, order, pa ? &pa->piece : nullptr, ctx->stream);
-  if (rc != 0) return fail(ctx, MD_E_HIP, "deflate kernel launch", (hipError_t)rc);
+  MD_LAUNCH_TRY(ctx, md_launch_deflate(format, level, queue_len, driver, dynamic, (uint32_t)n, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap,
+                                       d_out_len, d_status, d_checksum, &fr, pa ? pa->queue : ctx->scratch[kWs].p, ctx->dbg.as<uint64_t>(), gz_hdr,
+                                       gz_hdr_len, gz_crc, matcher, d_hist, order, pa ? &pa->piece : nullptr, ctx->stream));
   return MD_OK;
 }
 
@@ -184,9 +177,8 @@ static int def_ns_launch(md_ctx *ctx, int format, int level, size_t n, const uin
   uint32_t chunks = 0;
   int grc_ = front_workspace(ctx, n, d_in_len, 6, MD_MATCHER_DE, level, level >= 1 && level <= 4, total_in, &fr, &chunks);
   if (grc_ != MD_OK) return grc_;
-  int rc = md_launch_def_ns(format, level, (uint32_t)n, chunks, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len,
-                            d_status, d_checksum, &fr, ctx->stream);
-  if (rc != 0) return fail(ctx, MD_E_HIP, "Def.Ns kernel launch", (hipError_t)rc);
+  MD_LAUNCH_TRY(ctx, md_launch_def_ns(format, level, (uint32_t)n, chunks, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status,
+                                      d_checksum, &fr, ctx->stream));
   return MD_OK;
 }
 
@@ -419,8 +411,7 @@ static int deflate_capped(md_ctx *ctx, int format, const md_deflate_params &q, s
     int grc = ctx->gz_tmp.reserve(ctx, n * 24, "hipMalloc(gzip scratch)");
     if (grc != MD_OK) return grc;
     uint32_t *d_crc = (uint32_t *)((uint8_t *)ctx->gz_tmp.p + n * 20);
-    int e = md_launch_crc32((uint32_t)n, d_in, d_in_off, d_in_len, d_crc, ctx->stream);
-    if (e != 0) return fail(ctx, MD_E_HIP, "crc32 kernel launch", (hipError_t)e);
+    MD_LAUNCH_TRY(ctx, md_launch_crc32((uint32_t)n, d_in, d_in_off, d_in_len, d_crc, ctx->stream));
     crc.resize(n);
     HIP_TRY(ctx, hipMemcpyAsync(crc.data(), d_crc, n * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -788,19 +779,26 @@ static int deflate_batch_host(md_ctx *ctx, int format, const md_deflate_params *
       return fail(ctx, MD_E_INVALID_ARGUMENT, "output range out of bounds");
   }
   MD_ON_DEVICE(ctx);
-  int grc_ = ctx->scratch[kHostIn].reserve(ctx, in_bytes + 64, "hipMalloc(host path input)");
-  if (grc_ == MD_OK) grc_ = ctx->scratch[kHostOut].reserve(ctx, out_bytes + 64, "hipMalloc(host path output)");
-  if (grc_ == MD_OK) grc_ = ctx->scratch[kHostDesc].reserve(ctx, 5 * n * 8 + n * 8, "hipMalloc(host path descriptors)");
-  if (grc_ != MD_OK) return grc_;
+  int rc = ctx->scratch[kHostIn].reserve(ctx, in_bytes + 64, "hipMalloc(host path input)");
+  if (rc == MD_OK) rc = ctx->scratch[kHostOut].reserve(ctx, out_bytes + 64, "hipMalloc(host path output)");
+  if (rc != MD_OK) return rc;
   uint8_t *din = (uint8_t *)ctx->scratch[kHostIn].p, *dout = (uint8_t *)ctx->scratch[kHostOut].p;
-  uint64_t *d64 = (uint64_t *)ctx->scratch[kHostDesc].p;
-  int32_t *dstatus = (int32_t *)(d64 + 5 * n);
-  uint32_t *dsum = (uint32_t *)(dstatus + n);
+  uint64_t *d_in_off = nullptr, *d_in_len = nullptr, *d_out_off = nullptr, *d_out_cap = nullptr, *d_out_len = nullptr;
+  int32_t *dstatus = nullptr;
+  uint32_t *dsum = nullptr;
+  md::Carver c;
+  for (int pass = 0; pass < 2; pass++) {
+    if (pass && (rc = carve_from(ctx, ctx->scratch[kHostDesc], &c, "hipMalloc(host path descriptors)")) != MD_OK) return rc;
+    d_in_off = c.take<uint64_t>(n), d_in_len = c.take<uint64_t>(n), d_out_off = c.take<uint64_t>(n), d_out_cap = c.take<uint64_t>(n);
+    d_out_len = c.take<uint64_t>(n);
+    dstatus = c.take<int32_t>(n);
+    dsum = c.take<uint32_t>(n);
+  }
   hipStream_t st = ctx->stream;
-  HIP_TRY(ctx, hipMemcpyAsync(d64 + 0 * n, in_off, n * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(d64 + 1 * n, in_len, n * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(d64 + 2 * n, out_off, n * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(d64 + 3 * n, out_cap, n * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d_in_off, in_off, n * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d_in_len, in_len, n * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d_out_off, out_off, n * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d_out_cap, out_cap, n * 8, hipMemcpyHostToDevice, st));
   {  // long streams in a regular layout: slices of POSITIONS, input arriving and output leaving under the kernels
     const int prc = deflate_host_positions(ctx, format, params, n, h_in, in_bytes, in_off, in_len, h_out, out_bytes, out_off, out_cap,
                                            out_len, status, checksum, din, dout);
@@ -809,16 +807,16 @@ static int deflate_batch_host(md_ctx *ctx, int format, const md_deflate_params *
   // the sequential kernel holds 16 streams per CU: a slice of fewer than 4 096 streams leaves the chip part empty for as
   // long as a stream takes, so a batch is only cut where every slice still has that many
   const std::vector<HostSlice> sl = host_slices(n, in_off, in_len, out_off, out_cap, 4096, (size_t)ctx->host_slices_max, in_bytes, out_bytes);
-  int rc = host_pipeline(ctx, sl, h_in, din, h_out, dout, [&](size_t i0, size_t cnt) {
+  rc = host_pipeline(ctx, sl, h_in, din, h_out, dout, [&](size_t i0, size_t cnt) {
     md_deflate_params hp = *params;
     hp.total_in_bytes = 0;
     for (size_t i = i0; i < i0 + cnt; i++) hp.total_in_bytes += (size_t)in_len[i];
     if (hp.total_in_bytes == 0) hp.total_in_bytes = 1;  // all empty: still no read-back
-    return deflate_batch_device(ctx, format, &hp, cnt, din, d64 + i0, d64 + n + i0, dout, d64 + 2 * n + i0, d64 + 3 * n + i0,
-                                d64 + 4 * n + i0, dstatus + i0, dsum + i0, cnt == 1 ? ls : nullptr);
+    return deflate_batch_device(ctx, format, &hp, cnt, din, d_in_off + i0, d_in_len + i0, dout, d_out_off + i0, d_out_cap + i0, d_out_len + i0,
+                                dstatus + i0, dsum + i0, cnt == 1 ? ls : nullptr);
   });
   if (rc != MD_OK) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(out_len, d64 + 4 * n, n * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipMemcpyAsync(out_len, d_out_len, n * 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipMemcpyAsync(status, dstatus, n * 4, hipMemcpyDeviceToHost, st));
   if (checksum) HIP_TRY(ctx, hipMemcpyAsync(checksum, dsum, n * 4, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));

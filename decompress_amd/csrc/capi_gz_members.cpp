@@ -18,12 +18,6 @@ struct GzmIndex {
 };
 }  // namespace
 
-#define MD_LAUNCH_TRY(ctx, expr)                                        \
-  do {                                                                  \
-    const int e_ = (expr);                                              \
-    if (e_ != 0) return fail(ctx, MD_E_HIP, #expr, (hipError_t)e_);     \
-  } while (0)
-
 // Mark, chain and descriptors (gz_members.hip) for len bytes at d_src.  *indexed: the chain of BC size fields leads from
 // offset 0 to the end of the file; then ix holds the members, their headers parsed and their output offsets scanned.
 // Three small read-backs: the candidate count, the member count with the chain's verdict, the total size.
@@ -32,21 +26,29 @@ static int gzm_index(md_ctx *ctx, const uint8_t *d_src, uint64_t len, bool *inde
   if (len < 28) return MD_OK;  // (shorter than any indexed member)
   hipStream_t st = ctx->stream;
   const uint64_t nspans = (len + md::gzm::kMarkSpanBytes - 1) / md::gzm::kMarkSpanBytes, nwords = (len + 31) / 32;
-  const size_t words_bytes = (size_t)((nwords + nspans + 1) / 2 * 8);  // bitmap and counts, rounded to 8
-  int rc = ctx->scratch[kGzmWs].reserve(ctx, words_bytes + (nspans + 2) * 8, "hipMalloc(member scan)");
-  if (rc != MD_OK) return rc;
-  uint32_t *bits = (uint32_t *)ctx->scratch[kGzmWs].p, *cnt = bits + nwords;
-  uint64_t *base = (uint64_t *)((uint8_t *)ctx->scratch[kGzmWs].p + words_bytes), *last_nz = base + nspans + 1;
+  int rc = MD_OK;
+  uint32_t *bits = nullptr, *cnt = nullptr;  // the bitmap of marks, the marks per span
+  uint64_t *base = nullptr, *last_nz = nullptr;
+  md::Carver ws;
+  for (int pass = 0; pass < 2; pass++) {
+    if (pass && (rc = carve_from(ctx, ctx->scratch[kGzmWs], &ws, "hipMalloc(member scan)")) != MD_OK) return rc;
+    bits = ws.take<uint32_t>(nwords), cnt = ws.take<uint32_t>(nspans);
+    base = ws.take<uint64_t>(nspans + 1), last_nz = ws.take<uint64_t>(1);
+  }
   MD_LAUNCH_TRY(ctx, md_launch_gzm_mark(d_src, len, bits, cnt, last_nz, st));
   MD_LAUNCH_TRY(ctx, md_launch_gzm_scan32(cnt, nspans, base, st));
   uint64_t C = 0;
   HIP_TRY(ctx, hipMemcpyAsync(&C, base + nspans, 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
   if (C == 0 || C > 0x7ffffff0ull) return MD_OK;
-  rc = ctx->scratch[kGzmCand].reserve(ctx, (size_t)((3 * C + 1) * 8 + 3 * (C + 2) * 4), "hipMalloc(member candidates)");
-  if (rc != MD_OK) return rc;
-  uint64_t *cpos = (uint64_t *)ctx->scratch[kGzmCand].p, *cnext = cpos + C, *ridx = cnext + C;
-  uint32_t *jump_a = (uint32_t *)(ridx + C + 1), *jump_b = jump_a + C + 2, *reach = jump_b + C + 2;
+  uint64_t *cpos = nullptr, *cnext = nullptr, *ridx = nullptr;
+  uint32_t *jump_a = nullptr, *jump_b = nullptr, *reach = nullptr;
+  md::Carver cand;
+  for (int pass = 0; pass < 2; pass++) {
+    if (pass && (rc = carve_from(ctx, ctx->scratch[kGzmCand], &cand, "hipMalloc(member candidates)")) != MD_OK) return rc;
+    cpos = cand.take<uint64_t>(C), cnext = cand.take<uint64_t>(C), ridx = cand.take<uint64_t>(C + 1);
+    jump_a = cand.take<uint32_t>(C + 2), jump_b = cand.take<uint32_t>(C + 2), reach = cand.take<uint32_t>(C + 2);
+  }
   MD_LAUNCH_TRY(ctx, md_launch_gzm_compact(d_src, len, bits, base, cpos, cnext, st));
   MD_LAUNCH_TRY(ctx, md_launch_gzm_chain(C, cpos, cnext, last_nz, jump_a, jump_b, reach, st));
   MD_LAUNCH_TRY(ctx, md_launch_gzm_scan32(reach, C, ridx, st));
@@ -56,33 +58,21 @@ static int gzm_index(md_ctx *ctx, const uint8_t *d_src, uint64_t len, bool *inde
   HIP_TRY(ctx, hipMemcpyAsync(&at_end, reach + C, 4, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
   if (!at_end || M == 0) return MD_OK;
-  rc = ctx->scratch[kGzmDesc].reserve(ctx, (size_t)((8 * M + 2) * 8 + 2 * M * 4), "hipMalloc(member descriptors)");
-  if (rc != MD_OK) return rc;
   ix->M = M;
-  ix->mpos = (uint64_t *)ctx->scratch[kGzmDesc].p;
-  ix->mlen = ix->mpos + M;
-  ix->body_off = ix->mlen + M;
-  ix->body_len = ix->body_off + M;
-  ix->isize = ix->body_len + M;
-  ix->out_len = ix->isize + M;
-  ix->consumed = ix->out_len + M;
-  ix->out_off = ix->consumed + M;  // M + 1
-  ix->first = ix->out_off + M + 1;
-  ix->hstatus = (int32_t *)(ix->first + 1);
-  ix->status = ix->hstatus + M;
+  md::Carver desc;
+  for (int pass = 0; pass < 2; pass++) {
+    if (pass && (rc = carve_from(ctx, ctx->scratch[kGzmDesc], &desc, "hipMalloc(member descriptors)")) != MD_OK) return rc;
+    ix->mpos = desc.take<uint64_t>(M), ix->mlen = desc.take<uint64_t>(M), ix->body_off = desc.take<uint64_t>(M), ix->body_len = desc.take<uint64_t>(M);
+    ix->isize = desc.take<uint64_t>(M), ix->out_len = desc.take<uint64_t>(M), ix->consumed = desc.take<uint64_t>(M);
+    ix->out_off = desc.take<uint64_t>(M + 1), ix->first = desc.take<uint64_t>(1);
+    ix->hstatus = desc.take<int32_t>(M), ix->status = desc.take<int32_t>(M);
+  }
   MD_LAUNCH_TRY(ctx, md_launch_gzm_select(C, reach, ridx, cpos, cnext, ix->mpos, ix->mlen, st));
   MD_LAUNCH_TRY(ctx, md_launch_gzm_headers(M, d_src, ix->mpos, ix->mlen, ix->body_off, ix->body_len, ix->isize, ix->hstatus, st));
   MD_LAUNCH_TRY(ctx, md_launch_gzm_scan64(ix->isize, M, ix->out_off, st));
   HIP_TRY(ctx, hipMemcpyAsync(&ix->total, ix->out_off + M, 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
   *indexed = true;
-  return MD_OK;
-}
-
-static int gzm_upload(md_ctx *ctx, const uint8_t *src, size_t len) {
-  const int rc = ctx->scratch[kHostIn].reserve(ctx, len + 64, "hipMalloc(host path input)");
-  if (rc != MD_OK) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[kHostIn].p, src, len, hipMemcpyHostToDevice, ctx->stream));
   return MD_OK;
 }
 
@@ -93,7 +83,7 @@ int md_gz_members_scan(md_ctx *ctx, const uint8_t *src, size_t src_len, md_gz_me
   memset(info, 0, sizeof *info);
   if (src_len == 0) return MD_OK;
   MD_ON_DEVICE(ctx);
-  int rc = gzm_upload(ctx, src, src_len);
+  int rc = upload_host_in(ctx, src, src_len);
   if (rc != MD_OK) return rc;
   bool indexed = false;
   GzmIndex ix;
@@ -131,13 +121,8 @@ static int gzm_member(md_ctx *ctx, const uint8_t *src, size_t len, uint8_t *dst,
   if (st != MD_OK) return st;
   if (len - body - used < 8) return MD_UNEXPECTED_END_OF_INPUT;
   const uint8_t *t = src + body + used;
-  uint32_t want = 0, isize = 0;
-  for (int k = 0; k < 4; k++) {
-    want |= (uint32_t)t[k] << (8 * k);
-    isize |= (uint32_t)t[4 + k] << (8 * k);
-  }
-  if (want != md::crc32_update(0, dst + *written, wrote)) return MD_INVALID_CHECKSUM;
-  if (isize != (uint32_t)wrote) return MD_INVALID_SIZE;
+  if (md::le32(t) != md::crc32_update(0, dst + *written, wrote)) return MD_INVALID_CHECKSUM;
+  if (md::le32(t + 4) != (uint32_t)wrote) return MD_INVALID_SIZE;
   *pos = body + used + 8;
   *written += wrote;
   return MD_OK;
@@ -186,11 +171,15 @@ struct SpecBatch {
 static int gzm_spec_batch(md_ctx *ctx, const uint8_t *d_src, uint64_t len, uint64_t dst_cap, SpecBatch *b) {
   hipStream_t st = ctx->stream;
   const uint64_t nspans = (len + md::gzm::kMarkSpanBytes - 1) / md::gzm::kMarkSpanBytes, nwords = (len + 31) / 32;
-  const size_t words_bytes = (size_t)((nwords + nspans + 1) / 2 * 8);  // bitmap and counts, rounded to 8 (as gzm_index)
-  int rc = ctx->scratch[kGzmWs].reserve(ctx, words_bytes + (nspans + 2) * 8, nullptr);
-  if (rc != MD_OK) return rc;
-  uint32_t *bits = (uint32_t *)ctx->scratch[kGzmWs].p, *cnt = bits + nwords;
-  uint64_t *base = (uint64_t *)((uint8_t *)ctx->scratch[kGzmWs].p + words_bytes);
+  int rc = MD_OK;
+  uint32_t *bits = nullptr, *cnt = nullptr;  // (as gzm_index)
+  uint64_t *base = nullptr;
+  md::Carver ws;
+  for (int pass = 0; pass < 2; pass++) {
+    if (pass && (rc = carve_from(ctx, ctx->scratch[kGzmWs], &ws, nullptr)) != MD_OK) return rc;
+    bits = ws.take<uint32_t>(nwords), cnt = ws.take<uint32_t>(nspans);
+    base = ws.take<uint64_t>(nspans + 1);
+  }
   SPEC_TRY(md_launch_gzs_mark(d_src, len, bits, cnt, st));
   SPEC_TRY(md_launch_gzm_scan32(cnt, nspans, base, st));
   uint64_t C = 0;
@@ -200,13 +189,21 @@ static int gzm_spec_batch(md_ctx *ctx, const uint8_t *d_src, uint64_t len, uint6
   SPEC_TRY(hipStreamSynchronize(st));
   if (C < kSpecMinCandidates || !(word0 & 1) || C > 0x7ffffff0ull) return MD_NOT_HANDLED;
   rc = ctx->scratch[kGzmCand].reserve(ctx, (size_t)C * 8, nullptr);
-  if (rc == MD_OK) rc = ctx->scratch[kGzmDesc].reserve(ctx, (size_t)((10 * C + 1) * 8 + 2 * C * 4 + C), nullptr);
   if (rc != MD_OK) return rc;
   uint64_t *cpos = (uint64_t *)ctx->scratch[kGzmCand].p;
-  uint64_t *mlen = (uint64_t *)ctx->scratch[kGzmDesc].p, *body_off = mlen + C, *body_len = body_off + C, *guess = body_len + C, *pass = guess + C,
-           *dec_len = pass + C, *out_cap = dec_len + C, *out_len = out_cap + C, *consumed = out_len + C, *out_off = consumed + C;  // out_off: C + 1
-  int32_t *hstatus = (int32_t *)(out_off + C + 1), *status = hstatus + C;
-  uint8_t *flag = (uint8_t *)(status + C);
+  uint64_t *mlen = nullptr, *body_off = nullptr, *body_len = nullptr, *guess = nullptr, *pass = nullptr, *dec_len = nullptr, *out_cap = nullptr,
+           *out_len = nullptr, *consumed = nullptr, *out_off = nullptr;
+  int32_t *hstatus = nullptr, *status = nullptr;
+  uint8_t *flag = nullptr;
+  md::Carver desc;
+  for (int second = 0; second < 2; second++) {
+    if (second && (rc = carve_from(ctx, ctx->scratch[kGzmDesc], &desc, nullptr)) != MD_OK) return rc;
+    mlen = desc.take<uint64_t>(C), body_off = desc.take<uint64_t>(C), body_len = desc.take<uint64_t>(C), guess = desc.take<uint64_t>(C);
+    pass = desc.take<uint64_t>(C), dec_len = desc.take<uint64_t>(C), out_cap = desc.take<uint64_t>(C), out_len = desc.take<uint64_t>(C);
+    consumed = desc.take<uint64_t>(C), out_off = desc.take<uint64_t>(C + 1);
+    hstatus = desc.take<int32_t>(C), status = desc.take<int32_t>(C);
+    flag = desc.take<uint8_t>(C);
+  }
   SPEC_TRY(md_launch_gzs_compact(len, bits, base, cpos, st));
   SPEC_TRY(md_launch_gzs_spans(C, cpos, len, mlen, st));
   SPEC_TRY(md_launch_gzm_headers(C, d_src, cpos, mlen, body_off, body_len, guess, hstatus, st));
@@ -311,7 +308,7 @@ int md_gz_members_uncompress(md_ctx *ctx, const uint8_t *src, size_t src_len, ui
   stats = md_gz_members_stats{};
   if (src_len == 0) return MD_OK;
   MD_ON_DEVICE(ctx);
-  int rc = gzm_upload(ctx, src, src_len);
+  int rc = upload_host_in(ctx, src, src_len);
   if (rc != MD_OK) return rc;
   const uint8_t *d_src = (const uint8_t *)ctx->scratch[kHostIn].p;
   bool indexed = false;
@@ -402,30 +399,28 @@ int md_bgzf_compress(md_ctx *ctx, int level, size_t block, const uint8_t *src, s
   // slots of fixed stride for the bodies: a body longer than block + 5 bytes loses against the stored form anyway (the
   // encoder then says MD_UNEXPECTED_END_OF_OUTPUT for that slot, and the pack kernel writes the block stored)
   const size_t stride = (block + 5 + 15) & ~(size_t)15, bound = md_bgzf_compress_bound(src_len, block);
-  int rc = gzm_upload(ctx, src, src_len);
+  int rc = upload_host_in(ctx, src, src_len);
   if (rc == MD_OK) rc = ctx->scratch[kHostOut].reserve(ctx, nb * stride + 64, "hipMalloc(host path output)");
   if (rc == MD_OK) rc = ctx->scratch[kGzmOut].reserve(ctx, bound + 64, "hipMalloc(blocked gzip file)");
-  if (rc == MD_OK) rc = ctx->scratch[kGzmDesc].reserve(ctx, (7 * nb + 2) * 8 + (2 * nb + 2) * 4, "hipMalloc(member descriptors)");
   if (rc != MD_OK) return rc;
   const uint8_t *d_in = (const uint8_t *)ctx->scratch[kHostIn].p;
   uint8_t *slots = (uint8_t *)ctx->scratch[kHostOut].p, *d_file = (uint8_t *)ctx->scratch[kGzmOut].p;
-  uint64_t *in_off = (uint64_t *)ctx->scratch[kGzmDesc].p, *in_len = in_off + nb, *out_off = in_len + nb, *out_cap = out_off + nb, *out_len = out_cap + nb,
-           *msize = out_len + nb, *moff = msize + nb;  // moff: nb + 1
-  int32_t *status = (int32_t *)(moff + nb + 1), *err = status + nb;
-  uint32_t *crc = (uint32_t *)(err + 1);
+  uint64_t *in_off = nullptr, *in_len = nullptr, *out_off = nullptr, *out_cap = nullptr, *out_len = nullptr, *msize = nullptr, *moff = nullptr;
+  int32_t *status = nullptr, *err = nullptr;
+  uint32_t *crc = nullptr;
+  md::Carver desc;
+  for (int pass = 0; pass < 2; pass++) {
+    if (pass && (rc = carve_from(ctx, ctx->scratch[kGzmDesc], &desc, "hipMalloc(member descriptors)")) != MD_OK) return rc;
+    in_off = desc.take<uint64_t>(nb), in_len = desc.take<uint64_t>(nb), out_off = desc.take<uint64_t>(nb), out_cap = desc.take<uint64_t>(nb);
+    out_len = desc.take<uint64_t>(nb), msize = desc.take<uint64_t>(nb), moff = desc.take<uint64_t>(nb + 1);
+    status = desc.take<int32_t>(nb), err = desc.take<int32_t>(1);
+    crc = desc.take<uint32_t>(nb);
+  }
   hipStream_t st = ctx->stream;
   HIP_TRY(ctx, hipMemsetAsync(err, 0, 4, st));
   if (nb) {
     MD_LAUNCH_TRY(ctx, md_launch_bgzf_plan(nb, src_len, block, stride, in_off, in_len, out_off, out_cap, st));
-    // the parameters of MD_FORMAT_GZIP (Gz.Def's make_block: Zl driver, dynamic blocks, queue 4096), the raw body alone
-    md_deflate_params p;
-    memset(&p, 0, sizeof p);
-    p.level = level;
-    p.queue_len = 4096;
-    p.driver = MD_DRIVER_ZL;
-    p.dynamic = 1;
-    p.matcher = MD_MATCHER_DE;
-    p.total_in_bytes = src_len;
+    const md_deflate_params p = gzip_body_params(level, src_len);
     rc = md_deflate_batch_device(ctx, MD_FORMAT_DEFLATE, &p, nb, d_in, in_off, in_len, slots, out_off, out_cap, out_len, status, nullptr);
     if (rc != MD_OK) return rc;
     MD_LAUNCH_TRY(ctx, md_launch_crc32((uint32_t)nb, d_in, in_off, in_len, crc, st));
@@ -445,4 +440,3 @@ int md_bgzf_compress(md_ctx *ctx, int level, size_t block, const uint8_t *src, s
   *written = (size_t)total + 28;
   return MD_OK;
 }
-#undef MD_LAUNCH_TRY

@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "ctx.hpp"
+#include "gz_frame.hpp"
 #include "host_pipeline.hpp"
 
 constexpr size_t kOrderFrom = 2049;  // 256 CUs x 8 resident wavefronts: smaller batches start all at once
@@ -24,18 +25,21 @@ int md_inflate_batch_device(md_ctx *ctx, int format, size_t n, const uint8_t *d_
   MD_ON_DEVICE(ctx);
   if (format == MD_FORMAT_GZIP) {
     // Gz.Inf = header, De.Inf on the body, checksum (lib/gz.ml:463-531, :344-356)
-    int rc = ctx->gz_tmp.reserve(ctx, n * 24, "hipMalloc(gzip scratch)");
-    if (rc != MD_OK) return rc;
-    uint64_t *body_off = (uint64_t *)ctx->gz_tmp.p, *body_len = body_off + n;
-    int32_t *hstatus = (int32_t *)(body_len + n);
-    int e = md_launch_gz_header((uint32_t)n, d_in, d_in_off, d_in_len, body_off, body_len, hstatus, ctx->stream);
-    if (e != 0) return fail(ctx, MD_E_HIP, "gz header kernel launch", (hipError_t)e);
+    int rc = MD_OK;
+    uint64_t *body_off = nullptr, *body_len = nullptr;
+    int32_t *hstatus = nullptr;
+    md::Carver c;
+    for (int pass = 0; pass < 2; pass++) {
+      if (pass && (rc = carve_from(ctx, ctx->gz_tmp, &c, "hipMalloc(gzip scratch)")) != MD_OK) return rc;
+      body_off = c.take<uint64_t>(n), body_len = c.take<uint64_t>(n);
+      hstatus = c.take<int32_t>(n);
+    }
+    MD_LAUNCH_TRY(ctx, md_launch_gz_header((uint32_t)n, d_in, d_in_off, d_in_len, body_off, body_len, hstatus, ctx->stream));
     rc = md_inflate_batch_device(ctx, MD_FORMAT_DEFLATE, n, d_in, body_off, body_len, d_out, d_out_off, d_out_cap,
                                  d_out_len, d_consumed, d_status, nullptr);
     if (rc != MD_OK) return rc;
-    e = md_launch_gz_finish((uint32_t)n, d_in, d_in_off, d_in_len, body_off, hstatus, d_out, d_out_off, d_out_len,
-                            d_consumed, d_status, d_checksum, ctx->stream);
-    if (e != 0) return fail(ctx, MD_E_HIP, "gz finish kernel launch", (hipError_t)e);
+    MD_LAUNCH_TRY(ctx, md_launch_gz_finish((uint32_t)n, d_in, d_in_off, d_in_len, body_off, hstatus, d_out, d_out_off, d_out_len, d_consumed, d_status,
+                                           d_checksum, ctx->stream));
     return MD_OK;
   }
   // a batch of more streams than are resident at once (8 per CU) is started longest stream first; the scratch for the
@@ -43,9 +47,8 @@ int md_inflate_batch_device(md_ctx *ctx, int format, size_t n, const uint8_t *d_
   uint32_t *order = nullptr;
   const int orc = launch_order(ctx, n, kOrderFrom, &order);
   if (orc != MD_OK) return orc;
-  int rc = md_launch_inflate_wave(format, (uint32_t)n, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len,
-                                  d_consumed, d_status, d_checksum, ctx->dbg.as<uint64_t>(), order, ctx->inflate_waves, nullptr, ctx->stream);
-  if (rc != 0) return fail(ctx, MD_E_HIP, "inflate kernel launch", (hipError_t)rc);
+  MD_LAUNCH_TRY(ctx, md_launch_inflate_wave(format, (uint32_t)n, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_consumed, d_status,
+                                            d_checksum, ctx->dbg.as<uint64_t>(), order, ctx->inflate_waves, nullptr, ctx->stream));
   return MD_OK;
 }
 
@@ -133,30 +136,36 @@ int md_inflate_batch_host(md_ctx *ctx, int format, size_t n, const uint8_t *h_in
       return MD_OK;
     }
   }
-  const size_t desc_words = 6 * n;  // in_off in_len out_off out_cap out_len consumed
-  int grc_ = ctx->scratch[kHostIn].reserve(ctx, in_bytes + 64, "hipMalloc(host path input)");
-  if (grc_ == MD_OK) grc_ = ctx->scratch[kHostOut].reserve(ctx, out_bytes + 64, "hipMalloc(host path output)");
-  if (grc_ == MD_OK) grc_ = ctx->scratch[kHostDesc].reserve(ctx, desc_words * 8 + n * 8, "hipMalloc(host path descriptors)");
-  if (grc_ != MD_OK) return grc_;
+  int rc = ctx->scratch[kHostIn].reserve(ctx, in_bytes + 64, "hipMalloc(host path input)");
+  if (rc == MD_OK) rc = ctx->scratch[kHostOut].reserve(ctx, out_bytes + 64, "hipMalloc(host path output)");
+  if (rc != MD_OK) return rc;
   uint8_t *din = (uint8_t *)ctx->scratch[kHostIn].p, *dout = (uint8_t *)ctx->scratch[kHostOut].p;
-  uint64_t *d64 = (uint64_t *)ctx->scratch[kHostDesc].p;
-  int32_t *dstatus = (int32_t *)(d64 + desc_words);
-  uint32_t *dsum = (uint32_t *)(dstatus + n);
+  uint64_t *d_in_off = nullptr, *d_in_len = nullptr, *d_out_off = nullptr, *d_out_cap = nullptr, *d_out_len = nullptr, *d_consumed = nullptr;
+  int32_t *dstatus = nullptr;
+  uint32_t *dsum = nullptr;
+  md::Carver c;
+  for (int pass = 0; pass < 2; pass++) {
+    if (pass && (rc = carve_from(ctx, ctx->scratch[kHostDesc], &c, "hipMalloc(host path descriptors)")) != MD_OK) return rc;
+    d_in_off = c.take<uint64_t>(n), d_in_len = c.take<uint64_t>(n), d_out_off = c.take<uint64_t>(n), d_out_cap = c.take<uint64_t>(n);
+    d_out_len = c.take<uint64_t>(n), d_consumed = c.take<uint64_t>(n);
+    dstatus = c.take<int32_t>(n);
+    dsum = c.take<uint32_t>(n);
+  }
   hipStream_t st = ctx->stream;
-  HIP_TRY(ctx, hipMemcpyAsync(d64 + 0 * n, in_off, n * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(d64 + 1 * n, in_len, n * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(d64 + 2 * n, out_off, n * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(d64 + 3 * n, out_cap, n * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d_in_off, in_off, n * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d_in_len, in_len, n * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d_out_off, out_off, n * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d_out_cap, out_cap, n * 8, hipMemcpyHostToDevice, st));
   // a slice of 1 024 streams (4 per CU) runs at half the batch's rate per stream - still several times what the link to
   // the host moves (57 GB/s each way measured), so the copies stay the longer leg and more slices hide more of the kernels
   const std::vector<HostSlice> sl = host_slices(n, in_off, in_len, out_off, out_cap, 1024, (size_t)ctx->host_slices_max, in_bytes, out_bytes);
-  int rc = host_pipeline(ctx, sl, h_in, din, h_out, dout, [&](size_t i0, size_t cnt) {
-    return md_inflate_batch_device(ctx, format, cnt, din, d64 + i0, d64 + n + i0, dout, d64 + 2 * n + i0, d64 + 3 * n + i0,
-                                   d64 + 4 * n + i0, d64 + 5 * n + i0, dstatus + i0, dsum + i0);
+  rc = host_pipeline(ctx, sl, h_in, din, h_out, dout, [&](size_t i0, size_t cnt) {
+    return md_inflate_batch_device(ctx, format, cnt, din, d_in_off + i0, d_in_len + i0, dout, d_out_off + i0, d_out_cap + i0, d_out_len + i0,
+                                   d_consumed + i0, dstatus + i0, dsum + i0);
   });
   if (rc != MD_OK) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(out_len, d64 + 4 * n, n * 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipMemcpyAsync(consumed, d64 + 5 * n, n * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipMemcpyAsync(out_len, d_out_len, n * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipMemcpyAsync(consumed, d_consumed, n * 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipMemcpyAsync(status, dstatus, n * 4, hipMemcpyDeviceToHost, st));
   if (checksum) HIP_TRY(ctx, hipMemcpyAsync(checksum, dsum, n * 4, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
@@ -181,9 +190,8 @@ int md_inflate_continue_batch_device(md_ctx *ctx, size_t n, const uint8_t *d_in,
   const int orc = launch_order(ctx, n, kOrderFrom, &order);
   if (orc != MD_OK) return orc;
   const md::wv::Cont cont{d_start_bit, d_hist_len, d_adler_in, d_resume_bits, d_resume_out, d_resume_adler, d_resume_last};
-  int rc = md_launch_inflate_wave(MD_FORMAT_DEFLATE, (uint32_t)n, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len,
-                                  d_consumed, d_status, d_checksum, ctx->dbg.as<uint64_t>(), order, ctx->inflate_waves, &cont, ctx->stream);
-  if (rc != 0) return fail(ctx, MD_E_HIP, "inflate kernel launch", (hipError_t)rc);
+  MD_LAUNCH_TRY(ctx, md_launch_inflate_wave(MD_FORMAT_DEFLATE, (uint32_t)n, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_consumed,
+                                            d_status, d_checksum, ctx->dbg.as<uint64_t>(), order, ctx->inflate_waves, &cont, ctx->stream));
   return MD_OK;
 }
 
@@ -205,54 +213,74 @@ int md_de_inf_continue_host(md_ctx *ctx, const uint8_t *src, size_t src_len, uns
   }
   return continue_serial(ctx, src, src_len, start_bit, dst, hist_len, dst_cap, adler_in, flags, dst_len, status, resume);
 }
-int continue_serial(md_ctx *ctx, const uint8_t *src, size_t src_len, unsigned start_bit, uint8_t *dst, size_t hist_len,
-                    size_t dst_cap, uint32_t adler_in, unsigned flags, size_t *dst_len, int *status, md_inf_resume *resume) {
+int inflate_piece(md_ctx *ctx, const uint8_t *src, size_t src_len, unsigned start_bit, const uint8_t *hist, size_t hist_len, uint64_t room,
+                  uint32_t adler_in, InfPiece *r) {
   // the context's scratch, grow-only: a long stream comes in many pieces, and three hipMalloc / hipFree per piece
   // cost more than a short piece's kernel
+  md::DevBuf &din = ctx->scratch[kContIn], &dout = ctx->scratch[kContOut];
+  int rc = din.reserve(ctx, src_len + 16, "hipMalloc(decoder piece input)");
+  if (rc == MD_OK) rc = dout.reserve(ctx, hist_len + room + 16, "hipMalloc(decoder piece output)");
+  if (rc != MD_OK) return rc;
   // descriptors: in_off in_len out_off out_cap out_len consumed resume_bits resume_out (u64); status, checksum,
   // start_bit, hist_len, adler_in, resume_adler, resume_last (u32)
-  md::DevBuf &din = ctx->scratch[kContIn], &dout = ctx->scratch[kContOut], &ddesc = ctx->scratch[kContDesc];
-  int grc_ = din.reserve(ctx, src_len + 16, "hipMalloc(decoder piece input)");
-  if (grc_ == MD_OK) grc_ = dout.reserve(ctx, dst_cap + 16, "hipMalloc(decoder piece output)");
-  if (grc_ == MD_OK) grc_ = ddesc.reserve(ctx, 8 * 8 + 8 * 4 + 4 * 8 + 2 * 4, "hipMalloc(decoder piece descriptors)");
-  if (grc_ != MD_OK) return grc_;
-  uint64_t h64[8] = {0, (uint64_t)src_len, 0, (uint64_t)dst_cap, 0, 0, 0, 0};
+  uint64_t h64[8] = {0, (uint64_t)src_len, 0, hist_len + room, 0, 0, 0, 0};
   uint32_t h32[7] = {0, 0, start_bit, (uint32_t)hist_len, adler_in, 0, 0};
-  uint64_t *d64 = (uint64_t *)ddesc.p;
-  uint32_t *d32 = (uint32_t *)(d64 + 8);
+  uint64_t *d64 = nullptr;
+  uint32_t *d32 = nullptr;
+  md::Carver c;
+  for (int pass = 0; pass < 2; pass++) {
+    if (pass && (rc = carve_from(ctx, ctx->scratch[kContDesc], &c, "hipMalloc(decoder piece descriptors)")) != MD_OK) return rc;
+    d64 = c.take<uint64_t>(8);
+    d32 = c.take<uint32_t>(7);
+  }
   hipStream_t st = ctx->stream;
   if (src_len) HIP_TRY(ctx, hipMemcpyAsync(din.p, src, src_len, hipMemcpyHostToDevice, st));
-  if (hist_len) HIP_TRY(ctx, hipMemcpyAsync(dout.p, dst, hist_len, hipMemcpyHostToDevice, st));
+  if (hist_len) HIP_TRY(ctx, hipMemcpyAsync(dout.p, hist, hist_len, hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipMemcpyAsync(d64, h64, sizeof h64, hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipMemcpyAsync(d32, h32, sizeof h32, hipMemcpyHostToDevice, st));
   const md::wv::Cont cont{d32 + 2, d32 + 3, d32 + 4, d64 + 6, d64 + 7, d32 + 5, d32 + 6};
-  int rc = md_launch_inflate_wave(MD_FORMAT_DEFLATE, 1, (const uint8_t *)din.p, d64 + 0, d64 + 1, (uint8_t *)dout.p, d64 + 2,
-                                  d64 + 3, d64 + 4, d64 + 5, (int32_t *)d32, d32 + 1, nullptr, nullptr, ctx->inflate_waves,
-                                  &cont, st);
-  if (rc != 0) return fail(ctx, MD_E_HIP, "inflate kernel launch", (hipError_t)rc);
+  MD_LAUNCH_TRY(ctx, md_launch_inflate_wave(MD_FORMAT_DEFLATE, 1, (const uint8_t *)din.p, d64 + 0, d64 + 1, (uint8_t *)dout.p, d64 + 2, d64 + 3, d64 + 4,
+                                            d64 + 5, (int32_t *)d32, d32 + 1, nullptr, nullptr, ctx->inflate_waves, &cont, st));
   HIP_TRY(ctx, hipMemcpyAsync(h64, d64, sizeof h64, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipMemcpyAsync(h32, d32, sizeof h32, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
-  const size_t produced = (size_t)h64[4];
-  if (produced > hist_len) HIP_TRY(ctx, hipMemcpy(dst + hist_len, (const uint8_t *)dout.p + hist_len, produced - hist_len, hipMemcpyDeviceToHost));
+  *r = InfPiece{(int32_t)h32[0], h64[4], h64[5], h64[6], h64[7], h32[1], h32[5], h32[6]};
+  return MD_OK;
+}
+
+int continue_serial(md_ctx *ctx, const uint8_t *src, size_t src_len, unsigned start_bit, uint8_t *dst, size_t hist_len,
+                    size_t dst_cap, uint32_t adler_in, unsigned flags, size_t *dst_len, int *status, md_inf_resume *resume) {
+  InfPiece r;
+  int rc = inflate_piece(ctx, src, src_len, start_bit, dst, hist_len, dst_cap - hist_len, adler_in, &r);
+  if (rc != MD_OK) return rc;
+  const uint8_t *d_out = ctx->scratch[kContOut].as<const uint8_t>();
+  hipStream_t st = ctx->stream;
+  const size_t produced = (size_t)r.out_len;
+  if (produced > hist_len) HIP_TRY(ctx, hipMemcpy(dst + hist_len, d_out + hist_len, produced - hist_len, hipMemcpyDeviceToHost));
   *dst_len = produced;
-  *status = (int32_t)h32[0];
-  resume->bits = h64[6];
-  resume->out = h64[7];
-  resume->adler = h32[5];
-  resume->last = h32[6];
-  resume->consumed = h64[5];
-  resume->checksum = h32[1];
+  *status = r.status;
+  resume->bits = r.resume_bits;
+  resume->out = r.resume_out;
+  resume->adler = r.resume_adler;
+  resume->last = r.resume_last;
+  resume->consumed = r.consumed;
+  resume->checksum = r.checksum;
   resume->crc_out = resume->crc_end = 0;
   if (flags & MD_CONT_CRC32) {  // CRC-32 of the new output up to the block boundary, and up to where decoding got
-    uint64_t *c64 = (uint64_t *)(d32 + 8);
-    uint32_t *c32 = (uint32_t *)(c64 + 4);
+    // (the piece's descriptors have been read: their block serves again)
+    uint64_t *c64 = nullptr;
+    uint32_t *c32 = nullptr;
+    md::Carver c;
+    for (int pass = 0; pass < 2; pass++) {
+      if (pass && (rc = carve_from(ctx, ctx->scratch[kContDesc], &c, "hipMalloc(decoder piece descriptors)")) != MD_OK) return rc;
+      c64 = c.take<uint64_t>(4);  // two offsets, two lengths
+      c32 = c.take<uint32_t>(2);
+    }
     const uint64_t to_out = resume->out > hist_len ? resume->out - hist_len : 0, to_end = produced > hist_len ? produced - hist_len : 0;
     const uint64_t hc[4] = {(uint64_t)hist_len, (uint64_t)hist_len, to_out, to_end};
     uint32_t crc[2] = {0, 0};
     HIP_TRY(ctx, hipMemcpyAsync(c64, hc, sizeof hc, hipMemcpyHostToDevice, st));
-    int e = md_launch_crc32(2, (const uint8_t *)dout.p, c64, c64 + 2, c32, st);
-    if (e != 0) return fail(ctx, MD_E_HIP, "crc32 kernel launch", (hipError_t)e);
+    MD_LAUNCH_TRY(ctx, md_launch_crc32(2, d_out, c64, c64 + 2, c32, st));
     HIP_TRY(ctx, hipMemcpyAsync(crc, c32, sizeof crc, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     resume->crc_out = crc[0];
@@ -301,38 +329,21 @@ int md_zl_higher_uncompress(md_ctx *ctx, const uint8_t *src, size_t src_len, uin
 // where the header fields sit in src.  Framing only — the kernels have validated the header.
 static void gz_meta_of(const uint8_t *s, size_t n, md_gz_meta *m) {
   memset(m, 0, sizeof *m);
-  if (n < 10) return;
-  m->flg = s[3];
-  m->mtime = ((uint32_t)s[4] << 24) | ((uint32_t)s[5] << 16) | ((uint32_t)s[6] << 8) | s[7];
-  m->xfl = s[8];
-  m->os = s[9];
-  size_t p = 10;
-  if (m->flg & 4) {
-    if (n - p < 2) return;
-    const size_t xl = ((size_t)s[p] << 8) | s[p + 1];
-    p += 2;
-    if (n - p < xl) return;
-    m->has_extra = 1;
-    m->extra_off = p;
-    m->extra_len = xl;
-    p += xl;
-  }
-  for (int which = 0; which < 2; which++) {
-    if (!(m->flg & (which == 0 ? 8u : 16u))) continue;
-    size_t q = p;
-    while (q < n && s[q] != 0) q++;
-    if (q >= n) return;
-    if (which == 0) {
-      m->has_name = 1;
-      m->name_off = p;
-      m->name_len = q - p;
-    } else {
-      m->has_comment = 1;
-      m->comment_off = p;
-      m->comment_len = q - p;
-    }
-    p = q + 1;
-  }
+  md::gz::InfHeader h;
+  if (md::gz::inf_header(s, n, &h) != MD_OK) return;
+  m->flg = h.flg;
+  m->mtime = h.mtime;
+  m->xfl = h.xfl;
+  m->os = h.os;
+  m->has_extra = (h.flg & 4) != 0;
+  m->extra_off = h.extra_off;
+  m->extra_len = h.extra_len;
+  m->has_name = (h.flg & 8) != 0;
+  m->name_off = h.name_off;
+  m->name_len = h.name_len;
+  m->has_comment = (h.flg & 16) != 0;
+  m->comment_off = h.comment_off;
+  m->comment_len = h.comment_len;
 }
 
 int md_gz_higher_uncompress(md_ctx *ctx, const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap,

@@ -18,12 +18,15 @@ int md_inflate_sizes_batch_device(md_ctx *ctx, int format, size_t n, const uint8
   const uint64_t *off = d_in_off, *len = d_in_len;
   int32_t *hstatus = nullptr;
   if (format == MD_FORMAT_GZIP) {  // header, the count kernel on the bodies, trailer (as md_inflate_batch_device)
-    const int rc = ctx->gz_tmp.reserve(ctx, n * 24, "hipMalloc(gzip scratch)");
-    if (rc != MD_OK) return rc;
-    uint64_t *body_off = (uint64_t *)ctx->gz_tmp.p, *body_len = body_off + n;
-    hstatus = (int32_t *)(body_len + n);
-    const int e = md_launch_gz_header((uint32_t)n, d_in, d_in_off, d_in_len, body_off, body_len, hstatus, ctx->stream);
-    if (e != 0) return fail(ctx, MD_E_HIP, "gz header kernel launch", (hipError_t)e);
+    uint64_t *body_off = nullptr, *body_len = nullptr;
+    md::Carver c;
+    for (int pass = 0; pass < 2; pass++) {
+      int rc = MD_OK;
+      if (pass && (rc = carve_from(ctx, ctx->gz_tmp, &c, "hipMalloc(gzip scratch)")) != MD_OK) return rc;
+      body_off = c.take<uint64_t>(n), body_len = c.take<uint64_t>(n);
+      hstatus = c.take<int32_t>(n);
+    }
+    MD_LAUNCH_TRY(ctx, md_launch_gz_header((uint32_t)n, d_in, d_in_off, d_in_len, body_off, body_len, hstatus, ctx->stream));
     off = body_off;
     len = body_len;
   }
@@ -32,13 +35,10 @@ int md_inflate_sizes_batch_device(md_ctx *ctx, int format, size_t n, const uint8
   if (orc != MD_OK) return orc;
   uint64_t *dbg = ctx->dbg.as<uint64_t>();
   if (dbg) HIP_TRY(ctx, hipMemsetAsync(dbg, 0, 3 * 8, ctx->stream));
-  int e = md_launch_inflate_count(format == MD_FORMAT_GZIP ? MD_FORMAT_DEFLATE : format, (uint32_t)n, d_in, off, len, d_out_len,
-                                  d_consumed, d_status, dbg, order, ctx->stream);
-  if (e != 0) return fail(ctx, MD_E_HIP, "inflate count kernel launch", (hipError_t)e);
-  if (format == MD_FORMAT_GZIP) {
-    e = md_launch_sizes_gz_finish((uint32_t)n, d_in, d_in_off, d_in_len, off, hstatus, d_out_len, d_consumed, d_status, ctx->stream);
-    if (e != 0) return fail(ctx, MD_E_HIP, "gz size finish kernel launch", (hipError_t)e);
-  }
+  MD_LAUNCH_TRY(ctx, md_launch_inflate_count(format == MD_FORMAT_GZIP ? MD_FORMAT_DEFLATE : format, (uint32_t)n, d_in, off, len, d_out_len, d_consumed,
+                                             d_status, dbg, order, ctx->stream));
+  if (format == MD_FORMAT_GZIP)
+    MD_LAUNCH_TRY(ctx, md_launch_sizes_gz_finish((uint32_t)n, d_in, d_in_off, d_in_len, off, hstatus, d_out_len, d_consumed, d_status, ctx->stream));
   return MD_OK;
 }
 
@@ -61,19 +61,24 @@ int md_inflate_sizes_batch_host(md_ctx *ctx, int format, size_t n, const uint8_t
   }
   MD_ON_DEVICE(ctx);
   int rc = ctx->scratch[kHostIn].reserve(ctx, in_bytes + 64, "hipMalloc(host path input)");
-  if (rc == MD_OK) rc = ctx->scratch[kHostDesc].reserve(ctx, n * (4 * 8 + 4), "hipMalloc(host path descriptors)");
   if (rc != MD_OK) return rc;
   uint8_t *din = (uint8_t *)ctx->scratch[kHostIn].p;
-  uint64_t *d64 = (uint64_t *)ctx->scratch[kHostDesc].p;  // in_off in_len out_len consumed, then status
-  int32_t *dstatus = (int32_t *)(d64 + 4 * n);
+  uint64_t *d_in_off = nullptr, *d_in_len = nullptr, *d_out_len = nullptr, *d_consumed = nullptr;
+  int32_t *dstatus = nullptr;
+  md::Carver c;
+  for (int pass = 0; pass < 2; pass++) {
+    if (pass && (rc = carve_from(ctx, ctx->scratch[kHostDesc], &c, "hipMalloc(host path descriptors)")) != MD_OK) return rc;
+    d_in_off = c.take<uint64_t>(n), d_in_len = c.take<uint64_t>(n), d_out_len = c.take<uint64_t>(n), d_consumed = c.take<uint64_t>(n);
+    dstatus = c.take<int32_t>(n);
+  }
   hipStream_t st = ctx->stream;
   if (hi > lo) HIP_TRY(ctx, hipMemcpyAsync(din + lo, h_in + lo, hi - lo, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(d64, in_off, n * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(d64 + n, in_len, n * 8, hipMemcpyHostToDevice, st));
-  rc = md_inflate_sizes_batch_device(ctx, format, n, din, d64, d64 + n, d64 + 2 * n, d64 + 3 * n, dstatus);
+  HIP_TRY(ctx, hipMemcpyAsync(d_in_off, in_off, n * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d_in_len, in_len, n * 8, hipMemcpyHostToDevice, st));
+  rc = md_inflate_sizes_batch_device(ctx, format, n, din, d_in_off, d_in_len, d_out_len, d_consumed, dstatus);
   if (rc != MD_OK) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(out_len, d64 + 2 * n, n * 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipMemcpyAsync(consumed, d64 + 3 * n, n * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipMemcpyAsync(out_len, d_out_len, n * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipMemcpyAsync(consumed, d_consumed, n * 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipMemcpyAsync(status, dstatus, n * 4, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
   return MD_OK;
@@ -85,7 +90,6 @@ int md_inflate_plan_device(md_ctx *ctx, size_t n, const uint64_t *d_out_len, siz
   if (align == 0 || (align & (align - 1)) != 0) return fail(ctx, MD_E_INVALID_ARGUMENT, "align is not a power of two");
   if (!d_total || (n != 0 && (!d_out_len || !d_out_off || !d_out_cap))) return fail(ctx, MD_E_INVALID_ARGUMENT, "null array");
   MD_ON_DEVICE(ctx);
-  const int e = md_launch_inflate_plan(n, d_out_len, align, d_out_off, d_out_cap, d_total, ctx->stream);
-  if (e != 0) return fail(ctx, MD_E_HIP, "inflate plan kernel launch", (hipError_t)e);
+  MD_LAUNCH_TRY(ctx, md_launch_inflate_plan(n, d_out_len, align, d_out_off, d_out_cap, d_total, ctx->stream));
   return MD_OK;
 }

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "ctx.hpp"
+#include "gz_frame.hpp"
 
 // De.Higher.uncompress / Zl.Higher.uncompress / Gz on ONE big input (lib/de.ml:4555-4571, lib/zl.ml:650-666,
 // bin/decompress.ml:77-100).  Returns MD_NOT_HANDLED whenever anything is not exactly as a well-formed stream decoded in
@@ -60,18 +61,22 @@ static int par_decode(md_ctx *ctx, const ParIn &in, ParOut *out, std::vector<Par
   // -- the body on the device, candidate block starts
   int rc = ctx->scratch[kParIn].reserve(ctx, body_len + 64, "hipMalloc(parallel inflate input)");
   if (rc != MD_OK) return rc;
-  const size_t desc_bytes = (size_t)nchunks * 2 * 160 + 4096;
-  rc = ctx->scratch[kParDesc].reserve(ctx, desc_bytes, "hipMalloc(parallel inflate descriptors)");
-  if (rc != MD_OK) return rc;
+  // (the slack: room for the descriptors of the rounds below, 93 bytes a row and about two rows a chunk, so that the block
+  // does not grow between the rounds)
+  uint64_t *d_cand = nullptr;
+  md::Carver cd;
+  for (int pass = 0; pass < 2; pass++) {
+    if (pass && (rc = carve_from(ctx, ctx->scratch[kParDesc], &cd, "hipMalloc(parallel inflate descriptors)", (size_t)nchunks * 2 * 160 + 4096)) != MD_OK)
+      return rc;
+    d_cand = cd.take<uint64_t>(nchunks - 1);
+  }
   uint8_t *d_body = (uint8_t *)ctx->scratch[kParIn].p;
   HIP_TRY(ctx, hipMemcpyAsync(d_body, body, body_len, hipMemcpyHostToDevice, st));
-  uint64_t *d_cand = (uint64_t *)ctx->scratch[kParDesc].p;
   if (dbg_t) {
     hipStreamSynchronize(st);
     stamp("body on the device");
   }
-  int e = md_launch_find_blocks(d_body, body_len, K, nchunks - 1, d_cand, st);
-  if (e != 0) return fail(ctx, MD_E_HIP, "find_blocks launch", (hipError_t)e);
+  MD_LAUNCH_TRY(ctx, md_launch_find_blocks(d_body, body_len, K, nchunks - 1, d_cand, st));
   std::vector<uint64_t> cand(nchunks - 1);
   HIP_TRY(ctx, hipMemcpyAsync(cand.data(), d_cand, (nchunks - 1) * 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
@@ -157,38 +162,44 @@ static int par_decode(md_ctx *ctx, const ParIn &in, ParOut *out, std::vector<Par
     if (at > ((uint64_t)64 << 30)) return MD_NOT_HANDLED;
     rc = ctx->scratch[kParOut].reserve(ctx, at + 64, "hipMalloc(parallel inflate output)");
     if (rc != MD_OK) return rc;
-    // descriptors: u64 x n: in_off in_len out_off out_cap out_len consumed resume_bits resume_out; u32 x n: start_bit hist
-    // adler_in status checksum resume_adler resume_last; u8 x n: variant
-    const size_t need = n * (8 * 8 + 7 * 4 + 1) + 256;
-    rc = ctx->scratch[kParDesc].reserve(ctx, need, "hipMalloc(parallel inflate descriptors)");
-    if (rc != MD_OK) return rc;
-    uint64_t *d64 = (uint64_t *)ctx->scratch[kParDesc].p;
-    uint32_t *d32 = (uint32_t *)(d64 + 8 * n);
-    uint8_t *d8 = (uint8_t *)(d32 + 7 * n);
+    // the rows' descriptors, n entries each
+    uint64_t *d_in_off = nullptr, *d_in_len = nullptr, *d_out_off = nullptr, *d_out_cap = nullptr, *d_out_len = nullptr, *d_consumed = nullptr,
+             *d_resume_bits = nullptr, *d_resume_out = nullptr;
+    uint32_t *d_start_bit = nullptr, *d_hist = nullptr, *d_adler_in = nullptr, *d_checksum = nullptr, *d_resume_adler = nullptr, *d_resume_last = nullptr;
+    int32_t *d_status = nullptr;
+    uint8_t *d_variant = nullptr;
+    md::Carver c;
+    for (int pass = 0; pass < 2; pass++) {
+      if (pass && (rc = carve_from(ctx, ctx->scratch[kParDesc], &c, "hipMalloc(parallel inflate descriptors)", 256)) != MD_OK) return rc;
+      d_in_off = c.take<uint64_t>(n), d_in_len = c.take<uint64_t>(n), d_out_off = c.take<uint64_t>(n), d_out_cap = c.take<uint64_t>(n);
+      d_out_len = c.take<uint64_t>(n), d_consumed = c.take<uint64_t>(n), d_resume_bits = c.take<uint64_t>(n), d_resume_out = c.take<uint64_t>(n);
+      d_start_bit = c.take<uint32_t>(n), d_hist = c.take<uint32_t>(n), d_adler_in = c.take<uint32_t>(n);
+      d_status = c.take<int32_t>(n);
+      d_checksum = c.take<uint32_t>(n), d_resume_adler = c.take<uint32_t>(n), d_resume_last = c.take<uint32_t>(n);
+      d_variant = c.take<uint8_t>(n);
+    }
     uint8_t *d_out = (uint8_t *)ctx->scratch[kParOut].p;
     if (hl) HIP_TRY(ctx, hipMemcpyAsync(d_out, in.hist, hl, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(d64 + 0 * n, in_off.data(), n * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(d64 + 1 * n, in_len.data(), n * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(d64 + 2 * n, out_off.data(), n * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(d64 + 3 * n, out_cap.data(), n * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(d32 + 0 * n, start_bit.data(), n * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(d32 + 1 * n, hist.data(), n * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(d32 + 2 * n, adler_in.data(), n * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(d8, variant.data(), n, hipMemcpyHostToDevice, st));
-    e = md_launch_fill_windows((uint32_t)n, d_out, d64 + 2 * n, d8, st);
-    if (e != 0) return fail(ctx, MD_E_HIP, "fill_windows launch", (hipError_t)e);
-    rc = md_inflate_continue_batch_device(ctx, n, d_body, d64 + 0 * n, d64 + 1 * n, d_out, d64 + 2 * n, d64 + 3 * n, d32 + 0 * n,
-                                          d32 + 1 * n, d32 + 2 * n, d64 + 4 * n, d64 + 5 * n, (int32_t *)(d32 + 3 * n), d32 + 4 * n,
-                                          d64 + 6 * n, d64 + 7 * n, d32 + 5 * n, d32 + 6 * n);
+    HIP_TRY(ctx, hipMemcpyAsync(d_in_off, in_off.data(), n * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d_in_len, in_len.data(), n * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d_out_off, out_off.data(), n * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d_out_cap, out_cap.data(), n * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d_start_bit, start_bit.data(), n * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d_hist, hist.data(), n * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d_adler_in, adler_in.data(), n * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d_variant, variant.data(), n, hipMemcpyHostToDevice, st));
+    MD_LAUNCH_TRY(ctx, md_launch_fill_windows((uint32_t)n, d_out, d_out_off, d_variant, st));
+    rc = md_inflate_continue_batch_device(ctx, n, d_body, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_start_bit, d_hist, d_adler_in, d_out_len,
+                                          d_consumed, d_status, d_checksum, d_resume_bits, d_resume_out, d_resume_adler, d_resume_last);
     if (rc != MD_OK) return rc;
     std::vector<uint64_t> r_used(n), r_bits(n), r_out(n);
     std::vector<int32_t> r_st(n);
     std::vector<uint32_t> r_last(n);
-    HIP_TRY(ctx, hipMemcpyAsync(r_used.data(), d64 + 5 * n, n * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(r_bits.data(), d64 + 6 * n, n * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(r_out.data(), d64 + 7 * n, n * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(r_st.data(), d32 + 3 * n, n * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(r_last.data(), d32 + 6 * n, n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(r_used.data(), d_consumed, n * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(r_bits.data(), d_resume_bits, n * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(r_out.data(), d_resume_out, n * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(r_st.data(), d_status, n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(r_last.data(), d_resume_last, n * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     stamp("pieces decoded");
     // The pieces in order: piece p must end - its last complete block - exactly where piece p + 1 starts ("links").  From
@@ -300,29 +311,29 @@ static int par_decode(md_ctx *ctx, const ParIn &in, ParOut *out, std::vector<Par
     rc = ctx->scratch[kParWin].reserve(ctx, win_bytes + (jumping ? md_windows_work_bytes((uint32_t)np, kGroup) : 0) + 64,
               "hipMalloc(parallel inflate windows)");
     if (rc != MD_OK) return rc;
-    const size_t need = np * 32 + 256;
-    rc = ctx->scratch[kParDesc].reserve(ctx, need, "hipMalloc(parallel inflate descriptors)");
-    if (rc != MD_OK) return rc;
-    uint64_t *d64 = (uint64_t *)ctx->scratch[kParDesc].p;  // offa offb u pos | flag
-    uint32_t *d_flag = (uint32_t *)(d64 + 4 * np);
-    uint8_t *d_out = (uint8_t *)ctx->scratch[kParOut].p;
-    HIP_TRY(ctx, hipMemcpyAsync(d64 + 0 * np, offa.data(), np * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(d64 + 1 * np, offb.data(), np * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(d64 + 2 * np, u.data(), np * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(d64 + 3 * np, pos.data(), np * 8, hipMemcpyHostToDevice, st));
+    uint64_t *d_offa = nullptr, *d_offb = nullptr, *d_u = nullptr, *d_pos = nullptr;
+    uint32_t *d_flag = nullptr;
+    md::Carver c;
+    for (int pass = 0; pass < 2; pass++) {
+      if (pass && (rc = carve_from(ctx, ctx->scratch[kParDesc], &c, "hipMalloc(parallel inflate descriptors)", 256)) != MD_OK) return rc;
+      d_offa = c.take<uint64_t>(np), d_offb = c.take<uint64_t>(np), d_u = c.take<uint64_t>(np), d_pos = c.take<uint64_t>(np);
+      d_flag = c.take<uint32_t>(16);
+    }
+    uint8_t *d_out = (uint8_t *)ctx->scratch[kParOut].p, *d_win = (uint8_t *)ctx->scratch[kParWin].p;
+    HIP_TRY(ctx, hipMemcpyAsync(d_offa, offa.data(), np * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d_offb, offb.data(), np * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d_u, u.data(), np * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d_pos, pos.data(), np * 8, hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipMemsetAsync(d_flag, 0, 64, st));
     if (jumping)
-      e = md_launch_windows_parallel((uint32_t)np, kGroup, d_out, u[0], d_out, d64 + 0 * np, d64 + 1 * np, d64 + 2 * np, d64 + 3 * np,
-                                     (uint8_t *)ctx->scratch[kParWin].p, (uint32_t *)((uint8_t *)ctx->scratch[kParWin].p + win_bytes), d_flag, st);
-    else e = md_launch_window_chain((uint32_t)np, d_out, d_out, d64 + 0 * np, d64 + 1 * np, d64 + 2 * np, (uint8_t *)ctx->scratch[kParWin].p, d_flag, st);
-    if (e != 0) return fail(ctx, MD_E_HIP, "window_chain launch", (hipError_t)e);
+      MD_LAUNCH_TRY(ctx, md_launch_windows_parallel((uint32_t)np, kGroup, d_out, u[0], d_out, d_offa, d_offb, d_u, d_pos, d_win, (uint32_t *)(d_win + win_bytes),
+                                                    d_flag, st));
+    else MD_LAUNCH_TRY(ctx, md_launch_window_chain((uint32_t)np, d_out, d_out, d_offa, d_offb, d_u, d_win, d_flag, st));
     if (dbg_t) {
       hipStreamSynchronize(st);
       stamp("window chain");
     }
-    e = md_launch_resolve((uint32_t)np, d_out, d_out, d64 + 0 * np, d64 + 1 * np, d64 + 2 * np, d64 + 3 * np,
-                          (const uint8_t *)ctx->scratch[kParWin].p, d_flag, st);
-    if (e != 0) return fail(ctx, MD_E_HIP, "resolve launch", (hipError_t)e);
+    MD_LAUNCH_TRY(ctx, md_launch_resolve((uint32_t)np, d_out, d_out, d_offa, d_offb, d_u, d_pos, d_win, d_flag, st));
     // (the flag is read by the caller together with what it needs next)
     uint32_t flag = 0;
     HIP_TRY(ctx, hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, st));
@@ -364,11 +375,14 @@ int par_adler(md_ctx *ctx, const uint8_t *d, uint64_t n, uint32_t adler, uint32_
   *res = adler;
   if (n == 0) return MD_OK;
   const size_t nseg = (size_t)((n + 65535) / 65536);
-  int rc = ctx->scratch[kParDesc].reserve(ctx, nseg * 8 + 64, "hipMalloc(parallel inflate descriptors)");
-  if (rc != MD_OK) return rc;
-  uint32_t *d_sums = (uint32_t *)ctx->scratch[kParDesc].p;
-  int e = md_launch_adler_segments(d, n, 65536, d_sums, ctx->stream);
-  if (e != 0) return fail(ctx, MD_E_HIP, "adler_segments launch", (hipError_t)e);
+  int rc = MD_OK;
+  uint32_t *d_sums = nullptr;  // a pair of sums per segment
+  md::Carver c;
+  for (int pass = 0; pass < 2; pass++) {
+    if (pass && (rc = carve_from(ctx, ctx->scratch[kParDesc], &c, "hipMalloc(parallel inflate descriptors)", 64)) != MD_OK) return rc;
+    d_sums = c.take<uint32_t>(2 * nseg);
+  }
+  MD_LAUNCH_TRY(ctx, md_launch_adler_segments(d, n, 65536, d_sums, ctx->stream));
   std::vector<uint32_t> sums(2 * nseg);
   HIP_TRY(ctx, hipMemcpyAsync(sums.data(), d_sums, nseg * 8, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -385,10 +399,15 @@ int par_crc(md_ctx *ctx, const uint8_t *d_base, uint64_t off, uint64_t n, uint32
   *res = 0;
   if (n == 0) return MD_OK;
   const size_t ncrc = (size_t)((n + ((1u << 20) - 1)) >> 20);
-  int rc = ctx->scratch[kParDesc].reserve(ctx, ncrc * 24 + 64, "hipMalloc(parallel inflate descriptors)");
-  if (rc != MD_OK) return rc;
-  uint64_t *d_off = (uint64_t *)ctx->scratch[kParDesc].p, *d_len = d_off + ncrc;
-  uint32_t *d_crc = (uint32_t *)(d_len + ncrc);
+  int rc = MD_OK;
+  uint64_t *d_off = nullptr, *d_len = nullptr;
+  uint32_t *d_crc = nullptr;
+  md::Carver c;
+  for (int pass = 0; pass < 2; pass++) {
+    if (pass && (rc = carve_from(ctx, ctx->scratch[kParDesc], &c, "hipMalloc(parallel inflate descriptors)", 64)) != MD_OK) return rc;
+    d_off = c.take<uint64_t>(ncrc), d_len = c.take<uint64_t>(ncrc);
+    d_crc = c.take<uint32_t>(ncrc);
+  }
   std::vector<uint64_t> co(ncrc), cl(ncrc);
   for (size_t s = 0; s < ncrc; s++) {
     co[s] = off + ((uint64_t)s << 20);
@@ -396,8 +415,7 @@ int par_crc(md_ctx *ctx, const uint8_t *d_base, uint64_t off, uint64_t n, uint32
   }
   HIP_TRY(ctx, hipMemcpyAsync(d_off, co.data(), ncrc * 8, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(d_len, cl.data(), ncrc * 8, hipMemcpyHostToDevice, ctx->stream));
-  int e = md_launch_crc32((uint32_t)ncrc, d_base, d_off, d_len, d_crc, ctx->stream);
-  if (e != 0) return fail(ctx, MD_E_HIP, "crc32 launch", (hipError_t)e);
+  MD_LAUNCH_TRY(ctx, md_launch_crc32((uint32_t)ncrc, d_base, d_off, d_len, d_crc, ctx->stream));
   std::vector<uint32_t> crcs(ncrc);
   HIP_TRY(ctx, hipMemcpyAsync(crcs.data(), d_crc, ncrc * 4, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -472,23 +490,9 @@ int inflate_parallel(md_ctx *ctx, int format, const uint8_t *src, size_t src_len
     hdr = 2;
     trailer = 4;
   } else if (format == MD_FORMAT_GZIP) {
-    if (src_len < 18 || src[0] != 0x1f || src[1] != 0x8b || (src[3] & 2)) return MD_NOT_HANDLED;  // (a header CRC: serial path)
-    size_t p = 10;
-    const uint32_t flg = src[3];
-    if (flg & 4) {  // FEXTRA, big-endian length as the reference reads it (lib/gz.ml:455)
-      if (src_len - p < 2) return MD_NOT_HANDLED;
-      const size_t xl = ((size_t)src[p] << 8) | src[p + 1];
-      p += 2;
-      if (src_len - p < xl) return MD_NOT_HANDLED;
-      p += xl;
-    }
-    for (int which = 0; which < 2; which++) {
-      if (!(flg & (which == 0 ? 8u : 16u))) continue;
-      while (p < src_len && src[p] != 0) p++;
-      if (p >= src_len) return MD_NOT_HANDLED;
-      p++;
-    }
-    hdr = p;
+    md::gz::InfHeader h;
+    if (md::gz::inf_header(src, src_len, &h) != MD_OK || (h.flg & 2)) return MD_NOT_HANDLED;  // (a header CRC: serial path)
+    hdr = h.body;
     trailer = 8;
   } else if (format != MD_FORMAT_DEFLATE) return MD_NOT_HANDLED;
   if (src_len < hdr + trailer) return MD_NOT_HANDLED;
@@ -509,20 +513,14 @@ int inflate_parallel(md_ctx *ctx, int format, const uint8_t *src, size_t src_len
     rc = par_adler(ctx, d_out, total, 1u, &adler);
     if (rc != MD_OK) return rc;
     if (format == MD_FORMAT_ZLIB) {
-      const uint32_t want = ((uint32_t)t[0] << 24) | ((uint32_t)t[1] << 16) | ((uint32_t)t[2] << 8) | t[3];
-      good = want == adler;
+      good = md::be32(t) == adler;
     }
     if (checksum) *checksum = adler;
   } else if (format == MD_FORMAT_GZIP) {
     uint32_t crc = 0;
     rc = par_crc(ctx, d_out, 0, total, &crc);
     if (rc != MD_OK) return rc;
-    uint32_t want = 0, isize = 0;
-    for (int k = 0; k < 4; k++) {
-      want |= (uint32_t)t[k] << (8 * k);
-      isize |= (uint32_t)t[4 + k] << (8 * k);
-    }
-    good = want == crc && isize == (uint32_t)total;
+    good = md::le32(t) == crc && md::le32(t + 4) == (uint32_t)total;
     if (checksum) *checksum = crc;
   }
   if (!good) {  // the serial path reports it

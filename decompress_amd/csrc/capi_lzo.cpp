@@ -18,11 +18,10 @@ static int lzo_batch_device(md_ctx *ctx, bool compress, size_t n, const uint8_t 
     if (rc != MD_OK) return rc;
   }
   HIP_TRY(ctx, hipMemsetAsync(ctx->counters.as<uint32_t>(), 0, 4, ctx->stream));
-  const int e = compress ? md_launch_lzo_compress((uint32_t)n, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap,
-                                                  d_out_len, d_status, ctx->lzo_ws.as<uint16_t>(), ctx->counters.as<uint32_t>(), slots, ctx->stream)
-                         : md_launch_lzo_uncompress((uint32_t)n, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap,
-                                                    d_out_len, d_status, ctx->counters.as<uint32_t>(), slots, ctx->stream);
-  if (e != 0) return fail(ctx, MD_E_HIP, "lzo kernel launch", (hipError_t)e);
+  MD_LAUNCH_TRY(ctx, compress ? md_launch_lzo_compress((uint32_t)n, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status,
+                                                       ctx->lzo_ws.as<uint16_t>(), ctx->counters.as<uint32_t>(), slots, ctx->stream)
+                              : md_launch_lzo_uncompress((uint32_t)n, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status,
+                                                         ctx->counters.as<uint32_t>(), slots, ctx->stream));
   return MD_OK;
 }
 
@@ -66,9 +65,7 @@ int md_lzo_sizes_batch_device(md_ctx *ctx, size_t n, const uint8_t *d_in, const 
   MD_ON_DEVICE(ctx);
   const uint32_t slots = md_lzo_slots(2, (uint32_t)ctx->cus);
   HIP_TRY(ctx, hipMemsetAsync(ctx->counters.as<uint32_t>(), 0, 4, ctx->stream));
-  const int e = md_launch_lzo_count((uint32_t)n, d_in, d_in_off, d_in_len, d_out_len, d_status, ctx->counters.as<uint32_t>(), slots,
-                                    ctx->stream);
-  if (e != 0) return fail(ctx, MD_E_HIP, "lzo count kernel launch", (hipError_t)e);
+  MD_LAUNCH_TRY(ctx, md_launch_lzo_count((uint32_t)n, d_in, d_in_off, d_in_len, d_out_len, d_status, ctx->counters.as<uint32_t>(), slots, ctx->stream));
   return MD_OK;
 }
 
@@ -90,18 +87,23 @@ int md_lzo_sizes_batch_host(md_ctx *ctx, size_t n, const uint8_t *h_in, size_t i
   }
   MD_ON_DEVICE(ctx);
   int rc = ctx->scratch[kHostIn].reserve(ctx, in_bytes + 64, "hipMalloc(host path input)");
-  if (rc == MD_OK) rc = ctx->scratch[kHostDesc].reserve(ctx, n * (3 * 8 + 4), "hipMalloc(host path descriptors)");
   if (rc != MD_OK) return rc;
   uint8_t *din = (uint8_t *)ctx->scratch[kHostIn].p;
-  uint64_t *d64 = (uint64_t *)ctx->scratch[kHostDesc].p;  // in_off in_len out_len, then status
-  int32_t *dstatus = (int32_t *)(d64 + 3 * n);
+  uint64_t *d_in_off = nullptr, *d_in_len = nullptr, *d_out_len = nullptr;
+  int32_t *dstatus = nullptr;
+  md::Carver c;
+  for (int pass = 0; pass < 2; pass++) {
+    if (pass && (rc = carve_from(ctx, ctx->scratch[kHostDesc], &c, "hipMalloc(host path descriptors)")) != MD_OK) return rc;
+    d_in_off = c.take<uint64_t>(n), d_in_len = c.take<uint64_t>(n), d_out_len = c.take<uint64_t>(n);
+    dstatus = c.take<int32_t>(n);
+  }
   hipStream_t st = ctx->stream;
   if (hi > lo) HIP_TRY(ctx, hipMemcpyAsync(din + lo, h_in + lo, hi - lo, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(d64, in_off, n * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(d64 + n, in_len, n * 8, hipMemcpyHostToDevice, st));
-  rc = md_lzo_sizes_batch_device(ctx, n, din, d64, d64 + n, d64 + 2 * n, dstatus);
+  HIP_TRY(ctx, hipMemcpyAsync(d_in_off, in_off, n * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d_in_len, in_len, n * 8, hipMemcpyHostToDevice, st));
+  rc = md_lzo_sizes_batch_device(ctx, n, din, d_in_off, d_in_len, d_out_len, dstatus);
   if (rc != MD_OK) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(out_len, d64 + 2 * n, n * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipMemcpyAsync(out_len, d_out_len, n * 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipMemcpyAsync(status, dstatus, n * 4, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
   return MD_OK;

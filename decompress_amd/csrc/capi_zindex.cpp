@@ -9,29 +9,11 @@
 #include <vector>
 
 #include "ctx.hpp"
+#include "gz_frame.hpp"
 #include "zindex.hpp"
-
-#define MD_LAUNCH_TRY(ctx, expr)                                        \
-  do {                                                                  \
-    const int e_ = (expr);                                              \
-    if (e_ != 0) return fail(ctx, MD_E_HIP, #expr, (hipError_t)e_);     \
-  } while (0)
 
 namespace {
 using md::zix::kWindow;
-
-// device memory carved from one scratch block, every piece on 16 bytes
-struct Carver {
-  uint8_t *p;
-  size_t at = 0;
-  explicit Carver(void *base) : p((uint8_t *)base) {}
-  template <class T>
-  T *take(size_t n) {
-    T *r = p ? (T *)(p + at) : nullptr;
-    at += (n * sizeof(T) + 15) & ~(size_t)15;
-    return r;
-  }
-};
 
 // compressed input that one piece of the build hands to the whole-chip decoder (its scratch is about 14 times that)
 constexpr size_t kParPieceIn = (size_t)32 << 20;
@@ -39,8 +21,7 @@ constexpr size_t kParPieceIn = (size_t)32 << 20;
 constexpr uint64_t kIdsAhead = 4096;
 static_assert(md::zix::kWin == md::zix::kWindow, "one window size: internal.hpp's for the kernels, zindex.hpp's for the host");
 
-// The frame's header on the host, by the rules of stream_frame.hpp (Gz.Inf's walk: FEXTRA's length big-endian, FHCRC the
-// upper half of the CRC-32 of the fixed bytes, name and comment; Zl.Inf's two bytes): MD_OK and the body's offset
+// The frame's header on the host (Gz.Inf's walk: gz_frame.hpp; Zl.Inf's two bytes): MD_OK and the body's offset
 int frame_header(int format, const uint8_t *s, size_t n, uint64_t *body) {
   *body = 0;
   if (format == MD_FORMAT_DEFLATE) return MD_OK;
@@ -50,34 +31,10 @@ int frame_header(int format, const uint8_t *s, size_t n, uint64_t *body) {
     *body = 2;
     return MD_OK;
   }
-  if (n >= 10 && (s[0] != 0x1f || s[1] != 0x8b)) return MD_INVALID_GZIP_HEADER;
-  if (n < 10) return MD_UNEXPECTED_END_OF_INPUT;
-  const uint32_t flg = s[3];
-  size_t p = 10, after_extra = 10;
-  if (flg & 4) {
-    if (n - p < 2) return MD_UNEXPECTED_END_OF_INPUT;
-    const size_t xl = ((size_t)s[p] << 8) | s[p + 1];
-    p += 2;
-    if (n - p < xl) return MD_UNEXPECTED_END_OF_INPUT;
-    p += xl;
-    after_extra = p;
-  }
-  for (int which = 0; which < 2; which++) {
-    if (!(flg & (which == 0 ? 8u : 16u))) continue;
-    for (;;) {
-      if (p >= n) return MD_UNEXPECTED_END_OF_INPUT;
-      if (s[p++] == 0) break;
-    }
-  }
-  if (flg & 2) {
-    if (n - p < 2) return MD_UNEXPECTED_END_OF_INPUT;
-    uint32_t c = md::crc32_update(0, s, 10);
-    c = md::crc32_update(c, s + after_extra, p - after_extra);
-    if (((c & 0xffff0000u) >> 16) != (((uint32_t)s[p] << 8) | s[p + 1])) return MD_INVALID_GZIP_HEADER_CHECKSUM;
-    p += 2;
-  }
-  *body = p;
-  return MD_OK;
+  md::gz::InfHeader h;
+  const int st = md::gz::inf_header(s, n, &h);
+  *body = h.body;
+  return st;
 }
 
 // The stored blocks that are not final from bit `pos` on, read off the stream (header, padding, LEN, NLEN): the bit behind
@@ -97,36 +54,6 @@ uint64_t stored_run(const uint8_t *src, uint64_t src_len, uint64_t pos, uint64_t
     *payload += len;
   }
   return pos;
-}
-
-// One piece through one pair of wavefronts, its output LEFT ON THE DEVICE (continue_serial copies it out): hist in front
-// of kContOut, new output behind.  h64: in_off in_len out_off out_cap out_len consumed resume_bits resume_out; h32:
-// status checksum start_bit hist_len adler_in resume_adler resume_last.
-int serial_piece(md_ctx *ctx, const uint8_t *src, size_t src_len, unsigned start_bit, const uint8_t *hist, size_t hl, uint64_t room,
-                 uint32_t adler_in, uint64_t h64[8], uint32_t h32[7]) {
-  md::DevBuf &din = ctx->scratch[kContIn], &dout = ctx->scratch[kContOut], &ddesc = ctx->scratch[kContDesc];
-  int rc = din.reserve(ctx, src_len + 16, "hipMalloc(decoder piece input)");
-  if (rc == MD_OK) rc = dout.reserve(ctx, hl + room + 16, "hipMalloc(decoder piece output)");
-  if (rc == MD_OK) rc = ddesc.reserve(ctx, 8 * 8 + 8 * 4 + 4 * 8 + 2 * 4, "hipMalloc(decoder piece descriptors)");
-  if (rc != MD_OK) return rc;
-  const uint64_t d64_init[8] = {0, (uint64_t)src_len, 0, hl + room, 0, 0, 0, 0};
-  const uint32_t d32_init[7] = {0, 0, start_bit, (uint32_t)hl, adler_in, 0, 0};
-  memcpy(h64, d64_init, sizeof d64_init);
-  memcpy(h32, d32_init, sizeof d32_init);
-  uint64_t *d64 = (uint64_t *)ddesc.p;
-  uint32_t *d32 = (uint32_t *)(d64 + 8);
-  hipStream_t st = ctx->stream;
-  HIP_TRY(ctx, hipMemcpyAsync(din.p, src, src_len, hipMemcpyHostToDevice, st));
-  if (hl) HIP_TRY(ctx, hipMemcpyAsync(dout.p, hist, hl, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(d64, h64, 64, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(d32, h32, 28, hipMemcpyHostToDevice, st));
-  const md::wv::Cont cont{d32 + 2, d32 + 3, d32 + 4, d64 + 6, d64 + 7, d32 + 5, d32 + 6};
-  MD_LAUNCH_TRY(ctx, md_launch_inflate_wave(MD_FORMAT_DEFLATE, 1, (const uint8_t *)din.p, d64 + 0, d64 + 1, (uint8_t *)dout.p, d64 + 2, d64 + 3,
-                                            d64 + 4, d64 + 5, (int32_t *)d32, d32 + 1, nullptr, nullptr, ctx->inflate_waves, &cont, st));
-  HIP_TRY(ctx, hipMemcpyAsync(h64, d64, 64, hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipMemcpyAsync(h32, d32, 28, hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipStreamSynchronize(st));
-  return MD_OK;
 }
 
 // The stream decoded once, in pieces; x receives the points.  Returns the stream's status (or a call-level error).
@@ -196,28 +123,27 @@ int build_index(md_ctx *ctx, int format, const uint8_t *src, size_t src_len, uin
         uint64_t room = (std::max<uint64_t>(std::max<uint64_t>(2 * span, 4 * (uint64_t)L), stored_payload) + 65536) * factor;
         const bool at_max = room >= room_max, limited = room >= cap_left;
         room = std::min(std::min(room, room_max), cap_left);
-        uint64_t h64[8];
-        uint32_t h32[7];
-        const int rc = serial_piece(ctx, src + b0, L, sb, hist.data(), hl, room, adler, h64, h32);
+        InfPiece r;
+        const int rc = inflate_piece(ctx, src + b0, L, sb, hist.data(), hl, room, adler, &r);
         if (rc != MD_OK) return rc;
-        const int pst = (int32_t)h32[0];
+        const int pst = r.status;
         d_base = (const uint8_t *)ctx->scratch[kContOut].p;
         if (pst == MD_OK) {
-          if (!settle && out_pos + (h64[4] - hl) >= last_kept + span && L - lo > 1) {
+          if (!settle && out_pos + (r.out_len - hl) >= last_kept + span && L - lo > 1) {
             hi = L;
             want = lo + (hi - lo) / 2;
             continue;
           }
           final = true;
-          produced = h64[4] - hl;
-          used = h64[5];
-          piece_adler = h32[1];
+          produced = r.out_len - hl;
+          used = r.consumed;
+          piece_adler = r.checksum;
           break;
         }
-        if (h64[6] > sb) {  // a complete block: on from its end, whatever stopped the piece behind it
-          produced = h64[7] - hl;
-          resume_bits = h64[6];
-          piece_adler = h32[5];
+        if (r.resume_bits > sb) {  // a complete block: on from its end, whatever stopped the piece behind it
+          produced = r.resume_out - hl;
+          resume_bits = r.resume_bits;
+          piece_adler = r.resume_adler;
           break;
         }
         if (pst == MD_UNEXPECTED_END_OF_INPUT) {
@@ -254,10 +180,15 @@ int build_index(md_ctx *ctx, int format, const uint8_t *src, size_t src_len, uin
     if (!k_bit.empty()) {
       const size_t m = k_bit.size();
       int rc = ctx->scratch[kZixWin].reserve(ctx, m * kWindow, "hipMalloc(index windows)");
-      if (rc == MD_OK) rc = ctx->scratch[kZixDesc].reserve(ctx, m * 12 + 64, "hipMalloc(index descriptors)");
       if (rc != MD_OK) return rc;
-      uint64_t *d_src = ctx->scratch[kZixDesc].as<uint64_t>();
-      uint32_t *d_len = (uint32_t *)(d_src + m);
+      uint64_t *d_src = nullptr;
+      uint32_t *d_len = nullptr;
+      md::Carver c;
+      for (int pass = 0; pass < 2; pass++) {
+        if (pass && (rc = carve_from(ctx, ctx->scratch[kZixDesc], &c, "hipMalloc(index descriptors)", 64)) != MD_OK) return rc;
+        d_src = c.take<uint64_t>(m);
+        d_len = c.take<uint32_t>(m);
+      }
       uint8_t *d_wins = ctx->scratch[kZixWin].as<uint8_t>();
       HIP_TRY(ctx, hipMemcpyAsync(d_src, k_src.data(), m * 8, hipMemcpyHostToDevice, stream));
       HIP_TRY(ctx, hipMemcpyAsync(d_len, k_len.data(), m * 4, hipMemcpyHostToDevice, stream));
@@ -408,14 +339,18 @@ int md_inflate_index_read(md_ctx *ctx, const md_inflate_index *idx, const uint8_
   hipStream_t st = ctx->stream;
   const size_t P = idx->bit.size(), words = (P + 31) / 32;
   // tables, ranges, and the descriptors of a round (at most P pieces), in one block
-  size_t need;
   md::zix::Tables t{};
   md::zix::Round r{};
   uint64_t *d_off = nullptr, *d_len = nullptr, *d_pack = nullptr, *d_plan = nullptr;
   int32_t *d_status = nullptr;
   uint64_t *d_bit = nullptr, *d_outs = nullptr;
+  md::Carver c;
   for (int pass = 0; pass < 2; pass++) {  // (sizes first, then the pointers)
-    Carver c(pass ? ctx->scratch[kZixDesc].p : nullptr);
+    if (pass) {
+      int rc = carve_from(ctx, ctx->scratch[kZixDesc], &c, "hipMalloc(index descriptors)", 64);
+      if (rc == MD_OK) rc = ctx->scratch[kZixOut].reserve(ctx, total + 64, "hipMalloc(index ranges)");
+      if (rc != MD_OK) return rc;
+    }
     d_plan = c.take<uint64_t>(md::zix::kPlanWords);
     d_bit = c.take<uint64_t>(P);
     d_outs = c.take<uint64_t>(P);
@@ -432,12 +367,6 @@ int md_inflate_index_read(md_ctx *ctx, const md_inflate_index *idx, const uint8_
     t.round_of = c.take<uint32_t>(P);
     t.verdict = c.take<int32_t>(P);
     d_status = c.take<int32_t>(n);
-    need = c.at;
-    if (pass == 0) {
-      int rc = ctx->scratch[kZixDesc].reserve(ctx, need + 64, "hipMalloc(index descriptors)");
-      if (rc == MD_OK) rc = ctx->scratch[kZixOut].reserve(ctx, total + 64, "hipMalloc(index ranges)");
-      if (rc != MD_OK) return rc;
-    }
   }
   t.points = P;
   t.size = f.size;

@@ -8,26 +8,7 @@
 #include "ctx.hpp"
 #include "zip_dir.hpp"
 
-#define MD_LAUNCH_TRY(ctx, expr)                                        \
-  do {                                                                  \
-    const int e_ = (expr);                                              \
-    if (e_ != 0) return fail(ctx, MD_E_HIP, #expr, (hipError_t)e_);     \
-  } while (0)
-
 namespace {
-// device memory carved from one scratch block, every piece on 16 bytes
-struct Carver {
-  uint8_t *p;
-  size_t at = 0;
-  explicit Carver(void *base) : p((uint8_t *)base) {}
-  template <class T>
-  T *take(size_t n) {
-    T *r = p ? (T *)(p + at) : nullptr;
-    at += (n * sizeof(T) + 15) & ~(size_t)15;
-    return r;
-  }
-};
-
 // The table segment -> entry of entries of len[j] bytes in segments of seg bytes: first[j] = entry j's first segment
 // (k + 1 words), seg_entry[s] = the entry of segment s.  An empty entry has no segment.
 void segment_table(const std::vector<uint64_t> &len, uint64_t seg, std::vector<uint64_t> *first, std::vector<uint32_t> *seg_entry) {
@@ -112,43 +93,38 @@ static int zip_uncompress(md_ctx *ctx, const uint8_t *src, size_t src_len, const
 
   MD_ON_DEVICE(ctx);
   hipStream_t st = ctx->stream;
-  Carver size(nullptr), cv(nullptr);
+  md::Carver c;
   md::zip::Row *d_rows = nullptr;
   uint64_t *d_usize = nullptr, *d_out_off = nullptr, *d_first = nullptr, *in_off = nullptr, *in_len = nullptr, *out_cap = nullptr, *body_off = nullptr,
            *out_len = nullptr, *consumed = nullptr, *failed = nullptr;
   int32_t *hstatus = nullptr, *d_status = nullptr;
   uint32_t *d_seg_entry = nullptr, *crc = nullptr;
   uint8_t *kind = nullptr, *d_names = nullptr;
-  for (Carver *c : {&size, &cv}) {  // (once for the size, once for the pointers)
-    if (c == &cv) {
-      rc = ctx->scratch[kZipDesc].reserve(ctx, size.at, "hipMalloc(zip descriptors)");
-      if (rc != MD_OK) return rc;
-      cv.p = (uint8_t *)ctx->scratch[kZipDesc].p;
-    }
-    d_rows = c->take<md::zip::Row>(k);
-    d_usize = c->take<uint64_t>(k);
-    d_out_off = c->take<uint64_t>(k + 1);
-    d_first = c->take<uint64_t>(k + 1);
-    in_off = c->take<uint64_t>(k);
-    in_len = c->take<uint64_t>(k);
-    out_cap = c->take<uint64_t>(k);
-    body_off = c->take<uint64_t>(k);
-    out_len = c->take<uint64_t>(k);
-    consumed = c->take<uint64_t>(k);
-    failed = c->take<uint64_t>(1);
-    hstatus = c->take<int32_t>(k);
-    d_status = c->take<int32_t>(k);
-    d_seg_entry = c->take<uint32_t>(nseg);
-    crc = c->take<uint32_t>(nseg);
-    kind = c->take<uint8_t>(k);
-    d_names = c->take<uint8_t>(names.size());
+  for (int pass = 0; pass < 2; pass++) {  // (once for the size, once for the pointers)
+    if (pass && (rc = carve_from(ctx, ctx->scratch[kZipDesc], &c, "hipMalloc(zip descriptors)")) != MD_OK) return rc;
+    d_rows = c.take<md::zip::Row>(k);
+    d_usize = c.take<uint64_t>(k);
+    d_out_off = c.take<uint64_t>(k + 1);
+    d_first = c.take<uint64_t>(k + 1);
+    in_off = c.take<uint64_t>(k);
+    in_len = c.take<uint64_t>(k);
+    out_cap = c.take<uint64_t>(k);
+    body_off = c.take<uint64_t>(k);
+    out_len = c.take<uint64_t>(k);
+    consumed = c.take<uint64_t>(k);
+    failed = c.take<uint64_t>(1);
+    hstatus = c.take<int32_t>(k);
+    d_status = c.take<int32_t>(k);
+    d_seg_entry = c.take<uint32_t>(nseg);
+    crc = c.take<uint32_t>(nseg);
+    kind = c.take<uint8_t>(k);
+    d_names = c.take<uint8_t>(names.size());
   }
   const size_t span = (size_t)(hi - lo);
-  rc = ctx->scratch[kHostIn].reserve(ctx, span + 64, "hipMalloc(host path input)");
+  rc = upload_host_in(ctx, src + lo, span);
   if (rc == MD_OK) rc = ctx->scratch[kHostOut].reserve(ctx, (size_t)need + 64, "hipMalloc(host path output)");
   if (rc != MD_OK) return rc;
   uint8_t *d_src = (uint8_t *)ctx->scratch[kHostIn].p, *d_out = (uint8_t *)ctx->scratch[kHostOut].p;
-  if (span) HIP_TRY(ctx, hipMemcpyAsync(d_src, src + lo, span, hipMemcpyHostToDevice, st));
   if ((rc = upload(ctx, d_rows, rows)) != MD_OK || (rc = upload(ctx, d_usize, usize)) != MD_OK || (rc = upload(ctx, d_out_off, offs)) != MD_OK ||
       (rc = upload(ctx, d_first, first)) != MD_OK || (rc = upload(ctx, d_seg_entry, seg_entry)) != MD_OK || (rc = upload(ctx, d_names, names)) != MD_OK)
     return rc;
@@ -246,44 +222,39 @@ static int zip_compress(md_ctx *ctx, int level, size_t n, const md_zip_source *f
 
   MD_ON_DEVICE(ctx);
   hipStream_t st = ctx->stream;
-  Carver size(nullptr), cv(nullptr);
+  md::Carver c;
   uint64_t *in_off = nullptr, *in_len = nullptr, *slot_off = nullptr, *out_len = nullptr, *name_pos = nullptr, *lsize = nullptr, *loff = nullptr,
            *d_first = nullptr;
   int32_t *status = nullptr, *err = nullptr;
   uint32_t *name_len = nullptr, *dos = nullptr, *rec = nullptr, *d_seg_entry = nullptr, *crc = nullptr;
   uint8_t *kind = nullptr, *d_names = nullptr;
   int rc = MD_OK;
-  for (Carver *c : {&size, &cv}) {  // (once for the size, once for the pointers)
-    if (c == &cv) {
-      rc = ctx->scratch[kZipDesc].reserve(ctx, size.at, "hipMalloc(zip descriptors)");
-      if (rc != MD_OK) return rc;
-      cv.p = (uint8_t *)ctx->scratch[kZipDesc].p;
-    }
-    in_off = c->take<uint64_t>(n);
-    in_len = c->take<uint64_t>(n);
-    slot_off = c->take<uint64_t>(n);
-    out_len = c->take<uint64_t>(n);
-    name_pos = c->take<uint64_t>(n);
-    lsize = c->take<uint64_t>(n);
-    loff = c->take<uint64_t>(n + 1);
-    d_first = c->take<uint64_t>(n + 1);
-    status = c->take<int32_t>(n);
-    err = c->take<int32_t>(1);
-    name_len = c->take<uint32_t>(n);
-    dos = c->take<uint32_t>(n);
-    rec = c->take<uint32_t>(4 * n);
-    d_seg_entry = c->take<uint32_t>(nseg);
-    crc = c->take<uint32_t>(nseg);
-    kind = c->take<uint8_t>(n);
-    d_names = c->take<uint8_t>(names.size());
+  for (int pass = 0; pass < 2; pass++) {  // (once for the size, once for the pointers)
+    if (pass && (rc = carve_from(ctx, ctx->scratch[kZipDesc], &c, "hipMalloc(zip descriptors)")) != MD_OK) return rc;
+    in_off = c.take<uint64_t>(n);
+    in_len = c.take<uint64_t>(n);
+    slot_off = c.take<uint64_t>(n);
+    out_len = c.take<uint64_t>(n);
+    name_pos = c.take<uint64_t>(n);
+    lsize = c.take<uint64_t>(n);
+    loff = c.take<uint64_t>(n + 1);
+    d_first = c.take<uint64_t>(n + 1);
+    status = c.take<int32_t>(n);
+    err = c.take<int32_t>(1);
+    name_len = c.take<uint32_t>(n);
+    dos = c.take<uint32_t>(n);
+    rec = c.take<uint32_t>(4 * n);
+    d_seg_entry = c.take<uint32_t>(nseg);
+    crc = c.take<uint32_t>(nseg);
+    kind = c.take<uint8_t>(n);
+    d_names = c.take<uint8_t>(names.size());
   }
-  rc = ctx->scratch[kHostIn].reserve(ctx, span + 64, "hipMalloc(host path input)");
+  rc = upload_host_in(ctx, src + lo, span);
   if (rc == MD_OK) rc = ctx->scratch[kHostOut].reserve(ctx, (size_t)slots_bytes + 64, "hipMalloc(host path output)");
   if (rc == MD_OK) rc = ctx->scratch[kZipOut].reserve(ctx, (size_t)image_max + 64, "hipMalloc(zip file image)");
   if (rc != MD_OK) return rc;
   const uint8_t *d_in = (const uint8_t *)ctx->scratch[kHostIn].p;
   uint8_t *slots = (uint8_t *)ctx->scratch[kHostOut].p, *d_file = (uint8_t *)ctx->scratch[kZipOut].p;
-  if (span) HIP_TRY(ctx, hipMemcpyAsync((void *)d_in, src + lo, span, hipMemcpyHostToDevice, st));
   if ((rc = upload(ctx, in_off, h_in_off)) != MD_OK || (rc = upload(ctx, in_len, h_in_len)) != MD_OK || (rc = upload(ctx, slot_off, h_slot_off)) != MD_OK ||
       (rc = upload(ctx, name_pos, h_name_pos)) != MD_OK || (rc = upload(ctx, name_len, h_name_len)) != MD_OK || (rc = upload(ctx, dos, h_dos)) != MD_OK ||
       (rc = upload(ctx, d_first, first)) != MD_OK || (rc = upload(ctx, d_seg_entry, seg_entry)) != MD_OK || (rc = upload(ctx, d_names, names)) != MD_OK)
@@ -291,16 +262,8 @@ static int zip_compress(md_ctx *ctx, int level, size_t n, const md_zip_source *f
   HIP_TRY(ctx, hipMemsetAsync(err, 0, 4, st));
   if (n) HIP_TRY(ctx, hipMemsetAsync(kind, md::zip::kStored, n, st));
   if (n && level != 0) {
-    // the parameters of MD_FORMAT_GZIP (Gz.Def's make_block: Zl driver, dynamic blocks, queue 4096), the raw body alone;
     // the room of a file is its own length (in_len serves as out_cap): a body that is not shorter loses against stored
-    md_deflate_params p;
-    memset(&p, 0, sizeof p);
-    p.level = level;
-    p.queue_len = 4096;
-    p.driver = MD_DRIVER_ZL;
-    p.dynamic = 1;
-    p.matcher = MD_MATCHER_DE;
-    p.total_in_bytes = (size_t)total_in;
+    const md_deflate_params p = gzip_body_params(level, (size_t)total_in);
     rc = md_deflate_batch_device(ctx, MD_FORMAT_DEFLATE, &p, n, d_in, in_off, in_len, slots, slot_off, in_len, out_len, status, nullptr);
     if (rc != MD_OK) return rc;
   }
@@ -395,4 +358,3 @@ int md_zip_compress(md_ctx *ctx, int level, size_t n, const md_zip_source *files
     return fail(ctx, MD_E_OUT_OF_MEMORY, "host memory for the archive's descriptors");
   }
 }
-#undef MD_LAUNCH_TRY

@@ -1,6 +1,8 @@
 // ctx.hpp — what the host translation units (capi*.cpp, stream_*.cpp) share and no kernel sees: the context, the one
-// type that owns device or pinned memory, the error helpers, and every function that one of those files defines and
-// another calls.  The defining file and every caller include it, as with internal.hpp.  Plain host C++.
+// type that owns device or pinned memory, the error helpers (fail, HIP_TRY, MD_LAUNCH_TRY), the device guard of the entry
+// points, the carving of a scratch block into arrays (md::Carver of host_util.hpp, carve_from), and every function that
+// one of those files defines and another calls.  The defining file and every caller include it, as with internal.hpp.
+// Plain host C++.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -26,11 +28,32 @@ int fail(md_ctx *ctx, int code, const char *what, hipError_t e = hipSuccess);
     if (e_ != hipSuccess) return fail(ctx, MD_E_HIP, #expr, e_); \
   } while (0)
 
+// the same for a launcher of internal.hpp, which returns HIP's error as an int
+#define MD_LAUNCH_TRY(ctx, expr)                                    \
+  do {                                                              \
+    const int e_ = (expr);                                          \
+    if (e_ != 0) return fail(ctx, MD_E_HIP, #expr, (hipError_t)e_); \
+  } while (0)
+
 #define MD_ON_DEVICE(ctx)                 \
   md::DeviceGuard guard_((ctx)->device);  \
   if (!guard_.ok) return fail(ctx, MD_E_HIP, "hipSetDevice")
 
 namespace md {
+
+// every entry point works on the context's device and leaves the caller's current device as it found it
+struct DeviceGuard {
+  int prev = -1;
+  bool ok = true;
+  explicit DeviceGuard(int dev) {
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    if (prev != dev) ok = hipSetDevice(dev) == hipSuccess;
+    if (!ok) (void)hipGetLastError();  // (the call reports the failure itself: no stale error for whoever asks next)
+  }
+  ~DeviceGuard() {
+    if (prev >= 0) (void)hipSetDevice(prev);
+  }
+};
 
 // most input that one src call of a streaming encoder, or one round of a decoder of a batch, hands over: positions
 // within a launch are 32-bit
@@ -208,6 +231,40 @@ inline int launch_order(md_ctx *ctx, size_t n, size_t from, uint32_t **order) {
   return rc;
 }
 
+// A block carved in two passes, the takes written once: the first pass counts over a null base, then `buf` is reserved
+// for what it counted and `slack` bytes more, and c starts again over the block.
+//   md::Carver c;
+//   for (int pass = 0; pass < 2; pass++) {
+//     if (pass && (rc = carve_from(ctx, buf, &c, "hipMalloc(..)")) != MD_OK) return rc;
+//     a = c.take<uint64_t>(n), b = c.take<int32_t>(n);
+//   }
+inline int carve_from(md_ctx *ctx, md::DevBuf &buf, md::Carver *c, const char *what, size_t slack = 0) {
+  const int rc = buf.reserve(ctx, c->at + slack, what);
+  if (rc == MD_OK) *c = md::Carver(buf.p);
+  return rc;
+}
+
+// the caller's bytes into kHostIn, on the context's stream
+inline int upload_host_in(md_ctx *ctx, const uint8_t *src, size_t len) {
+  const int rc = ctx->scratch[kHostIn].reserve(ctx, len + 64, "hipMalloc(host path input)");
+  if (rc != MD_OK) return rc;
+  if (len) HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[kHostIn].p, src, len, hipMemcpyHostToDevice, ctx->stream));
+  return MD_OK;
+}
+
+// the parameters of MD_FORMAT_GZIP (Gz.Def's make_block: Zl driver, dynamic blocks, queue 4096) for the raw body alone, as
+// the writers of blocked gzip and of ZIP archives hand them to md_deflate_batch_device with MD_FORMAT_DEFLATE
+inline md_deflate_params gzip_body_params(int level, size_t total_in_bytes) {
+  md_deflate_params p = {};
+  p.level = level;
+  p.queue_len = 4096;
+  p.driver = MD_DRIVER_ZL;
+  p.dynamic = 1;
+  p.matcher = MD_MATCHER_DE;
+  p.total_in_bytes = total_in_bytes;
+  return p;
+}
+
 // One host buffer through a batch of one: input, output (16 bytes of slack each: Lzo's compressor over-copies into it)
 // and the descriptor (in_off in_len out_off out_cap out_len, status) live for the call; `launch(d_in, d64, d_out,
 // d_status, d_extra)` enqueues the batch entry point with n = 1 on the context's stream.  extra_bytes of device memory
@@ -271,6 +328,18 @@ int md_get_profile(md_ctx *ctx, uint64_t *out32);
 
 #pragma GCC visibility push(hidden)
 // ---- capi_inflate.cpp ----
+// One piece of a raw DEFLATE stream through one pair of wavefronts, its output LEFT ON THE DEVICE: src[0, src_len) starts
+// start_bit bits into src[0], hist[0, hist_len) is the output in front of it and goes to the start of kContOut, the new
+// bytes follow it there, `room` of them at the most.  out_len and resume_out count from the start of kContOut (the window
+// included); resume_* say where the last complete block of the piece ended.
+struct InfPiece {
+  int status;
+  uint64_t out_len, consumed, resume_bits, resume_out;
+  uint32_t checksum, resume_adler, resume_last;
+};
+int inflate_piece(md_ctx *ctx, const uint8_t *src, size_t src_len, unsigned start_bit, const uint8_t *hist, size_t hist_len, uint64_t room,
+                  uint32_t adler_in, InfPiece *r);
+// the same with the output copied out behind the window in dst, and the CRC-32s that flags ask for
 int continue_serial(md_ctx *ctx, const uint8_t *src, size_t src_len, unsigned start_bit, uint8_t *dst, size_t hist_len,
                     size_t dst_cap, uint32_t adler_in, unsigned flags, size_t *dst_len, int *status, md_inf_resume *resume);
 // ---- capi_long_stream.cpp: both return MD_NOT_HANDLED for what the serial path has to answer ----

@@ -1,7 +1,8 @@
 // host_util.hpp — small host-side helpers of capi*.cpp and stream_*.cpp: checksums of the few bytes the host
-// handles itself, 32-bit reads of header and trailer fields, and the device guard of the entry points.
+// handles itself, 32-bit reads of header and trailer fields, and the carver that splits one block of memory into
+// arrays.  Plain C++ without HIP: a host compiler alone takes it (gz_frame.hpp and the sanitizer programs of tests/ do).
 #pragma once
-#include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <string.h>
 
@@ -77,17 +78,18 @@ inline uint32_t crc32_concat(uint32_t crc_a, uint32_t crc_b, uint64_t len_b) {
   return crc32_gf_mul(crc_a, r) ^ crc_b;
 }
 
-// every entry point works on the context's device and leaves the caller's current device as it found it
-struct DeviceGuard {
-  int prev = -1;
-  bool ok = true;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) ok = hipSetDevice(dev) == hipSuccess;
-    if (!ok) (void)hipGetLastError();  // (the call reports the failure itself: no stale error for whoever asks next)
-  }
-  ~DeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
+// One block of memory split into arrays, every array on 16 bytes from the block's start.  Over a null base it hands out
+// null pointers and only counts: `at` is then the size of the block that a second carver, over the block itself, splits
+// in the same way.
+struct Carver {
+  uint8_t *p;
+  size_t at = 0;
+  explicit Carver(void *base = nullptr) : p((uint8_t *)base) {}
+  template <class T>
+  T *take(size_t n) {
+    T *r = p ? (T *)(p + at) : nullptr;
+    at += (n * sizeof(T) + 15) & ~(size_t)15;
+    return r;
   }
 };
 

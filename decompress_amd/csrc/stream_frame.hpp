@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "ctx.hpp"
+#include "gz_frame.hpp"
 
 #pragma GCC visibility push(hidden)
 
@@ -27,60 +28,6 @@ struct InfFrame {
   uint32_t crc = 0;           // GZip: CRC-32 of the output handed out so far
   uint64_t total_out = 0;     // ... and its length
 };
-
-// where the DEFLATE body of a GZip member begins (Gz.Inf's header walk, lib/gz.ml:465-531: FEXTRA's length is read
-// big-endian there); 0 when the header is cut short
-inline size_t gz_body_offset(const std::vector<uint8_t> &in) {
-  if (in.size() < 10) return 0;
-  const uint32_t flg = in[3];
-  size_t p = 10;
-  if (flg & 4) {
-    if (in.size() - p < 2) return 0;
-    const size_t xl = ((size_t)in[p] << 8) | in[p + 1];
-    p += 2;
-    if (in.size() - p < xl) return 0;
-    p += xl;
-  }
-  for (int which = 0; which < 2; which++) {
-    if (!(flg & (which == 0 ? 8u : 16u))) continue;
-    for (;;) {
-      if (p >= in.size()) return 0;
-      if (in[p++] == 0) break;
-    }
-  }
-  if (flg & 2) {
-    if (in.size() - p < 2) return 0;
-    p += 2;
-  }
-  return p;
-}
-
-// Gz.Inf's header walk with its checks (lib/gz.ml:463-491, as gz_header_kernel does it for the batch path): the offset
-// of the body, or 0 with *st = MD_OK when the header is not all there yet, or 0 with the status of a bad header
-inline size_t gz_header_check(const std::vector<uint8_t> &in, int *st) {
-  *st = MD_OK;
-  // (the reference looks at the ID bytes only once the ten fixed bytes are there, lib/gz.ml:463-491: a cut header of
-  // fewer bytes is "unexpected end of input" whatever its first bytes are)
-  if (in.size() >= 10 && (in[0] != 0x1f || in[1] != 0x8b)) {
-    *st = MD_INVALID_GZIP_HEADER;
-    return 0;
-  }
-  const size_t body = gz_body_offset(in);
-  if (body == 0) return 0;
-  const uint32_t flg = in[3];
-  if (flg & 2) {  // FHCRC: the upper half of the CRC-32 of the fixed bytes + name + comment (FEXTRA excluded), big-endian
-    uint32_t c = md::crc32_update(0, in.data(), 10);
-    size_t p = 10;
-    if (flg & 4) p += 2 + (((size_t)in[10] << 8) | in[11]);
-    c = md::crc32_update(c, in.data() + p, body - 2 - p);
-    const uint32_t want = (c & 0xffff0000u) >> 16, have = ((uint32_t)in[body - 2] << 8) | in[body - 1];
-    if (want != have) {
-      *st = MD_INVALID_GZIP_HEADER_CHECKSUM;
-      return 0;
-    }
-  }
-  return body;
-}
 
 // A piece's output room: the window, 4x the input and 64 KiB, times `factor` (x4 each time the piece ran out of it),
 // MD_MAX_STREAM at the most
@@ -114,15 +61,14 @@ inline void frame_bad_size(InfFrame *f, uint32_t expect, uint32_t inflated) {
 inline bool frame_head(InfFrame *f) {
   const bool final = f->eoi;
   if (f->format == MD_FORMAT_GZIP && !f->hdr_done) {
-    int hst = MD_OK;
-    const size_t body = gz_header_check(f->in, &hst);
-    if (hst != MD_OK) return frame_fail(f, hst), false;
-    if (body == 0) {
-      if (final) frame_fail(f, MD_UNEXPECTED_END_OF_INPUT);
-      else f->need = f->in.size() + 1;
+    md::gz::InfHeader h;
+    const int hst = md::gz::inf_header(f->in.data(), f->in.size(), &h);
+    if (hst == MD_UNEXPECTED_END_OF_INPUT && !final) {  // not all there yet
+      f->need = f->in.size() + 1;
       return false;
     }
-    f->in.erase(f->in.begin(), f->in.begin() + body);
+    if (hst != MD_OK) return frame_fail(f, hst), false;
+    f->in.erase(f->in.begin(), f->in.begin() + h.body);
     f->hdr_done = true;
   }
   if (f->format == MD_FORMAT_ZLIB && !f->hdr_done) {  // Zl.Inf's header, lib/zl.ml:142-165 (as the kernel checks it)

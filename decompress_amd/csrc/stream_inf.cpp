@@ -99,8 +99,10 @@ uint32_t md_inf_checksum(const md_inf_stream *s) { return s ? s->checksum : 0; }
 static void inf_detail(md_inf_stream *s) {
   s->message = md_status_string(s->status);
   if (s->status != MD_INVALID_CHECKSUM && s->status != MD_INVALID_SIZE) return;
-  const size_t body = s->format == MD_FORMAT_ZLIB ? 2 : gz_body_offset(s->in);
-  if (body == 0 || body > s->in.size()) return;
+  md::gz::InfHeader gz{};
+  if (s->format != MD_FORMAT_ZLIB && md::gz::inf_header(s->in.data(), s->in.size(), &gz) != MD_OK) return;
+  const size_t body = s->format == MD_FORMAT_ZLIB ? 2 : gz.body;
+  if (body > s->in.size()) return;
   uint64_t in_off = body, in_len = s->in.size() - body, out_off = 0, out_cap = s->out.size(), out_len = 0, used = 0;
   int32_t st = 0;
   std::vector<uint8_t> scratch(s->out.size() + 16);
@@ -271,20 +273,15 @@ struct InfRound {
   md::ib::HandRow *hand;
   size_t bytes;
   InfRound(void *base, size_t L, size_t m, bool first) {
-    uintptr_t p = (uintptr_t)base;
-    take(p, gather_in, first ? L : 0), take(p, gather_out, L);
-    take(p, in_off, m), take(p, in_len, m), take(p, out_off, m), take(p, out_cap, m);
-    take(p, start_bit, m), take(p, hist, m), take(p, adler_in, m), take(p, flags, m);
-    upload = p - (uintptr_t)base;
-    take(p, out_len, m), take(p, consumed, m), take(p, resume_bits, m), take(p, resume_out, m);
-    take(p, status, m), take(p, checksum, m), take(p, resume_adler, m), take(p, resume_last, m);
-    take(p, hand, m);
-    bytes = p - (uintptr_t)base;
-  }
-  template <class T>
-  static void take(uintptr_t &p, T *&array, size_t count) {
-    array = (T *)p;
-    p += count * sizeof(T);
+    md::Carver c(base);
+    gather_in = c.take<md::GatherRow>(first ? L : 0), gather_out = c.take<md::GatherRow>(L);
+    in_off = c.take<uint64_t>(m), in_len = c.take<uint64_t>(m), out_off = c.take<uint64_t>(m), out_cap = c.take<uint64_t>(m);
+    start_bit = c.take<uint32_t>(m), hist = c.take<uint32_t>(m), adler_in = c.take<uint32_t>(m), flags = c.take<uint32_t>(m);
+    upload = c.at;
+    out_len = c.take<uint64_t>(m), consumed = c.take<uint64_t>(m), resume_bits = c.take<uint64_t>(m), resume_out = c.take<uint64_t>(m);
+    status = c.take<int32_t>(m), checksum = c.take<uint32_t>(m), resume_adler = c.take<uint32_t>(m), resume_last = c.take<uint32_t>(m);
+    hand = c.take<md::ib::HandRow>(m);
+    bytes = c.at;
   }
 };
 
