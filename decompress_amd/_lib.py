@@ -154,6 +154,16 @@ SYMBOLS = [
     ("md_inflate_index_free", None, [c_vp]),
     ("md_inflate_index_read", ctypes.c_int, [c_vp, c_vp, c_vp, c_sz, c_sz, c_vp, c_vp, c_vp, c_vp, c_vp]),
     ("md_inflate_index_last", ctypes.c_int, [c_vp, c_vp]),
+    ("md_bgzf_index_build", ctypes.c_int, [c_vp, c_vp, c_sz, ctypes.POINTER(c_vp)]),
+    ("md_bgzf_index_from_gzi", ctypes.c_int, [c_vp, c_sz, c_vp, c_sz, ctypes.POINTER(c_vp)]),
+    ("md_bgzf_index_gzi_size", c_sz, [c_vp]),
+    ("md_bgzf_index_to_gzi", ctypes.c_int, [c_vp, c_vp, c_sz, c_szp]),
+    ("md_bgzf_index_get", ctypes.c_int, [c_vp, c_vp]),
+    ("md_bgzf_index_entries", ctypes.c_int, [c_vp, c_vp, c_vp, c_sz]),
+    ("md_bgzf_index_free", None, [c_vp]),
+    ("md_bgzf_read", ctypes.c_int, [c_vp, c_vp, c_vp, c_sz, c_sz, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    ("md_bgzf_read_virtual", ctypes.c_int, [c_vp, c_vp, c_vp, c_sz, c_sz, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    ("md_bgzf_read_last", ctypes.c_int, [c_vp, c_vp]),
 ]
 
 
@@ -166,6 +176,16 @@ class InflateIndexInfo(ctypes.Structure):
 class InflateIndexStats(ctypes.Structure):
     """md_inflate_index_stats of include/mdeflate.h"""
     _fields_ = [(k, ctypes.c_uint64) for k in ("pieces", "launches", "bytes_in", "bytes_windows", "bytes_scratch")]
+
+
+class BgzfIndexInfo(ctypes.Structure):
+    """md_bgzf_index_info of include/mdeflate.h"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("src_len", "members", "size")]
+
+
+class BgzfReadStats(ctypes.Structure):
+    """md_bgzf_read_stats of include/mdeflate.h"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("members", "launches", "bytes_in", "bytes_scratch")]
 
 
 class ZipEntry(ctypes.Structure):

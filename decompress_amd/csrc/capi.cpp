@@ -273,6 +273,11 @@ int md_set_option(md_ctx *ctx, const char *key, int value) {
     ctx->zix_workspace = (size_t)value << 20;
     return MD_OK;
   }
+  if (!strcmp(key, "bgzf_read_workspace")) {  // MiB of packed input and output slots per round of md_bgzf_read; 0 = one member a round
+    if (value < 0 || value > (1 << 20)) return fail(ctx, MD_E_INVALID_ARGUMENT, "bgzf_read_workspace is 0 .. 2^20 (MiB)");
+    ctx->bgr_workspace = (size_t)value << 20;
+    return MD_OK;
+  }
   if (!strcmp(key, "host_pipeline_slices")) {  // md_*_batch_host: slices of streams in flight (1 = no overlap of copies and kernels)
     if (value < 1 || value > 64) return fail(ctx, MD_E_INVALID_ARGUMENT, "host_pipeline_slices is 1 .. 64");
     ctx->host_slices_max = value;

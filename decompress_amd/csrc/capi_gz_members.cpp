@@ -8,20 +8,11 @@
 
 // RFC 1952 as libz reads it (gz_rfc.hpp), not Gz.Inf's reading.  The internals work on device pointers; the entry
 // points are copy-in, kernels, copy-out.
-namespace {
-// the members of an indexed file: device arrays of M entries (out_off: M + 1), carved from ctx->scratch[kGzmDesc].p
-struct GzmIndex {
-  uint64_t M = 0, total = 0;  // members, the sum of their ISIZE fields
-  uint64_t *mpos = nullptr, *mlen = nullptr, *body_off = nullptr, *body_len = nullptr, *isize = nullptr, *out_len = nullptr,
-           *consumed = nullptr, *out_off = nullptr, *first = nullptr;
-  int32_t *hstatus = nullptr, *status = nullptr;
-};
-}  // namespace
 
 // Mark, chain and descriptors (gz_members.hip) for len bytes at d_src.  *indexed: the chain of BC size fields leads from
 // offset 0 to the end of the file; then ix holds the members, their headers parsed and their output offsets scanned.
 // Three small read-backs: the candidate count, the member count with the chain's verdict, the total size.
-static int gzm_index(md_ctx *ctx, const uint8_t *d_src, uint64_t len, bool *indexed, GzmIndex *ix) {
+int gzm_index(md_ctx *ctx, const uint8_t *d_src, uint64_t len, bool *indexed, GzmIndex *ix) {
   *indexed = false;
   if (len < 28) return MD_OK;  // (shorter than any indexed member)
   hipStream_t st = ctx->stream;

@@ -134,6 +134,9 @@ enum Scratch {
   // the index of a long stream (md_inflate_index_*): compressed bytes of the pieces of a round, the pieces' slots (window +
   // output), windows on their way in (read) or out (build), tables and descriptors, the ranges' bytes
   kZixIn, kZixSlots, kZixWin, kZixDesc, kZixOut,
+  // byte ranges of a blocked GZip file (md_bgzf_read): the touched members of a round packed back to back, their output
+  // slots (tables and descriptors go through kGzmDesc, the ranges' bytes through kHostOut)
+  kBgrIn, kBgrSlots,
   kScratchCount
 };
 
@@ -181,6 +184,10 @@ struct md_ctx {
   // piece a round) and the counts of the last md_inflate_index_read (md_inflate_index_last)
   size_t zix_workspace = (size_t)256 << 20;
   md_inflate_index_stats zix_last = {};
+  // byte ranges of a blocked GZip file: md_set_option "bgzf_read_workspace" (bytes of packed input and output slots per
+  // round of md_bgzf_read; 0 = one member a round) and the counts of the last read (md_bgzf_read_last)
+  size_t bgr_workspace = (size_t)256 << 20;
+  md_bgzf_read_stats bgr_last = {};
   std::string err;
 };
 
@@ -342,6 +349,18 @@ int inflate_piece(md_ctx *ctx, const uint8_t *src, size_t src_len, unsigned star
 // the same with the output copied out behind the window in dst, and the CRC-32s that flags ask for
 int continue_serial(md_ctx *ctx, const uint8_t *src, size_t src_len, unsigned start_bit, uint8_t *dst, size_t hist_len,
                     size_t dst_cap, uint32_t adler_in, unsigned flags, size_t *dst_len, int *status, md_inf_resume *resume);
+// ---- capi_gz_members.cpp ----
+// the members of an indexed file: device arrays of M entries (out_off: M + 1), carved from ctx->scratch[kGzmDesc].p
+struct GzmIndex {
+  uint64_t M = 0, total = 0;  // members, the sum of their ISIZE fields
+  uint64_t *mpos = nullptr, *mlen = nullptr, *body_off = nullptr, *body_len = nullptr, *isize = nullptr, *out_len = nullptr,
+           *consumed = nullptr, *out_off = nullptr, *first = nullptr;
+  int32_t *hstatus = nullptr, *status = nullptr;
+};
+// Mark, chain and descriptors (gz_members.hip) for len bytes at d_src, no decoding.  *indexed: the chain of BC size fields
+// leads from offset 0 to the end of the file; then ix holds the members, their headers parsed and their output offsets
+// scanned (md_gz_members_scan, md_gz_members_uncompress, md_bgzf_index_build).
+int gzm_index(md_ctx *ctx, const uint8_t *d_src, uint64_t len, bool *indexed, GzmIndex *ix);
 // ---- capi_long_stream.cpp: both return MD_NOT_HANDLED for what the serial path has to answer ----
 int continue_parallel(md_ctx *ctx, const uint8_t *src, size_t src_len, unsigned start_bit, uint8_t *dst, size_t hist_len,
                       size_t dst_cap, uint32_t adler_in, unsigned flags, size_t *dst_len, int *status, md_inf_resume *resume);

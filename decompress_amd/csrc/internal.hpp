@@ -138,6 +138,25 @@ struct Round {
   int32_t *status;
 };
 }  // namespace zix
+
+namespace bgr {
+// Byte ranges of a blocked GZip file (bgzf_read.hip).  A round of a read packs its members back to back into the input
+// blob and gives each an output slot of slot_stride(capacity) bytes; the host plans both, by the index alone.
+constexpr uint64_t slot_stride(uint64_t cap) { return ((cap + 63) & ~(uint64_t)63) + 64; }
+// bytes of a range that one wavefront of the gather copies at a time
+constexpr uint64_t kGatherSegment = 16384;
+// The members of a round, in member order: device arrays of `count` entries.
+struct Round {
+  // the index's word: position and length in the blob, slot and capacity in the slots, the offset of the member's first
+  // byte in the file's output (ascending strictly: a member without output is never part of a round)
+  const uint64_t *mpos, *mlen, *slot, *cap, *u0;
+  // the member's own word: md_launch_gzm_headers' results, the inflate launch's status and consumed bytes of the body
+  // (copied aside in front of md_launch_gz_finish, which replaces them), and the status behind md_launch_gz_finish
+  const uint64_t *body_len, *isize, *inf_consumed;
+  const int32_t *hstatus, *inf_status, *status;
+  int32_t *verdict;  // 0 = good, else the status the ranges over this member get
+};
+}  // namespace bgr
 }  // namespace md
 
 extern "C" {
@@ -301,6 +320,15 @@ int md_launch_zix_verdict(uint32_t count, const md::zix::Tables *t, const md::zi
 // the bytes of this round's good pieces into dst + dst_off[i]; status[i] (preset to 0) = the first failing piece's verdict
 int md_launch_zix_gather(const md::zix::Tables *t, uint64_t n, uint64_t longest, const uint64_t *off, const uint64_t *len,
                          uint32_t round, const uint8_t *slots, uint8_t *dst, const uint64_t *dst_off, int32_t *status,
+                         hipStream_t stream);
+
+// ---- bgzf_read.hip: byte ranges of a blocked GZip file (md_bgzf_read) ----
+// behind md_launch_gz_finish: verdict[j] of every member of the round (blob = the round's packed members)
+int md_launch_bgr_verdict(uint32_t count, const uint8_t *blob, const md::bgr::Round *r, hipStream_t stream);
+// ranges ids[0 .. nr) are those with bytes in this round; longest = the most bytes one of them has in it.  The bytes of the
+// round's good members into dst + dst_off[i]; status[i] (preset to 0) = the first failing member's verdict
+int md_launch_bgr_gather(uint32_t count, const md::bgr::Round *r, uint32_t nr, const uint32_t *ids, uint64_t longest, const uint64_t *off,
+                         const uint64_t *len, const uint8_t *slots, uint8_t *dst, const uint64_t *dst_off, int32_t *status,
                          hipStream_t stream);
 
 // ---- lzo_kernels.hip ----

@@ -3,8 +3,10 @@
 `csrc/gz_kernels.hip`, the DEFLATE body in the batched inflate / deflate kernels."""
 import ctypes
 
+import numpy as _np
+
 from . import engine as _engine
-from ._lib import GzMembersInfo, GzMembersStats, GzMeta
+from ._lib import BgzfIndexInfo, BgzfReadStats, GzMembersInfo, GzMembersStats, GzMeta
 from ._lib import load as _load
 
 # Gz.os, lib/gz.ml:158-246 (RFC1952 numbering)
@@ -169,6 +171,111 @@ class Bgzf:
         if st != 0:
             raise _engine.Error(_engine.STATUS_NAMES[st])
         return dst.raw[:wrote.value]
+
+
+class BgzfIndex:
+    """Random access to a blocked GZip file (md_bgzf_index_*, md_bgzf_read*): where every member begins in the file and in
+    its output, so that any set of byte ranges - or BGZF virtual offsets - is read as one batch, only the members they
+    touch copied to the device and decoded, each checked against its CRC-32.  There is no CPU fallback.
+
+        idx = BgzfIndex.build(src)                  # the member scan, nothing decoded
+        idx = BgzfIndex.from_gzi(blob, src)         # a .gzi beside the file; no device needed
+        idx.read(src, off, n)                       # bytes, or ("Error", name)
+        idx.read_many(src, [(off, n), ...])         # [("Ok", bytes) | ("Error", name)], ONE batch
+        idx.read_virtual_many(src, [(voff, n)])     # voff = member's offset in src << 16 | offset in its output
+    """
+
+    def __init__(self, handle, device=0):
+        self._h = handle
+        self._free = _load().md_bgzf_index_free  # (kept: the module may be gone when the last index goes)
+        self.device = device
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self._free(self._h)
+            self._h = None
+
+    @staticmethod
+    def build(src, device=0):
+        eng = _engine.default_engine(device)
+        src, n = _raw(src)
+        h = ctypes.c_void_p()
+        st = eng.lib.md_bgzf_index_build(eng.ctx, src, n, ctypes.byref(h))
+        if st < 0:
+            eng._check(st)
+        if st != 0:
+            raise _engine.Error(_engine.STATUS_NAMES[st])
+        return BgzfIndex(h.value, device)
+
+    @staticmethod
+    def from_gzi(blob, src, device=0):
+        blob, src = bytes(blob), _raw(src)[0]
+        h = ctypes.c_void_p()
+        st = _load().md_bgzf_index_from_gzi(blob, len(blob), src, len(src), ctypes.byref(h))
+        if st != 0:
+            raise _engine.Error(_load().md_status_string(st).decode())
+        return BgzfIndex(h.value, device)
+
+    def to_gzi(self):
+        lib = _load()
+        n = lib.md_bgzf_index_gzi_size(self._h)
+        buf, got = ctypes.create_string_buffer(n), ctypes.c_size_t()
+        assert lib.md_bgzf_index_to_gzi(self._h, buf, n, ctypes.byref(got)) == 0 and got.value == n
+        return buf.raw
+
+    def info(self):
+        """-> dict: src_len, members, size (of the output)"""
+        f = BgzfIndexInfo()
+        assert _load().md_bgzf_index_get(self._h, ctypes.byref(f)) == 0
+        return {k: int(getattr(f, k)) for k, _ in f._fields_}
+
+    def entries(self):
+        """-> the M + 1 pairs (c_off, u_off): every member's start, then the end of the last one"""
+        n = self.info()["members"] + 1
+        c_off, u_off = (ctypes.c_uint64 * n)(), (ctypes.c_uint64 * n)()
+        assert _load().md_bgzf_index_entries(self._h, c_off, u_off, n) == 0
+        return list(zip(c_off, u_off))
+
+    def _read(self, fn, src, where, size_known):
+        eng = _engine.default_engine(self.device)
+        src, slen = _raw(src)
+        n = len(where)
+        if any(int(o) < 0 or int(m) < 0 or int(o) >> 64 or int(m) >> 64 for o, m in where):
+            raise _engine.Error("Invalid argument: a range's offset and length are 0 .. 2^64 - 1")
+        off = _np.array([int(r[0]) for r in where], dtype=_np.uint64)
+        ln = _np.array([int(r[1]) for r in where], dtype=_np.uint64)
+        dst_off = _np.zeros(n, dtype=_np.uint64)
+        if n > 1:
+            _np.cumsum(ln[:-1], out=dst_off[1:])
+        size = self.info()["size"]
+        # (a range behind the end: the call refuses it, no room needed)
+        inside = all(int(m) <= size and (not size_known or int(o) + int(m) <= size) for o, m in where)
+        dst = _np.zeros(max(1, sum(int(m) for _, m in where)) if inside else 1, dtype=_np.uint8)
+        status = _np.zeros(max(1, n), dtype=_np.int32)
+        eng._check(fn(eng.ctx, self._h, src, slen, n, off.ctypes.data, ln.ctypes.data, dst.ctypes.data, dst_off.ctypes.data,
+                      status.ctypes.data))
+        return [("Ok", dst[int(dst_off[i]):int(dst_off[i] + ln[i])].tobytes()) if status[i] == 0 else
+                ("Error", _engine.STATUS_NAMES[int(status[i])]) for i in range(n)]
+
+    def read_many(self, src, ranges):
+        """md_bgzf_read: [(off, n), ...] -> [("Ok", bytes) | ("Error", name)]"""
+        return self._read(_engine.default_engine(self.device).lib.md_bgzf_read, src, ranges, True)
+
+    def read_virtual_many(self, src, ranges):
+        """md_bgzf_read_virtual: [(voff, n), ...] -> [("Ok", bytes) | ("Error", name)]"""
+        return self._read(_engine.default_engine(self.device).lib.md_bgzf_read_virtual, src, ranges, False)
+
+    def read(self, src, off, n):
+        st, data = self.read_many(src, [(off, n)])[0]
+        return data if st == "Ok" else (st, data)
+
+    def last_stats(self):
+        """md_bgzf_read_last of this index's device: members decoded, inflate launches, bytes of src copied in, bytes of
+        output slots - of the last read there"""
+        eng = _engine.default_engine(self.device)
+        s = BgzfReadStats()
+        eng._check(eng.lib.md_bgzf_read_last(eng.ctx, ctypes.byref(s)))
+        return {k: int(getattr(s, k)) for k, _ in s._fields_}
 
 
 def inflated_size(src, device=0):

@@ -67,9 +67,10 @@ enum {
   MD_INVALID_ZIP_DIRECTORY = 18, /* "Invalid ZIP directory": end record(s) or central directory */
   MD_INVALID_ZIP_HEADER = 19,    /* "Invalid ZIP local header": an entry's local header or where its body lies */
   MD_ZIP_UNSUPPORTED = 20,       /* "Unsupported ZIP entry": encrypted, or a method other than 0 and 8 */
-  /* the index of a long stream (md_inflate_index_* below) */
+  /* the index of a long stream (md_inflate_index_* below) and of a blocked GZip file (md_bgzf_index_*) */
   MD_INVALID_INDEX = 21          /* "Invalid index": a serialised index that breaks a rule of its layout, an index used with
-                                  * another src than it was built from, a piece that does not end on the next point */
+                                  * another src than it was built from, a piece that does not end on the next point; a file
+                                  * without BC size fields, a virtual offset or a member that is not as the index says */
 };
 
 /* Call-level errors (negative): misuse raises Invalid_argument in the
@@ -192,6 +193,9 @@ int md_synchronize(md_ctx *ctx);
  *                                md_inflate_index_read decodes - every piece's window and output, laid end to end.  A read
  *                                whose pieces need more goes in several rounds, one inflate launch each; a piece larger
  *                                than the value gets a round to itself.  0 is the minimum: one piece a round.
+ *   "bgzf_read_workspace"        MiB (0 .. 2^20; default 256): device memory for the members that ONE round of md_bgzf_read
+ *                                decodes - their bytes packed back to back plus their output slots.  A read whose members
+ *                                need more goes in several rounds, one inflate launch each.  0: one member a round.
  *   "debug_inflate_lds_pad", "debug_known_bounds"   measurement aids of tools/dbg (occupancy curve, known-boundaries floor).
  *   "profile"                    0 / 1: in-kernel phase profile of stream 0 (md_get_profile, a debugging aid).
  * Unknown keys and values out of range: MD_E_INVALID_ARGUMENT. */
@@ -871,6 +875,82 @@ void md_inflate_index_free(md_inflate_index *idx);
 int md_inflate_index_read(md_ctx *ctx, const md_inflate_index *idx, const uint8_t *src, size_t src_len, size_t n,
                           const uint64_t *off, const uint64_t *len, uint8_t *dst, const uint64_t *dst_off, int32_t *status);
 int md_inflate_index_last(const md_ctx *ctx, md_inflate_index_stats *stats);
+
+/* ---- Random access to a blocked GZip file (BGZF: bgzip, htslib, .bam, .vcf.gz, tabix) ------------------------------------
+ * Such a file exists so that a reader fetches a few kilobytes out of gigabytes: every member is a complete stream of at
+ * most 64 KiB with its own CRC-32 and says how long it is, so a read needs no windows and can check every byte it returns.
+ *
+ * md_bgzf_index: src_len and, for the file's M members, M + 1 pairs (c_off[k], u_off[k]), all on the host.  c_off[0] =
+ * u_off[0] = 0; member k is src[c_off[k], c_off[k + 1]) and its output is bytes [u_off[k], u_off[k + 1]) of the file's;
+ * c_off[M] is the byte behind the last member (<= src_len: NUL padding may follow) and u_off[M] = size.  Empty members -
+ * the 28-byte EOF marker, or one in the middle - are ordinary entries with u_off[k + 1] == u_off[k].
+ *
+ * md_bgzf_index_build runs the member scan of md_gz_members_scan (nothing is decoded) and keeps its table.  A file that is
+ * not indexed in that call's sense: MD_INVALID_INDEX and *idx = NULL.  An empty src gives an index of 0 members.
+ *
+ * md_bgzf_index_from_gzi takes no context and touches no device.  The .gzi layout is htslib's, written here from its
+ * description (nobody could run htslib against it): a little-endian u64 count N, then N pairs of u64 (compressed offset,
+ * uncompressed offset); the first block (0, 0) is not stored.  MD_INVALID_INDEX unless the blob is exactly 8 + 16 N bytes,
+ * the compressed offsets increase strictly (from the implied 0) and are < src_len, the uncompressed offsets do not decrease,
+ * and no member's output is more than 1 032 times its length (DEFLATE's limit: it bounds what a read allocates).  .gzi
+ * says neither where the file ends nor how large its output is, so the host completes the table from src: from the last
+ * entry on (offset 0 when N is 0) it follows the BSIZE fields member by member - the member scan's rule for a member: 1f 8b
+ * 08, FEXTRA, a BC subfield of length 2 whose BSIZE + 1 fits the header and src - to the end of src or to NUL padding that
+ * reaches it, and takes each ISIZE from its trailer; whether the writer of the .gzi listed the EOF marker does not matter.
+ * Anything that does not chain to the end: MD_INVALID_INDEX.  The entries in front of the last are not compared with src
+ * here: a read checks every member it decodes against them.
+ * md_bgzf_index_to_gzi writes members 1 .. M - 1 in that layout (count 0 for an index of <= 1 member);
+ * MD_UNEXPECTED_END_OF_OUTPUT when cap is short, *len = the bytes written (or needed) = md_bgzf_index_gzi_size.
+ * from_gzi(to_gzi(x), src) reproduces x entry for entry.  md_bgzf_index_entries: the first `cap` of the M + 1 pairs.
+ *
+ * md_bgzf_read: n ranges [off[i], off[i] + len[i]) of the file's output into dst + dst_off[i] (host pointers; copy in,
+ * kernels, copy out, synchronise).  src_len other than the index's: MD_INVALID_INDEX as the call's return value; a range
+ * with off + len > size: MD_E_INVALID_ARGUMENT; len 0 is fine and touches nothing.  Otherwise MD_OK and status[i] per range.
+ * md_bgzf_read_virtual: the same with BGZF virtual offsets, voff = c_off << 16 | offset in that member's output.  voff >> 16
+ * must be some c_off[k] with k < M (binary search on the host) and voff & 0xffff at most that member's output length;
+ * otherwise that range alone gets MD_INVALID_INDEX and the call is still MD_OK.  A valid one is the byte range that starts
+ * at u_off[k] + (voff & 0xffff); it runs on into the following members.
+ * The HOST plans, from the index alone: a binary search over u_off gives each range its first and last member with output,
+ * the touched members are marked once however many ranges touch them (empty ones never), and they go in member order, in
+ * rounds of as many as fit md_set_option "bgzf_read_workspace" (MiB of packed input plus output slots per round, 0 .. 2^20,
+ * default 256; a member that alone needs more gets a round to itself; 0 = one member a round).  Per round only the touched
+ * members' bytes are copied to the device, packed back to back (a run of consecutive members by one copy); nothing comes
+ * back between the rounds.  On the device, per round: the header walk (RFC 1952, as md_gz_members_uncompress), ONE inflate
+ * launch over the bodies, each into a slot of exactly the output length the index gives, CRC-32 and ISIZE per member, and
+ * the member's verdict - the first of:
+ *   the header's status
+ *   the decoder's status         except MD_UNEXPECTED_END_OF_OUTPUT: the slot's size is the index's word, so running out of
+ *                                it is MD_INVALID_INDEX unless the member's own ISIZE is that size (then MD_INVALID_SIZE)
+ *   MD_INVALID_SIZE              the body did not end exactly at the trailer
+ *   MD_INVALID_CHECKSUM, MD_INVALID_SIZE   the trailer's CRC-32, then its ISIZE, against the decoded bytes
+ *   MD_INVALID_INDEX             the member is sound but not the one the index describes: the BSIZE + 1 of its BC subfield
+ *                                is not the length the index gives, or its ISIZE is not the output length the index gives
+ * and a gather of the good members' bytes into the ranges (one wavefront per range and 16 KiB).  status[i] is MD_OK when
+ * every member of range i is good, otherwise the first failing member's verdict.  A failing range leaves its dst bytes
+ * unspecified (as it stands nothing is written to them); other ranges are not affected: a damaged member never fails the
+ * call.  The ranges' bytes are staged on the device as they lie in dst, max(dst_off + len) bytes.
+ * md_bgzf_read_last: the counts of the context's last read - distinct members decoded, inflate launches, bytes of src
+ * copied to the device, bytes of output slots (summed over the rounds). */
+typedef struct md_bgzf_index md_bgzf_index;
+typedef struct md_bgzf_index_info {
+  uint64_t src_len, members, size;
+} md_bgzf_index_info;
+typedef struct md_bgzf_read_stats {
+  uint64_t members, launches, bytes_in, bytes_scratch;
+} md_bgzf_read_stats;
+int md_bgzf_index_build(md_ctx *ctx, const uint8_t *src, size_t src_len, md_bgzf_index **idx);
+int md_bgzf_index_from_gzi(const uint8_t *gzi, size_t gzi_len, const uint8_t *src, size_t src_len, md_bgzf_index **idx);
+size_t md_bgzf_index_gzi_size(const md_bgzf_index *idx); /* 0 for NULL */
+int md_bgzf_index_to_gzi(const md_bgzf_index *idx, uint8_t *buf, size_t cap, size_t *len);
+int md_bgzf_index_get(const md_bgzf_index *idx, md_bgzf_index_info *info);
+/* c_off / u_off may be NULL when cap is 0 */
+int md_bgzf_index_entries(const md_bgzf_index *idx, uint64_t *c_off, uint64_t *u_off, size_t cap);
+void md_bgzf_index_free(md_bgzf_index *idx);
+int md_bgzf_read(md_ctx *ctx, const md_bgzf_index *idx, const uint8_t *src, size_t src_len, size_t n, const uint64_t *off,
+                 const uint64_t *len, uint8_t *dst, const uint64_t *dst_off, int32_t *status);
+int md_bgzf_read_virtual(md_ctx *ctx, const md_bgzf_index *idx, const uint8_t *src, size_t src_len, size_t n, const uint64_t *voff,
+                         const uint64_t *len, uint8_t *dst, const uint64_t *dst_off, int32_t *status);
+int md_bgzf_read_last(const md_ctx *ctx, md_bgzf_read_stats *stats);
 
 #ifdef __cplusplus
 }
