@@ -32,6 +32,7 @@ namespace lzo {
 constexpr int kWave = 64;
 
 __device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+__device__ __forceinline__ uint32_t rdl(uint32_t v, uint32_t l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l); }
 __device__ __forceinline__ uint8_t ld_nt8(const uint8_t *p) { return __builtin_nontemporal_load(p); }
 // Workgroup -> stream: PERSISTENT workgroups draw streams from a counter in device memory.  With one workgroup per
 // stream a batch whose cheap and expensive streams alternate (C5: text, noise, text, ...) ended up with all its expensive
@@ -42,6 +43,17 @@ __device__ __forceinline__ uint32_t next_stream(uint32_t *counter, uint32_t lane
   if (lane == 0) v = atomicAdd(counter, 1u);
   return uni(v);
 }
+// 32-bit cursors: a stream of more than MD_MAX_STREAM bytes is a descriptor out of range (mdeflate.h), answered here
+__device__ __forceinline__ bool too_long(uint64_t len, uint32_t sid, uint32_t lane, uint64_t *out_len, int32_t *status) {
+  if (len <= MD_MAX_STREAM) return false;
+  if (lane == 0) {
+    status[sid] = MD_E_INVALID_ARGUMENT;
+    out_len[sid] = 0;
+  }
+  return true;
+}
+// room in the output, in 32 bits like the stream's cursors
+__device__ __forceinline__ uint32_t clamp_cap(uint64_t cap) { return cap > 0xfffffff0ull ? 0xfffffff0u : (uint32_t)cap; }
 
 // 256-byte window of the input in registers: lane l holds bytes [wbase + 4l, wbase + 4l + 4)
 struct Win {
@@ -66,7 +78,15 @@ struct Win {
   }
 };
 
+// The two readers of an instruction stream.  Both go through the same interpreter (fiber_step), first byte (first_byte)
+// and window walk (walk_words, walk); each brings its length type, its three actions - transmit, copy, count - and the
+// status of a two-byte operand that runs over the input's end.
+//   Dec  the decoder, Lzo.uncompress: 32-bit lengths, bytes written, Out_of_bound
+//   Cnt  the size query, Lzo.uncompress_with_buffer with room that never runs out: nothing written, a 64-bit position
+//        in the output (every zero byte of a length adds 255 bytes: 17 MB of input describe 4 GiB), "Malformed input"
 struct Dec {
+  typedef uint32_t len_t;
+  static constexpr int kOver = MD_LZO_OUT_OF_BOUND;
   Win in;
   uint8_t *dst;
   uint32_t cap, i_pos, o_pos, lane;
@@ -75,6 +95,14 @@ struct Dec {
   uint32_t prof[8];
   uint64_t prof_t;
 #endif
+};
+struct Cnt {
+  typedef uint64_t len_t;
+  static constexpr int kOver = MD_LZO_MALFORMED_INPUT;  // (the exception Out_of_bound, lib/lzo.ml:414)
+  Win in;
+  uint32_t i_pos, lane;
+  uint64_t o_pos;
+  int state;
 };
 
 // transmit (lib/lzo.ml:188-192) with blit's bounds (:81-89).  Long runs (incompressible input is ONE literal run) go 16
@@ -126,6 +154,52 @@ __device__ __forceinline__ int count(Dec &d, uint32_t *out) {
   return MD_LZO_INVALID_INPUT;
 }
 
+// transmit_to_buffer (lib/lzo.ml:199-204): the literals have to be there; nothing is read
+__device__ __forceinline__ int transmit(Cnt &d, uint64_t len) {
+  if (d.i_pos > d.in.n || len > d.in.n - d.i_pos) return MD_LZO_MALFORMED_INPUT;
+  d.i_pos += (uint32_t)len;
+  d.o_pos += len;
+  return MD_OK;
+}
+// copy_to_buffer (lib/lzo.ml:206-216): an offset beyond the bytes so far is `Invalid_dictionary
+__device__ __forceinline__ int copy(Cnt &d, uint32_t off, uint64_t len) {
+  if (off > d.o_pos) return MD_INVALID_DICTIONARY;
+  d.o_pos += len;
+  return MD_OK;
+}
+// count (lib/lzo.ml:218-236) over runs of zero bytes that are megabytes long in the reference's own vectors: whole
+// KiB of zeros 16 bytes a lane, then the 256 bytes of the register window at once
+__device__ __forceinline__ int count(Cnt &d, uint64_t *out) {
+  const uint32_t n = d.in.n, first = d.i_pos;
+  uint32_t idx = first;
+  while (idx < n && n - idx >= 1024u) {
+    uint4 v;
+    __builtin_memcpy(&v, d.in.src + idx + 16 * d.lane, 16);
+    if (__ballot((v.x | v.y | v.z | v.w) != 0)) break;
+    idx += 1024;
+  }
+  for (;;) {
+    if (idx >= n) return MD_LZO_INVALID_INPUT;
+    if (idx - d.in.wbase >= 256u) d.in.fill(idx);
+    // this lane's first byte at or behind idx that ends the run: it is not zero, or it is the input's end
+    const uint64_t a = (uint64_t)d.in.wbase + 4 * d.lane;
+    uint32_t k = 4;
+#pragma unroll
+    for (int j = 3; j >= 0; j--)
+      if (a + j >= idx && (a + j >= n || ((d.in.w >> (8 * j)) & 0xff) != 0)) k = (uint32_t)j;
+    const uint64_t m = __ballot(k < 4);
+    if (m) {
+      const uint32_t l = (uint32_t)__builtin_ctzll(m);
+      const uint64_t p = (uint64_t)d.in.wbase + 4 * l + rdl(k, l);
+      if (p >= n) return MD_LZO_INVALID_INPUT;
+      *out = (uint64_t)((uint32_t)p - first) * 255 + d.in.byte((uint32_t)p);
+      d.i_pos = (uint32_t)p + 1;
+      return MD_OK;
+    }
+    idx = d.in.wbase + 256;  // (below n: the window held no byte at or behind the input's end)
+  }
+}
+
 #define LZ_EOI() \
   if (d.i_pos >= d.in.n) return MD_UNEXPECTED_END_OF_INPUT;
 #define LZ_TRY(e)             \
@@ -138,11 +212,15 @@ __device__ __forceinline__ int count(Dec &d, uint32_t *out) {
 // buffer: the interpreter of rounds 2-5, now the slow path - what the batched decoder below does not take (an instruction
 // near the end of the input, a length that goes on over zero bytes, the end marker, anything that fails) comes here, so
 // the error cases and their order are the reference's by construction.  *end: the end-of-stream instruction.
-__device__ __forceinline__ int fiber_step(Dec &d, bool *end) {
+// For the size query (D = Cnt) it is the same instruction with the same checks in the same order: nothing is written, a
+// run of literals takes O(1), and the statuses are uncompress_with_buffer's (the actions' own, and D::kOver).
+template <class D>
+__device__ __forceinline__ int fiber_step(D &d, bool *end) {
   LZ_EOI()
   uint32_t chr = d.in.byte(d.i_pos++);
   const int st = d.state & 3;  // -1 land 3 = 3
-  uint32_t len, off, cnt;
+  uint32_t off;
+  typename D::len_t len, cnt;
   int nstate;
   if (chr < 16 && st == 0) {
     if (chr == 0) {
@@ -169,7 +247,7 @@ __device__ __forceinline__ int fiber_step(Dec &d, bool *end) {
       len = 7 + cnt;
     }
     LZ_EOI()
-    if (d.i_pos + 2 > d.in.n) return MD_LZO_OUT_OF_BOUND;
+    if (d.i_pos + 2 > d.in.n) return D::kOver;
     const uint32_t s = d.in.byte(d.i_pos) | (d.in.byte(d.i_pos + 1) << 8);
     d.i_pos += 2;
     off = 16384 + (((chr & 8) >> 3) << 14) + (s >> 2);
@@ -186,7 +264,7 @@ __device__ __forceinline__ int fiber_step(Dec &d, bool *end) {
       len = 31 + cnt;
     }
     LZ_EOI()
-    if (d.i_pos + 2 > d.in.n) return MD_LZO_OUT_OF_BOUND;
+    if (d.i_pos + 2 > d.in.n) return D::kOver;
     const uint32_t s = d.in.byte(d.i_pos) | (d.in.byte(d.i_pos + 1) << 8);
     d.i_pos += 2;
     nstate = (int)(s & 0xff);
@@ -202,7 +280,21 @@ __device__ __forceinline__ int fiber_step(Dec &d, bool *end) {
   LZ_EOI()
   d.state = nstate;
   LZ_TRY(copy(d, off, len + 2))
-  LZ_TRY(transmit(d, (uint32_t)(nstate & 3)))
+  LZ_TRY(transmit(d, (typename D::len_t)(nstate & 3)))
+  return MD_OK;
+}
+// the first byte of a stream, lib/lzo.ml:372-393
+template <class D>
+__device__ __forceinline__ int first_byte(D &d) {
+  LZ_EOI()
+  const uint32_t chr = d.in.byte(0);
+  if (chr == 16) return MD_LZO_NO_DICTIONARY;
+  if (chr >= 18) {
+    d.i_pos = 1;
+    d.state = 0;
+    LZ_EOI()
+    LZ_TRY(transmit(d, chr - 17))
+  }
   return MD_OK;
 }
 
@@ -246,6 +338,8 @@ struct InRing {
   uint32_t n, lane;
   uint32_t lo;   // blocks lo and lo + 1 are in the ring (slot = block & 1); 0xffffffff: nothing
   uint4 ahead;   // this lane's 16 bytes of block lo + 2
+  __device__ __forceinline__ InRing(lds_u8 *ring_, const uint8_t *src_, uint32_t n_, uint32_t lane_)
+      : ring(ring_), src(src_), n(n_), lane(lane_), lo(0xfffffff0u), ahead(make_uint4(0, 0, 0, 0)) {}
   __device__ __forceinline__ uint4 load(uint32_t blk) const {
     const uint64_t a = (uint64_t)blk * kInBlk + lane * 16;
     uint4 v = make_uint4(0, 0, 0, 0);
@@ -279,8 +373,6 @@ struct InRing {
   }
   __device__ __forceinline__ const lds_u8 *at(uint32_t pos) const { return ring + (pos & (kInRing - 1)); }
 };
-
-__device__ __forceinline__ uint32_t rdl(uint32_t v, uint32_t l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l); }
 
 // The instruction that would start with the bytes b (b0 = opcode): opcodes from 16 on are the same in both states of the
 // decoder, below 16 a run of literals in state zero and a two-byte match otherwise (lib/lzo.ml:322-369).  Straight-line
@@ -324,6 +416,67 @@ __device__ __forceinline__ uint32_t walk_word(uint32_t k, uint32_t lit, bool mat
   const uint32_t fast = (k + lit) | ((match && lit == 0) ? kNextZero : 0u);
   return (exotic || !inside) ? (64u | kExotic) : fast;
 }
+// decode -> walk: lane `lane` has decoded the instruction that would start at input byte base + lane; its two walk
+// words in one register, state not zero | state zero << 16 (one lane read per instruction: the word of the state is
+// picked by a shift).  (ia by value, here and in marked_ins: through a reference its selects become selects of addresses
+// and it stays in memory)
+__device__ __forceinline__ uint32_t walk_words(InsAll ia, uint32_t base, uint32_t lane, uint32_t n) {
+  const uint32_t p = base + lane;
+  const uint32_t kzz = ia.low ? ia.kz : ia.kc, lzz = ia.low ? ia.litz : ia.litc, knn = ia.low ? 2u : ia.kc, lnn = ia.low ? ia.litn : ia.litc;
+  const bool ezz = ia.low ? ia.exz : ia.exc, enn = !ia.low && ia.exc;
+  uint32_t wz, wn;
+  // far from the input's end (an instruction is <= 4 + 273 bytes): nothing to test.  base + kFar <= n, as a difference:
+  // base is a stream's i_pos, which never passes n, while the sum wraps for an n near MD_MAX_STREAM (and in 64 bits the
+  // compare is the vector unit's)
+  constexpr uint32_t kFar = 64u + 4u + 273u + 1u;
+  if (__builtin_expect(n - base >= kFar, 1)) {  // (the usual window falls through)
+    wz = walk_word<false>(kzz, lzz, !ia.low, ezz, p, n);
+    wn = walk_word<false>(knn, lnn, true, enn, p, n);
+  } else {
+    wz = walk_word<true>(kzz, lzz, !ia.low, ezz, p, n);
+    wn = walk_word<true>(knn, lnn, true, enn, p, n);
+  }
+  return wn | (wz << 16);
+}
+// walk (wave-uniform): a dozen scalar instructions per instruction - the two ways out of the fast path are not tested
+// here: an instruction that is not for the fast path leaves the window by itself (walk_word) and is looked at after the
+// loop, a batch that is full is cut by the caller where the places are known (the walk is the stream's own chain: with
+// both tests, and what the compiler made of the three exits, it was 30)
+struct Walk {
+  uint64_t taken, zmask;  // the lanes that are instructions; those of them met in state zero
+  uint32_t cur, zero;     // where the next window starts (relative to base), and in which state
+  bool exotic;            // it stopped in front of an instruction that is the slow path's
+};
+__device__ __forceinline__ Walk walk(uint32_t wboth, int state) {
+  Walk r;
+  uint32_t wd = 0;
+  r.cur = 0, r.zero = (state & 3) == 0 ? 1u : 0u, r.taken = 0, r.zmask = 0;
+  do {
+    wd = rdl(wboth, r.cur) >> (r.zero << 4);
+    r.taken |= 1ull << r.cur;
+    r.zmask |= (uint64_t)r.zero << r.cur;
+    r.cur += wd & 1023;
+    r.zero = (wd >> kNextZeroBit) & 1;
+  } while (r.cur < 64);
+  r.exotic = wd & kExotic;
+  if (r.exotic) {  // the window ends in front of it
+    const uint32_t last = 63u - (uint32_t)__builtin_clzll(r.taken);
+    r.taken &= ~(1ull << last);
+    r.cur = last;
+    r.zero = (uint32_t)((r.zmask >> last) & 1);
+  }
+  return r;
+}
+// a marked lane's instruction, met in state zero (mz) or not
+struct Ins {
+  uint32_t k, off, mlen, lit;  // opcode bytes, offset, match bytes (0: a run of literals), literals
+};
+__device__ __forceinline__ Ins marked_ins(InsAll ia, bool mz) {
+  Ins r;
+  r.k = ia.low ? (mz ? ia.kz : 2u) : ia.kc, r.off = ia.low ? (mz ? 0u : ia.offn) : ia.offc;
+  r.mlen = ia.low ? (mz ? 0u : 2u) : ia.mlenc, r.lit = ia.low ? (mz ? ia.litz : ia.litn) : ia.litc;
+  return r;
+}
 #ifdef MD_LZO_PROF  // measurement build (tools/dbg/lzo_phases.py): cycles per phase of the decoder, left in out_len
 #define LZ_PROF_MARK(k)                                   \
   {                                                       \
@@ -335,23 +488,10 @@ __device__ __forceinline__ uint32_t walk_word(uint32_t k, uint32_t lit, bool mat
 #define LZ_PROF_MARK(k)
 #endif
 __device__ __forceinline__ int uncompress_stream(Dec &d, LSmem MD_LDS *sm) {
-  LZ_EOI()
-  uint32_t chr = d.in.byte(0);
-  if (chr == 16) return MD_LZO_NO_DICTIONARY;
-  if (chr >= 18) {  // the first byte, lib/lzo.ml:372-393
-    d.i_pos = 1;
-    d.state = 0;
-    LZ_EOI()
-    LZ_TRY(transmit(d, chr - 17))
-  }
+  LZ_TRY(first_byte(d))
   const uint32_t lane = d.lane;
   lds_u8 *stage = (lds_u8 *)sm->stage;
-  InRing ir;
-  ir.ring = (lds_u8 *)sm->in;
-  ir.src = d.in.src;
-  ir.n = d.in.n;
-  ir.lane = lane;
-  ir.lo = 0xfffffff0u;
+  InRing ir((lds_u8 *)sm->in, d.in.src, d.in.n, lane);
   bool slow = false;
   for (;;) {
     if (slow) {
@@ -380,44 +520,14 @@ __device__ __forceinline__ int uncompress_stream(Dec &d, LSmem MD_LDS *sm) {
         const uint32_t p = base + lane;
         const uint32_t b = *reinterpret_cast<const MD_LDS wv::u32_u *>(ir.at(p));
         const InsAll ia = decode_all(b);
-        const uint32_t kzz = ia.low ? ia.kz : ia.kc, lzz = ia.low ? ia.litz : ia.litc, knn = ia.low ? 2u : ia.kc, lnn = ia.low ? ia.litn : ia.litc;
-        const bool ezz = ia.low ? ia.exz : ia.exc, enn = !ia.low && ia.exc;
-        uint32_t wz, wn;
-        if (base + 64u + 4u + 273u + 1u <= n) {  // far from the input's end (an instruction is <= 4 + 273 bytes): nothing to test
-          wz = walk_word<false>(kzz, lzz, !ia.low, ezz, p, n);
-          wn = walk_word<false>(knn, lnn, true, enn, p, n);
-        } else {
-          wz = walk_word<true>(kzz, lzz, !ia.low, ezz, p, n);
-          wn = walk_word<true>(knn, lnn, true, enn, p, n);
-        }
-        // walk (wave-uniform): a dozen scalar instructions per instruction - the two ways out of the fast path are not
-        // tested here: an instruction that is not for the fast path leaves the window by itself (pack_ins) and is looked
-        // at after the loop, a batch that is full is cut where the places are known (the walk is the stream's own chain:
-        // with both tests, and what the compiler made of the three exits, it was 30)
-        uint32_t cur = 0, zero = (d.state & 3) == 0 ? 1u : 0u, wd = 0;
-        uint64_t taken = 0, zmask = 0;
-        const uint32_t wboth = wn | (wz << 16);  // (one lane read per instruction: the word of the state is picked by a shift)
+        const uint32_t wboth = walk_words(ia, base, lane, n);
         LZ_PROF_MARK(4)  // (measurement build: the window's decode)
-        do {
-          wd = rdl(wboth, cur) >> (zero << 4);
-          taken |= 1ull << cur;
-          zmask |= (uint64_t)zero << cur;
-          cur += wd & 1023;
-          zero = (wd >> kNextZeroBit) & 1;
-        } while (cur < 64);
-        if (wd & kExotic) {  // the slow path's: the batch ends in front of it
-          const uint32_t last = 63u - (uint32_t)__builtin_clzll(taken);
-          taken &= ~(1ull << last);
-          cur = last;
-          zero = (uint32_t)((zmask >> last) & 1);
-          slow = true;
-        }
+        auto [taken, zmask, cur, zero, exotic] = walk(wboth, d.state);  // (a cut below moves taken, cur and zero)
+        if (exotic) slow = true;  // the slow path's: the batch ends in front of it
         LZ_PROF_MARK(5)  // (the walk)
         // the marked lanes: their instruction, their place in the output
         bool mine = (taken >> lane) & 1;
-        const bool mz = (zmask >> lane) & 1;
-        const uint32_t k = ia.low ? (mz ? ia.kz : 2u) : ia.kc, off = ia.low ? (mz ? 0u : ia.offn) : ia.offc;
-        const uint32_t mlen = ia.low ? (mz ? 0u : 2u) : ia.mlenc, lit = ia.low ? (mz ? ia.litz : ia.litn) : ia.litc;
+        const auto [k, off, mlen, lit] = marked_ins(ia, (zmask >> lane) & 1);
         const uint32_t orel = osum + wv::wave_excl_scan(mine ? mlen + lit : 0u, lane);
         const uint32_t oabs = o0 + orel;
         {  // the batch is full: the next one starts at that instruction.  What does not fit the output is the slow path's
@@ -570,18 +680,12 @@ __global__ __launch_bounds__(kWave) void lzo_uncompress_kernel(
     Dec d;
     d.in.src = in + in_off[sid];
     const uint64_t l64 = in_len[sid], c64 = out_cap[sid];
-    if (l64 > MD_MAX_STREAM) {  // 32-bit cursors: the descriptor is out of range (mdeflate.h)
-      if (lane == 0) {
-        status[sid] = MD_E_INVALID_ARGUMENT;
-        out_len[sid] = 0;
-      }
-      continue;
-    }
+    if (too_long(l64, sid, lane, out_len, status)) continue;
     d.in.n = (uint32_t)l64;
     d.in.lane = lane;
     d.in.fill(0);
     d.dst = out + out_off[sid];
-    d.cap = c64 > 0xfffffff0ull ? 0xfffffff0u : (uint32_t)c64;
+    d.cap = clamp_cap(c64);
     d.i_pos = d.o_pos = 0;
     d.lane = lane;
     d.state = 0;
@@ -612,159 +716,21 @@ __global__ __launch_bounds__(kWave) void lzo_uncompress_kernel(
 // opcode bytes, a run of literals is skipped without reading it, and an offset can only reach too far back while fewer
 // than 49 152 bytes have been produced: the count is the decoder's decode and walk of a window of 64 input bytes and a
 // sum over the marked lanes.  No staging, no records, no batch to fill - LDS is the input ring alone.
-// The position in the output is 64-bit: every zero byte of a length adds 255 bytes, 17 MB of input describe 4 GiB.
-struct Cnt {
-  Win in;
-  uint32_t i_pos, lane;
-  uint64_t o_pos;
-  int state;
-};
 struct NSmem {
   alignas(16) uint8_t in[kInRing + 32];
 };
 
-// transmit_to_buffer (lib/lzo.ml:199-204): the literals have to be there; nothing is read
-__device__ __forceinline__ int transmit_n(Cnt &d, uint64_t len) {
-  if (d.i_pos > d.in.n || len > d.in.n - d.i_pos) return MD_LZO_MALFORMED_INPUT;
-  d.i_pos += (uint32_t)len;
-  d.o_pos += len;
-  return MD_OK;
-}
-// copy_to_buffer (lib/lzo.ml:206-216)
-__device__ __forceinline__ int copy_n(Cnt &d, uint32_t off, uint64_t len) {
-  if (off > d.o_pos) return MD_INVALID_DICTIONARY;
-  d.o_pos += len;
-  return MD_OK;
-}
-// count (lib/lzo.ml:218-236) over runs of zero bytes that are megabytes long in the reference's own vectors: whole
-// KiB of zeros 16 bytes a lane, then the 256 bytes of the register window at once
-__device__ __forceinline__ int count_n(Cnt &d, uint64_t *out) {
-  const uint32_t n = d.in.n, first = d.i_pos;
-  uint32_t idx = first;
-  while (idx < n && n - idx >= 1024u) {
-    uint4 v;
-    __builtin_memcpy(&v, d.in.src + idx + 16 * d.lane, 16);
-    if (__ballot((v.x | v.y | v.z | v.w) != 0)) break;
-    idx += 1024;
-  }
-  for (;;) {
-    if (idx >= n) return MD_LZO_INVALID_INPUT;
-    if (idx - d.in.wbase >= 256u) d.in.fill(idx);
-    // this lane's first byte at or behind idx that ends the run: it is not zero, or it is the input's end
-    const uint64_t a = (uint64_t)d.in.wbase + 4 * d.lane;
-    uint32_t k = 4;
-#pragma unroll
-    for (int j = 3; j >= 0; j--)
-      if (a + j >= idx && (a + j >= n || ((d.in.w >> (8 * j)) & 0xff) != 0)) k = (uint32_t)j;
-    const uint64_t m = __ballot(k < 4);
-    if (m) {
-      const uint32_t l = (uint32_t)__builtin_ctzll(m);
-      const uint64_t p = (uint64_t)d.in.wbase + 4 * l + rdl(k, l);
-      if (p >= n) return MD_LZO_INVALID_INPUT;
-      *out = (uint64_t)((uint32_t)p - first) * 255 + d.in.byte((uint32_t)p);
-      d.i_pos = (uint32_t)p + 1;
-      return MD_OK;
-    }
-    idx = d.in.wbase + 256;  // (below n: the window held no byte at or behind the input's end)
-  }
-}
-
-// fiber_step's twin: ONE instruction with the same checks in the same order, nothing written, a run of literals in
-// O(1).  The statuses are uncompress_with_buffer's: an offset beyond the bytes so far is `Invalid_dictionary, literals or
-// a two-byte operand over the input's end are "Malformed input" (the exception Out_of_bound, lib/lzo.ml:414).
-__device__ __forceinline__ int count_step(Cnt &d, bool *end) {
-  LZ_EOI()
-  uint32_t chr = d.in.byte(d.i_pos++);
-  const int st = d.state & 3;  // -1 land 3 = 3
-  uint32_t off;
-  uint64_t len, cnt;
-  int nstate;
-  if (chr < 16 && st == 0) {
-    if (chr == 0) {
-      LZ_EOI()
-      LZ_TRY(count_n(d, &cnt))
-      len = 3 + 15 + cnt;
-    } else len = chr + 3;
-    d.state = -1;
-    LZ_EOI()
-    LZ_TRY(transmit_n(d, len))
-    return MD_OK;
-  }
-  if (chr < 16) {
-    LZ_EOI()
-    const uint32_t h = d.in.byte(d.i_pos++);
-    off = (h << 2) + (chr >> 2) + 1;
-    len = 0;
-    nstate = (int)(chr & 3);
-  } else if (chr < 32) {
-    len = chr & 7;
-    if (len == 0) {
-      LZ_EOI()
-      LZ_TRY(count_n(d, &cnt))
-      len = 7 + cnt;
-    }
-    LZ_EOI()
-    if (d.i_pos + 2 > d.in.n) return MD_LZO_MALFORMED_INPUT;
-    const uint32_t s = d.in.byte(d.i_pos) | (d.in.byte(d.i_pos + 1) << 8);
-    d.i_pos += 2;
-    off = 16384 + (((chr & 8) >> 3) << 14) + (s >> 2);
-    nstate = (int)(s & 0xff);
-    if (off == 16384) {  // end_of_lzo
-      *end = true;
-      return MD_OK;
-    }
-  } else if (chr < 64) {
-    len = chr & 31;
-    if (len == 0) {
-      LZ_EOI()
-      LZ_TRY(count_n(d, &cnt))
-      len = 31 + cnt;
-    }
-    LZ_EOI()
-    if (d.i_pos + 2 > d.in.n) return MD_LZO_MALFORMED_INPUT;
-    const uint32_t s = d.in.byte(d.i_pos) | (d.in.byte(d.i_pos + 1) << 8);
-    d.i_pos += 2;
-    nstate = (int)(s & 0xff);
-    off = (s >> 2) + 1;
-  } else {
-    nstate = (int)chr;
-    len = (chr >> 5) - 1;
-    LZ_EOI()
-    const uint32_t h = d.in.byte(d.i_pos++);
-    off = (h << 3) + ((chr >> 2) & 7) + 1;
-  }
-  LZ_EOI()
-  d.state = nstate;
-  LZ_TRY(copy_n(d, off, len + 2))
-  LZ_TRY(transmit_n(d, (uint64_t)(nstate & 3)))
-  return MD_OK;
-}
-
 // Every pass of the loop takes at least one input byte or ends the stream: a window whose first instruction is not the
-// fast path's goes to count_step, which reads its opcode byte or fails; i_pos never passes n.
+// fast path's goes to fiber_step, which reads its opcode byte or fails; i_pos never passes n.
 __device__ __forceinline__ int count_stream(Cnt &d, NSmem MD_LDS *sm) {
-  LZ_EOI()
-  const uint32_t chr = d.in.byte(0);
-  if (chr == 16) return MD_LZO_NO_DICTIONARY;
-  if (chr >= 18) {  // the first byte, lib/lzo.ml:372-393
-    d.i_pos = 1;
-    d.state = 0;
-    LZ_EOI()
-    LZ_TRY(transmit_n(d, chr - 17))
-  }
+  LZ_TRY(first_byte(d))
   const uint32_t lane = d.lane, n = d.in.n;
-  InRing ir;
-  ir.ring = (lds_u8 *)sm->in;
-  ir.src = d.in.src;
-  ir.n = n;
-  ir.lane = lane;
-  ir.lo = 0xfffffff0u;
-  ir.ahead = make_uint4(0, 0, 0, 0);
+  InRing ir((lds_u8 *)sm->in, d.in.src, n, lane);
   bool slow = false;
   for (;;) {
     if (slow) {
       bool end = false;
-      LZ_TRY(count_step(d, &end))
+      LZ_TRY(fiber_step(d, &end))
       if (end) return MD_OK;
       slow = false;
       continue;
@@ -772,48 +738,20 @@ __device__ __forceinline__ int count_stream(Cnt &d, NSmem MD_LDS *sm) {
     // decode and walk: the decoder's (uncompress_stream), one window at a time
     const uint32_t base = d.i_pos;
     ir.ensure(base);
-    const uint32_t p = base + lane;
-    const uint32_t b = *reinterpret_cast<const MD_LDS wv::u32_u *>(ir.at(p));
-    const InsAll ia = decode_all(b);
-    const uint32_t kzz = ia.low ? ia.kz : ia.kc, lzz = ia.low ? ia.litz : ia.litc, knn = ia.low ? 2u : ia.kc, lnn = ia.low ? ia.litn : ia.litc;
-    const bool ezz = ia.low ? ia.exz : ia.exc, enn = !ia.low && ia.exc;
-    uint32_t wz, wn;
-    if ((uint64_t)base + 64u + 4u + 273u + 1u <= n) {
-      wz = walk_word<false>(kzz, lzz, !ia.low, ezz, p, n);
-      wn = walk_word<false>(knn, lnn, true, enn, p, n);
-    } else {
-      wz = walk_word<true>(kzz, lzz, !ia.low, ezz, p, n);
-      wn = walk_word<true>(knn, lnn, true, enn, p, n);
-    }
-    uint32_t cur = 0, zero = (d.state & 3) == 0 ? 1u : 0u, wd = 0;
-    uint64_t taken = 0, zmask = 0;
-    const uint32_t wboth = wn | (wz << 16);
-    do {
-      wd = rdl(wboth, cur) >> (zero << 4);
-      taken |= 1ull << cur;
-      zmask |= (uint64_t)zero << cur;
-      cur += wd & 1023;
-      zero = (wd >> kNextZeroBit) & 1;
-    } while (cur < 64);
-    if (wd & kExotic) {  // count_step's: the window ends in front of it
-      const uint32_t last = 63u - (uint32_t)__builtin_clzll(taken);
-      taken &= ~(1ull << last);
-      cur = last;
-      zero = (uint32_t)((zmask >> last) & 1);
-      slow = true;
-    }
+    const InsAll ia = decode_all(*reinterpret_cast<const MD_LDS wv::u32_u *>(ir.at(base + lane)));
+    auto [taken, zmask, cur, zero, exotic] = walk(walk_words(ia, base, lane, n), d.state);
+    if (exotic) slow = true;  // fiber_step's: the window ends in front of it
     // the marked lanes' bytes.  While an offset can still reach behind the stream's start every match needs its exact
     // place: a prefix sum; from 49 152 bytes on (the format's offsets end at 49 151) the sum alone.
-    const bool mine = (taken >> lane) & 1, mz = (zmask >> lane) & 1;
-    const uint32_t off = ia.low ? (mz ? 0u : ia.offn) : ia.offc;
-    const uint32_t mlen = ia.low ? (mz ? 0u : 2u) : ia.mlenc, lit = ia.low ? (mz ? ia.litz : ia.litn) : ia.litc;
+    const bool mine = (taken >> lane) & 1;
+    const auto [k, off, mlen, lit] = marked_ins(ia, (zmask >> lane) & 1);
     const uint32_t bytes = mine ? mlen + lit : 0u;
     const uint32_t incl = wv::wave_incl_scan(bytes);
     uint32_t wsum = rdl(incl, 63);
     if (d.o_pos < 49152u) {
       const uint32_t excl = incl - bytes;
       const uint64_t bad = __ballot(mine && mlen != 0 && off > (uint32_t)d.o_pos + excl);
-      if (bad) {  // it fails in count_step, with the reference's error
+      if (bad) {  // it fails in fiber_step, with the reference's error
         const uint32_t fb = (uint32_t)__builtin_ctzll(bad);
         wsum = rdl(excl, fb);
         cur = fb;
@@ -836,13 +774,7 @@ __global__ __launch_bounds__(kWave) void lzo_count_kernel(uint32_t n, const uint
     const uint32_t sid = next_stream(counter, lane);
     if (sid >= n) return;
     const uint64_t l64 = in_len[sid];
-    if (l64 > MD_MAX_STREAM) {  // 32-bit cursors in the input, as the decoder's
-      if (lane == 0) {
-        status[sid] = MD_E_INVALID_ARGUMENT;
-        out_len[sid] = 0;
-      }
-      continue;
-    }
+    if (too_long(l64, sid, lane, out_len, status)) continue;
     Cnt d;
     d.in.src = in + in_off[sid];
     d.in.n = (uint32_t)l64;
@@ -1276,28 +1208,16 @@ __global__ __launch_bounds__(kWave, MD_LZO_C_WAVES) void lzo_compress_kernel(
     Cmp c;
     c.src = in + in_off[sid];
     const uint64_t l64 = in_len[sid], c64 = out_cap[sid];
-    if (l64 > MD_MAX_STREAM) {  // 32-bit cursors: the descriptor is out of range (mdeflate.h)
-      if (lane == 0) {
-        status[sid] = MD_E_INVALID_ARGUMENT;
-        out_len[sid] = 0;
-      }
-      continue;
-    }
+    if (too_long(l64, sid, lane, out_len, status)) continue;
     c.n = (uint32_t)l64;
     c.dst = out + out_off[sid];
-    c.cap = c64 > 0xfffffff0ull ? 0xfffffff0u : (uint32_t)c64;
+    c.cap = clamp_cap(c64);
     c.lane = lane;
     c.op = 0;
     c.oob = false;
     c.patch = 0;
     c.pend = 0, c.pend_n = 0, c.pend_pos = 0;
-    InRing ring;
-    ring.ring = sm->in;
-    ring.src = c.src;
-    ring.n = c.n;
-    ring.lane = lane;
-    ring.lo = 0xfffffff0u;
-    ring.ahead = make_uint4(0, 0, 0, 0);
+    InRing ring(sm->in, c.src, c.n, lane);
     // Lzo.compress, lib/lzo.ml:648-660
     uint32_t idx = 0, len = c.n, t = 0;
     while (len > 20) {
