@@ -108,13 +108,13 @@ static int deflate_launch(md_ctx *ctx, int format, int level, int queue_len, int
                           const PieceArgs *pa = nullptr, const LinkSegs *ls = nullptr) {
   int grc_ = MD_OK;
   // (the Lz77-alone / encode-alone / scripted drivers leave the kernel before it saves a piece's state)
-  if (pa && driver >= 3) return fail(ctx, MD_E_INVALID_ARGUMENT, "a stream in pieces needs one of the three public drivers");
+  if (pa && driver >= md::defl::DRV_LZ77) return fail(ctx, MD_E_INVALID_ARGUMENT, "a stream in pieces needs one of the three public drivers");
   if (!pa) grc_ = ctx->scratch[kWs].reserve(ctx, md_deflate_queue_bytes((uint32_t)n, queue_len), "hipMalloc(deflate command queues)");
   if (grc_ != MD_OK) return grc_;
   const uint64_t *d_front_len = pa ? pa->d_front_len : d_in_len;  // (a piece: the front kernels see [w0, n) as a stream)
   uint32_t max_chain = 0, nice = 0;
   md_deflate_level_params(driver, matcher, level, &max_chain, &nice);
-  const bool matcher_runs = max_chain != 0 && driver < 4;  // level 0 copies; De.Def.encode has no text
+  const bool matcher_runs = max_chain != 0 && driver < md::defl::DRV_ENCODE;  // level 0 copies; De.Def.encode has no text
   md::defl::Front fr;
   uint32_t chunks = 0;
   grc_ = front_workspace(ctx, n, d_front_len, driver, matcher, level, matcher_runs, total_in, &fr, &chunks);
@@ -162,9 +162,20 @@ static int deflate_launch(md_ctx *ctx, int format, int level, int queue_len, int
                               : md_launch_deflate_front((uint32_t)n, chunks, d_in, d_in_off, d_front_len, matcher, max_chain, nice, &fr, order,
                                                         pa ? pa->match_skip : 0u, ctx->stream));
   }
-  MD_LAUNCH_TRY(ctx, md_launch_deflate(format, level, queue_len, driver, dynamic, (uint32_t)n, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap,
-                                       d_out_len, d_status, d_checksum, &fr, pa ? pa->queue : ctx->scratch[kWs].p, ctx->dbg.as<uint64_t>(), gz_hdr,
-                                       gz_hdr_len, gz_crc, matcher, d_hist, order, pa ? &pa->piece : nullptr, ctx->stream));
+  md::defl::SeqArgs args = {};
+  args.format = format, args.level = level, args.qcap = queue_len, args.driver = driver, args.dynamic = dynamic, args.matcher = matcher;
+  args.n = (uint32_t)n;
+  args.in = d_in, args.in_off = d_in_off, args.in_len = d_in_len;
+  args.out = d_out, args.out_off = d_out_off, args.out_cap = d_out_cap;
+  args.out_len = d_out_len, args.status = d_status, args.checksum = d_checksum;
+  args.fr = fr;
+  args.queue_ws = (int *)(pa ? pa->queue : ctx->scratch[kWs].p);
+  args.dbg = ctx->dbg.as<uint64_t>();
+  args.gz_hdr = gz_hdr, args.gz_hdr_len = gz_hdr_len, args.gz_crc = gz_crc;
+  args.hist = d_hist;
+  args.order = order;
+  if (pa) args.pcs = pa->piece;
+  MD_LAUNCH_TRY(ctx, md_launch_deflate(&args, ctx->stream));
   return MD_OK;
 }
 
@@ -175,7 +186,7 @@ static int def_ns_launch(md_ctx *ctx, int format, int level, size_t n, const uin
                          uint64_t *d_out_len, int32_t *d_status, uint32_t *d_checksum, size_t total_in) {
   md::defl::Front fr;
   uint32_t chunks = 0;
-  int grc_ = front_workspace(ctx, n, d_in_len, 6, MD_MATCHER_DE, level, level >= 1 && level <= 4, total_in, &fr, &chunks);
+  int grc_ = front_workspace(ctx, n, d_in_len, md::defl::DRV_NS, MD_MATCHER_DE, level, level >= 1 && level <= 4, total_in, &fr, &chunks);
   if (grc_ != MD_OK) return grc_;
   MD_LAUNCH_TRY(ctx, md_launch_def_ns(format, level, (uint32_t)n, chunks, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status,
                                       d_checksum, &fr, ctx->stream));

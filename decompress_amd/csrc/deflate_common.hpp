@@ -48,13 +48,14 @@ __device__ __forceinline__ uint32_t hash_of(int matcher, uint32_t w4) {
 }
 // positions < p_end are inserted whatever the matcher decides: the last ones are not (lookahead < MIN_MATCH), and
 // De's hash of position len - 3 reads a byte beyond the data (H7): that one is left to the sequential kernel
-__device__ __forceinline__ uint32_t stream_p_end(int matcher, uint32_t eff_level, uint32_t len) {
+__host__ __device__ __forceinline__ uint32_t stream_p_end(int matcher, uint32_t eff_level, uint32_t len) {
   if (matcher == MD_MATCHER_LZ) return len >= 3 ? len - 2 : 0;
   return (eff_level != 0 && len >= 4) ? len - 3 : 0;
 }
-__device__ __forceinline__ uint32_t effective_level(int driver, int matcher, int level) {
-  if (driver == 1 /* DRV_HIGHER */) return 4;               // H6: De.Higher.compress has no ?level
-  if (matcher == MD_MATCHER_LZ && level < 4) return 4;      // Lz.state: 0..4 are _4 (lib/lz.ml:535)
+// the level the matcher runs at
+__host__ __device__ __forceinline__ uint32_t effective_level(int driver, int matcher, int level) {
+  if (driver == DRV_HIGHER) return 4;                       // H6: De.Higher.compress has no ?level
+  if (matcher == MD_MATCHER_LZ && level < 4) return 4;      // Lz.state: 0..4 are _4, no copy mode (lib/lz.ml:535)
   return (uint32_t)level;
 }
 

@@ -23,6 +23,14 @@
 // The window is the input buffer itself: w[rel] = in[base + rel]; bytes the
 // reference reads beyond the data (H7) follow its 64 KiB sliding buffer exactly
 // (zero before the first slide, the byte 32 KiB earlier after it).  See DESIGN.md 4.
+//
+// The kernel (deflate_kernel, at the end of the file) is a page that names its phases, each a function above it, in order:
+//   set up   stream_open, tables_setup, adler_of, frame_header, piece_resume or a fresh start (stream_begin),
+//            command_list_load
+//   loop     ring_fill, literal_run, parse_step, wave_goes_on; lane 0's turn: stream_step or script_step, then
+//            lane0_publish; then what lane 0 asked for: enc_write_wave or trees_wave
+//   finish   the LZ77-alone exit, piece_suspend or frame_trailer (all through `report`)
+// Prof<PROF> keeps the profiled instantiation's clocks and counts; in the plain one it is empty.
 #include "deflate_common.hpp"
 
 namespace md {
@@ -44,17 +52,17 @@ __constant__ uint16_t c_base_dist[32] = {0,    1,    2,    3,    4,    6,     8,
                                          16,   24,   32,   48,   64,   96,    128,   192,
                                          256,  384,  512,  768,  1024, 1536,  2048,  3072,
                                          4096, 6144, 8192, 12288, 16384, 24576, 0,   0};
-// level table lib/de.ml:4030-4049: {max_chain, max_lazy, good_length, nice_length}
-__constant__ uint16_t c_levels[10][4] = {{0, 0, 0, 0},         {4, 4, 4, 8},        {8, 5, 4, 16},
-                                         {32, 6, 4, 32},       {16, 4, 4, 16},      {32, 16, 8, 32},
-                                         {128, 16, 8, 128},    {256, 32, 8, 128},   {1024, 128, 32, 258},
-                                         {4096, 258, 32, 258}};
+// level table lib/de.ml:4030-4049: {max_chain, max_lazy, good_length, nice_length}.  Stated once: the kernel reads the
+// device object, md_deflate_level_params (for the front kernels' launch) the host object of the same initializer.
+#define MD_LEVEL_TABLE                                                                                             \
+  {{0, 0, 0, 0},      {4, 4, 4, 8},      {8, 5, 4, 16},      {32, 6, 4, 32},        {16, 4, 4, 16},                \
+   {32, 16, 8, 32},   {128, 16, 8, 128}, {256, 32, 8, 128},  {1024, 128, 32, 258},  {4096, 258, 32, 258}}
+enum { LV_MAX_CHAIN = 0, LV_MAX_LAZY = 1, LV_GOOD_LENGTH = 2, LV_NICE_LENGTH = 3 };
+__constant__ uint16_t c_levels[10][4] = MD_LEVEL_TABLE;
+static const uint16_t h_levels[10][4] = MD_LEVEL_TABLE;
+#undef MD_LEVEL_TABLE
 
 enum { KIND_FLAT = 0, KIND_FIXED = 1, KIND_DYNAMIC = 2 };
-enum { DRV_ZL = 0, DRV_HIGHER = 1, DRV_CLI = 2,
-       DRV_LZ77 = 3,     // De.Lz77.compress alone: the queue fills are written out as commands (md_de_lz77_compress)
-       DRV_ENCODE = 4,   // De.Def.encode alone: the input IS the command list of one last block (md_de_def_encode)
-       DRV_SCRIPT = 5 }; // De.Def.encode driven step by step: the input is a list of operations (md_de_def_run)
 // operations of DRV_SCRIPT, 32-bit words (mdeflate.h MD_OP_*)
 enum { OP_FILL = 1, OP_BLOCK = 2, OP_FLUSH = 3, OP_SUCC_LITERAL = 4, OP_SUCC_LENGTH = 5, OP_SUCC_DISTANCE = 6, OP_NEW_FREQS = 7,
        OP_QUEUE_RESET = 8 };
@@ -598,6 +606,33 @@ struct Enc {  // De.Def.encoder, lib/de.ml:2465-2478
   unsigned qw, qr, qc;  // the queue's cursors (shared with the matcher)
   int *q;
 };
+// Lane 0 hands a command loop to the wave (ACT_WRITE): the encoder's registers go where enc_write_wave reads them
+__device__ __forceinline__ void enc_publish(DS *s, Enc *e) {
+  s->w.hold = e->hold;
+  s->w.bits = (uint32_t)e->bits;
+  s->w.o_pos = e->o_pos;
+  s->w.o_cap = e->o_cap;
+  s->w.qr = e->qr;
+  s->w.qw = e->qw;
+  s->w.qc = e->qc;
+  s->w.kind = (uint32_t)e->kind;
+  s->w.last = (uint32_t)e->last;
+  s->w.overflow = 0;
+  s->w.o = e->o;
+  s->w.q = e->q;
+  s->w.hdr = e->hdr ? 1u : 0u;
+  e->hdr = false;
+}
+// a command loop just finished: take its result (returns the encoder's answer, R_OK / R_BLOCK)
+__device__ __forceinline__ int enc_take(const DS *s, Enc *e) {
+  e->hold = s->w.hold;
+  e->bits = (int)s->w.bits;
+  e->o_pos = s->w.o_pos;
+  e->qr = s->w.qr;
+  e->overflow = e->overflow || s->w.overflow;
+  e->k = (int)s->w.k;
+  return (int)s->w.rc;
+}
 __device__ __forceinline__ void out_byte(Enc *e, unsigned b) {
   if (e->o_pos < e->o_cap) e->o[e->o_pos] = (uint8_t)b;
   else e->overflow = true;
@@ -937,6 +972,16 @@ struct Lz {
   int matcher;            // MD_MATCHER_DE: De.Lz77 (lib/de.ml:4013-4515); MD_MATCHER_LZ: Lz (lib/lz.ml)
   int steps;              // steps executed in this lz_compress call (bulk-yield policy)
   uint32_t n_steps, n_lm, n_chain;  // profile: matcher steps, longest_match calls, chain links walked
+  // A stream in pieces: the origin of the positions moved (they are absolute; differences of them are all that is ever
+  // used).  Every field that holds a position is listed here - a new one is added here and nowhere else.
+  __device__ __forceinline__ void rebase(uint32_t by) {
+    base -= by;
+    filled -= by;
+    strstart -= by;
+    match_start -= by;
+    prev_match -= by;
+    prepared_end -= by;
+  }
 };
 // window byte at absolute position a (H7: beyond the data the reference reads what its
 // 64 KiB buffer holds: zero before the first slide, the byte 32 KiB earlier after it)
@@ -1087,6 +1132,21 @@ __device__ __forceinline__ bool lz_copy(DS *s, Enc *e, Lz *z) {  // level 0, lib
   }
   return flush;
 }
+// The two reasons for which the matcher hands back to the wave (lz_compress's LZ_NEED exits); the wave asks the same
+// before it wakes lane 0, so as not to run the matcher only to hear them.
+// One step may insert up to 258 positions: make sure the ring covers them (or the tail began)
+__device__ __forceinline__ bool ring_runs_short(uint32_t strstart, uint32_t prepared_end, uint32_t p_end) {
+  return prepared_end < p_end && strstart + 260 > prepared_end;
+}
+// literal-run state (previous position had no match, its literal is pending): the wave can
+// take the following no-match positions 64 at a time — hand over after one step
+// (and in the fresh state after a match: the wave parses ahead from the look-ahead's verdicts)
+// (lookahead: at most 2 * WSIZE and never negative at either caller)
+__device__ __forceinline__ bool wave_takes_next(const DS *s, uint32_t strstart, int lookahead, uint32_t prepared_end,
+                                                uint32_t qavail) {
+  return lookahead > MIN_LOOKAHEAD && strstart + 1 < prepared_end && qavail >= 8 &&
+         s->flg[strstart & (RING - 1)] != 0 && s->flg[(strstart + 1) & (RING - 1)] != 0;
+}
 // Lz77.compress until `Flush or `End; the whole input is available, `Await = end of input
 __device__ __forceinline__ int lz_compress(DS *s, Enc *e, Lz *z, const Ws *ws) {
   for (;;) {
@@ -1129,14 +1189,9 @@ __device__ __forceinline__ int lz_compress(DS *s, Enc *e, Lz *z, const Ws *ws) {
       }
     }
     z->k = LK_ENOUGH;
-    // one step may insert up to 258 positions: make sure the ring covers them (or the tail began)
-    if (z->level != 0 && z->prepared_end < z->p_end && z->strstart + 260 > z->prepared_end) return LZ_NEED;
-    // literal-run state (previous position had no match, its literal is pending): the wave can
-    // take the following no-match positions 64 at a time — hand over after one step
-    // (and in the fresh state after a match: the wave parses ahead from the look-ahead's verdicts)
+    if (z->level != 0 && ring_runs_short(z->strstart, z->prepared_end, z->p_end)) return LZ_NEED;
     if (z->level != 0 && z->steps > 0 && z->match_length == MIN_MATCH - 1 &&
-        z->lookahead > MIN_LOOKAHEAD && z->strstart + 1 < z->prepared_end && e->qc - (e->qw - e->qr) >= 8 &&
-        s->flg[z->strstart & (RING - 1)] != 0 && s->flg[(z->strstart + 1) & (RING - 1)] != 0)
+        wave_takes_next(s, z->strstart, z->lookahead, z->prepared_end, e->qc - (e->qw - e->qr)))
       return LZ_NEED;
     z->steps++;
     z->n_steps++;
@@ -1161,65 +1216,42 @@ struct Run {  // the two state machines of one stream (lane 0's registers)
   Enc e;
   Lz z;
   bool first;
+  bool qfull;   // the reference would have raised Queue.Full
+  bool sc_bad;  // DRV_SCRIPT: a malformed operation list
   int phase;
-  bool qfull;  // the reference would have raised Queue.Full
   int ol, oc;  // end-of-block code of the block that was open when new trees were asked for
   int mode;    // tree mode asked for (TM_*)
   uint32_t ncmd;  // DRV_LZ77: commands written out so far
   uint32_t sc_pos, sc_nrc;  // DRV_SCRIPT: next operation word, results reported so far
   int sc_last;
-  bool sc_bad;              // DRV_SCRIPT: a malformed operation list
+  uint32_t adler;  // Adler-32 of the input so far (the caller's running checksum where it is the caller's): needed at the
+                   // exits only, so it waits here and not in a register of every lane; a piece's state carries it along
 };
 
 __device__ __forceinline__ void stream_begin(Run *r, const Ws *ws, const uint8_t *in, uint32_t n, uint8_t *out, uint32_t cap,
                              int level, int qcap, int driver, int matcher) {
+  // every cursor, count and flag of the two machines starts at zero; what follows is what does not
+  static_assert(K_FIRST_ENTRY == 0 && LK_ENOUGH == 0 && PH_LZ == 0, "the states a stream begins in");
+  *r = Run{};
   Enc &e = r->e;
   e.kind = KIND_FIXED;
-  e.last = 0;
-  e.hold = 0;
-  e.bits = 0;
-  e.flat = 0;
-  e.fmax = 0;
-  e.k = K_FIRST_ENTRY;
   e.o = out;
-  e.o_pos = 0;
   e.o_cap = cap;
-  e.overflow = false;
-  e.hdr = false;
-  e.qw = e.qr = 0;
   e.qc = (unsigned)qcap;
   e.q = ws->queue;
   Lz &z = r->z;
-  z.level = driver == DRV_HIGHER ? 4 : level;  // H6: De.Higher.compress has no ?level
+  z.level = (int)effective_level(driver, matcher, level);
   z.matcher = matcher;
-  if (matcher == MD_MATCHER_LZ && z.level < 4) z.level = 4;  // Lz.state: 0..4 are _4, no copy mode (lib/lz.ml:535)
-  z.max_chain = c_levels[z.level][0];
-  z.max_lazy = c_levels[z.level][1];
-  z.good_length = c_levels[z.level][2];
-  z.nice_length = c_levels[z.level][3];
+  z.max_chain = c_levels[z.level][LV_MAX_CHAIN];
+  z.max_lazy = c_levels[z.level][LV_MAX_LAZY];
+  z.good_length = c_levels[z.level][LV_GOOD_LENGTH];
+  z.nice_length = c_levels[z.level][LV_NICE_LENGTH];
   z.in = in;
   z.n = n;
-  z.base = 0;
-  z.filled = 0;
-  z.strstart = 0;
-  z.lookahead = 0;
-  z.match_start = z.prev_match = 0;
+  z.p_end = stream_p_end(matcher, (uint32_t)z.level, n);
   z.match_length = z.prev_length = matcher == MD_MATCHER_LZ ? MIN_MATCH - 1 : 0;  // lib/lz.ml:563-566
-  z.match_available = 0;
   z.eoi = n == 0;
-  z.more = false;
-  z.k = LK_ENOUGH;
-  z.prepared_end = 0;
-  z.steps = 0;
-  z.n_steps = z.n_lm = z.n_chain = 0;
-  z.p_end = matcher == MD_MATCHER_LZ ? (n >= 3 ? n - 2 : 0) : (z.level != 0 && n >= 4) ? n - 3 : 0;
   r->first = true;
-  r->qfull = false;
-  r->ncmd = 0;
-  r->sc_pos = r->sc_nrc = 0;
-  r->sc_last = 0;
-  r->sc_bad = false;
-  r->phase = PH_LZ;
 }
 
 // DRV_SCRIPT: De.Def.encode (lib/de.ml:2965-3038) driven the way the reference's tests drive it
@@ -1241,14 +1273,8 @@ __device__ __forceinline__ int script_step(DS *s, Run *r, uint32_t *res, uint32_
     rc = enc_begin(s, &e, V_BLOCK, KIND_DYNAMIC, r->sc_last, r->ol, r->oc);
     goto have_rc;
   }
-  if (r->phase == PH_SC_WRITE) {  // a command loop just finished: take its result
-    e.hold = s->w.hold;
-    e.bits = (int)s->w.bits;
-    e.o_pos = s->w.o_pos;
-    e.qr = s->w.qr;
-    e.overflow = e.overflow || s->w.overflow;
-    e.k = (int)s->w.k;
-    rc = (int)s->w.rc;
+  if (r->phase == PH_SC_WRITE) {
+    rc = enc_take(s, &e);
     goto record;
   }
   for (;;) {
@@ -1327,13 +1353,26 @@ bad:
   return ACT_DONE;
 }
 
+// Ask the encoder for a block of the kind the driver plans (`Block {kind; last}): its answer in rc.  When the kind
+// needs trees first, remember the mode and the phase to come back in and return false: the caller answers ACT_TREES.
+__device__ __forceinline__ bool block_begin(const DS *s, Run *r, int driver, int dynamic, int last, int trees_phase, int &rc) {
+  const int kind = block_plan(driver, dynamic, r->z.level, last);
+  if (kind < 0) {
+    r->mode = -kind;
+    r->phase = trees_phase;
+    return false;
+  }
+  rc = enc_begin(s, &r->e, V_BLOCK, kind, last, r->ol, r->oc);
+  return true;
+}
+
 // Lane 0: runs the matcher and the encoder's serial parts until the wave has to do something:
 // more look-ahead (ACT_PREP), the command loop of a block (ACT_WRITE), or nothing more (ACT_DONE).
 // `phase` remembers which driver step a pending command loop belongs to.
 __device__ __forceinline__ int stream_step(DS *s, const Ws *ws, Run *r, int driver, int dynamic) {
   Enc &e = r->e;
   Lz &z = r->z;
-  int rc, res, kind;
+  int rc, res;
   if (r->phase == PH_TREES_END) {  // the last block's trees are there
     rc = enc_begin(s, &e, V_BLOCK, s->kind_result, 1, r->ol, r->oc);
     goto last_block_sent;
@@ -1343,14 +1382,7 @@ __device__ __forceinline__ int stream_step(DS *s, const Ws *ws, Run *r, int driv
     goto block_sent;
   }
   if (r->phase != PH_LZ) {
-    // a command loop just finished: take its result
-    e.hold = s->w.hold;
-    e.bits = (int)s->w.bits;
-    e.o_pos = s->w.o_pos;
-    e.qr = s->w.qr;
-    e.overflow = e.overflow || s->w.overflow;
-    e.k = (int)s->w.k;
-    rc = (int)s->w.rc;
+    rc = enc_take(s, &e);
     if (r->phase == PH_END) return ACT_DONE;
     goto after_flush_write;
   }
@@ -1385,13 +1417,7 @@ __device__ __forceinline__ int stream_step(DS *s, const Ws *ws, Run *r, int driv
         else if (z.matcher == MD_MATCHER_LZ &&
                  !(e.qw != e.qr && g_ldi(e.q + ((e.qw - 1) & (e.qc - 1))) == Q_EOB))
           e.q[e.qw++ & (e.qc - 1)] = Q_EOB;  // Lz leaves the end-of-block command to its driver
-        kind = block_plan(driver, dynamic, z.level, 1);
-        if (kind < 0) {
-          r->mode = -kind;
-          r->phase = PH_TREES_END;
-          return ACT_TREES;
-        }
-        rc = enc_begin(s, &e, V_BLOCK, kind, 1, r->ol, r->oc);
+        if (!block_begin(s, r, driver, dynamic, 1, PH_TREES_END, rc)) return ACT_TREES;
       last_block_sent:
         if (rc == W_PENDING) {
           r->phase = PH_END;
@@ -1402,13 +1428,7 @@ __device__ __forceinline__ int stream_step(DS *s, const Ws *ws, Run *r, int driv
       if (driver == DRV_ZL && !r->first) rc = enc_begin(s, &e, V_FLUSH, 0, 0, r->ol, r->oc);
       else {
         r->first = false;
-        kind = block_plan(driver, dynamic, z.level, 0);
-        if (kind < 0) {
-          r->mode = -kind;
-          r->phase = PH_TREES;
-          return ACT_TREES;
-        }
-        rc = enc_begin(s, &e, V_BLOCK, kind, 0, r->ol, r->oc);
+        if (!block_begin(s, r, driver, dynamic, 0, PH_TREES, rc)) return ACT_TREES;
       }
     }
     for (;;) {
@@ -1421,13 +1441,7 @@ __device__ __forceinline__ int stream_step(DS *s, const Ws *ws, Run *r, int driv
       r->phase = PH_LZ;
       if (rc == R_BLOCK && driver != DRV_CLI) {  // `Block reply: send a block again
         lit_code(s, &e, 256, &r->ol, &r->oc);
-        kind = block_plan(driver, dynamic, z.level, 0);
-        if (kind < 0) {
-          r->mode = -kind;
-          r->phase = PH_TREES;
-          return ACT_TREES;
-        }
-        rc = enc_begin(s, &e, V_BLOCK, kind, 0, r->ol, r->oc);
+        if (!block_begin(s, r, driver, dynamic, 0, PH_TREES, rc)) return ACT_TREES;
         continue;
       }
       break;
@@ -1443,82 +1457,177 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
 
 // the next group of the ring, on its way from the front workspace: 8 positions per lane
 typedef uint32_t v2u __attribute__((ext_vector_type(2)));
+// The sizeof(V) bytes of the text at x0 as little-endian words (V: v2u / v4u): one load, or - where the text ends
+// inside them - what there is, byte by byte, zeros behind it
+template <typename V>
+__device__ __forceinline__ V text_load(const uint8_t *__restrict__ src, uint32_t slen, uint32_t x0) {
+  V v = {};
+  if (x0 + (uint32_t)sizeof(V) <= slen) __builtin_memcpy(&v, src + x0, sizeof(V));
+  else
+    for (uint32_t k = 0; k < (uint32_t)sizeof(V) && x0 + k < slen; k++) v[k >> 2] |= (uint32_t)src[x0 + k] << (8 * (k & 3));
+  return v;
+}
 struct RingPf {
   v4u la, lb;   // link words of positions q0 .. q0 + 7
   v2u f;        // their verdicts
-  uint2 b;      // their bytes
+  v2u b;        // their bytes
   uint32_t pe;  // the group these belong to (0xffffffff: none)
-  __device__ __forceinline__ void fetch(const Ws &ws, const uint8_t *__restrict__ src, uint32_t slen, uint32_t slot_len,
-                                        uint32_t at, uint32_t lane) {
-    pe = at;
-    const uint32_t q0 = at + lane * 8;
+  __device__ __forceinline__ void clear() {
+    pe = 0xffffffffu;
     la = lb = v4u{0, 0, 0, 0};
     f = v2u{0, 0};
-    b = make_uint2(0, 0);
+    b = v2u{0, 0};
+  }
+  __device__ __forceinline__ void fetch(const Ws &ws, const uint8_t *__restrict__ src, uint32_t slen, uint32_t slot_len,
+                                        uint32_t at, uint32_t lane) {
+    clear();
+    pe = at;
+    const uint32_t q0 = at + lane * 8;
     if (q0 + 8 <= slot_len) {  // (every position a fill uses is inside the slot: it ends 64 past the input at least)
       la = __builtin_nontemporal_load(reinterpret_cast<const v4u *>(ws.link + q0));
       lb = __builtin_nontemporal_load(reinterpret_cast<const v4u *>(ws.link + q0 + 4));
       f = __builtin_nontemporal_load(reinterpret_cast<const v2u *>(ws.flg + q0));
     }
-    if (q0 + 8 <= slen) __builtin_memcpy(&b, src + q0, 8);
-    else
-      for (uint32_t k = 0; k < 8 && q0 + k < slen; k++) (k < 4 ? b.x : b.y) |= (uint32_t)src[q0 + k] << (8 * (k & 3));
+    b = text_load<v2u>(src, slen, q0);
   }
 };
 
+// What the profiled instantiation measures on stream 0 (md_set_option "profile"), 32 words: [0] setup [1] look-ahead
+// [2] bulk literal runs [3] matcher/driver (lane 0) [4] bit packing [5] trees, in clock ticks; [8..11] event counts
+// (ring groups, literal-run steps, commands the wave wrote, lane-0 turns); [12..14] the matcher's own counts; [16..19] /
+// [20..23] time / number of lane-0 turns by the action they ended with; [24] the longest turn; [25..27] a turn's
+// entry / step / publish; [28..31] trees_wave's ticks.  The plain instantiation has the empty form: nothing is kept.
 template <bool PROF>
-__global__ __launch_bounds__(kWave, 4) void deflate_kernel(
-    int format, int level, int qcap, int driver, int dynamic, uint32_t n, const uint8_t *__restrict__ in,
-    const uint64_t *__restrict__ in_off, const uint64_t *__restrict__ in_len, uint8_t *__restrict__ out,
-    const uint64_t *__restrict__ out_off, const uint64_t *__restrict__ out_cap,
-    uint64_t *__restrict__ out_len, int32_t *__restrict__ status, uint32_t *__restrict__ checksum,
-    Front fr, int *__restrict__ ws_queue, uint64_t *__restrict__ dbg, const uint8_t *__restrict__ gz_hdr, uint32_t gz_hdr_len,
-    const uint32_t *__restrict__ gz_crc, int matcher, uint32_t *__restrict__ hist, const uint32_t *__restrict__ order, Piece pcs) {
-  __shared__ DS ds;
-  // optional phase profile of stream 0 (md_set_option "profile"): [0] setup [1] look-ahead [2] bulk
-  // literal runs [3] matcher/driver (lane 0) [4] bit packing [5] trees, in clock ticks; [8..] event counts
-  const bool prof = PROF && dbg != nullptr && blockIdx.x == 0;
-  uint64_t pt[6] = {0, 0, 0, 0, 0, 0}, pc[4] = {0, 0, 0, 0}, pa[4] = {0, 0, 0, 0}, pn[4] = {0, 0, 0, 0}, pmax = 0, pq[3] = {0, 0, 0};
-  uint64_t t_prev = prof ? wall_clock64() : 0;
-#define PROF_MARK(i)                      \
-  if (prof) {                             \
-    const uint64_t t_now = wall_clock64(); \
-    pt[i] += t_now - t_prev;              \
-    t_prev = t_now;                       \
+struct Prof {
+  __device__ __forceinline__ explicit Prof(const uint64_t *) {}
+  __device__ __forceinline__ void mark(int) {}
+  __device__ __forceinline__ void count(int, uint32_t) {}
+  __device__ __forceinline__ void step_begin() {}
+  __device__ __forceinline__ void step_end() {}
+  __device__ __forceinline__ void published() {}
+  __device__ __forceinline__ void turn(uint32_t) {}
+  __device__ __forceinline__ void write(uint64_t *, const DS &, const Lz &, uint32_t) {}
+};
+template <>
+struct Prof<true> {
+  bool on;
+  uint64_t pt[6] = {0, 0, 0, 0, 0, 0}, pa[4] = {0, 0, 0, 0}, pmax = 0, pq[3] = {0, 0, 0};  // ticks
+  uint32_t pc[4] = {0, 0, 0, 0}, pn[4] = {0, 0, 0, 0};  // event counts: none exceeds a stream's positions, <= MD_MAX_STREAM
+  static_assert(MD_MAX_STREAM <= 0xffffffffull, "32-bit event counts");
+  uint64_t t_prev, q0 = 0, q1 = 0;
+  __device__ __forceinline__ explicit Prof(const uint64_t *dbg) : on(dbg != nullptr && blockIdx.x == 0) { t_prev = on ? wall_clock64() : 0; }
+  __device__ __forceinline__ void mark(int i) {  // the time since the mark before belongs to phase i
+    if (on) {
+      const uint64_t t_now = wall_clock64();
+      pt[i] += t_now - t_prev;
+      t_prev = t_now;
+    }
   }
-  const uint32_t lane = threadIdx.x;
-  if (blockIdx.x >= n) return;
-  const uint32_t sid = order ? order[blockIdx.x] : blockIdx.x;  // workgroups start in index order: longest streams first
+  __device__ __forceinline__ void count(int i, uint32_t by) { pc[i] += by; }
+  // lane 0's turn: up to its step function, the step function, publishing the result
+  __device__ __forceinline__ void step_begin() { q0 = on ? wall_clock64() : 0; }
+  __device__ __forceinline__ void step_end() {
+    q1 = on ? wall_clock64() : 0;
+    if (on) {
+      pq[0] += q0 - t_prev;
+      pq[1] += q1 - q0;
+    }
+  }
+  __device__ __forceinline__ void published() {
+    if (on) pq[2] += wall_clock64() - q1;
+  }
+  __device__ __forceinline__ void turn(uint32_t act) {  // lane-0 turn time by the action it ended with
+    if (on) {
+      const uint64_t t_now = wall_clock64(), dt = t_now - t_prev;
+#pragma unroll
+      for (uint32_t i = 0; i < 4; i++) {  // (constant indices: an index computed at run time would put the whole struct in scratch)
+        pa[i] += (act & 3) == i ? dt : 0;
+        pn[i] += (act & 3) == i ? 1 : 0;
+      }
+      if (dt > pmax) pmax = dt;
+    }
+  }
+  __device__ __forceinline__ void write(uint64_t *dbg, const DS &ds, const Lz &z, uint32_t lane) {
+    if (on && lane == 0) {
+      for (int i = 0; i < 6; i++) dbg[i] = pt[i];
+      for (int i = 0; i < 4; i++) dbg[8 + i] = pc[i];
+      for (int i = 0; i < 4; i++) {
+        dbg[16 + i] = pa[i];
+        dbg[20 + i] = pn[i];
+      }
+      dbg[24] = pmax;
+      for (int i = 0; i < 4; i++) dbg[28 + i] = ((uint64_t)ds.tp[2 * i + 1] << 32) | ds.tp[2 * i];
+      for (int i = 0; i < 3; i++) dbg[25 + i] = pq[i];
+      dbg[12] = z.n_steps;
+      dbg[13] = z.n_lm;
+      dbg[14] = z.n_chain;
+    }
+  }
+};
+
+// One stream of the batch as this launch sees it, all wave-uniform: which one, what piece of it, its text and output
+struct Strm {
+  uint32_t sid;
+  bool piece, p_first, p_last;  // struct Piece: in pieces at all, the first one, the last one
+  uint32_t pflags;
+  uint32_t w0, rebase;          // position of the first byte the launch holds; what the state's positions come down by
+  size_t sslot;                 // the state slot
+  const uint8_t *src;           // the text, addressed by absolute position
+  uint32_t slen;
+  uint8_t *dst;
+  uint32_t cap;
+  uint32_t slot_len;            // positions [w0, slot_len) have a cell
+};
+// the one writer of a stream's three result words
+__device__ __forceinline__ void report(const SeqArgs &a, uint32_t sid, uint64_t len, int st, uint32_t sum) {
+  a.out_len[sid] = len;
+  a.status[sid] = st;
+  if (a.checksum) a.checksum[sid] = sum;
+}
+
+// ---- stream open: which stream this workgroup takes and what the descriptors say about it.  False: nothing to do for
+//      it (no such stream; it ended in an earlier slice; its descriptor is refused, which is reported here).
+__device__ __forceinline__ bool stream_open(const SeqArgs &a, uint32_t lane, Strm &t, Ws &ws) {
+  const Front &fr = a.fr;
+  const Piece &pcs = a.pcs;
+  if (blockIdx.x >= a.n) return false;
+  const uint32_t sid = a.order ? a.order[blockIdx.x] : blockIdx.x;  // workgroups start in index order: longest streams first
   // a stream in pieces (struct Piece): in_off points at the byte of absolute position w0, in_len is the absolute length
   // so far; positions stay absolute everywhere below, the text and the front workspace are addressed from w0
   const bool piece = pcs.flags != nullptr;
   const uint32_t pflags = piece ? pcs.flags[sid] : 3u;
-  const bool p_first = pflags & 1, p_last = (pflags & 2) != 0;
-  if (pflags & 8) return;  // (a stream that ended in an earlier slice of the batch)
-  const uint32_t w0 = piece ? (uint32_t)pcs.pos[4 * sid] : 0u, rebase = piece ? (uint32_t)pcs.pos[4 * sid + 1] : 0u;
-  const size_t sslot = piece ? (size_t)pcs.pos[4 * sid + 2] : 0, qslot = piece ? (size_t)pcs.pos[4 * sid + 3] : sid;
-  const uint8_t *src = in + in_off[sid] - w0;
-  if (in_len[sid] > MD_MAX_STREAM || fr.flags[0]) {  // 32-bit cursors: the descriptor is out of range (mdeflate.h);
-                                                       // or the batch is larger than md_deflate_params.total_in_bytes said
-    if (lane == 0) {
-      status[sid] = MD_E_INVALID_ARGUMENT;
-      out_len[sid] = 0;
-      if (checksum) checksum[sid] = 0;
-    }
-    return;
+  if (pflags & 8) return false;  // (a stream that ended in an earlier slice of the batch)
+  const uint32_t w0 = piece ? (uint32_t)pcs.pos[4 * sid] : 0u;
+  const size_t qslot = piece ? (size_t)pcs.pos[4 * sid + 3] : sid;
+  t.sid = sid;
+  t.piece = piece;
+  t.pflags = pflags;
+  t.p_first = pflags & 1;
+  t.p_last = (pflags & 2) != 0;
+  t.w0 = w0;
+  t.rebase = piece ? (uint32_t)pcs.pos[4 * sid + 1] : 0u;
+  t.sslot = piece ? (size_t)pcs.pos[4 * sid + 2] : 0;
+  t.src = a.in + a.in_off[sid] - w0;
+  if (a.in_len[sid] > MD_MAX_STREAM || fr.flags[0]) {  // 32-bit cursors: the descriptor is out of range (mdeflate.h);
+                                                         // or the batch is larger than md_deflate_params.total_in_bytes said
+    if (lane == 0) report(a, sid, 0, MD_E_INVALID_ARGUMENT, 0);
+    return false;
   }
-  const uint32_t slen = (uint32_t)in_len[sid];
-  uint8_t *dst = out + out_off[sid];
-  uint64_t cap64 = out_cap[sid];
-  uint32_t cap = cap64 > 0xfffffff0ull ? 0xfffffff0u : (uint32_t)cap64;  // more room than 32-bit cursors can use
+  t.slen = (uint32_t)a.in_len[sid];
+  t.dst = a.out + a.out_off[sid];
+  const uint64_t cap64 = a.out_cap[sid];
+  t.cap = cap64 > 0xfffffff0ull ? 0xfffffff0u : (uint32_t)cap64;  // more room than 32-bit cursors can use
   const uint64_t so = fr.slot[sid];
-  const uint32_t slot_len = (uint32_t)(fr.slot[sid + 1] - so) + w0;  // positions [w0, slot_len) have a cell
+  t.slot_len = (uint32_t)(fr.slot[sid + 1] - so) + w0;  // positions [w0, slot_len) have a cell
   // (the front kernels saw the piece as a stream of its own beginning at w0: their positions - the tails - are relative)
   const uint32_t tl0 = fr.tail[2 * sid], tl1 = fr.tail[2 * sid + 1];
-  Ws ws{fr.link + so - w0, fr.flg + so - w0, fr.m + so - w0, fr.mq + so - w0, ws_queue + qslot * qcap,
-        tl0 ? tl0 + w0 : 0u, tl1 ? tl1 + w0 : 0u};
+  ws = Ws{fr.link + so - w0, fr.flg + so - w0, fr.m + so - w0, fr.mq + so - w0, a.queue_ws + qslot * a.qcap,
+          tl0 ? tl0 + w0 : 0u, tl1 ? tl1 + w0 : 0u};
+  return true;
+}
 
-  // ---- cooperative setup: histograms, code tables, Adler-32 of the input
+// ---- cooperative setup: histograms and the code tables of the bit packer
+__device__ __forceinline__ void tables_setup(DS &ds, uint32_t lane) {
   for (uint32_t i = lane; i < (uint32_t)L_CODES; i += kWave) ds.lits[i] = i == 256 ? 1 : 0;  // make_literals
   if (lane < D_CODES) ds.dsts[lane] = 0;
   if (lane < 32) {
@@ -1527,123 +1636,525 @@ __global__ __launch_bounds__(kWave, 4) void deflate_kernel(
     ds.t_xd[lane] = c_extra_dbits[lane];
     ds.t_bd[lane] = c_base_dist[lane];
   }
-  // Lz77's update_crc (Adler-32 of the input), lib/de.ml:4217-4218: of [from, slen), continuing `seed`
-  // 4 KiB a step, 4 x 16 bytes per lane (the loads of the next step are under way while this one is summed: a stream's
-  // only wavefront would otherwise wait out an HBM round trip per step); sums by dot products: with k the index of a
-  // byte in its 16, sum (end - pos) * byte = (end - first) * sum(byte) - sum(k * byte)
-  auto adler_load = [&](uint32_t ps, v4u (&w)[4]) {
+}
+
+// ---- input Adler-32.  Lz77's update_crc (Adler-32 of the input), lib/de.ml:4217-4218: of [from, slen), continuing `seed`
+// 4 KiB a step, 4 x 16 bytes per lane (the loads of the next step are under way while this one is summed: a stream's
+// only wavefront would otherwise wait out an HBM round trip per step); sums by dot products: with k the index of a
+// byte in its 16, sum (end - pos) * byte = (end - first) * sum(byte) - sum(k * byte)
+__device__ __forceinline__ void adler_load(const uint8_t *__restrict__ src, uint32_t slen, uint32_t lane, uint32_t ps, v4u (&w)[4]) {
+#pragma unroll
+  for (uint32_t j = 0; j < 4; j++) w[j] = text_load<v4u>(src, slen, ps + j * 1024 + lane * 16);
+}
+__device__ __forceinline__ uint32_t adler_of(const uint8_t *__restrict__ src, uint32_t slen, uint32_t lane, uint32_t from, uint32_t seed) {
+  uint32_t a = seed & 0xffff, b = seed >> 16;
+  v4u cur[4], nxt[4];
+  if (from < slen) adler_load(src, slen, lane, from, cur);
+  for (uint32_t ps = from; ps < slen; ps += 4096) {
+    const uint32_t b0 = ps + 4096 < slen ? ps + 4096 : slen;
+    if (b0 < slen) adler_load(src, slen, lane, b0, nxt);
+    uint32_t s1 = 0, s2 = 0;
 #pragma unroll
     for (uint32_t j = 0; j < 4; j++) {
       const uint32_t x0 = ps + j * 1024 + lane * 16;
-      w[j] = v4u{0u, 0u, 0u, 0u};
-      if (x0 + 16 <= slen) __builtin_memcpy(&w[j], src + x0, 16);
-      else
-        for (uint32_t k = 0; x0 + k < slen && k < 16; k++) w[j][k >> 2] |= (uint32_t)src[x0 + k] << (8 * (k & 3));
-    }
-  };
-  auto adler_of = [&](uint32_t from, uint32_t seed) {
-    uint32_t a = seed & 0xffff, b = seed >> 16;
-    v4u cur[4], nxt[4];
-    if (from < slen) adler_load(from, cur);
-    for (uint32_t ps = from; ps < slen; ps += 4096) {
-      const uint32_t b0 = ps + 4096 < slen ? ps + 4096 : slen;
-      if (b0 < slen) adler_load(b0, nxt);
-      uint32_t s1 = 0, s2 = 0;
+      uint32_t t1 = 0, tk = 0;
 #pragma unroll
-      for (uint32_t j = 0; j < 4; j++) {
-        const uint32_t x0 = ps + j * 1024 + lane * 16;
-        uint32_t t1 = 0, tk = 0;
-#pragma unroll
-        for (uint32_t q = 0; q < 4; q++) {
-          t1 = __builtin_amdgcn_udot4(cur[j][q], 0x01010101u, t1, false);
-          tk = __builtin_amdgcn_udot4(cur[j][q], 0x03020100u + 0x04040404u * q, tk, false);
-        }
-        s1 += t1;
-        s2 += (b0 - x0) * t1 - tk;  // (nothing at or beyond the end: t1 = tk = 0)
+      for (uint32_t q = 0; q < 4; q++) {
+        t1 = __builtin_amdgcn_udot4(cur[j][q], 0x01010101u, t1, false);
+        tk = __builtin_amdgcn_udot4(cur[j][q], 0x03020100u + 0x04040404u * q, tk, false);
       }
-      s1 = wave_sum(s1);
-      s2 = wave_sum(s2);
-      b = (b + (b0 - ps) * a + s2) % 65521u;
-      a = (a + s1) % 65521u;
-#pragma unroll
-      for (uint32_t j = 0; j < 4; j++) cur[j] = nxt[j];
+      s1 += t1;
+      s2 += (b0 - x0) * t1 - tk;  // (nothing at or beyond the end: t1 = tk = 0)
     }
-    return (b << 16) | a;
-  };
-  // in pieces: the host's running checksum, or (P_SUM: the batch in slices) ours, carried in the state
-  const bool own_sum = piece && (pflags & 4) && format != MD_FORMAT_GZIP;
-  uint32_t adler = !piece ? adler_of(0, 1u) : own_sum ? (p_first ? adler_of(0, 1u) : 1u) : pcs.sum[2 * sid];
-  const uint32_t isize = piece ? pcs.sum[2 * sid + 1] : slen;
-  __threadfence_block();
-  __syncthreads();
+    s1 = wave_sum(s1);
+    s2 = wave_sum(s2);
+    b = (b + (b0 - ps) * a + s2) % 65521u;
+    a = (a + s1) % 65521u;
+#pragma unroll
+    for (uint32_t j = 0; j < 4; j++) cur[j] = nxt[j];
+  }
+  return (b << 16) | a;
+}
 
+// ---- frame header (with the first piece only): its length, written as far as the output has room
+__device__ __forceinline__ uint32_t frame_header(const SeqArgs &a, const Strm &t, uint32_t lane) {
   uint32_t hdr = 0;
-  if (!p_first) {
+  if (!t.p_first) {
     // (the frame's header went out with the first piece)
-  } else if (format == MD_FORMAT_ZLIB) {
+  } else if (a.format == MD_FORMAT_ZLIB) {
     // Zl.Def header, lib/zl.ml:511-517 (FLEVEL map lib/zl.ml:580-581)
-    int flevel = level == 0 ? 0 : level <= 5 ? 1 : level == 6 ? 2 : 3;
+    int flevel = a.level == 0 ? 0 : a.level <= 5 ? 1 : a.level == 6 ? 2 : 3;
     unsigned h = (8 + ((15 - 8) << 4)) << 8;
     h |= (unsigned)flevel << 6;
     h += 31 - (h % 31);
-    if (lane == 0 && cap >= 2) {
-      dst[0] = (uint8_t)(h >> 8);
-      dst[1] = (uint8_t)h;
+    if (lane == 0 && t.cap >= 2) {
+      t.dst[0] = (uint8_t)(h >> 8);
+      t.dst[1] = (uint8_t)h;
     }
     hdr = 2;
-  } else if (format == MD_FORMAT_GZIP) {
+  } else if (a.format == MD_FORMAT_GZIP) {
     // Gz.Def header (lib/gz.ml:796-812), prepared by md_gz_set_header
-    for (uint32_t i = lane; i < gz_hdr_len && i < cap; i += kWave) dst[i] = gz_hdr[i];
-    hdr = gz_hdr_len;
+    for (uint32_t i = lane; i < a.gz_hdr_len && i < t.cap; i += kWave) t.dst[i] = a.gz_hdr[i];
+    hdr = a.gz_hdr_len;
   }
+  return hdr;
+}
+
+// ---- piece resume / piece suspend.  What a stream in pieces keeps between two launches, kPieceState bytes per state
+// slot: the two LDS structs as they are (the running Adler-32 is in Run).
+static_assert(sizeof(DS) % 4 == 0 && sizeof(Run) % 4 == 0 && sizeof(DS) + sizeof(Run) + 4 <= kPieceState, "piece state");
+// the structs, to the slot (SAVE) or from it: the one list of what moves, for both directions
+template <bool SAVE>
+__device__ __forceinline__ void piece_state_move(DS &ds, Run &run, uint32_t *st, uint32_t lane) {
+  uint32_t *const d = reinterpret_cast<uint32_t *>(&ds), *const r = reinterpret_cast<uint32_t *>(&run);
+  for (uint32_t i = lane; i < (sizeof(DS) + sizeof(Run)) / 4; i += kWave) {
+    uint32_t &w = i < sizeof(DS) / 4 ? d[i] : r[i - sizeof(DS) / 4];
+    if (SAVE) st[i] = w;
+    else w = st[i];
+  }
+}
+// The state the piece before left, then what belongs to this launch.  `sum`: the caller's running checksum; where the
+// Adler-32 is the kernel's own (own_sum) the one in the state is brought up to the end of this piece instead.
+__device__ __forceinline__ void piece_resume(const SeqArgs &a, const Strm &t, const Ws &ws, DS &ds, Run &run, bool own_sum, uint32_t sum,
+                                             uint32_t lane) {
+  __syncthreads();
+  piece_state_move<false>(ds, run, reinterpret_cast<uint32_t *>(a.pcs.state + t.sslot * kPieceState), lane);
+  __syncthreads();
+  if (lane == 0) {
+    run.e.o = t.dst;  // the encoder's output cursor counts within the piece
+    run.e.o_pos = 0;
+    run.e.o_cap = t.cap;
+    run.e.q = ws.queue;
+    run.z.rebase(t.rebase);
+    ds.zs.strstart -= t.rebase;  // (the wave's copies of two of Lz's positions)
+    ds.zs.base -= t.rebase;
+    run.z.in = t.src;
+    run.z.n = t.slen;
+    run.z.p_end = stream_p_end(run.z.matcher, (uint32_t)run.z.level, t.slen);
+    run.z.more = !t.p_last;
+    ds.ctl[0] = run.z.strstart;
+    ds.ctl[1] = 0;
+    ds.ctl[2] = 0;
+    ds.ctl[3] = ACT_PREP;
+    ds.ring_dead = 1;  // the ring is loaded again, from the new front workspace
+    ds.w.o = run.e.o;
+    ds.w.q = run.e.q;
+    ds.w.o_pos = 0;
+    ds.w.o_cap = t.cap;
+  }
+  if (own_sum) {  // the bytes that are new: from where the slice before ended (the matcher had filled up to there)
+    __syncthreads();
+    const uint32_t from = run.z.filled;
+    sum = adler_of(t.src, t.slen, lane, from < t.slen ? from : t.slen, run.adler);
+  }
+  if (lane == 0) run.adler = sum;
+}
+// the matcher waits for input the piece does not hold: the state goes out, nothing else
+__device__ __forceinline__ void piece_suspend(const SeqArgs &a, const Strm &t, DS &ds, Run &run, uint32_t hdr, uint32_t lane) {
+  __syncthreads();
+  piece_state_move<true>(ds, run, reinterpret_cast<uint32_t *>(a.pcs.state + t.sslot * kPieceState), lane);
+  if (lane == 0) report(a, t.sid, hdr + run.e.o_pos, run.e.overflow ? MD_UNEXPECTED_END_OF_OUTPUT : MD_PIECE_AWAIT, run.adler);
+}
+
+// ---- command-list load (DRV_ENCODE): the input is a list of De.Queue commands (lib/de.ml:2245-2266) for ONE last
+// block: load the queue and count the frequencies the way test/test.ml's `encode_dynamic` does (:84-95); nothing is
+// left for the matcher
+__device__ __forceinline__ void command_list_load(const Strm &t, const Ws &ws, DS &ds, Run &run, uint32_t qcap, uint32_t lane) {
+  const uint32_t ncmds = t.slen / 4;
+  __syncthreads();
+  if (lane == 0) {
+    for (uint32_t i = 0; i < ncmds && i < qcap; i++) {
+      uint32_t c;
+      __builtin_memcpy(&c, t.src + 4 * i, 4);
+      ws.queue[i] = (int)c;
+      if (c == (uint32_t)Q_EOB) continue;
+      if (c & Q_COPY) {
+        ds.lits[257 + length_code_of((int)((c >> 16) & 0x1ff) + 3)]++;
+        ds.dsts[distance_code(&ds, (int)(c & 0xffff))]++;
+      } else ds.lits[c & 0xff]++;
+    }
+    run.e.qw = ncmds < qcap ? ncmds : qcap;
+    run.z.n = 0;
+    run.z.eoi = 1;
+    run.z.p_end = 0;
+    if (ncmds > qcap) run.qfull = true;
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __syncthreads();
+}
+
+// ---- ring fill.  The ring runs ahead of the matcher: hash heads, verdicts and bytes of the next positions, PG steps of
+// 64 positions per load (all of it was computed for the whole batch by deflate_front.hip).  Returns the new end of
+// what is prepared.
+template <bool PROF>
+__device__ __forceinline__ uint32_t ring_fill(const Strm &t, const Ws &ws, DS &ds, RingPf &rp, uint32_t p_end, uint32_t lane, Prof<PROF> &pf) {
+  const uint32_t ss = ds.ctl[0];
+  uint32_t pe = ds.ctl[2];
+  // the tree builder used the ring's space, and the code-length symbols of the header it made sit there until the
+  // command loop that follows ACT_TREES has packed them: then the ring is loaded again, from the pending literal on
+  const bool hold = ds.ctl[3] == ACT_TREES;
+  if (ds.ring_dead && !hold) {
+    pe = (ss ? ss - 1 : 0u) & ~63u;
+    if (pe > p_end) pe = p_end;
+    __syncthreads();
+    if (lane == 0) ds.ring_dead = 0;
+  }
+  for (;;) {
+    uint32_t nb = 0;
+    if (pe < p_end && !hold) {
+      const uint32_t space = (ss + RING - 1 - pe) / kWave;  // slot of position ss - 1 stays intact
+      const uint32_t left = (p_end - pe + kWave - 1) / kWave;
+      nb = space < left ? space : left;
+      if (nb > (uint32_t)PG) nb = PG;
+      // wait for a full group unless the matcher is about to run dry or this is the tail
+      if (nb < (uint32_t)PG && nb != left && pe >= ss + 324) nb = 0;
+    }
+    if (nb == 0) break;
+    // a lane takes 8 consecutive positions: two 16-byte loads of link words, one 8-byte load of verdicts, one of
+    // input bytes, and three LDS stores — for the whole group (pe is a multiple of 64 here, so a lane's 8 ring cells
+    // are contiguous and aligned).  The loads were started when the previous group was stored: the fill does not
+    // wait for HBM unless the ring was restarted somewhere else.
+    if (rp.pe != pe) rp.fetch(ws, t.src, t.slen, t.slot_len, pe, lane);
+    if (lane * 8 < nb * kWave) {
+      const uint32_t r0 = (pe + lane * 8) & (RING - 1);
+      // the low halves of the 8 link words (the high halves are the match kernel's fingerprints)
+      const uint4 l8 = make_uint4((rp.la.x & 0xffffu) | (rp.la.y << 16),
+                                  (rp.la.z & 0xffffu) | (rp.la.w << 16), (rp.lb.x & 0xffffu) | (rp.lb.y << 16),
+                                  (rp.lb.z & 0xffffu) | (rp.lb.w << 16));
+      *reinterpret_cast<uint4 *>(&ds.hl[r0]) = l8;
+      *reinterpret_cast<uint2 *>(&ds.flg[r0]) = make_uint2(rp.f.x, rp.f.y);
+      *reinterpret_cast<uint2 *>(&ds.byt[r0]) = make_uint2(rp.b.x, rp.b.y);
+    }
+    {
+      const uint32_t pn = pe + nb * kWave;
+      rp.pe = 0xffffffffu;
+      if (pn < p_end) rp.fetch(ws, t.src, t.slen, t.slot_len, pn, lane);
+    }
+    pe = pe + nb * kWave < p_end ? pe + nb * kWave : p_end;
+    pf.count(0, nb);
+  }
+  return pe;
+}
+
+// a literal the wave found: into the queue at cursor `at`, and counted (emit_literal; many lanes at once, so by atomics)
+__device__ __forceinline__ void push_literal(DS &ds, int *queue, uint32_t qcap, uint32_t at, uint32_t byte) {
+  queue[at & (qcap - 1)] = (int)byte;
+  atomicAdd(&ds.lits[byte], 1);
+}
+
+// ---- literal run (bulk): in the literal-run state a position is trivial when its chain is
+//      empty / out of reach, or none of its pre-walked candidates passes the 3-byte filter
+//      and the chain ends within them (longest_match would return prev_length = 2).
+// Returns whether the run ended inside a step (or did not run): the parse step may go on from there.
+template <bool PROF>
+__device__ __forceinline__ bool literal_run(const Ws &ws, DS &ds, uint32_t qcap, uint32_t pe, uint32_t lane, Prof<PROF> &pf) {
+  if (ds.zs.trivial == 2) {  // fresh state: nothing for the literal-run step, the parse step counts from 0
+    __syncthreads();
+    if (lane == 0) ds.zs.bulked = 0;
+    __syncthreads();
+  }
+  bool short_step = true;
+  if (ds.zs.trivial == 1) {
+    // up to 8 steps of 64 positions per turn of the main loop (its fixed cost per turn was a third of a literal-only
+    // stream's time): the state stays in registers between the steps
+    uint32_t s0 = ds.zs.strstart, la = ds.zs.lookahead, qw = ds.zs.qw, total = 0;
+    const uint32_t base = ds.zs.base, qr = ds.zs.qr;
+    for (int rep = 0; rep < 8; rep++) {
+      const uint32_t avail = qcap - (qw - qr);
+      uint32_t maxk = la > (uint32_t)MIN_LOOKAHEAD ? la - MIN_LOOKAHEAD + 1 : 0;
+      if (maxk > (uint32_t)kWave) maxk = kWave;
+      if (avail < 3) maxk = 0;
+      else if (maxk > avail - 2) maxk = avail - 2;
+      if (s0 >= pe) maxk = 0;
+      else if (maxk > pe - s0) maxk = pe - s0;
+      const uint32_t p = s0 + lane, r = p & (RING - 1);
+      const uint32_t hlv = ds.hl[r], hhv = hlv ? p - hlv : 0u;
+      bool triv = lane < maxk;
+      if (triv && hhv > base && p - hhv <= (uint32_t)MAX_DIST) triv = ds.flg[r] == FL_ENDED;
+      const uint64_t nt = __ballot(!triv);
+      const uint32_t K = nt ? (uint32_t)__builtin_ctzll(nt) : (uint32_t)kWave;
+      // the pending literal of the previous position
+      if (lane < K) push_literal(ds, ws.queue, qcap, qw + lane, ds.byt[(p - 1) & (RING - 1)]);
+      s0 += K;
+      la -= K;
+      qw += K;
+      total += K;
+      pf.count(1, 1);
+      short_step = K < (uint32_t)kWave;
+      if (short_step) break;
+    }
+    if (lane == 0) {
+      ds.zs.strstart = s0;
+      ds.zs.lookahead = la;
+      ds.zs.qw = qw;
+      ds.zs.bulked = total;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __syncthreads();
+    pf.count(2, total);
+  }
+  return short_step;
+}
+
+// ---- parse step: lazy evaluation (lib/de.ml:4351-4410) of up to 64 positions from the
+//      look-ahead's verdicts, when the literal run above stopped at a match.  Every position
+//      evaluates, as if it were reached with prev_length 2, its own lazy chain: a match at p is
+//      deferred while the next position's match is strictly longer (full chain below
+//      good_length, quartered from there on, no search from max_lazy on), and is emitted when
+//      it is not.  The path from s0 through these chains is then walked and emitted.
+template <bool PROF>
+__device__ __forceinline__ void parse_step(const Ws &ws, DS &ds, uint32_t qcap, uint32_t eff_level, uint32_t slot_len, uint32_t pe,
+                                           uint32_t p_end, uint32_t lane, Prof<PROF> &pf) {
+  const uint32_t s0 = ds.zs.strstart, la = ds.zs.lookahead, base = ds.zs.base;
+  uint32_t qw = ds.zs.qw;
+  const uint32_t qavail = qcap - (qw - ds.zs.qr);
+  // positions that may be evaluated: prepared with room for a full match behind them
+  // (insert_string of lib/de.ml:4386-4391 stays inside the ring) and MIN_LOOKAHEAD ahead
+  uint32_t E = la >= (uint32_t)MIN_LOOKAHEAD ? s0 + la - MIN_LOOKAHEAD + 1 : s0;
+  if (pe < p_end) {
+    const uint32_t lim = pe > 260 ? pe - 260 : 0;
+    if (E > lim) E = lim;
+  } else if (E > pe) E = pe;
+  __syncthreads();
+  {
+    // what the look-ahead knows about positions s0 .. s0 + 79: lane -> position s0 + lane, lanes 0 .. 15 also
+    // s0 + 64 + lane; the four loads of match results are issued before anything waits for them (no branch around
+    // them: a position without a match reads its cell and drops it)
+    const uint32_t q0 = s0 + lane, q1 = s0 + 64 + (lane & 15);
+    const uint32_t g0 = q0 < slot_len ? q0 : slot_len - 1, g1 = q1 < slot_len ? q1 : slot_len - 1;
+    const uint32_t ma0 = g_ld(ws.m + g0), mb0 = g_ld(ws.mq + g0), ma1 = g_ld(ws.m + g1), mb1 = g_ld(ws.mq + g1);
+    auto fill = [&](uint32_t j, uint32_t q, uint32_t a, uint32_t b) {
+      const uint32_t r = q & (RING - 1);
+      uint32_t k = 0, lf = 2, df = 0, lq = 2, dq = 0;
+      if (q < E) {
+        const uint32_t f = ds.flg[r], l1v = ds.hl[r], c1v = l1v ? q - l1v : 0u;
+        if (f == FL_ENDED || f == FL_MATCH) k = 1;
+        if (c1v > base && q - c1v <= (uint32_t)MAX_DIST) k |= 2;
+        if (f == FL_MATCH) {
+          lf = a >> 16;
+          df = a & 0xffff;
+          lq = b >> 16;
+          dq = b & 0xffff;
+        }
+      }
+      ds.pm_k[j] = (uint8_t)k;
+      ds.pm_lf[j] = (uint16_t)lf;
+      ds.pm_df[j] = (uint16_t)df;
+      ds.pm_lq[j] = (uint16_t)lq;
+      ds.pm_dq[j] = (uint16_t)dq;
+    };
+    fill(lane, q0, ma0, mb0);
+    if (lane < 16) fill(64 + lane, q1, ma1, mb1);
+  }
+  __syncthreads();
+  // the lazy chain that starts at window position `lane`
+  const uint32_t lv_max_lazy = c_levels[eff_level][LV_MAX_LAZY], lv_good = c_levels[eff_level][LV_GOOD_LENGTH];
+  uint32_t typ = 2, ck = 0, cl = 0, cd = 0;  // typ 0 literal, 1 match chain, 2 unknown
+  {
+    const uint32_t k0 = ds.pm_k[lane];
+    if (k0 & 1) {
+      uint32_t L = (k0 & 2) ? ds.pm_lf[lane] : 2u, d = ds.pm_df[lane];
+      if (L == (uint32_t)MIN_MATCH && d > (uint32_t)TOO_FAR) L = 2;  // lib/de.ml:4363-4367
+      if (L < (uint32_t)MIN_MATCH) typ = 0;
+      else {
+        uint32_t t = lane + 1;
+        typ = 1;
+        for (;;) {
+          if (t >= 80 || !(ds.pm_k[t] & 1)) {
+            typ = 2;
+            break;
+          }
+          if (L >= lv_max_lazy) break;  // prev_length >= max_lazy: no search
+          const bool quart = L >= lv_good;
+          const uint32_t m = (ds.pm_k[t] & 2) ? (quart ? ds.pm_lq[t] : ds.pm_lf[t]) : 2u;
+          if (m <= L) break;
+          d = quart ? ds.pm_dq[t] : ds.pm_df[t];
+          L = m;
+          t++;
+        }
+        ck = t - 1 - lane;  // positions lane .. t-2 become literals, the match sits at t-1
+        cl = L;
+        cd = d;
+      }
+    }
+  }
+  // ---- the path from s0 through these chains, and its commands, by the whole wave.  The matcher arrives at a
+  //      position, and leaves it for the next one (no match there: its literal waits, `pending`) or for the end of
+  //      the chain's match.  Which positions it arrives at is a walk along these jumps from position 0: six rounds
+  //      of pointer doubling (a position's jump and the set of arrivals from it, over 1, 2, 4 ... jumps).  An arrival
+  //      writes the literal that waited (the position before was an arrival without a match) and, at a chain, the
+  //      chain's literals and its match; a prefix sum of these counts places them in the queue, and the arrivals that
+  //      fit the queue (an arrival's commands all or none) are the ones that happen.  (It was one wave-uniform loop
+  //      turn per literal run and per chain, ~80 dependent instructions each: three quarters of a text stream's time.)
+  const uint32_t nxt1 = typ == 2 ? 64u : typ == 1 ? lane + ck + cl : lane + 1;  // (>= 64: out of the window)
+  uint64_t arr = typ == 2 ? 0ull : 1ull << lane;
+  {
+    uint32_t J = nxt1 < 64u ? nxt1 : 64u;
+#pragma unroll
+    for (int r = 0; r < 6; r++) {
+      const int from = (int)(J & 63u);
+      const uint32_t alo = (uint32_t)__shfl((int)(uint32_t)arr, from), ahi = (uint32_t)__shfl((int)(uint32_t)(arr >> 32), from);
+      const uint32_t jn = (uint32_t)__shfl((int)J, from);
+      if (J < 64u) {
+        arr |= ((uint64_t)ahi << 32) | alo;
+        J = jn;
+      }
+      if ((uint32_t)__builtin_amdgcn_readfirstlane((int)J) >= 64u) break;  // the walk from position 0 is complete
+    }
+  }
+  const uint64_t vis = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(arr >> 32)) << 32) |
+                       (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)arr);  // the arrivals from position 0
+  const uint32_t pending0 = ds.zs.trivial == 1 ? 1u : 0u;
+  const uint64_t waits = vis & __builtin_amdgcn_ballot_w64(typ == 0);  // arrivals that leave their literal waiting
+  const bool here = (vis >> lane) & 1;
+  const uint32_t pend_in = lane ? (uint32_t)((waits >> (lane - 1)) & 1) : pending0;
+  const uint32_t mine = here ? pend_in + (typ == 1 ? ck + 1 : 0u) : 0u;
+  const uint32_t upto = wave_incl_scan(mine);
+  const uint32_t cmax = qavail >= 3 ? qavail - 2 : 0;
+  const bool happens = here && upto <= cmax;
+  const uint64_t hm = __builtin_amdgcn_ballot_w64(happens);
+  uint32_t cur = 0, pending = pending0, cmds = 0;
+  if (hm) {
+    const int last = 63 - __builtin_clzll(hm);
+    cmds = (uint32_t)__builtin_amdgcn_readlane((int)upto, last);
+    cur = (uint32_t)__builtin_amdgcn_readlane((int)nxt1, last);
+    pending = (uint32_t)((waits >> last) & 1);
+    if (happens) {
+      uint32_t at = qw + upto - mine;
+      if (pend_in) push_literal(ds, ws.queue, qcap, at++, ds.byt[(s0 + lane - 1) & (RING - 1)]);
+      if (typ == 1) {
+        for (uint32_t j = 0; j < ck; j++) push_literal(ds, ws.queue, qcap, at++, ds.byt[(s0 + lane + j) & (RING - 1)]);
+        // emit_match, lib/de.ml:4236-4245
+        ws.queue[at & (qcap - 1)] = (int)(((cl - 3) << 16) | (cd - 1) | Q_COPY);
+        atomicAdd(&ds.lits[257 + length_code_of((int)cl)], 1);
+        atomicAdd(&ds.dsts[distance_code(&ds, (int)(cd - 1))], 1);
+      }
+    }
+  }
+  if (lane == 0 && cur > 0) {
+    ds.zs.strstart = s0 + cur;
+    ds.zs.lookahead = la - cur;
+    ds.zs.qw = qw + cmds;
+    ds.zs.trivial = pending ? 1u : 2u;
+    ds.zs.bulked += cur;
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __syncthreads();
+  pf.count(2, cmds);
+}
+
+// Would the matcher hand straight back (lz_compress's two LZ_NEED exits)?  Then don't run it: its state machine is a
+// long walk through divergent code even when it has nothing to do.  True: the wave goes round again (ctl is set for it).
+__device__ __forceinline__ bool wave_goes_on(DS &ds, uint32_t qcap, uint32_t pe, uint32_t p_end, uint32_t lane) {
+  if (ds.zs.trivial && ds.zs.bulked > 0) {
+    const uint32_t la = ds.zs.lookahead, s2 = ds.zs.strstart;
+    const uint32_t avail = qcap - (ds.zs.qw - ds.zs.qr);
+    if (la >= (uint32_t)MIN_LOOKAHEAD && (ring_runs_short(s2, pe, p_end) || wave_takes_next(&ds, s2, (int)la, pe, avail))) {
+      __syncthreads();
+      if (lane == 0) {
+        ds.ctl[0] = s2;
+        ds.ctl[2] = pe;
+      }
+      __syncthreads();
+      return true;
+    }
+  }
+  return false;
+}
+
+// ---- lane-0 turn.  The kernel itself hands the matcher the state the wave left and calls the driver's step function
+// (stream_step / script_step: the one user of &ws, and the view stays in registers only while its address goes no further
+// than that call); here, what the wave needs for what lane 0 asked is published
+__device__ __forceinline__ void lane0_publish(DS &ds, Run &run, int act, uint32_t pe) {
+  if (act == ACT_WRITE) enc_publish(&ds, &run.e);
+  if (act == ACT_TREES) ds.ctl[4] = (uint32_t)run.mode;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");  // chain links / queue commands have landed
+  ds.ctl[0] = run.z.strstart;
+  ds.ctl[1] = act == ACT_DONE ? 1 : act == ACT_AWAIT ? 2 : 0;
+  ds.ctl[2] = pe;
+  ds.ctl[3] = (uint32_t)act;
+  ds.zs.strstart = run.z.strstart;
+  ds.zs.lookahead = (uint32_t)run.z.lookahead;
+  ds.zs.base = run.z.base;
+  ds.zs.qw = run.e.qw;
+  ds.zs.qr = run.e.qr;
+  ds.zs.bulked = 0;
+  ds.zs.trivial = (act == ACT_PREP && run.z.level != 0 && run.z.match_length == MIN_MATCH - 1 &&
+                   run.phase == PH_LZ)
+                      ? (run.z.match_available ? 1u : 2u)
+                      : 0u;
+}
+
+// ---- exits (the LZ77-alone one is in the kernel).  The stream ended: its status, and the frame's trailer behind the body (lane 0)
+__device__ __forceinline__ void frame_trailer(const SeqArgs &a, const Strm &t, const Run &run, uint32_t hdr, bool room) {
+  const uint32_t adler = run.adler;
+  // The output pointer and the input's length mod 2^32 for gzip's trailer (in pieces: the caller's count) are read from
+  // the descriptors again here, where they are needed: carried through the loop they cost registers and a spill
+  uint8_t *dst = a.out + a.out_off[t.sid];
+  const uint32_t isize = a.format != MD_FORMAT_GZIP ? 0u : t.piece ? a.pcs.sum[2 * t.sid + 1] : (uint32_t)a.in_len[t.sid];
+  uint32_t body = room ? run.e.o_pos : 0;
+  int st = !room || run.e.overflow ? MD_UNEXPECTED_END_OF_OUTPUT : MD_OK;
+  if (room && run.qfull) st = MD_QUEUE_FULL;
+  if (a.driver == DRV_SCRIPT) {
+    if (room && run.sc_bad) st = MD_E_INVALID_ARGUMENT;
+    if (a.hist) a.hist[(size_t)t.sid * (L_CODES + D_CODES)] = room ? run.sc_nrc : 0u;
+  }
+  uint32_t total = hdr + body;
+  if (a.format == MD_FORMAT_ZLIB && st == MD_OK) {
+    if (t.cap - total < 4) st = MD_UNEXPECTED_END_OF_OUTPUT;
+    else {
+      for (int k = 0; k < 4; k++) dst[total + k] = (uint8_t)(adler >> (24 - 8 * k));  // big-endian
+      total += 4;
+    }
+  }
+  uint32_t sum = adler;
+  if (a.format == MD_FORMAT_GZIP) {
+    sum = t.piece ? adler : a.gz_crc[t.sid];  // (in pieces: the host's running CRC-32)
+    if (st == MD_OK) {
+      // Gz.Def checksum (lib/gz.ml:715-722): CRC-32, then the input size mod 2^32, little-endian
+      if (t.cap - total < 8) st = MD_UNEXPECTED_END_OF_OUTPUT;
+      else {
+        for (int k = 0; k < 4; k++) {
+          dst[total + k] = (uint8_t)(sum >> (8 * k));
+          dst[total + 4 + k] = (uint8_t)(isize >> (8 * k));
+        }
+        total += 8;
+      }
+    }
+  }
+  report(a, t.sid, st == MD_OK ? total : 0, st, sum);
+}
+
+// The kernel: open the stream, set up, loop (the wave's steps, then lane 0's turn, then what lane 0 asked for), finish.
+template <bool PROF>
+__global__ __launch_bounds__(kWave, 4) void deflate_kernel(const SeqArgs a) {
+  __shared__ DS ds;
   // the two state machines of the stream: lane 0's, kept in LDS — as registers they cost every lane of the wave ~100
   // VGPRs (a value only lane 0 uses still takes a whole vector register) and with them half of the occupancy
   __shared__ Run run;
-  const bool room = cap >= hdr;
-  if (piece && !p_first) {
-    // the state the piece before left: the two structs as they were, then what belongs to this launch
-    static_assert(sizeof(DS) % 4 == 0 && sizeof(Run) % 4 == 0 && sizeof(DS) + sizeof(Run) + 4 <= kPieceState, "piece state");
-    const uint32_t *st = reinterpret_cast<const uint32_t *>(pcs.state + sslot * kPieceState);
-    __syncthreads();
-    for (uint32_t i = lane; i < sizeof(DS) / 4; i += kWave) reinterpret_cast<uint32_t *>(&ds)[i] = st[i];
-    for (uint32_t i = lane; i < sizeof(Run) / 4; i += kWave) reinterpret_cast<uint32_t *>(&run)[i] = st[sizeof(DS) / 4 + i];
-    __syncthreads();
-    if (lane == 0) {
-      run.e.o = dst;  // the encoder's output cursor counts within the piece
-      run.e.o_pos = 0;
-      run.e.o_cap = cap;
-      run.e.q = ws.queue;
-      // the origin of the positions moved (Lz's are absolute; differences of them are all that is ever used)
-      run.z.base -= rebase;
-      run.z.filled -= rebase;
-      run.z.strstart -= rebase;
-      run.z.match_start -= rebase;
-      run.z.prev_match -= rebase;
-      run.z.prepared_end -= rebase;
-      ds.zs.strstart -= rebase;
-      ds.zs.base -= rebase;
-      run.z.in = src;
-      run.z.n = slen;
-      run.z.p_end = matcher == MD_MATCHER_LZ ? (slen >= 3 ? slen - 2 : 0) : (run.z.level != 0 && slen >= 4) ? slen - 3 : 0;
-      run.z.more = !p_last;
-      ds.ctl[0] = run.z.strstart;
-      ds.ctl[1] = 0;
-      ds.ctl[2] = 0;
-      ds.ctl[3] = ACT_PREP;
-      ds.ring_dead = 1;  // the ring is loaded again, from the new front workspace
-      ds.w.o = run.e.o;
-      ds.w.q = run.e.q;
-      ds.w.o_pos = 0;
-      ds.w.o_cap = cap;
-    }
-    if (own_sum) {  // the bytes that are new: from where the slice before ended (the matcher had filled up to there)
-      __syncthreads();
-      const uint32_t from = run.z.filled;
-      adler = adler_of(from < slen ? from : slen, st[(sizeof(DS) + sizeof(Run)) / 4]);
-    }
-  } else if (lane == 0) {
-    if (room) stream_begin(&run, &ws, src, slen, dst + hdr, cap - hdr, level, qcap, driver, matcher);
-    if (room && piece && !p_last) {
+  Prof<PROF> pf(a.dbg);
+  const uint32_t lane = threadIdx.x;
+  Strm t;
+  Ws ws;
+  if (!stream_open(a, lane, t, ws)) return;
+  tables_setup(ds, lane);
+  // in pieces: the host's running checksum, or (P_SUM: the batch in slices) ours, carried in the state
+  const bool own_sum = t.piece && (t.pflags & 4) && a.format != MD_FORMAT_GZIP;
+  // (a lambda that captures `lane` by reference, as the kernel had before it was split: the compiler then passes no
+  // range of `lane` on to trees_wave and enc_write_wave, and their code is what it was.  Without it tree_make_wave's
+  // clearing loop is unrolled and trees + packing measured 2 % slower.  To re-check: hipcc --save-temps, and diff the ISA
+  // of tree_make_wave / trees_wave / enc_write_wave against the build before the edit)
+  auto adler_from0 = [&]() { return adler_of(t.src, t.slen, lane, 0, 1u); };
+  const uint32_t sum = !t.piece ? adler_from0() : own_sum ? (t.p_first ? adler_from0() : 1u) : a.pcs.sum[2 * t.sid];
+  __threadfence_block();
+  __syncthreads();
+
+  const uint32_t hdr = frame_header(a, t, lane);
+  const bool room = t.cap >= hdr;
+  if (t.piece && !t.p_first) piece_resume(a, t, ws, ds, run, own_sum, sum, lane);
+  else if (lane == 0) {  // a stream (or its first piece) begins: the two state machines and what the wave reads of them
+    if (room) stream_begin(&run, &ws, t.src, t.slen, t.dst + hdr, t.cap - hdr, a.level, a.qcap, a.driver, a.matcher);
+    if (room && t.piece && !t.p_last) {
       run.z.more = true;
       run.z.eoi = false;
     }
@@ -1655,317 +2166,24 @@ __global__ __launch_bounds__(kWave, 4) void deflate_kernel(
     ds.zs.trivial = 0;
     ds.zs.bulked = 0;
     for (int i = 0; i < 8; i++) ds.tp[i] = 0;
+    run.adler = sum;
   }
-  if (driver == DRV_ENCODE && room) {
-    // the input is a list of De.Queue commands (lib/de.ml:2245-2266) for ONE last block: load the queue and count the
-    // frequencies the way test/test.ml's `encode_dynamic` does (:84-95); nothing is left for the matcher
-    const uint32_t ncmds = slen / 4;
-    __syncthreads();
-    if (lane == 0) {
-      for (uint32_t i = 0; i < ncmds && i < (uint32_t)qcap; i++) {
-        uint32_t c;
-        __builtin_memcpy(&c, src + 4 * i, 4);
-        ws.queue[i] = (int)c;
-        if (c == (uint32_t)Q_EOB) continue;
-        if (c & Q_COPY) {
-          ds.lits[257 + length_code_of((int)((c >> 16) & 0x1ff) + 3)]++;
-          ds.dsts[distance_code(&ds, (int)(c & 0xffff))]++;
-        } else ds.lits[c & 0xff]++;
-      }
-      run.e.qw = ncmds < (uint32_t)qcap ? ncmds : (uint32_t)qcap;
-      run.z.n = 0;
-      run.z.eoi = 1;
-      run.z.p_end = 0;
-      if (ncmds > (uint32_t)qcap) run.qfull = true;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __syncthreads();
-  }
-  const bool no_text = driver == DRV_ENCODE || driver == DRV_SCRIPT;
-  const uint32_t eff_level = driver == DRV_HIGHER ? 4 : (matcher == MD_MATCHER_LZ && level < 4) ? 4 : level;
-  const uint32_t p_end = no_text ? 0
-                         : matcher == MD_MATCHER_LZ ? (slen >= 3 ? slen - 2 : 0)
-                                                    : (eff_level != 0 && slen >= 4) ? slen - 3 : 0;
+  if (a.driver == DRV_ENCODE && room) command_list_load(t, ws, ds, run, (uint32_t)a.qcap, lane);
+  const uint32_t eff_level = effective_level(a.driver, a.matcher, a.level), qcap = (uint32_t)a.qcap;
+  const uint32_t p_end = a.driver == DRV_ENCODE || a.driver == DRV_SCRIPT ? 0 : stream_p_end(a.matcher, eff_level, t.slen);  // (no text)
   __syncthreads();
-  PROF_MARK(0)
+  pf.mark(0);
   RingPf rp;
-  rp.pe = 0xffffffffu;
-  rp.la = rp.lb = v4u{0, 0, 0, 0};
-  rp.f = v2u{0, 0};
-  rp.b = make_uint2(0, 0);
+  rp.clear();
   for (;;) {
     if (ds.ctl[1]) break;
-    const uint32_t ss = ds.ctl[0];
-    uint32_t pe = ds.ctl[2];
-    // the tree builder used the ring's space, and the code-length symbols of the header it made sit there until the
-    // command loop that follows ACT_TREES has packed them: then the ring is loaded again, from the pending literal on
-    const bool hold = ds.ctl[3] == ACT_TREES;
-    if (ds.ring_dead && !hold) {
-      pe = (ss ? ss - 1 : 0u) & ~63u;
-      if (pe > p_end) pe = p_end;
-      __syncthreads();
-      if (lane == 0) ds.ring_dead = 0;
-    }
-    // ---- the ring runs ahead of the matcher: hash heads, verdicts and bytes of the next positions, PG steps of 64
-    //      positions per load (all of it was computed for the whole batch by deflate_front.hip)
-    for (;;) {
-      uint32_t nb = 0;
-      if (pe < p_end && !hold) {
-        const uint32_t room = (ss + RING - 1 - pe) / kWave;  // slot of position ss - 1 stays intact
-        const uint32_t left = (p_end - pe + kWave - 1) / kWave;
-        nb = room < left ? room : left;
-        if (nb > (uint32_t)PG) nb = PG;
-        // wait for a full group unless the matcher is about to run dry or this is the tail
-        if (nb < (uint32_t)PG && nb != left && pe >= ss + 324) nb = 0;
-      }
-      if (nb == 0) break;
-      // a lane takes 8 consecutive positions: two 16-byte loads of link words, one 8-byte load of verdicts, one of
-      // input bytes, and three LDS stores — for the whole group (pe is a multiple of 64 here, so a lane's 8 ring cells
-      // are contiguous and aligned).  The loads were started when the previous group was stored: the fill does not
-      // wait for HBM unless the ring was restarted somewhere else.
-      if (rp.pe != pe) rp.fetch(ws, src, slen, slot_len, pe, lane);
-      if (lane * 8 < nb * kWave) {
-        const uint32_t r0 = (pe + lane * 8) & (RING - 1);
-        // the low halves of the 8 link words (the high halves are the match kernel's fingerprints)
-        const uint4 l8 = make_uint4((rp.la.x & 0xffffu) | (rp.la.y << 16),
-                                    (rp.la.z & 0xffffu) | (rp.la.w << 16), (rp.lb.x & 0xffffu) | (rp.lb.y << 16),
-                                    (rp.lb.z & 0xffffu) | (rp.lb.w << 16));
-        *reinterpret_cast<uint4 *>(&ds.hl[r0]) = l8;
-        *reinterpret_cast<uint2 *>(&ds.flg[r0]) = make_uint2(rp.f.x, rp.f.y);
-        *reinterpret_cast<uint2 *>(&ds.byt[r0]) = rp.b;
-      }
-      {
-        const uint32_t pn = pe + nb * kWave;
-        rp.pe = 0xffffffffu;
-        if (pn < p_end) rp.fetch(ws, src, slen, slot_len, pn, lane);
-      }
-      pe = pe + nb * kWave < p_end ? pe + nb * kWave : p_end;
-      pc[0] += nb;
-    }
+    const uint32_t pe = ring_fill(t, ws, ds, rp, p_end, lane, pf);
     __syncthreads();
-    PROF_MARK(1)
-    // ---- bulk literal run: in the literal-run state a position is trivial when its chain is
-    //      empty / out of reach, or none of its pre-walked candidates passes the 3-byte filter
-    //      and the chain ends within them (longest_match would return prev_length = 2)
-    if (ds.zs.trivial == 2) {  // fresh state: nothing for the literal-run step, the parse step counts from 0
-      __syncthreads();
-      if (lane == 0) ds.zs.bulked = 0;
-      __syncthreads();
-    }
-    bool short_step = true;  // the literal run ended inside a step (or did not run): the parse step may go on from there
-    if (ds.zs.trivial == 1) {
-      // up to 8 steps of 64 positions per turn of the main loop (its fixed cost per turn was a third of a literal-only
-      // stream's time): the state stays in registers between the steps
-      uint32_t s0 = ds.zs.strstart, la = ds.zs.lookahead, qw = ds.zs.qw, total = 0;
-      const uint32_t base = ds.zs.base, qr = ds.zs.qr;
-      for (int rep = 0; rep < 8; rep++) {
-        const uint32_t avail = (uint32_t)qcap - (qw - qr);
-        uint32_t maxk = la > (uint32_t)MIN_LOOKAHEAD ? la - MIN_LOOKAHEAD + 1 : 0;
-        if (maxk > (uint32_t)kWave) maxk = kWave;
-        if (avail < 3) maxk = 0;
-        else if (maxk > avail - 2) maxk = avail - 2;
-        if (s0 >= pe) maxk = 0;
-        else if (maxk > pe - s0) maxk = pe - s0;
-        const uint32_t p = s0 + lane, r = p & (RING - 1);
-        const uint32_t hlv = ds.hl[r], hhv = hlv ? p - hlv : 0u;
-        bool triv = lane < maxk;
-        if (triv && hhv > base && p - hhv <= (uint32_t)MAX_DIST) triv = ds.flg[r] == FL_ENDED;
-        const uint64_t nt = __ballot(!triv);
-        const uint32_t K = nt ? (uint32_t)__builtin_ctzll(nt) : (uint32_t)kWave;
-        if (lane < K) {
-          const uint32_t byte = ds.byt[(p - 1) & (RING - 1)];  // the pending literal of the previous position
-          ws.queue[(qw + lane) & ((uint32_t)qcap - 1)] = (int)byte;
-          atomicAdd(&ds.lits[byte], 1);
-        }
-        s0 += K;
-        la -= K;
-        qw += K;
-        total += K;
-        pc[1]++;
-        short_step = K < (uint32_t)kWave;
-        if (short_step) break;
-      }
-      if (lane == 0) {
-        ds.zs.strstart = s0;
-        ds.zs.lookahead = la;
-        ds.zs.qw = qw;
-        ds.zs.bulked = total;
-      }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-      __syncthreads();
-      pc[2] += total;
-    }
-    // ---- parse step: lazy evaluation (lib/de.ml:4351-4410) of up to 64 positions from the
-    //      look-ahead's verdicts, when the literal run above stopped at a match.  Every position
-    //      evaluates, as if it were reached with prev_length 2, its own lazy chain: a match at p is
-    //      deferred while the next position's match is strictly longer (full chain below
-    //      good_length, quartered from there on, no search from max_lazy on), and is emitted when
-    //      it is not.  The path from s0 through these chains is then walked and emitted.
-    if (ds.zs.trivial && (ds.zs.trivial == 2 || short_step)) {
-      const uint32_t s0 = ds.zs.strstart, la = ds.zs.lookahead, base = ds.zs.base;
-      uint32_t qw = ds.zs.qw;
-      const uint32_t qavail = (uint32_t)qcap - (qw - ds.zs.qr);
-      // positions that may be evaluated: prepared with room for a full match behind them
-      // (insert_string of lib/de.ml:4386-4391 stays inside the ring) and MIN_LOOKAHEAD ahead
-      uint32_t E = la >= (uint32_t)MIN_LOOKAHEAD ? s0 + la - MIN_LOOKAHEAD + 1 : s0;
-      if (pe < p_end) {
-        const uint32_t lim = pe > 260 ? pe - 260 : 0;
-        if (E > lim) E = lim;
-      } else if (E > pe) E = pe;
-      __syncthreads();
-      {
-        // what the look-ahead knows about positions s0 .. s0 + 79: lane -> position s0 + lane, lanes 0 .. 15 also
-        // s0 + 64 + lane; the four loads of match results are issued before anything waits for them (no branch around
-        // them: a position without a match reads its cell and drops it)
-        const uint32_t q0 = s0 + lane, q1 = s0 + 64 + (lane & 15);
-        const uint32_t g0 = q0 < slot_len ? q0 : slot_len - 1, g1 = q1 < slot_len ? q1 : slot_len - 1;
-        const uint32_t ma0 = g_ld(ws.m + g0), mb0 = g_ld(ws.mq + g0), ma1 = g_ld(ws.m + g1), mb1 = g_ld(ws.mq + g1);
-        auto fill = [&](uint32_t j, uint32_t q, uint32_t a, uint32_t b) {
-          const uint32_t r = q & (RING - 1);
-          uint32_t k = 0, lf = 2, df = 0, lq = 2, dq = 0;
-          if (q < E) {
-            const uint32_t f = ds.flg[r], l1v = ds.hl[r], c1v = l1v ? q - l1v : 0u;
-            if (f == FL_ENDED || f == FL_MATCH) k = 1;
-            if (c1v > base && q - c1v <= (uint32_t)MAX_DIST) k |= 2;
-            if (f == FL_MATCH) {
-              lf = a >> 16;
-              df = a & 0xffff;
-              lq = b >> 16;
-              dq = b & 0xffff;
-            }
-          }
-          ds.pm_k[j] = (uint8_t)k;
-          ds.pm_lf[j] = (uint16_t)lf;
-          ds.pm_df[j] = (uint16_t)df;
-          ds.pm_lq[j] = (uint16_t)lq;
-          ds.pm_dq[j] = (uint16_t)dq;
-        };
-        fill(lane, q0, ma0, mb0);
-        if (lane < 16) fill(64 + lane, q1, ma1, mb1);
-      }
-      __syncthreads();
-      // the lazy chain that starts at window position `lane`
-      const uint32_t lv_max_lazy = c_levels[eff_level][1], lv_good = c_levels[eff_level][2];
-      uint32_t typ = 2, ck = 0, cl = 0, cd = 0;  // typ 0 literal, 1 match chain, 2 unknown
-      {
-        const uint32_t k0 = ds.pm_k[lane];
-        if (k0 & 1) {
-          uint32_t L = (k0 & 2) ? ds.pm_lf[lane] : 2u, d = ds.pm_df[lane];
-          if (L == (uint32_t)MIN_MATCH && d > (uint32_t)TOO_FAR) L = 2;  // lib/de.ml:4363-4367
-          if (L < (uint32_t)MIN_MATCH) typ = 0;
-          else {
-            uint32_t t = lane + 1;
-            typ = 1;
-            for (;;) {
-              if (t >= 80 || !(ds.pm_k[t] & 1)) {
-                typ = 2;
-                break;
-              }
-              if (L >= lv_max_lazy) break;  // prev_length >= max_lazy: no search
-              const bool quart = L >= lv_good;
-              const uint32_t m = (ds.pm_k[t] & 2) ? (quart ? ds.pm_lq[t] : ds.pm_lf[t]) : 2u;
-              if (m <= L) break;
-              d = quart ? ds.pm_dq[t] : ds.pm_df[t];
-              L = m;
-              t++;
-            }
-            ck = t - 1 - lane;  // positions lane .. t-2 become literals, the match sits at t-1
-            cl = L;
-            cd = d;
-          }
-        }
-      }
-      // ---- the path from s0 through these chains, and its commands, by the whole wave.  The matcher arrives at a
-      //      position, and leaves it for the next one (no match there: its literal waits, `pending`) or for the end of
-      //      the chain's match.  Which positions it arrives at is a walk along these jumps from position 0: six rounds
-      //      of pointer doubling (a position's jump and the set of arrivals from it, over 1, 2, 4 ... jumps).  An arrival
-      //      writes the literal that waited (the position before was an arrival without a match) and, at a chain, the
-      //      chain's literals and its match; a prefix sum of these counts places them in the queue, and the arrivals that
-      //      fit the queue (an arrival's commands all or none) are the ones that happen.  (It was one wave-uniform loop
-      //      turn per literal run and per chain, ~80 dependent instructions each: three quarters of a text stream's time.)
-      const uint32_t nxt1 = typ == 2 ? 64u : typ == 1 ? lane + ck + cl : lane + 1;  // (>= 64: out of the window)
-      uint64_t arr = typ == 2 ? 0ull : 1ull << lane;
-      {
-        uint32_t J = nxt1 < 64u ? nxt1 : 64u;
-#pragma unroll
-        for (int r = 0; r < 6; r++) {
-          const int from = (int)(J & 63u);
-          const uint32_t alo = (uint32_t)__shfl((int)(uint32_t)arr, from), ahi = (uint32_t)__shfl((int)(uint32_t)(arr >> 32), from);
-          const uint32_t jn = (uint32_t)__shfl((int)J, from);
-          if (J < 64u) {
-            arr |= ((uint64_t)ahi << 32) | alo;
-            J = jn;
-          }
-          if ((uint32_t)__builtin_amdgcn_readfirstlane((int)J) >= 64u) break;  // the walk from position 0 is complete
-        }
-      }
-      const uint64_t vis = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(arr >> 32)) << 32) |
-                           (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)arr);  // the arrivals from position 0
-      const uint32_t pending0 = ds.zs.trivial == 1 ? 1u : 0u;
-      const uint64_t waits = vis & __builtin_amdgcn_ballot_w64(typ == 0);  // arrivals that leave their literal waiting
-      const bool here = (vis >> lane) & 1;
-      const uint32_t pend_in = lane ? (uint32_t)((waits >> (lane - 1)) & 1) : pending0;
-      const uint32_t mine = here ? pend_in + (typ == 1 ? ck + 1 : 0u) : 0u;
-      const uint32_t upto = wave_incl_scan(mine);
-      const uint32_t cmax = qavail >= 3 ? qavail - 2 : 0;
-      const bool happens = here && upto <= cmax;
-      const uint64_t hm = __builtin_amdgcn_ballot_w64(happens);
-      uint32_t cur = 0, pending = pending0, cmds = 0;
-      if (hm) {
-        const int last = 63 - __builtin_clzll(hm);
-        cmds = (uint32_t)__builtin_amdgcn_readlane((int)upto, last);
-        cur = (uint32_t)__builtin_amdgcn_readlane((int)nxt1, last);
-        pending = (uint32_t)((waits >> last) & 1);
-        if (happens) {
-          uint32_t at = qw + upto - mine;
-          if (pend_in) {
-            const uint32_t byte = ds.byt[(s0 + lane - 1) & (RING - 1)];
-            ws.queue[at++ & ((uint32_t)qcap - 1)] = (int)byte;
-            atomicAdd(&ds.lits[byte], 1);
-          }
-          if (typ == 1) {
-            for (uint32_t j = 0; j < ck; j++) {
-              const uint32_t byte = ds.byt[(s0 + lane + j) & (RING - 1)];
-              ws.queue[at++ & ((uint32_t)qcap - 1)] = (int)byte;
-              atomicAdd(&ds.lits[byte], 1);
-            }
-            // emit_match, lib/de.ml:4236-4245
-            ws.queue[at & ((uint32_t)qcap - 1)] = (int)(((cl - 3) << 16) | (cd - 1) | Q_COPY);
-            atomicAdd(&ds.lits[257 + length_code_of((int)cl)], 1);
-            atomicAdd(&ds.dsts[distance_code(&ds, (int)(cd - 1))], 1);
-          }
-        }
-      }
-      if (lane == 0 && cur > 0) {
-        ds.zs.strstart = s0 + cur;
-        ds.zs.lookahead = la - cur;
-        ds.zs.qw = qw + cmds;
-        ds.zs.trivial = pending ? 1u : 2u;
-        ds.zs.bulked += cur;
-      }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-      __syncthreads();
-      pc[2] += cmds;
-    }
-    PROF_MARK(2)
-    // would the matcher hand straight back (lz_compress's two LZ_NEED exits)?  Then don't run it:
-    // its state machine is a long walk through divergent code even when it has nothing to do
-    if (ds.zs.trivial && ds.zs.bulked > 0) {
-      const uint32_t la = ds.zs.lookahead, s2 = ds.zs.strstart;
-      const uint32_t avail = (uint32_t)qcap - (ds.zs.qw - ds.zs.qr);
-      const bool need_ring = pe < p_end && s2 + 260 > pe;
-      const bool next_bulk = la > (uint32_t)MIN_LOOKAHEAD && s2 + 1 < pe && avail >= 8 &&
-                             ds.flg[s2 & (RING - 1)] != 0 && ds.flg[(s2 + 1) & (RING - 1)] != 0;
-      if (la >= (uint32_t)MIN_LOOKAHEAD && (need_ring || next_bulk)) {
-        __syncthreads();
-        if (lane == 0) {
-          ds.ctl[0] = s2;
-          ds.ctl[2] = pe;
-        }
-        __syncthreads();
-        continue;
-      }
-    }
+    pf.mark(1);
+    const bool short_step = literal_run(ws, ds, qcap, pe, lane, pf);
+    if (ds.zs.trivial && (ds.zs.trivial == 2 || short_step)) parse_step(ws, ds, qcap, eff_level, t.slot_len, pe, p_end, lane, pf);
+    pf.mark(2);
+    if (wave_goes_on(ds, qcap, pe, p_end, lane)) continue;
     if (lane == 0) {
       run.z.prepared_end = pe;
       if (ds.zs.trivial) {
@@ -1977,149 +2195,40 @@ __global__ __launch_bounds__(kWave, 4) void deflate_kernel(
       }
       // after a bulk run that made progress the wave gets another go before the matcher steps
       run.z.steps = (ds.zs.trivial && ds.zs.bulked > 0) ? 1 : 0;
-      const uint64_t q0 = prof ? wall_clock64() : 0;
-      int act = driver == DRV_SCRIPT ? script_step(&ds, &run, hist ? hist + (size_t)sid * (L_CODES + D_CODES) : nullptr, L_CODES + D_CODES)
-                                     : stream_step(&ds, &ws, &run, driver, dynamic);
-      const uint64_t q1 = prof ? wall_clock64() : 0;
-      if (prof) {
-        pq[0] += q0 - t_prev;
-        pq[1] += q1 - q0;
-      }
-      if (act == ACT_WRITE) {
-        Enc &e = run.e;
-        ds.w.hold = e.hold;
-        ds.w.bits = (uint32_t)e.bits;
-        ds.w.o_pos = e.o_pos;
-        ds.w.o_cap = e.o_cap;
-        ds.w.qr = e.qr;
-        ds.w.qw = e.qw;
-        ds.w.qc = e.qc;
-        ds.w.kind = (uint32_t)e.kind;
-        ds.w.last = (uint32_t)e.last;
-        ds.w.overflow = 0;
-        ds.w.o = e.o;
-        ds.w.q = e.q;
-        ds.w.hdr = e.hdr ? 1u : 0u;
-        e.hdr = false;
-      }
-      if (act == ACT_TREES) ds.ctl[4] = (uint32_t)run.mode;
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");  // chain links / queue commands have landed
-      ds.ctl[0] = run.z.strstart;
-      ds.ctl[1] = act == ACT_DONE ? 1 : act == ACT_AWAIT ? 2 : 0;
-      ds.ctl[2] = pe;
-      ds.ctl[3] = (uint32_t)act;
-      ds.zs.strstart = run.z.strstart;
-      ds.zs.lookahead = (uint32_t)run.z.lookahead;
-      ds.zs.base = run.z.base;
-      ds.zs.qw = run.e.qw;
-      ds.zs.qr = run.e.qr;
-      ds.zs.bulked = 0;
-      ds.zs.trivial = (act == ACT_PREP && run.z.level != 0 && run.z.match_length == MIN_MATCH - 1 &&
-                       run.phase == PH_LZ)
-                          ? (run.z.match_available ? 1u : 2u)
-                          : 0u;
-      if (prof) pq[2] += wall_clock64() - q1;
+      pf.step_begin();
+      const int act = a.driver == DRV_SCRIPT ? script_step(&ds, &run, a.hist ? a.hist + (size_t)t.sid * (L_CODES + D_CODES) : nullptr,
+                                                           L_CODES + D_CODES)
+                                             : stream_step(&ds, &ws, &run, a.driver, a.dynamic);
+      pf.step_end();
+      lane0_publish(ds, run, act, pe);
+      pf.published();
     }
     __syncthreads();
-    if (prof) {  // lane-0 turn time by the action it ended with
-      const uint64_t t_now = wall_clock64(), dt = t_now - t_prev;
-      const uint32_t a = ds.ctl[3] & 3;
-      pa[a] += dt;
-      pn[a]++;
-      if (dt > pmax) pmax = dt;
-    }
-    PROF_MARK(3)
-    pc[3]++;
+    pf.turn(ds.ctl[3]);
+    pf.mark(3);
+    pf.count(3, 1);
     if (ds.ctl[3] == ACT_WRITE) {
       enc_write_wave(&ds, lane);
       __syncthreads();
-      PROF_MARK(4)
+      pf.mark(4);
     } else if (ds.ctl[3] == ACT_TREES) {
       trees_wave<PROF>(&ds, (int)ds.ctl[4], lane);
       if (lane == 0) ds.ring_dead = 1;
       __syncthreads();
-      PROF_MARK(5)
+      pf.mark(5);
     }
   }
-  if (prof && lane == 0) {
-    for (int i = 0; i < 6; i++) dbg[i] = pt[i];
-    for (int i = 0; i < 4; i++) dbg[8 + i] = pc[i];
-    for (int i = 0; i < 4; i++) {
-      dbg[16 + i] = pa[i];
-      dbg[20 + i] = pn[i];
+  pf.write(a.dbg, ds, run.z, lane);
+  if (a.driver == DRV_LZ77) {  // the commands are out; De.Lz77.literals / distances (lib/de.mli:464-470) for the caller
+    if (a.hist) {
+      uint32_t *hist = a.hist + (size_t)t.sid * (L_CODES + D_CODES);
+      for (uint32_t i = lane; i < (uint32_t)L_CODES; i += kWave) hist[i] = (uint32_t)ds.lits[i];
+      if (lane < (uint32_t)D_CODES) hist[L_CODES + lane] = (uint32_t)ds.dsts[lane];
     }
-    dbg[24] = pmax;
-    for (int i = 0; i < 4; i++) dbg[28 + i] = ((uint64_t)ds.tp[2 * i + 1] << 32) | ds.tp[2 * i];
-    for (int i = 0; i < 3; i++) dbg[25 + i] = pq[i];
-    dbg[12] = run.z.n_steps;
-    dbg[13] = run.z.n_lm;
-    dbg[14] = run.z.n_chain;
-  }
-#undef PROF_MARK
-  if (driver == DRV_LZ77) {  // the commands are out; De.Lz77.literals / distances (lib/de.mli:464-470) for the caller
-    if (hist) {
-      for (uint32_t i = lane; i < (uint32_t)L_CODES; i += kWave) hist[(size_t)sid * (L_CODES + D_CODES) + i] = (uint32_t)ds.lits[i];
-      if (lane < (uint32_t)D_CODES) hist[(size_t)sid * (L_CODES + D_CODES) + L_CODES + lane] = (uint32_t)ds.dsts[lane];
-    }
-    if (lane == 0) {
-      const bool ok = room && !run.e.overflow;
-      out_len[sid] = room ? 4ull * run.ncmd : 0;  // on overflow: the size the caller needs (mdeflate.h)
-      status[sid] = ok ? MD_OK : MD_UNEXPECTED_END_OF_OUTPUT;
-      if (checksum) checksum[sid] = adler;
-    }
-    return;
-  }
-  if (piece && ds.ctl[1] == 2) {  // the matcher waits for input the piece does not hold: the state goes out, nothing else
-    uint32_t *st = reinterpret_cast<uint32_t *>(pcs.state + sslot * kPieceState);
-    __syncthreads();
-    for (uint32_t i = lane; i < sizeof(DS) / 4; i += kWave) st[i] = reinterpret_cast<const uint32_t *>(&ds)[i];
-    for (uint32_t i = lane; i < sizeof(Run) / 4; i += kWave) st[sizeof(DS) / 4 + i] = reinterpret_cast<const uint32_t *>(&run)[i];
-    if (lane == 0) {
-      st[(sizeof(DS) + sizeof(Run)) / 4] = adler;
-      out_len[sid] = hdr + run.e.o_pos;
-      status[sid] = run.e.overflow ? MD_UNEXPECTED_END_OF_OUTPUT : MD_PIECE_AWAIT;
-      if (checksum) checksum[sid] = adler;
-    }
-    return;
-  }
-  if (lane == 0) {
-    uint32_t body = room ? run.e.o_pos : 0;
-    int st = !room || run.e.overflow ? MD_UNEXPECTED_END_OF_OUTPUT : MD_OK;
-    if (room && run.qfull) st = MD_QUEUE_FULL;
-    if (driver == DRV_SCRIPT) {
-      if (room && run.sc_bad) st = MD_E_INVALID_ARGUMENT;
-      if (hist) hist[(size_t)sid * (L_CODES + D_CODES)] = room ? run.sc_nrc : 0u;
-    }
-    uint32_t total = hdr + body;
-    if (format == MD_FORMAT_ZLIB && st == MD_OK) {
-      if (cap - total < 4) st = MD_UNEXPECTED_END_OF_OUTPUT;
-      else {
-        dst[total] = (uint8_t)(adler >> 24);
-        dst[total + 1] = (uint8_t)(adler >> 16);
-        dst[total + 2] = (uint8_t)(adler >> 8);
-        dst[total + 3] = (uint8_t)adler;
-        total += 4;
-      }
-    }
-    uint32_t sum = adler;
-    if (format == MD_FORMAT_GZIP) {
-      sum = piece ? adler : gz_crc[sid];  // (in pieces: the host's running CRC-32)
-      if (st == MD_OK) {
-        // Gz.Def checksum (lib/gz.ml:715-722): CRC-32, then the input size mod 2^32, little-endian
-        if (cap - total < 8) st = MD_UNEXPECTED_END_OF_OUTPUT;
-        else {
-          for (int k = 0; k < 4; k++) {
-            dst[total + k] = (uint8_t)(sum >> (8 * k));
-            dst[total + 4 + k] = (uint8_t)(isize >> (8 * k));
-          }
-          total += 8;
-        }
-      }
-    }
-    out_len[sid] = st == MD_OK ? total : 0;
-    status[sid] = st;
-    if (checksum) checksum[sid] = sum;
-  }
+    // on overflow: the size the caller needs (mdeflate.h)
+    if (lane == 0) report(a, t.sid, room ? 4ull * run.ncmd : 0, room && !run.e.overflow ? MD_OK : MD_UNEXPECTED_END_OF_OUTPUT, run.adler);
+  } else if (t.piece && ds.ctl[1] == 2) piece_suspend(a, t, ds, run, hdr, lane);
+  else if (lane == 0) frame_trailer(a, t, run, hdr, room);
 }
 
 }  // namespace defl
@@ -2127,32 +2236,18 @@ __global__ __launch_bounds__(kWave, 4) void deflate_kernel(
 
 extern "C" size_t md_deflate_queue_bytes(uint32_t n, int qcap) { return (size_t)n * (size_t)qcap * 4; }
 
-// fr: the front workspace of this batch, filled by md_launch_deflate_plan + md_launch_deflate_front
-extern "C" int md_launch_deflate(int format, int level, int qcap, int driver, int dynamic, uint32_t n,
-                                 const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len,
-                                 uint8_t *out, const uint64_t *out_off, const uint64_t *out_cap,
-                                 uint64_t *out_len, int32_t *status, uint32_t *checksum, const md::defl::Front *fr,
-                                 void *queue_ws, uint64_t *dbg, const uint8_t *gz_hdr, uint32_t gz_hdr_len,
-                                 const uint32_t *gz_crc, int matcher, uint32_t *hist, const uint32_t *order,
-                                 const md::defl::Piece *pieces, hipStream_t stream) {
-  if (n == 0) return 0;
-  if (dbg) order = nullptr;  // (the profile is stream 0's)
-  const md::defl::Piece pcs = pieces ? *pieces : md::defl::Piece{};
-  if (dbg)
-    hipLaunchKernelGGL(md::defl::deflate_kernel<true>, dim3(n), dim3(md::defl::kWave), 0, stream, format, level,
-                       qcap, driver, dynamic, n, in, in_off, in_len, out, out_off, out_cap, out_len, status,
-                       checksum, *fr, (int *)queue_ws, dbg, gz_hdr, gz_hdr_len, gz_crc, matcher, hist, order, pcs);
-  else
-    hipLaunchKernelGGL(md::defl::deflate_kernel<false>, dim3(n), dim3(md::defl::kWave), 0, stream, format, level,
-                       qcap, driver, dynamic, n, in, in_off, in_len, out, out_off, out_cap, out_len, status,
-                       checksum, *fr, (int *)queue_ws, dbg, gz_hdr, gz_hdr_len, gz_crc, matcher, hist, order, pcs);
+extern "C" int md_launch_deflate(const md::defl::SeqArgs *args, hipStream_t stream) {
+  if (args->n == 0) return 0;
+  md::defl::SeqArgs a = *args;
+  if (a.dbg) a.order = nullptr;  // (the profile is stream 0's)
+  const auto kernel = a.dbg ? md::defl::deflate_kernel<true> : md::defl::deflate_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3(a.n), dim3(md::defl::kWave), 0, stream, a);
   return (int)hipGetLastError();
 }
 
 // max_chain / nice_length of the level the matcher runs at (lib/de.ml:4030-4049) for the front kernels
 extern "C" void md_deflate_level_params(int driver, int matcher, int level, uint32_t *max_chain, uint32_t *nice) {
-  static const uint16_t lv[10][2] = {{0, 0}, {4, 8}, {8, 16}, {32, 32}, {16, 16}, {32, 32}, {128, 128}, {256, 128}, {1024, 258}, {4096, 258}};
-  int eff = driver == 1 ? 4 : (matcher == MD_MATCHER_LZ && level < 4) ? 4 : level;
-  *max_chain = lv[eff][0];
-  *nice = lv[eff][1];
+  const uint32_t eff = md::defl::effective_level(driver, matcher, level);
+  *max_chain = md::defl::h_levels[eff][md::defl::LV_MAX_CHAIN];
+  *nice = md::defl::h_levels[eff][md::defl::LV_NICE_LENGTH];
 }

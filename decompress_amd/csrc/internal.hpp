@@ -57,6 +57,36 @@ struct Piece {
 };
 constexpr uint32_t kPieceState = 12288;
 
+// Who drives the encoder (mdeflate.h MD_DRIVER_* are the first three; the rest are the library's own)
+enum { DRV_ZL = 0, DRV_HIGHER = 1, DRV_CLI = 2,
+       DRV_LZ77 = 3,     // De.Lz77.compress alone: the queue fills are written out as commands (md_de_lz77_compress)
+       DRV_ENCODE = 4,   // De.Def.encode alone: the input IS the command list of one last block (md_de_def_encode)
+       DRV_SCRIPT = 5,   // De.Def.encode driven step by step: the input is a list of operations (md_de_def_run)
+       DRV_NS = 6 };     // De.Def.Ns: only the front kernels know it (deflate_ns.hip has the rest)
+
+// What one launch of the sequential kernel (deflate_kernel.hip) takes: md_launch_deflate's argument, the kernel's too.
+struct SeqArgs {
+  int format, level, qcap, driver, dynamic, matcher;  // the mode of the whole batch
+  uint32_t n;
+  // the batch descriptors (device arrays of n entries, the blobs they index)
+  const uint8_t *in;
+  const uint64_t *in_off, *in_len;
+  uint8_t *out;
+  const uint64_t *out_off, *out_cap;
+  uint64_t *out_len;
+  int32_t *status;
+  uint32_t *checksum;  // or null
+  Front fr;            // the front workspace of this batch, filled by md_launch_deflate_plan + md_launch_deflate_front
+  int *queue_ws;       // the command queues: qcap words per queue slot (md_deflate_queue_bytes)
+  uint64_t *dbg;       // 32 profile words of stream 0 (md_set_option "profile"), or null
+  const uint8_t *gz_hdr;  // MD_FORMAT_GZIP: the header every stream begins with, its length, the streams' CRC-32s
+  uint32_t gz_hdr_len;
+  const uint32_t *gz_crc;
+  uint32_t *hist;         // the partial drivers' second result (histograms / replies), or null
+  const uint32_t *order;  // launch order (longest first), or null for index order
+  Piece pcs;              // every pointer null: whole streams
+};
+
 }  // namespace defl
 
 namespace wv {
@@ -216,12 +246,7 @@ int md_launch_link_chunked(const uint8_t *in, const uint64_t *in_off, const uint
 // ---- deflate_kernel.hip ----
 size_t md_deflate_queue_bytes(uint32_t n, int qcap);
 void md_deflate_level_params(int driver, int matcher, int level, uint32_t *max_chain, uint32_t *nice);
-// pieces = null for whole streams
-int md_launch_deflate(int format, int level, int qcap, int driver, int dynamic, uint32_t n, const uint8_t *in, const uint64_t *in_off,
-                      const uint64_t *in_len, uint8_t *out, const uint64_t *out_off, const uint64_t *out_cap, uint64_t *out_len,
-                      int32_t *status, uint32_t *checksum, const md::defl::Front *fr, void *queue_ws, uint64_t *dbg,
-                      const uint8_t *gz_hdr, uint32_t gz_hdr_len, const uint32_t *gz_crc, int matcher, uint32_t *hist,
-                      const uint32_t *order, const md::defl::Piece *pieces, hipStream_t stream);
+int md_launch_deflate(const md::defl::SeqArgs *args, hipStream_t stream);
 
 // ---- deflate_ns.hip ----
 int md_launch_def_ns(int format, int level, uint32_t n, uint32_t nchunks_max, const uint8_t *in, const uint64_t *in_off,

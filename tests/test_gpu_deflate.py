@@ -661,6 +661,29 @@ def test_workspace_cap_and_release(eng):
     assert all(st == 0 and zlib.decompress(z) == b for b, (st, z, _) in zip(bufs, want))
 
 
+def test_profiled_kernel_same_bytes_and_consistent_counters(eng):
+    """The profiled instantiation of the deflate kernel (md_set_option "profile") against the plain one: the same bytes,
+    statuses and checksums, and a profile whose event counts hang together - every lane-0 turn is counted once as an
+    iteration (word 11) and once under the action it ended with (words 20..23).  Random bytes, then text: full 8 x 64
+    literal-run steps, lazy chains, several dynamic blocks and so several ring restarts after trees."""
+    import decompress_amd
+    from decompress_amd import workloads
+    bufs = [random.Random(70 + i).randbytes(65536) + workloads.text(80 + i, 65536) for i in range(3)]
+    eng.set_option("profile", 1)
+    try:
+        got = eng.deflate_many(bufs, fmt=decompress_amd.FORMAT_ZLIB, level=6, queue=4096)
+        p = eng.get_profile_raw()
+    finally:
+        eng.set_option("profile", 0)
+    want = eng.deflate_many(bufs, fmt=decompress_amd.FORMAT_ZLIB, level=6, queue=4096)
+    assert got == want
+    assert all(st == 0 and zlib.decompress(z) == b for b, (st, z, _) in zip(bufs, want))
+    print("profile words", p)
+    assert sum(p[20:24]) == p[11], p
+    for i in (8, 9, 10, 12, 13, 14):
+        assert p[i] != 0, (i, p)
+
+
 @pytest.mark.parametrize("cap_mib", [2, 8, 24])
 def test_batch_in_slices_of_positions(eng, oracle, cap_mib):
     """streams of every length around the slice boundaries (32 KiB multiples) through a capped workspace: zlib, gzip and
