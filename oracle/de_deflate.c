@@ -634,7 +634,7 @@ static void lz_eoi(lz_t *s) {
 static size_t g_src_piece = 0, g_src_first = 0;
 void orc_set_src_piece(size_t piece) { g_src_piece = piece; }
 /* ... with a FIRST piece of another size (0: like the others): what decides how far the window is written when
- * fill_window first slides it (lib/de.ml:4294-4312) - H7's door, tests/test_gpu_deflate.py::test_h7_window_written_short */
+ * fill_window first slides it (lib/de.ml:4294-4312) - H7's door; the tail heads themselves: tests/lz77_cases.py, families E and F */
 void orc_set_src_first_piece(size_t first) { g_src_first = first; }
 static void lz_await(lz_t *s) {
   if (s->i_len + 1 < s->n_total) {
