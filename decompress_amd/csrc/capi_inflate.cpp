@@ -47,8 +47,13 @@ int md_inflate_batch_device(md_ctx *ctx, int format, size_t n, const uint8_t *d_
   uint32_t *order = nullptr;
   const int orc = launch_order(ctx, n, kOrderFrom, &order);
   if (orc != MD_OK) return orc;
-  MD_LAUNCH_TRY(ctx, md_launch_inflate_wave(format, (uint32_t)n, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_consumed, d_status,
-                                            d_checksum, ctx->dbg.as<uint64_t>(), order, ctx->inflate_waves, nullptr, ctx->stream));
+  md::wv::InfArgs a{};
+  a.format = format, a.n = (uint32_t)n;
+  a.in = d_in, a.in_off = d_in_off, a.in_len = d_in_len;
+  a.out = d_out, a.out_off = d_out_off, a.out_cap = d_out_cap;
+  a.out_len = d_out_len, a.consumed = d_consumed, a.status = d_status, a.checksum = d_checksum;
+  a.dbg = ctx->dbg.as<uint64_t>(), a.order = order, a.waves = ctx->inflate_waves;
+  MD_LAUNCH_TRY(ctx, md_launch_inflate_wave(&a, ctx->stream));
   return MD_OK;
 }
 
@@ -189,9 +194,15 @@ int md_inflate_continue_batch_device(md_ctx *ctx, size_t n, const uint8_t *d_in,
   uint32_t *order = nullptr;
   const int orc = launch_order(ctx, n, kOrderFrom, &order);
   if (orc != MD_OK) return orc;
-  const md::wv::Cont cont{d_start_bit, d_hist_len, d_adler_in, d_resume_bits, d_resume_out, d_resume_adler, d_resume_last};
-  MD_LAUNCH_TRY(ctx, md_launch_inflate_wave(MD_FORMAT_DEFLATE, (uint32_t)n, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_consumed,
-                                            d_status, d_checksum, ctx->dbg.as<uint64_t>(), order, ctx->inflate_waves, &cont, ctx->stream));
+  md::wv::InfArgs a{};
+  a.format = MD_FORMAT_DEFLATE, a.n = (uint32_t)n;
+  a.in = d_in, a.in_off = d_in_off, a.in_len = d_in_len;
+  a.out = d_out, a.out_off = d_out_off, a.out_cap = d_out_cap;
+  a.out_len = d_out_len, a.consumed = d_consumed, a.status = d_status, a.checksum = d_checksum;
+  a.dbg = ctx->dbg.as<uint64_t>(), a.order = order, a.waves = ctx->inflate_waves;
+  a.cont.start_bit = d_start_bit, a.cont.hist_len = d_hist_len, a.cont.adler_in = d_adler_in;
+  a.cont.resume_bits = d_resume_bits, a.cont.resume_out = d_resume_out, a.cont.resume_adler = d_resume_adler, a.cont.resume_last = d_resume_last;
+  MD_LAUNCH_TRY(ctx, md_launch_inflate_wave(&a, ctx->stream));
   return MD_OK;
 }
 
@@ -238,9 +249,15 @@ int inflate_piece(md_ctx *ctx, const uint8_t *src, size_t src_len, unsigned star
   if (hist_len) HIP_TRY(ctx, hipMemcpyAsync(dout.p, hist, hist_len, hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipMemcpyAsync(d64, h64, sizeof h64, hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipMemcpyAsync(d32, h32, sizeof h32, hipMemcpyHostToDevice, st));
-  const md::wv::Cont cont{d32 + 2, d32 + 3, d32 + 4, d64 + 6, d64 + 7, d32 + 5, d32 + 6};
-  MD_LAUNCH_TRY(ctx, md_launch_inflate_wave(MD_FORMAT_DEFLATE, 1, (const uint8_t *)din.p, d64 + 0, d64 + 1, (uint8_t *)dout.p, d64 + 2, d64 + 3, d64 + 4,
-                                            d64 + 5, (int32_t *)d32, d32 + 1, nullptr, nullptr, ctx->inflate_waves, &cont, st));
+  md::wv::InfArgs a{};  // (no profile, index order)
+  a.format = MD_FORMAT_DEFLATE, a.n = 1;
+  a.in = (const uint8_t *)din.p, a.in_off = d64 + 0, a.in_len = d64 + 1;
+  a.out = (uint8_t *)dout.p, a.out_off = d64 + 2, a.out_cap = d64 + 3;
+  a.out_len = d64 + 4, a.consumed = d64 + 5, a.status = (int32_t *)d32, a.checksum = d32 + 1;
+  a.waves = ctx->inflate_waves;
+  a.cont.start_bit = d32 + 2, a.cont.hist_len = d32 + 3, a.cont.adler_in = d32 + 4;
+  a.cont.resume_bits = d64 + 6, a.cont.resume_out = d64 + 7, a.cont.resume_adler = d32 + 5, a.cont.resume_last = d32 + 6;
+  MD_LAUNCH_TRY(ctx, md_launch_inflate_wave(&a, st));
   HIP_TRY(ctx, hipMemcpyAsync(h64, d64, sizeof h64, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipMemcpyAsync(h32, d32, sizeof h32, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));

@@ -12,8 +12,9 @@ namespace wv {
 
 // ---- the size query: md_inflate_sizes_batch_* ----------------------------------------------------
 // inflate_count_kernel walks a stream like the decoder and produces nothing: one wavefront per stream, no copier, no
-// staging buffer, no records, no checksum.  A round is 64 zones of S bits: the speculative pass, the counting passes and
-// the consistent prefix of lanes, exactly as in inflate_block.  Then
+// staging buffer, no records, no checksum.  The stream's opening and its block loop are the decoder's (open_stream,
+// block_loop in inflate_wave_core.hpp; CountBlocks below is this kernel's side of it), and so is a round: 64 zones of S
+// bits through sync_round - the speculative pass, the counting passes and the consistent prefix of lanes.  Then
 //   plain    (the input ends beyond the window, the output position is past 32 KiB, no accepted lane ran into a STOP
 //            entry) nothing else can fail: the lanes' byte counts are summed and the round is over - no second walk;
 //   checked  (the first 32 KiB of output, the tail of the input, a STOP entry) one walk over the accepted lanes with
@@ -97,59 +98,31 @@ __device__ __forceinline__ int count_block(lds_smem *sm, const uint8_t *__restri
   lds_u32 *win = (lds_u32 *)sm->win;
   const lds_u32 *lut = (const lds_u32 *)sm->lut;
   const uint32_t total_bits = body_len * 8;
-  constexpr uint32_t passes = S * PASSES >= PASS_BITS ? PASSES : PASS_BITS / S > PASSES_MAX ? PASSES_MAX : PASS_BITS / S;
-  constexpr uint32_t runin_ = (S * RUNIN_NUM) / RUNIN_DEN;
   for (;;) {
     const uint32_t base = (bp >> 5) << 2;
     wnd.ensure(win, body, body_len, base, lane);
     const uint32_t rbp = bp - base * 8, tot = total_bits - base * 8;  // window-relative
-    uint32_t start = rbp + lane * S, end = 0, stop = 0, nb = 0;
-    const uint32_t limit = rbp + (lane + 1) * S;
-    const uint32_t runin = runin_ < lane * S ? runin_ : lane * S;
-    bool counted = false;
-    sync_pass<false, BUDGET>(win, lut, lroot, true, start - runin, limit, end, stop, nb);
-    uint32_t np = 1;
-    for (uint32_t it = 0; it < passes; it++) {
-      const uint32_t pe = wave_shr1(end), ps = wave_shr1(stop);
-      const bool redo = lane == 0 ? !counted : (ps == 0 && (pe != start || !counted));
-      if (__ballot(redo) == 0) break;
-      if (redo && lane > 0) start = pe;
-      np++;
-      sync_pass<true, BUDGET>(win, lut, lroot, redo, start, limit, end, stop, nb);
-      counted = counted || redo;
-    }
-    uint32_t nvalid;
-    {
-      const uint32_t pe = wave_shr1(end), ps = wave_shr1(stop);
-      const uint64_t bad = __ballot(!counted || (lane > 0 && (ps != 0 || pe != start)));
-      nvalid = bad ? (uint32_t)__builtin_ctzll(bad) : 64;  // lane 0 is always counted: nvalid >= 1
-    }
-    const bool mine = lane < nvalid;
-    const uint32_t mybytes = mine ? nb & (kCountMatch - 1) : 0u;  // (a lane's own count fits; the matches are not needed)
-    const bool plain = tot >= rbp + kWave * S + 64 && pos >= 32768u && rdlane(stop, nvalid - 1) == 0;
+    const SyncRound r = sync_round<BUDGET, false>(win, lut, lroot, lane, rbp, S, g_count_pf);  // (S: passes and run-in are constants)
+    const bool mine = lane < r.nvalid;
+    const uint32_t mybytes = mine ? r.nb & (kCountMatch - 1) : 0u;  // (a lane's own count fits; the matches are not needed)
+    const bool plain = tot >= rbp + kWave * S + 64 && pos >= 32768u && rdlane(r.stop, r.nvalid - 1) == 0;
     uint32_t total, lstop = 0, nbp;
     if (plain) {
       total = wave_sum(mybytes);
-      nbp = base * 8 + rdlane(end, nvalid - 1);
+      nbp = base * 8 + rdlane(r.end, r.nvalid - 1);
     } else {
       const uint32_t boff = wave_excl_scan(mybytes, lane);
       const uint32_t ps32 = pos < 32768u ? (uint32_t)pos : 32768u;
       LaneOut lo;
-      lo.endp = end, lo.stopc = 0, lo.bytes = 0, lo.nm = 0;
-      check_pass<BUDGET>(win, lut, lroot, tot, mine, start, limit, ps32 + boff < 32768u ? ps32 + boff : 32768u, lo);
-      const uint64_t fm = __ballot(mine && lo.stopc != 0);  // the first stopped lane (stream order) ends the round
-      if (fm) {
-        const uint32_t fl = __builtin_ctzll(fm);
-        lstop = rdlane(lo.stopc, fl);
-        total = rdlane(boff, fl) + rdlane(lo.bytes, fl);
-        nvalid = fl + 1;
-      } else {
-        total = wave_sum(mine ? lo.bytes : 0u);
-      }
-      nbp = base * 8 + rdlane(lo.endp, nvalid - 1);
+      lo.endp = r.end, lo.stopc = 0, lo.bytes = 0, lo.nm = 0;
+      check_pass<BUDGET>(win, lut, lroot, tot, mine, r.start, r.limit, ps32 + boff < 32768u ? ps32 + boff : 32768u, lo);
+      const Verdict v = round_verdict(mine, lo, boff, 0, r.nvalid, wave_sum(mine ? lo.bytes : 0u), 0);
+      lstop = v.lstop;
+      total = v.total;
+      nbp = base * 8 + rdlane(lo.endp, v.nvalid - 1);
     }
     cc.rounds++;  // (wave-uniform: three scalar additions a round)
-    cc.passes += np;
+    cc.passes += r.np;
     cc.checked += plain ? 0u : 1u;
     wnd.fetch(body, body_len, (nbp >> 5) << 2, lane);  // the next round's (or the next block header's) window: on its way
     if (nbp == bp && (lstop == 0 || lstop == kStTrunc)) {
@@ -167,6 +140,39 @@ __device__ __forceinline__ int count_block(lds_smem *sm, const uint8_t *__restri
   return MD_OK;
 }
 
+// The size query's side of block_loop (inflate_wave_core.hpp): a stored block is arithmetic, a Huffman block is counted.
+struct CountBlocks {
+  lds_smem *sm;
+  MD_LDS uint32_t *hout;  // CountSmem::hout
+  const uint8_t *body;
+  uint32_t body_len, lane;
+  Window &wnd;
+  uint64_t pos;  // bytes so far
+  CountProf cc;
+  __device__ __forceinline__ int stored(uint32_t, uint32_t len) {
+    pos += len;
+    return MD_OK;
+  }
+  __device__ __forceinline__ void fixed(uint32_t &lroot) {
+    fixed_tables(sm, lane, (uint32_t *)&hout[0]);
+    lroot = hout[0];
+  }
+  __device__ __forceinline__ int dynamic(uint32_t rbp, uint32_t tot, uint32_t &hend, uint32_t &lroot) {
+    const int rc = dynamic_tables(sm, rbp, tot, lane, (uint32_t *)&hout[1], (uint32_t *)&hout[0], g_count_pf);
+    if (rc == MD_OK) {
+      lroot = hout[0];
+      hend = uni(hout[1]);
+    }
+    return rc;
+  }
+  __device__ __forceinline__ void header_done() {}
+  template <bool BUDGET>
+  __device__ __forceinline__ int huffman(uint32_t lroot, uint32_t &bp) {
+    return count_block<BUDGET>(sm, body, body_len, pos, lroot, lane, &bp, wnd, cc);
+  }
+  __device__ __forceinline__ void block_done(int &, uint32_t, bool) {}
+};
+
 template <bool PROF>
 __global__ __launch_bounds__(kWave, 5) void inflate_count_kernel(int format, uint32_t n, const uint8_t *__restrict__ in,
                                                                  const uint64_t *__restrict__ in_off,
@@ -180,8 +186,8 @@ __global__ __launch_bounds__(kWave, 5) void inflate_count_kernel(int format, uin
   if (blockIdx.x >= n) return;
   const uint32_t sid = order ? order[blockIdx.x] : blockIdx.x;
   const uint8_t *src = in + in_off[sid];
-  const uint64_t slen64 = in_len[sid];
-  if (slen64 > MD_MAX_INFLATE_IN) {  // as the decoder
+  const Opened o = open_stream(format, src, in_len[sid]);
+  if (o.rc == MD_E_INVALID_ARGUMENT) {
     if (lane == 0) {
       out_len[sid] = 0;
       consumed[sid] = 0;
@@ -189,115 +195,15 @@ __global__ __launch_bounds__(kWave, 5) void inflate_count_kernel(int format, uin
     }
     return;
   }
-  const uint32_t slen = (uint32_t)slen64;
-  int rc = MD_OK;
-  uint32_t body_off = 0, body_len = slen;
-  if (format == MD_FORMAT_ZLIB) {  // the decoder's prologue
-    if (slen < 2) rc = MD_UNEXPECTED_END_OF_INPUT;
-    else {
-      uint32_t cmf = src[0], flg = src[1];
-      if (((cmf << 8) + flg) % 31 != 0 || (cmf & 0xf) != 8) rc = MD_INVALID_HEADER;
-      else if (slen < 6) rc = MD_UNEXPECTED_END_OF_INPUT;
-      else {
-        body_off = 2;
-        body_len = slen - 6;
-      }
-    }
-  }
-  const uint8_t *body = src + body_off;
   if (lane < 4) sm->lut[kStopEobI + lane] = mk_entry(0, 0, 0, 0, kStopEobI + (lane & 2));  // the self-looping STOP entries
-  lds_u32 *win = (lds_u32 *)sm->win;
-  const uint32_t total_bits = body_len * 8;
-  uint64_t pos = 0;
   uint32_t bp = 0;
-  uint32_t fixed_lroot = 0;
-  CountProf cc = {0, 0, 0};
   Window wnd;
   wnd.base = 0xffffffffu;
-  if (rc == MD_OK) {
-    bool last = false;
-    uint32_t lds_base = 0xffffffffu;
-    while (!last && rc == MD_OK) {  // the decoder's block loop
-      uint32_t base = (bp >> 5) << 2;
-      if (lds_base != 0xffffffffu && bp >= lds_base * 8 && bp - lds_base * 8 <= 4096) base = lds_base;
-      else {
-        wnd.ensure(win, body, body_len, base, lane);
-        lds_base = base;
-      }
-      uint32_t rbp = bp - base * 8;
-      const uint32_t tot = total_bits - base * 8;
-      if ((int32_t)(tot - rbp) < 3) {
-        rc = MD_UNEXPECTED_END_OF_INPUT;
-        break;
-      }
-      const uint32_t hdr = uni(peek(win, rbp));
-      last = hdr & 1;
-      const uint32_t type = (hdr >> 1) & 3;
-      bp += 3;
-      rbp += 3;
-      bool block_done = false;
-      if (type == 1) {  // a run of empty fixed blocks
-        for (;;) {
-          if (rbp + 7 > tot || rbp + 64 > WIN_WORDS * 32 - 64 || (uni(peek(win, rbp)) & 0x7fu) != 0) break;
-          rbp += 7;
-          bp += 7;
-          block_done = true;
-          if (last || rbp + 3 > tot) break;
-          const uint32_t h = uni(peek(win, rbp)) & 7u;
-          if (((h >> 1) & 3) != 1) break;
-          last = h & 1;
-          rbp += 3;
-          bp += 3;
-          block_done = false;
-        }
-      }
-      if (block_done) {
-        // nothing to count
-      } else if (type == 0) {  // a stored block is arithmetic
-        uint32_t p = (bp + 7) >> 3;
-        if (body_len - p < 4) {
-          rc = MD_UNEXPECTED_END_OF_INPUT;
-          break;
-        }
-        uint32_t h4;
-        if (p + 4 <= base + (WIN_WORDS - 2) * 4) h4 = uni(peek(win, (p - base) * 8));
-        else h4 = (uint32_t)body[p] | ((uint32_t)body[p + 1] << 8) | ((uint32_t)body[p + 2] << 16) | ((uint32_t)body[p + 3] << 24);
-        const uint32_t len = h4 & 0xffff, nlen = h4 >> 16;
-        p += 4;
-        if (nlen != 0xffff - len) rc = MD_INVALID_COMPLEMENT_OF_LENGTH;
-        else if (len > body_len - p) rc = MD_UNEXPECTED_END_OF_INPUT;
-        else {
-          pos += len;
-          p += len;
-          bp = p * 8;
-        }
-      } else if (type == 3) {
-        rc = MD_INVALID_KIND_OF_BLOCK;
-      } else {
-        uint32_t lroot = 0;
-        if (type == 1) {
-          if (fixed_lroot == 0) {
-            fixed_tables(sm, lane, &smem.hout[0]);
-            fixed_lroot = uni(smem.hout[0]);
-          }
-          lroot = fixed_lroot;
-        } else {
-          fixed_lroot = 0;
-          rc = dynamic_tables(sm, rbp, tot, lane, &smem.hout[1], &smem.hout[0], g_count_pf);
-          if (rc == MD_OK) {
-            lroot = smem.hout[0];
-            bp = base * 8 + uni(smem.hout[1]);
-          }
-        }
-        lroot = uni(lroot);
-        if (rc == MD_OK) {
-          if (lroot & kLoopy) rc = count_block<true>(sm, body, body_len, pos, lroot & 15, lane, &bp, wnd, cc);
-          else rc = count_block<false>(sm, body, body_len, pos, lroot, lane, &bp, wnd, cc);
-          lds_base = 0xffffffffu;
-        }
-      }
-    }
-  }
+  CountBlocks h = {sm, (MD_LDS uint32_t *)smem.hout, src + o.body_off, o.body_len, lane, wnd, 0, {0, 0, 0}};
+  int rc = o.rc;
+  if (rc == MD_OK) rc = block_loop(h, sm, h.body, h.body_len, lane, bp, wnd);
+  const uint64_t pos = h.pos;
+  const CountProf &cc = h.cc;
   uint32_t used = (bp + 7) >> 3;
   if (rc == MD_OK && format == MD_FORMAT_ZLIB) used += 6;  // (the Adler-32 is not compared: no byte was produced)
   if (rc == (int)kStUnbounded) rc = MD_UNEXPECTED_END_OF_OUTPUT;  // what every finite room gets

@@ -63,16 +63,6 @@
 namespace md {
 namespace wv {
 
-#ifdef MD_DEBUG_KNOWN_BOUNDS
-// Measurement build only (tools/dbg/build_known_bounds.sh): mode & 3 == 1 records what the sync
-// passes of every round found (start, end, stop, counts per lane), == 2 replays the record instead of walking - the
-// time of that launch is what a PERFECT sync would leave of the kernel.  mode & 4: the copier skips the matches (far and
-// near) and only flushes; mode & 8: the copier does nothing at all (the decoder's time alone).  Results are only right in
-// modes 0..2.
-constexpr uint32_t KB_ROUNDS = 512;
-__device__ uint4 *g_kb_buf;
-__device__ int g_kb_mode;
-#endif
 // ---- output -------------------------------------------------------------------------------------
 struct Sink {
   lds_u8 *stage;
@@ -134,6 +124,52 @@ struct Sink {
   }
 };
 
+// ---- the measurement build ------------------------------------------------------------------------
+// -DMD_DEBUG_KNOWN_BOUNDS only (tools/dbg/build_known_bounds.sh): mode & 3 == 1 records what the sync
+// passes of every round found (start, end, stop, counts per lane), == 2 replays the record instead of walking - the
+// time of that launch is what a PERFECT sync would leave of the kernel.  mode & 4: the copier skips the matches (far and
+// near) and only flushes; mode & 8: the copier does nothing at all (the decoder's time alone).  Results are only right in
+// modes 0..2.  The product build has the empty form: nothing of it is left in the kernel.
+#ifdef MD_DEBUG_KNOWN_BOUNDS
+constexpr uint32_t KB_ROUNDS = 512;
+__device__ uint4 *g_kb_buf;
+__device__ int g_kb_mode;
+struct KnownBounds {
+  uint32_t round, sid;
+  uint4 *slot;  // of the round at hand, or null: beyond the record
+  __device__ __forceinline__ void init(uint32_t stream) { round = 0, sid = stream; }
+  // called once a round, in front of the sync passes: true = r is the replayed record, they are not walked
+  __device__ __forceinline__ bool replay(SyncRound &r, uint32_t rbp, uint32_t zs, uint32_t lane) {
+    slot = round < KB_ROUNDS ? g_kb_buf + ((size_t)sid * KB_ROUNDS + round) * kWave + lane : nullptr;
+    round++;
+    if ((__builtin_amdgcn_readfirstlane(g_kb_mode) & 3) != 2 || !slot) return false;
+    const uint4 v = *slot;
+    r.start = v.x, r.end = v.y, r.stop = v.z & 0xffffu, r.counted = (v.z >> 16) != 0, r.nb = v.w;
+    r.limit = rbp + (lane + 1) * zs;
+    r.midp = 0xffffffffu, r.midcnt = 0, r.np = 0;
+    r.nvalid = consistent_prefix(r, lane);
+    return true;
+  }
+  __device__ __forceinline__ void record(const SyncRound &r) {
+    if ((__builtin_amdgcn_readfirstlane(g_kb_mode) & 3) == 1 && slot) *slot = make_uint4(r.start, r.end, r.stop | (r.counted ? 0x10000u : 0u), r.nb);
+  }
+  // the copier's ablations: true = the round has been dealt with
+  static __device__ __forceinline__ bool skip_copy(Sink &sk, uint32_t total) {
+    const int kbm = __builtin_amdgcn_readfirstlane(g_kb_mode);
+    if (kbm & 8) sk.pos += total;
+    else if (kbm & 4) sk.flush(total);
+    return (kbm & 12) != 0;
+  }
+};
+#else
+struct KnownBounds {
+  __device__ __forceinline__ void init(uint32_t) {}
+  __device__ __forceinline__ bool replay(SyncRound &, uint32_t, uint32_t, uint32_t) { return false; }
+  __device__ __forceinline__ void record(const SyncRound &) {}
+  static __device__ __forceinline__ bool skip_copy(Sink &, uint32_t) { return false; }
+};
+#endif
+
 // Far matches (the whole source is older than this round: final in HBM/L2 once the flush of earlier rounds has
 // been waited for; d >= ml) and the heads of matches that straddle the round start.  The round's records are taken
 // in stream order, one per lane and row of 64.  FIRST the loads of ALL rows are started - 2 LDS reads per record, one
@@ -157,9 +193,8 @@ __device__ __forceinline__ FarRow far_row(const lds_u32 *mrec, const lds_u16 *mp
   f.has = r < nrec;
   const uint32_t tk = mrec[f.has ? r : 0u];
   f.qs = mpos[f.has ? r : 0u];
-  const uint32_t d = (tk & 0x7fff) + 1;
-  f.ml = ((tk >> 16) & 0xff) + 3;
-  const uint32_t s = rb + f.qs - d;
+  f.ml = rec_len(tk);
+  const uint32_t s = rb + f.qs - rec_dist(tk);
   f.near = f.has && (tk & kNearBit);
   const uint32_t head = s < R0 ? R0 - s : 0u;  // a near match that begins before the round start: its head is final too
   f.n = !f.has ? 0u : f.near ? head : f.ml;
@@ -277,19 +312,11 @@ __device__ __noinline__ void copy_far_guarded(const lds_u32 *mrec, const lds_u16
   uint32_t nnear = 0;
   for (uint32_t c0 = 0; c0 < nrec; c0 += kWave) {
     const uint32_t r = c0 + lane;
-    const bool has = r < nrec;
-    const uint32_t tk = mrec[has ? r : 0u], qs = mpos[has ? r : 0u];
-    const uint32_t d = (tk & 0x7fff) + 1, ml = ((tk >> 16) & 0xff) + 3;
-    const uint32_t s = rb + qs - d;
-    const bool near = has && (tk & kNearBit);
-    uint32_t n = has ? ml : 0u;
-    const uint64_t nb = __ballot(near);
-    if (near) {
-      list[nnear + lane_rank(nb)] = (uint16_t)r;
-      n = s < R0 ? R0 - s : 0u;
-    }
+    const FarRow f = far_row(mrec, mpos, r, nrec, rb, R0);
+    const uint64_t nb = __ballot(f.near);
+    if (f.near) list[nnear + lane_rank(nb)] = (uint16_t)r;
     nnear += (uint32_t)__builtin_popcountll(nb);
-    for (uint32_t j = 0; j < n; j += 8) lds_put(stage + qs + j, out_ld_guard(g, s + j, n - j, cap), n - j < 8 ? n - j : 8);
+    for (uint32_t j = 0; j < f.n; j += 8) lds_put(stage + f.qs + j, out_ld_guard(g, f.src + j, f.n - j, cap), f.n - j < 8 ? f.n - j : 8);
   }
   *nnear_out = nnear;
 }
@@ -347,7 +374,7 @@ __device__ __forceinline__ void copy_near_all(const lds_u32 *mrec, const lds_u16
     bool todo = c0 + lane < count;
     const uint32_t e = todo ? list[c0 + lane] : 0u;
     const uint32_t tk = mrec[e], qs = mpos[e];
-    const uint32_t d = (tk & 0x7fff) + 1, ml = ((tk >> 16) & 0xff) + 3;
+    const uint32_t d = rec_dist(tk), ml = rec_len(tk);
     // source bytes: staging [qs - d, min(qs - d + ml, qs)); the part before the round start came from HBM (copy_far)
     const int32_t s0 = (int32_t)qs - (int32_t)d;
     const uint32_t skip = s0 < (int32_t)head ? head - (uint32_t)s0 : 0u;
@@ -412,19 +439,7 @@ __device__ __forceinline__ void copy_round(lds_smem *sm, Sink &sk, uint32_t lane
   lds_u16 *list = (lds_u16 *)sm->list;
   const uint32_t R0 = sk.pos, rb = sk.sbase();
   uint32_t nnear = 0;
-#ifdef MD_DEBUG_KNOWN_BOUNDS
-  {
-    const int kbm = __builtin_amdgcn_readfirstlane(g_kb_mode);
-    if (kbm & 8) {
-      sk.pos += total;
-      return;
-    }
-    if (kbm & 4) {
-      sk.flush(total);
-      return;
-    }
-  }
-#endif
+  if (KnownBounds::skip_copy(sk, total)) return;
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");  // earlier rounds' flushes have landed
   if (R0 + 40 > sk.cap) {
     copy_far_guarded<PF>(mrec, mpos, list, sk.stage, sk.g, R0, rb, sk.cap, lane, nrec, &nnear);
@@ -462,6 +477,154 @@ __device__ __forceinline__ void mail_post(lds_smem *sm, uint32_t lane, uint32_t 
   if (lane == 0) mail_st(&sm->mail.emitted, sent);
 }
 
+// kJobEmit (inflate_wave_core.hpp): the job lies in `list`, the copier's own array, idle between two rounds - every lane's
+// request, behind them the wave-uniform words; the lanes' results come back in the words of their requests.
+struct EmitHalf {  // the second half of a lane's zone
+  uint32_t start, limit;  // window bits (start 0xffffffff: nothing to do)
+  uint32_t q0, rec0;      // output position of its first byte, its first record
+};
+struct EmitUni {  // emit_pass's arguments that are the same for all lanes; checked: emit_pass<true>
+  uint32_t lroot, tot, rb, R0, cap, checked;
+};
+struct EmitJob {
+  union {
+    EmitHalf ask;
+    LaneOut got;
+  } lane[kWave];
+  EmitUni uni;
+};
+static_assert(offsetof(EmitJob, uni) == kHxUni * 4 && sizeof(EmitJob) == (kHxUni + 6) * 4, "the emit job's words in `list`");
+__device__ __forceinline__ MD_LDS EmitJob *emit_job(lds_smem *sm) { return reinterpret_cast<MD_LDS EmitJob *>(sm->list); }
+__device__ __forceinline__ void emit_ask(lds_smem *sm, uint32_t lane, const EmitHalf &h, const EmitUni &u) {
+  MD_LDS EmitJob *j = emit_job(sm);
+  j->lane[lane].ask.start = h.start, j->lane[lane].ask.limit = h.limit, j->lane[lane].ask.q0 = h.q0, j->lane[lane].ask.rec0 = h.rec0;
+  if (lane == 0) j->uni.lroot = u.lroot, j->uni.tot = u.tot, j->uni.rb = u.rb, j->uni.R0 = u.R0, j->uni.cap = u.cap, j->uni.checked = u.checked;
+}
+__device__ __forceinline__ void emit_asked(lds_smem *sm, uint32_t lane, EmitHalf &h, EmitUni &u) {
+  const MD_LDS EmitJob *j = emit_job(sm);
+  h.start = j->lane[lane].ask.start, h.limit = j->lane[lane].ask.limit, h.q0 = j->lane[lane].ask.q0, h.rec0 = j->lane[lane].ask.rec0;
+  u.lroot = uni(j->uni.lroot), u.tot = uni(j->uni.tot), u.rb = uni(j->uni.rb), u.R0 = uni(j->uni.R0), u.cap = uni(j->uni.cap);
+  u.checked = uni(j->uni.checked);
+}
+__device__ __forceinline__ void emit_reply(lds_smem *sm, uint32_t lane, const LaneOut &lo) {
+  MD_LDS EmitJob *j = emit_job(sm);
+  j->lane[lane].got.endp = lo.endp, j->lane[lane].got.stopc = lo.stopc, j->lane[lane].got.bytes = lo.bytes, j->lane[lane].got.nm = lo.nm;
+}
+__device__ __forceinline__ LaneOut emit_replied(lds_smem *sm, uint32_t lane) {
+  const MD_LDS EmitJob *j = emit_job(sm);
+  LaneOut lo;
+  lo.endp = j->lane[lane].got.endp, lo.stopc = j->lane[lane].got.stopc, lo.bytes = j->lane[lane].got.bytes, lo.nm = j->lane[lane].got.nm;
+  return lo;
+}
+// a lane's verdict: its first half's if that stopped, else its second half's (bq, br: what the first half produces)
+__device__ __forceinline__ LaneOut merge_halves(const LaneOut &a, const LaneOut &b, uint32_t bq, uint32_t br) {
+  if (a.stopc != 0) return a;
+  LaneOut lo;
+  lo.endp = b.endp;
+  lo.stopc = b.stopc;
+  lo.bytes = bq + b.bytes;
+  lo.nm = br + b.nm;
+  return lo;
+}
+
+// ---- the phases of a round (inflate_block) ---------------------------------------------------------
+// Staging and record capacity: of the consistent lanes, keep the largest prefix that fits (a lone first lane truncates
+// itself; its matches always fit).  Every kept lane then knows where its bytes and its records go.
+struct Prefix {
+  uint32_t nvalid;      // lanes kept
+  bool mine;            // this lane is one of them
+  uint32_t all;         // what they produce together: bytes | records << 20
+  uint32_t boff, roff;  // the bytes / records of the lanes before this one
+};
+template <class PF>
+__device__ __forceinline__ Prefix fit_prefix(const SyncRound &r, const Sink &sk, uint32_t lane, PF &pf) {
+  const uint32_t R0 = sk.pos, rb = sk.sbase();
+  Prefix p;
+  p.nvalid = r.nvalid;
+  uint32_t mynb = lane < p.nvalid ? r.nb : 0;  // bytes | matches << 20
+  const uint32_t off = wave_excl_scan(mynb, lane);
+  if (p.nvalid < 64) pf.count(C_END_CHAIN);
+  const uint32_t bend = ((off + mynb) & (kCountMatch - 1)), rend = (off + mynb) >> 20;
+  const uint64_t fits = __ballot((R0 - rb) + bend <= STAGE - 16 && rend <= RMAX);
+  const uint32_t nfit = fits == ~0ull ? 64 : (uint32_t)__builtin_ctzll(~fits);
+  if (nfit < p.nvalid) {
+    pf.count(rdlane(rend, nfit) > RMAX ? C_END_RECORDS : C_END_FIT);
+    p.nvalid = nfit ? nfit : 1;
+  }
+  p.mine = lane < p.nvalid;
+  if (!p.mine) mynb = 0;
+  p.all = rdlane(off + mynb, p.nvalid - 1);
+  p.boff = off & (kCountMatch - 1), p.roff = off >> 20;
+  return p;
+}
+
+// The emit pass over the kept lanes.  Two wavefronts, one round: the copier has nothing to do until the round is emitted,
+// so it emits the second half of every zone while this wavefront emits the first (the counting pass left the boundary in
+// the middle and what lies before it: the halves' output positions and records are known) - the emit pass is half as
+// long.  Small zones are not worth the hand-over.  False: the copier gave up.
+template <bool PAIR, bool BUDGET>
+__device__ __forceinline__ bool emit_round(lds_smem *sm, const Sink &sk, uint32_t lroot, uint32_t lane, uint32_t rbp, uint32_t tot,
+                                           uint32_t zs, const SyncRound &r, const Prefix &p, uint32_t &sent, LaneOut &lo) {
+  constexpr bool kSplit = PAIR && !BUDGET && MD_EMIT_SPLIT != 0;
+  const lds_u32 *win = (const lds_u32 *)sm->win;
+  const lds_u32 *lut = (const lds_u32 *)sm->lut;
+  lds_u32 *mrec = (lds_u32 *)sm->mrec;
+  lds_u16 *mpos = (lds_u16 *)sm->mpos;
+  const uint32_t R0 = sk.pos, rb = sk.sbase();
+  const uint32_t q0 = R0 + p.boff;
+  lo.endp = r.end;
+  lo.stopc = 0;
+  lo.bytes = 0;
+  lo.nm = 0;
+  bool split = false;
+  if constexpr (kSplit) split = zs >= 128;
+  const uint32_t all = p.all & (kCountMatch - 1);  // bytes the round will produce
+  const bool plain = tot >= rbp + kWave * zs + 64 && R0 >= 32768u && all <= sk.cap - R0 && (R0 - rb) + all <= STAGE - 16;
+  uint32_t alimit = r.limit;
+  bool gob = false;         // this lane's zone has a second half for the copier
+  uint32_t bq = 0, br = 0;  // the bytes | records before it, relative to the lane's
+  if constexpr (kSplit) {
+    if (split) {
+      gob = p.mine && r.midp != 0xffffffffu && r.midp < r.limit && r.midp >= r.start;
+      bq = r.midcnt & (kCountMatch - 1);
+      br = r.midcnt >> 20;
+      emit_ask(sm, lane, EmitHalf{gob ? r.midp : 0xffffffffu, r.limit, q0 + bq, p.roff + br},
+               EmitUni{lroot, tot, rb, R0, sk.cap, plain ? 0u : 1u});
+      mail_post(sm, lane, kJobEmit, 0, 0, sent);
+      alimit = gob ? r.midp : r.limit;
+    }
+  }
+  if (plain && !BUDGET) emit_pass<false, false>(win, lut, lroot, mrec, mpos, sk.stage, p.roff, tot, p.mine, r.start, alimit, q0, rb, R0, sk.cap, lo);
+  else emit_pass<true, BUDGET>(win, lut, lroot, mrec, mpos, sk.stage, p.roff, tot, p.mine, r.start, alimit, q0, rb, R0, sk.cap, lo);
+  if constexpr (kSplit) {
+    if (split) {
+      if (!mail_wait_idle(sm, sent)) return false;
+      if (gob) lo = merge_halves(lo, emit_replied(sm, lane), bq, br);
+    }
+  }
+  return true;
+}
+// the copier's half of it
+__device__ __forceinline__ void emit_second_halves(lds_smem *sm, const Sink &sk, uint32_t lane) {
+  EmitHalf h;
+  EmitUni u;
+  emit_asked(sm, lane, h, u);
+  const bool go = h.start != 0xffffffffu;
+  LaneOut lo;
+  lo.endp = h.start, lo.stopc = 0, lo.bytes = 0, lo.nm = 0;
+  const lds_u32 *win = (const lds_u32 *)sm->win;
+  const lds_u32 *lut = (const lds_u32 *)sm->lut;
+  if (u.checked) emit_pass<true, false>(win, lut, u.lroot, (lds_u32 *)sm->mrec, (lds_u16 *)sm->mpos, sk.stage, h.rec0, u.tot, go, go ? h.start : 0u, h.limit, h.q0, u.rb, u.R0, u.cap, lo);
+  else emit_pass<false, false>(win, lut, u.lroot, (lds_u32 *)sm->mrec, (lds_u16 *)sm->mpos, sk.stage, h.rec0, u.tot, go, go ? h.start : 0u, h.limit, h.q0, u.rb, u.R0, u.cap, lo);
+  emit_reply(sm, lane, lo);
+}
+
+// next round: 64 zones that fill about 7/8 of the staging buffer at this round's bytes-per-bit
+__device__ __forceinline__ uint32_t next_zone(uint32_t bits, uint32_t total) {
+  const uint64_t want = (uint64_t)(STAGE - STAGE / 8) * bits / ((uint64_t)kWave * (total ? total : 1u));
+  return want > S ? S : want < SMIN ? SMIN : (uint32_t)want;
+}
+
 // ---------------------------------------------------------------------------
 // All rounds of one Huffman block.  bp is a bit position of the body; on return *bp_io is the bit after the EOB.
 // PAIR: this wavefront only decodes — a round's records and literals go to the copier wavefront (copier_main), which
@@ -471,12 +634,10 @@ __device__ __forceinline__ void mail_post(lds_smem *sm, uint32_t lane, uint32_t 
 template <class PF, bool PAIR, bool BUDGET>
 __device__ __forceinline__ int inflate_block(lds_smem *sm, const uint8_t *__restrict__ body, uint32_t body_len, Sink &sk,
                                              uint32_t lroot, uint32_t lane, uint32_t *bp_io, uint32_t *zone_io, Window &wnd,
-                                             uint32_t &sent, PF &pf) {
+                                             KnownBounds &kb, uint32_t &sent, PF &pf) {
   uint32_t bp = *bp_io;
   lds_u32 *win = (lds_u32 *)sm->win;
   const lds_u32 *lut = (const lds_u32 *)sm->lut;
-  lds_u32 *mrec = (lds_u32 *)sm->mrec;
-  lds_u16 *mpos = (lds_u16 *)sm->mpos;
   const uint32_t total_bits = body_len * 8;
   uint32_t zs = *zone_io;  // zone size of this round (wave-uniform), adapted to the expansion of the last one
   constexpr bool kSplit = PAIR && !BUDGET && MD_EMIT_SPLIT != 0;
@@ -486,173 +647,39 @@ __device__ __forceinline__ int inflate_block(lds_smem *sm, const uint8_t *__rest
     const uint32_t rbp = bp - base * 8, tot = total_bits - base * 8;  // window-relative
     pf.tick(P_ENSURE);
     pf.count(C_ROUNDS);
-    pf.count(C_PASSES);
-    uint32_t start = rbp + lane * zs, end = 0, stop = 0, nb = 0;
-    uint32_t midp = 0xffffffffu, midcnt = 0;  // (kSplit) where the zone is cut in two, and what its first half produces
-    const uint32_t limit = rbp + (lane + 1) * zs;
-    // the speculative pass starts a RUN-IN ahead of the zone (inside the zone before): all it has to deliver is the
-    // boundary at the zone's END, and the longer the walk, the likelier that it has synchronised by then - fewer lanes
-    // walk again in passes 2+, which cost a full pass each for a handful of lanes (the pass without counts is the
-    // cheap one: 24 instructions a step against 34)
-    const uint32_t runin_ = (zs * RUNIN_NUM) / RUNIN_DEN, runin = runin_ < lane * zs ? runin_ : lane * zs;  // (not before the round's start)
-    bool counted = false;
-#ifdef MD_DEBUG_KNOWN_BOUNDS
-    const int kbm = __builtin_amdgcn_readfirstlane(g_kb_mode);
-    const bool kb_can = wnd.kb_round < KB_ROUNDS;
-    uint4 *kbp = g_kb_buf + ((size_t)wnd.kb_sid * KB_ROUNDS + wnd.kb_round) * kWave + lane;
-    wnd.kb_round++;
-    if ((kbm & 3) == 2 && kb_can) {
-      const uint4 v = *kbp;
-      start = v.x;
-      end = v.y;
-      stop = v.z & 0xffffu;
-      counted = (v.z >> 16) != 0;
-      nb = v.w;
-    } else {
-#endif
-    sync_pass<false, BUDGET>(win, lut, lroot, true, start - runin, limit, end, stop, nb);
-    pf.tick(P_DECODE1);
-    const uint32_t passes = zs * PASSES >= PASS_BITS ? PASSES : PASS_BITS / zs > PASSES_MAX ? PASSES_MAX : PASS_BITS / zs;
-    for (uint32_t it = 0; it < passes; it++) {
-      const uint32_t pe = wave_shr1(end), ps = wave_shr1(stop);
-      const bool redo = lane == 0 ? !counted : (ps == 0 && (pe != start || !counted));
-      if (__ballot(redo) == 0) break;
-      if (redo && lane > 0) start = pe;
-      pf.count(C_PASSES);
-      if constexpr (kSplit) sync_pass<true, BUDGET, true>(win, lut, lroot, redo, start, limit, end, stop, nb, limit - (zs * MD_SPLIT_B) / 8, &midp, &midcnt);
-      else sync_pass<true, BUDGET>(win, lut, lroot, redo, start, limit, end, stop, nb);
-      counted = counted || redo;
+    SyncRound r;
+    if (!kb.replay(r, rbp, zs, lane)) {
+      r = sync_round<BUDGET, kSplit>(win, lut, lroot, lane, rbp, zs, pf);
+      kb.record(r);
     }
-#ifdef MD_DEBUG_KNOWN_BOUNDS
-      if ((kbm & 3) == 1 && kb_can) *kbp = make_uint4(start, end, stop | (counted ? 0x10000u : 0u), nb);
-    }
-#endif
     pf.tick(P_DECODE2);
-    uint32_t nvalid;
-    {
-      const uint32_t pe = wave_shr1(end), ps = wave_shr1(stop);
-      const uint64_t bad = __ballot(!counted || (lane > 0 && (ps != 0 || pe != start)));
-      nvalid = bad ? (uint32_t)__builtin_ctzll(bad) : 64;  // lane 0 is always counted: nvalid >= 1
-    }
-    const uint32_t R0 = sk.pos, rb = sk.sbase();
-    uint32_t mynb = lane < nvalid ? nb : 0;  // bytes | matches << 20
-    const uint32_t off = wave_excl_scan(mynb, lane);
-    if (nvalid < 64) pf.count(C_END_CHAIN);
-    {  // staging and record capacity: keep the largest prefix of lanes that fits (a lone first lane truncates itself;
-       // its matches always fit)
-      const uint32_t bend = ((off + mynb) & (kCountMatch - 1)), rend = (off + mynb) >> 20;
-      const uint64_t fits = __ballot((R0 - rb) + bend <= STAGE - 16 && rend <= RMAX);
-      const uint32_t nfit = fits == ~0ull ? 64 : (uint32_t)__builtin_ctzll(~fits);
-      if (nfit < nvalid) {
-        pf.count(rdlane(rend, nfit) > RMAX ? C_END_RECORDS : C_END_FIT);
-        nvalid = nfit ? nfit : 1;
-      }
-    }
-    const bool mine = lane < nvalid;
-    if (!mine) mynb = 0;
-    const uint32_t boff = off & (kCountMatch - 1), roff = off >> 20;
-    const uint32_t q0 = R0 + boff;
-    LaneOut lo;
-    lo.endp = end;
-    lo.stopc = 0;
-    lo.bytes = 0;
-    lo.nm = 0;
+    const Prefix p = fit_prefix(r, sk, lane, pf);
     if constexpr (PAIR) {  // the staging buffer and the record arrays are the copier's until it has written the last round out
       pf.tick(P_DECODE2);
       if (!mail_wait_idle(sm, sent)) return MD_E_HIP;
       pf.tick(P_WAIT_DEC);
     }
-    // Two wavefronts, one round: the copier has nothing to do until the round is emitted, so it emits the second half of
-    // every zone while this wavefront emits the first (the counting pass left the boundary in the middle and what lies
-    // before it: the halves' output positions and records are known) - the emit pass is half as long.  Small zones are
-    // not worth the hand-over.
-    bool split = false;
-    uint32_t bq = 0, br = 0;  // the second half's bytes | records before it, relative to the lane's
-    LaneOut lob;
-    lob.endp = 0, lob.stopc = 0, lob.bytes = 0, lob.nm = 0;
-    bool gob = false;
-    if constexpr (kSplit) split = zs >= 128;
-    {
-      const uint32_t all = rdlane(off + mynb, nvalid - 1) & (kCountMatch - 1);  // bytes the round will produce
-      const bool plain = tot >= rbp + kWave * zs + 64 && R0 >= 32768u && all <= sk.cap - R0 && (R0 - rb) + all <= STAGE - 16;
-      uint32_t alimit = limit;
-      if constexpr (kSplit) {
-        if (split) {
-          gob = mine && midp != 0xffffffffu && midp < limit && midp >= start;
-          bq = midcnt & (kCountMatch - 1);
-          br = midcnt >> 20;
-          lds_u32 *hx = reinterpret_cast<lds_u32 *>(sm->list);
-          hx[4 * lane + 0] = gob ? midp : 0xffffffffu;
-          hx[4 * lane + 1] = limit;
-          hx[4 * lane + 2] = q0 + bq;
-          hx[4 * lane + 3] = roff + br;
-          if (lane < 6) hx[kHxUni + lane] = lane == 0 ? lroot : lane == 1 ? tot : lane == 2 ? rb : lane == 3 ? R0 : lane == 4 ? sk.cap : (plain ? 0u : 1u);
-          mail_post(sm, lane, kJobEmit, 0, 0, sent);
-          alimit = gob ? midp : limit;
-        }
-      }
-      if (plain && !BUDGET) emit_pass<false, false>(win, lut, lroot, mrec, mpos, sk.stage, roff, tot, mine, start, alimit, q0, rb, R0, sk.cap, lo);
-      else emit_pass<true, BUDGET>(win, lut, lroot, mrec, mpos, sk.stage, roff, tot, mine, start, alimit, q0, rb, R0, sk.cap, lo);
-      if constexpr (kSplit) {
-        if (split) {
-          if (!mail_wait_idle(sm, sent)) return MD_E_HIP;
-          const lds_u32 *hx = reinterpret_cast<const lds_u32 *>(sm->list);
-          if (gob) {
-            lob.endp = hx[4 * lane + 0];
-            lob.stopc = hx[4 * lane + 1];
-            lob.bytes = hx[4 * lane + 2];
-            lob.nm = hx[4 * lane + 3];
-          }
-          // a lane's verdict: its first half's if that stopped, else its second half's
-          const bool sa = lo.stopc != 0;
-          if (!sa && gob) {
-            lo.endp = lob.endp;
-            lo.stopc = lob.stopc;
-            lo.bytes = bq + lob.bytes;
-            lo.nm = br + lob.nm;
-          }
-        }
-      }
-    }
+    LaneOut lo;
+    if (!emit_round<PAIR, BUDGET>(sm, sk, lroot, lane, rbp, tot, zs, r, p, sent, lo)) return MD_E_HIP;
     pf.tick(P_EMIT_A);
-    // the first stopped lane (stream order) ends the round
-    uint32_t total, lstop, nrec;
-    {
-      const uint64_t fm = __ballot(mine && lo.stopc != 0);
-      if (fm) {
-        const uint32_t fl = __builtin_ctzll(fm);
-        lstop = rdlane(lo.stopc, fl);
-        total = rdlane(boff, fl) + rdlane(lo.bytes, fl);
-        nrec = rdlane(roff, fl) + rdlane(lo.nm, fl);  // later lanes are void
-        if (lstop == kStEob) pf.count(C_END_EOB);
-        else if (lstop == kStTrunc) pf.count(C_END_STAGE);
-        nvalid = fl + 1;
-      } else {
-        lstop = 0;
-        const uint32_t all = rdlane(off + mynb, nvalid - 1);
-        total = all & (kCountMatch - 1);
-        nrec = all >> 20;
-      }
-    }
-    const uint32_t nbp = base * 8 + rdlane(lo.endp, nvalid - 1);
+    const Verdict v = round_verdict(p.mine, lo, p.boff, p.roff, p.nvalid, p.all & (kCountMatch - 1), p.all >> 20);
+    if (v.lstop == kStEob) pf.count(C_END_EOB);
+    else if (v.lstop == kStTrunc) pf.count(C_END_STAGE);
+    const uint32_t nbp = base * 8 + rdlane(lo.endp, v.nvalid - 1);
     wnd.fetch(body, body_len, (nbp >> 5) << 2, lane);  // the next round's (or the next block header's) window: on its way
     bool stuck = false;
     if constexpr (PAIR) {
-      mail_post(sm, lane, kJobRound, total, nrec, sent);
-      sk.pos += total;
+      mail_post(sm, lane, kJobRound, v.total, v.nrec, sent);
+      sk.pos += v.total;
     } else {
-      copy_round(sm, sk, lane, total, nrec, &stuck, pf);
+      copy_round(sm, sk, lane, v.total, v.nrec, &stuck, pf);
     }
-    pf.count(C_LANES, nvalid);
-    if (stuck || (nbp == bp && total == 0 && (lstop == 0 || lstop == kStTrunc))) return MD_E_HIP;  // defensive: no progress
-    {  // next round: 64 zones that fill about 7/8 of the staging buffer at this round's bytes-per-bit
-      const uint32_t bits = nbp - bp;
-      const uint64_t want = (uint64_t)(STAGE - STAGE / 8) * bits / ((uint64_t)kWave * (total ? total : 1u));
-      zs = want > S ? S : want < SMIN ? SMIN : (uint32_t)want;
-    }
+    pf.count(C_LANES, v.nvalid);
+    if (stuck || (nbp == bp && v.total == 0 && (v.lstop == 0 || v.lstop == kStTrunc))) return MD_E_HIP;  // defensive: no progress
+    zs = next_zone(nbp - bp, v.total);
     bp = nbp;
-    if (lstop == kStEob) break;
-    if (lstop != 0 && lstop != kStTrunc) return (int)lstop;
+    if (v.lstop == kStEob) break;
+    if (v.lstop != 0 && v.lstop != kStTrunc) return (int)v.lstop;
   }
   *bp_io = bp;
   *zone_io = zs;
@@ -686,23 +713,7 @@ __device__ __forceinline__ void copier_main(lds_smem *sm, const uint8_t *__restr
     bool stuck = false;
     if (kind == kJobRound) copy_round(sm, sk, lane, total, x, &stuck, pf);
     else if (kind == kJobEmit) {
-      if constexpr (MD_EMIT_SPLIT != 0) {
-        lds_u32 *hx = reinterpret_cast<lds_u32 *>(sm->list);
-        const uint32_t bstart = hx[4 * lane + 0], blimit = hx[4 * lane + 1], bq0 = hx[4 * lane + 2], brec = hx[4 * lane + 3];
-        const uint32_t lroot = uni(hx[kHxUni + 0]), tot = uni(hx[kHxUni + 1]), rb = uni(hx[kHxUni + 2]), R0 = uni(hx[kHxUni + 3]),
-                       cap = uni(hx[kHxUni + 4]), checked = uni(hx[kHxUni + 5]);
-        const bool go = bstart != 0xffffffffu;
-        LaneOut lo;
-        lo.endp = bstart, lo.stopc = 0, lo.bytes = 0, lo.nm = 0;
-        const lds_u32 *win = (const lds_u32 *)sm->win;
-        const lds_u32 *lut = (const lds_u32 *)sm->lut;
-        if (checked) emit_pass<true, false>(win, lut, lroot, (lds_u32 *)sm->mrec, (lds_u16 *)sm->mpos, sk.stage, brec, tot, go, go ? bstart : 0u, blimit, bq0, rb, R0, cap, lo);
-        else emit_pass<false, false>(win, lut, lroot, (lds_u32 *)sm->mrec, (lds_u16 *)sm->mpos, sk.stage, brec, tot, go, go ? bstart : 0u, blimit, bq0, rb, R0, cap, lo);
-        hx[4 * lane + 0] = lo.endp;
-        hx[4 * lane + 1] = lo.stopc;
-        hx[4 * lane + 2] = lo.bytes;
-        hx[4 * lane + 3] = lo.nm;
-      }
+      if constexpr (MD_EMIT_SPLIT != 0) emit_second_halves(sm, sk, lane);
     } else copy_stored(sk, body, x, total, lane);
     if (lane == 0) {
       sm->mail.a = sk.a;
@@ -715,27 +726,85 @@ __device__ __forceinline__ void copier_main(lds_smem *sm, const uint8_t *__restr
   }
 }
 
+// The decoder's side of block_loop (inflate_wave_core.hpp): a stored block's bytes are copied (PAIR: by the copier), a
+// Huffman block is decoded, and a stream in pieces notes every complete block.
+template <class PF, bool PAIR>
+struct DecodeBlocks {
+  lds_smem *sm;
+  const uint8_t *body;
+  uint32_t body_len, lane, sid;
+  Sink &sk;
+  Window &wnd;
+  KnownBounds &kb;
+  PF &pf;
+  const Cont &cont;
+  uint32_t zone;  // the next round's zone size
+  uint32_t sent;  // PAIR: jobs posted
+  __device__ __forceinline__ int stored(uint32_t p, uint32_t len) {
+    if (len > sk.cap - sk.pos) return MD_UNEXPECTED_END_OF_OUTPUT;
+    int rc = MD_OK;
+    if (len) {  // (an empty stored block - a flush point - is its header and nothing else)
+      if constexpr (PAIR) {
+        if (!mail_wait_idle(sm, sent)) rc = MD_E_HIP;
+        mail_post(sm, lane, kJobStored, len, p, sent);
+        sk.pos += len;
+      } else {
+        copy_stored(sk, body, p, len, lane);
+      }
+    }
+    return rc;
+  }
+  // (lane & 63 is lane.  The two builders are compiled on their own, and what they know of their arguments they learn at
+  // the call, before this struct has dissolved into the kernel: told that lane < 64, dynamic_tables keeps one
+  // callee-saved register fewer - 4 bytes of the kernel's 40 of scratch, which tests/test_inflate_resources.py caps)
+  __device__ __forceinline__ void fixed(uint32_t &lroot) { fixed_tables(sm, lane & (kWave - 1), &lroot); }
+  __device__ __forceinline__ int dynamic(uint32_t rbp, uint32_t tot, uint32_t &hend, uint32_t &lroot) {
+    return dynamic_tables(sm, rbp, tot, lane & (kWave - 1), &hend, &lroot, pf);
+  }
+  __device__ __forceinline__ void header_done() { pf.tick(P_HEADER); }
+  template <bool BUDGET>
+  __device__ __forceinline__ int huffman(uint32_t lroot, uint32_t &bp) {
+    return inflate_block<PF, PAIR, BUDGET>(sm, body, body_len, sk, lroot, lane, &bp, &zone, wnd, kb, sent, pf);
+  }
+  __device__ __forceinline__ void block_done(int &rc, uint32_t bp, bool last) {
+    if (cont.resume_bits && rc == MD_OK) {  // the next piece of the stream could start here
+      if constexpr (PAIR) {                 // (the checksum state is the copier's)
+        if (!mail_wait_idle(sm, sent)) rc = MD_E_HIP;
+        sk.a = uni(sm->mail.a);
+        sk.b = uni(sm->mail.b);
+      }
+      if (lane == 0) {
+        cont.resume_bits[sid] = bp;
+        cont.resume_out[sid] = sk.pos;
+        cont.resume_adler[sid] = (sk.b << 16) | sk.a;
+        cont.resume_last[sid] = last ? 1u : 0u;
+      }
+    }
+  }
+};
+
 // PAIR = two wavefronts per stream (decoder + copier, see inflate_block); otherwise one wavefront does both in turn.
-// cont: a stream decoded in pieces (struct Cont, internal.hpp), all null for whole streams.
+// a.cont: a stream decoded in pieces (struct Cont, internal.hpp), all null for whole streams.
 template <bool PROF, bool PAIR>
-__global__ __launch_bounds__(PAIR ? 2 * kWave : kWave, PAIR ? MD_PAIR_OCC : 2) void inflate_wave_kernel(
-    int format, uint32_t n, const uint8_t *__restrict__ in, const uint64_t *__restrict__ in_off,
-    const uint64_t *__restrict__ in_len, uint8_t *out, const uint64_t *__restrict__ out_off,
-    const uint64_t *__restrict__ out_cap, uint64_t *__restrict__ out_len,
-    uint64_t *__restrict__ consumed, int32_t *__restrict__ status, uint32_t *__restrict__ checksum,
-    uint64_t *__restrict__ dbg, const uint32_t *__restrict__ order, Cont cont) {
+__global__ __launch_bounds__(PAIR ? 2 * kWave : kWave, PAIR ? MD_PAIR_OCC : 2) void inflate_wave_kernel(const InfArgs a) {
   __shared__ Smem smem;  // static: LDS addresses fold into the instructions' offset fields
   lds_smem *sm = (lds_smem *)&smem;
   Prof<PROF> pf;
   pf.init();
   const uint32_t lane = threadIdx.x & (kWave - 1);
   const uint32_t wave = PAIR ? uni(threadIdx.x / kWave) : 0u;  // 0 = decoder, 1 = copier
-  if (blockIdx.x >= n) return;
-  const uint32_t sid = order ? order[blockIdx.x] : blockIdx.x;  // workgroups start in index order: longest streams first
+  if (blockIdx.x >= a.n) return;
+  const uint32_t sid = a.order ? a.order[blockIdx.x] : blockIdx.x;  // workgroups start in index order: longest streams first
+  const int format = a.format;
+  uint64_t *const out_len = a.out_len, *const consumed = a.consumed, *const dbg = a.dbg;
+  int32_t *const status = a.status;
+  uint32_t *const checksum = a.checksum;
+  const Cont &cont = a.cont;
 
-  const uint8_t *src = in + in_off[sid];
-  uint64_t slen64 = in_len[sid], cap64 = out_cap[sid];
-  if (slen64 > MD_MAX_INFLATE_IN) {  // 32-bit bit positions: the descriptor is out of range (mdeflate.h)
+  const uint8_t *src = a.in + a.in_off[sid];
+  const uint64_t cap64 = a.out_cap[sid];
+  const Opened o = open_stream(format, src, a.in_len[sid]);
+  if (o.rc == MD_E_INVALID_ARGUMENT) {
     if (threadIdx.x == 0) {
       out_len[sid] = 0;
       consumed[sid] = 0;
@@ -744,29 +813,15 @@ __global__ __launch_bounds__(PAIR ? 2 * kWave : kWave, PAIR ? MD_PAIR_OCC : 2) v
     }
     return;
   }
-  const uint32_t slen = (uint32_t)slen64;
   const bool cap_clamped = cap64 > MD_MAX_STREAM;  // more room than 32-bit cursors can use
   const uint32_t cap = cap_clamped ? (uint32_t)MD_MAX_STREAM : (uint32_t)cap64;
-
-  int rc = MD_OK;
-  uint32_t body_off = 0, body_len = slen;
-  if (format == MD_FORMAT_ZLIB) {  // Zl.Inf.Ns.inflate, lib/zl.ml:400-417
-    if (slen < 2) rc = MD_UNEXPECTED_END_OF_INPUT;
-    else {
-      uint32_t cmf = src[0], flg = src[1];
-      if (((cmf << 8) + flg) % 31 != 0 || (cmf & 0xf) != 8) rc = MD_INVALID_HEADER;
-      else if (slen < 6) rc = MD_UNEXPECTED_END_OF_INPUT;
-      else {
-        body_off = 2;
-        body_len = slen - 6;
-      }
-    }
-  }
-  const uint8_t *body = src + body_off;
+  int rc = o.rc;
+  const uint32_t body_len = o.body_len;
+  const uint8_t *body = src + o.body_off;
 
   Sink sk;  // PAIR: the copier's is the real one, the decoder's only follows the output position
   sk.stage = (lds_u8 *)sm->stage;
-  sk.g = out + out_off[sid];
+  sk.g = a.out + a.out_off[sid];
   sk.cap = cap;
   const uint32_t hist = cont.hist_len ? cont.hist_len[sid] : 0u, adler0 = cont.adler_in ? cont.adler_in[sid] : 1u;
   sk.pos = hist < cap ? hist : cap;  // (the history is the caller's: it fits the buffer)
@@ -794,18 +849,11 @@ __global__ __launch_bounds__(PAIR ? 2 * kWave : kWave, PAIR ? MD_PAIR_OCC : 2) v
     }
   }
 
-  lds_u32 *win = (lds_u32 *)sm->win;
-  const uint32_t total_bits = body_len * 8;
   uint32_t bp = cont.start_bit ? cont.start_bit[sid] & 7u : 0u;
-  uint32_t zone = S;
-  uint32_t sent = 0;  // PAIR: jobs posted
-  uint32_t fixed_lroot = 0;  // != 0: the tables in LDS are the fixed ones (and this is their root width)
   Window wnd;
   wnd.base = 0xffffffffu;
-#ifdef MD_DEBUG_KNOWN_BOUNDS
-  wnd.kb_round = 0;
-  wnd.kb_sid = sid;
-#endif
+  KnownBounds kb;
+  kb.init(sid);
   if (cont.resume_bits && lane == 0) {  // no block complete yet
     cont.resume_bits[sid] = bp;
     cont.resume_out[sid] = sk.pos;
@@ -813,121 +861,13 @@ __global__ __launch_bounds__(PAIR ? 2 * kWave : kWave, PAIR ? MD_PAIR_OCC : 2) v
     cont.resume_last[sid] = 0;
   }
 
-  if (rc == MD_OK) {
-    bool last = false;
-    uint32_t lds_base = 0xffffffffu;  // the window in LDS begins at this byte of the body (nothing else has been loaded since)
-    while (!last && rc == MD_OK) {
-      // a block header that still lies in the first part of the window in LDS is read from there: runs of tiny blocks
-      // (flush points, empty blocks) would otherwise load 2 KiB from the input for every few bytes of it
-      uint32_t base = (bp >> 5) << 2;
-      if (lds_base != 0xffffffffu && bp >= lds_base * 8 && bp - lds_base * 8 <= 4096) base = lds_base;
-      else {
-        wnd.ensure(win, body, body_len, base, lane);
-        lds_base = base;
-      }
-      uint32_t rbp = bp - base * 8;
-      const uint32_t tot = total_bits - base * 8;
-      if ((int32_t)(tot - rbp) < 3) {
-        rc = MD_UNEXPECTED_END_OF_INPUT;
-        break;
-      }
-      const uint32_t hdr = uni(peek(win, rbp));
-      last = hdr & 1;
-      uint32_t type = (hdr >> 1) & 3;
-      bp += 3;
-      rbp += 3;
-      bool block_done = false;  // the block was dealt with here (an empty fixed one)
-      if (type == 1) {
-        // a run of EMPTY fixed blocks - header, then the 7-bit end-of-block code 0000000 (lib/de.ml:821-833) - is walked
-        // through right here: ten bits a block instead of a round each
-        for (;;) {
-          if (rbp + 7 > tot || rbp + 64 > WIN_WORDS * 32 - 64 || (uni(peek(win, rbp)) & 0x7fu) != 0) break;  // not one of them
-          rbp += 7;
-          bp += 7;
-          block_done = true;  // the block whose header was consumed last is complete
-          if (last || rbp + 3 > tot) break;
-          const uint32_t h = uni(peek(win, rbp)) & 7u;
-          if (((h >> 1) & 3) != 1) break;  // another kind of block: back to the loop above
-          last = h & 1;
-          rbp += 3;
-          bp += 3;
-          block_done = false;
-        }
-      }
-      if (block_done) {
-        // nothing to decode
-      } else if (type == 0) {
-        // flat, lib/de.ml:1613-1627
-        uint32_t p = (bp + 7) >> 3;
-        if (body_len - p < 4) {
-          rc = MD_UNEXPECTED_END_OF_INPUT;
-          break;
-        }
-        uint32_t h4;
-        if (p + 4 <= base + (WIN_WORDS - 2) * 4) h4 = uni(peek(win, (p - base) * 8));
-        else h4 = (uint32_t)body[p] | ((uint32_t)body[p + 1] << 8) | ((uint32_t)body[p + 2] << 16) | ((uint32_t)body[p + 3] << 24);
-        uint32_t len = h4 & 0xffff, nlen = h4 >> 16;
-        p += 4;
-        if (nlen != 0xffff - len) rc = MD_INVALID_COMPLEMENT_OF_LENGTH;
-        else if (len > body_len - p) rc = MD_UNEXPECTED_END_OF_INPUT;
-        else if (len > sk.cap - sk.pos) rc = MD_UNEXPECTED_END_OF_OUTPUT;
-        else {
-          if (len) {  // (an empty stored block - a flush point - is its header and nothing else)
-            if constexpr (PAIR) {
-              if (!mail_wait_idle(sm, sent)) rc = MD_E_HIP;
-              mail_post(sm, lane, kJobStored, len, p, sent);
-              sk.pos += len;
-            } else {
-              copy_stored(sk, body, p, len, lane);
-            }
-          }
-          p += len;
-          bp = p * 8;
-        }
-      } else if (type == 3) {
-        rc = MD_INVALID_KIND_OF_BLOCK;
-      } else {
-        uint32_t lroot = 0;
-        if (type == 1) {
-          if (fixed_lroot == 0) {  // (a run of fixed blocks builds their tables once)
-            fixed_tables(sm, lane, &lroot);
-            fixed_lroot = uni(lroot);
-          }
-          lroot = fixed_lroot;
-        } else {
-          uint32_t hend = 0;
-          fixed_lroot = 0;
-          rc = dynamic_tables(sm, rbp, tot, lane, &hend, &lroot, pf);
-          bp = base * 8 + hend;
-        }
-        lroot = uni(lroot);
-        pf.tick(P_HEADER);
-        if (rc == MD_OK) {
-          if (lroot & kLoopy) rc = inflate_block<Prof<PROF>, PAIR, true>(sm, body, body_len, sk, lroot & 15, lane, &bp, &zone, wnd, sent, pf);
-          else rc = inflate_block<Prof<PROF>, PAIR, false>(sm, body, body_len, sk, lroot, lane, &bp, &zone, wnd, sent, pf);
-          lds_base = 0xffffffffu;
-        }
-      }
-      if (cont.resume_bits && rc == MD_OK) {  // a block is complete: the next piece of the stream could start here
-        if constexpr (PAIR) {                 // (the checksum state is the copier's)
-          if (!mail_wait_idle(sm, sent)) rc = MD_E_HIP;
-          sk.a = uni(sm->mail.a);
-          sk.b = uni(sm->mail.b);
-        }
-        if (lane == 0) {
-          cont.resume_bits[sid] = bp;
-          cont.resume_out[sid] = sk.pos;
-          cont.resume_adler[sid] = (sk.b << 16) | sk.a;
-          cont.resume_last[sid] = last ? 1u : 0u;
-        }
-      }
-    }
-  }
+  DecodeBlocks<Prof<PROF>, PAIR> h = {sm, body, body_len, lane, sid, sk, wnd, kb, pf, cont, S, 0};
+  if (rc == MD_OK) rc = block_loop(h, sm, body, body_len, lane, bp, wnd);
   if constexpr (PAIR) {  // everything posted is written out; the checksum state comes back, the copier goes home
-    if (!mail_wait_idle(sm, sent) && rc == MD_OK) rc = MD_E_HIP;
+    if (!mail_wait_idle(sm, h.sent) && rc == MD_OK) rc = MD_E_HIP;
     sk.a = uni(sm->mail.a);
     sk.b = uni(sm->mail.b);
-    mail_post(sm, lane, kJobQuit, 0, 0, sent);
+    mail_post(sm, lane, kJobQuit, 0, 0, h.sent);
   }
   uint32_t used = (bp + 7) >> 3;  // i_pos - (bits lsr 3), lib/de.ml:1805
   uint32_t adler = (sk.b << 16) | sk.a;
@@ -1040,29 +980,19 @@ extern "C" int md_i_debug_known_bounds(int mode, uint32_t nstreams) {
 #endif
 }
 
-extern "C" int md_launch_inflate_wave(int format, uint32_t n, const uint8_t *in, const uint64_t *in_off,
-                                      const uint64_t *in_len, uint8_t *out, const uint64_t *out_off,
-                                      const uint64_t *out_cap, uint64_t *out_len, uint64_t *consumed,
-                                      int32_t *status, uint32_t *checksum, uint64_t *dbg, uint32_t *order,
-                                      int waves, const md::wv::Cont *cont, hipStream_t stream) {
-  if (n == 0) return 0;
+template <bool PROF, bool PAIR>
+static void launch_inflate(const md::wv::InfArgs &a, hipStream_t stream) {
   using namespace md::wv;
-  const bool single = waves == 1;  // the one-wavefront form of the kernel: same results, kept for comparison
-  dim3 grid(n), block(single ? kWave : 2 * kWave);
-  if (order) hipLaunchKernelGGL(inflate_order_kernel, dim3(1), dim3(kOrderThreads), 0, stream, n, in_len, order);
-  const uint32_t *ord = dbg ? nullptr : order;
-  const Cont cn = cont ? *cont : Cont{};
-  const uint32_t lds_pad = g_debug_lds_pad;
-#define MD_LAUNCH_INFLATE(P, Q)                                                                                          \
-  hipLaunchKernelGGL((inflate_wave_kernel<P, Q>), grid, block, (P) ? 0u : lds_pad, stream, format, n, in, in_off, in_len, out, out_off, \
-                     out_cap, out_len, consumed, status, checksum, dbg, ord, cn)
-  if (dbg) {
-    if (single) MD_LAUNCH_INFLATE(true, false);
-    else MD_LAUNCH_INFLATE(true, true);
-  } else {
-    if (single) MD_LAUNCH_INFLATE(false, false);
-    else MD_LAUNCH_INFLATE(false, true);
-  }
-#undef MD_LAUNCH_INFLATE
+  hipLaunchKernelGGL((inflate_wave_kernel<PROF, PAIR>), dim3(a.n), dim3(PAIR ? 2 * kWave : kWave), PROF ? 0u : g_debug_lds_pad, stream, a);
+}
+extern "C" int md_launch_inflate_wave(const md::wv::InfArgs *args, hipStream_t stream) {
+  if (args->n == 0) return 0;
+  using namespace md::wv;
+  InfArgs a = *args;
+  if (a.order) hipLaunchKernelGGL(inflate_order_kernel, dim3(1), dim3(kOrderThreads), 0, stream, a.n, a.in_len, a.order);
+  if (a.dbg) a.order = nullptr;      // (a profiled launch runs in index order)
+  const bool single = a.waves == 1;  // the one-wavefront form of the kernel: same results, kept for comparison
+  if (a.dbg) single ? launch_inflate<true, false>(a, stream) : launch_inflate<true, true>(a, stream);
+  else single ? launch_inflate<false, false>(a, stream) : launch_inflate<false, true>(a, stream);
   return (int)hipGetLastError();
 }

@@ -67,6 +67,8 @@ static_assert(kDistB % 2 == 0 && kLitB % 2 == 0 && kStopEobI % 2 == 0 && kLutWor
 constexpr uint32_t kStEob = 100, kStTrunc = 101;  // lane stop reasons; < 100 = MD_* status
 constexpr uint32_t kCountMatch = 1u << 20;         // a walk counts bytes | matches << 20 (64 lanes: < 2^20 bytes, < 2^12 matches)
 constexpr uint32_t kNearBit = 0x8000u;            // match record: len-3[23:16] | near[15] | dist-1[14:0]
+__device__ __forceinline__ uint32_t rec_dist(uint32_t tk) { return (tk & 0x7fff) + 1; }
+__device__ __forceinline__ uint32_t rec_len(uint32_t tk) { return ((tk >> 16) & 0xff) + 3; }
 
 // The two wavefronts of a stream talk through this: the decoder posts jobs, the copier reports them done.  A wavefront's
 // LDS operations execute in order, so a job's records and literals are in LDS before `emitted` says so, and the
@@ -82,9 +84,9 @@ struct Mail {
 };
 constexpr uint32_t kJobRound = 0, kJobStored = 1, kJobQuit = 2, kJobEmit = 3;
 // kJobEmit: the copier emits the second halves of the round's zones while the decoder emits the first ones.  What it needs
-// lies in `list` (the copier's own array, idle between two rounds): four words per lane - start, limit, output position,
-// first record (0xffffffff: nothing to do) -, then six wave-uniform words; the lanes' results come back in the same place.
-constexpr uint32_t kHxUni = 4 * 64;  // word index of the uniform part: lroot, tot, rb, R0, cap, checked
+// lies in `list` (the copier's own array, idle between two rounds): four words per lane, then six wave-uniform words; the
+// lanes' results come back in the same place (struct EmitJob, inflate_wave.hip).
+constexpr uint32_t kHxUni = 4 * 64;  // word index of the uniform part
 struct Smem {  // the kernel's only LDS object: it sits at LDS address 0
   uint32_t win[WIN_WORDS];
   uint32_t lut[kLutWords];
@@ -154,9 +156,6 @@ __device__ __forceinline__ uint32_t dist_value(uint32_t m, uint32_t xb, uint32_t
 struct Window {
   uint32_t w[8], wx;
   uint32_t base;  // of the fetched words; 0xffffffff = nothing fetched
-#ifdef MD_DEBUG_KNOWN_BOUNDS
-  uint32_t kb_round, kb_sid;
-#endif
   __device__ __forceinline__ void fetch(const uint8_t *__restrict__ body, uint32_t nbytes, uint32_t b, uint32_t lane) {
     base = b;
     const uint32_t off = b + lane * 32;
@@ -737,6 +736,215 @@ __device__ __forceinline__ void emit_pass(const lds_u32 *win, const lds_u32 *lut
     lo.bytes = q - q0;
     lo.nm = rec - rec0;
   }
+}
+
+// ---- a round's sync passes and its verdict ----------------------------------------------------------
+// What the sync passes of a round leave: per lane the validated start of its zone, where its walk ended, the STOP table it
+// ran into (0: none), what its tokens produce (bytes | matches << 20) and whether that was counted from the validated
+// start; wave-uniform the consistent prefix of lanes and the passes walked.  MID: the cut in the zone's middle and what
+// lies before it (sync_pass).
+struct SyncRound {
+  uint32_t start, end, stop, nb, limit;
+  bool counted;
+  uint32_t nvalid, np;
+  uint32_t midp, midcnt;
+};
+// the lanes whose chain start_i == end_{i-1} holds from lane 0 on (lane 0 is always counted: >= 1)
+__device__ __forceinline__ uint32_t consistent_prefix(const SyncRound &r, uint32_t lane) {
+  const uint32_t pe = wave_shr1(r.end), ps = wave_shr1(r.stop);
+  const uint64_t bad = __ballot(!r.counted || (lane > 0 && (ps != 0 || pe != r.start)));
+  return bad ? (uint32_t)__builtin_ctzll(bad) : 64;
+}
+// 64 zones of zs bits from window bit rbp on: the speculative pass, the counting passes, the consistent prefix.  pf gets
+// the time of the first pass and a count per pass.
+template <bool BUDGET, bool MID, class PF>
+__device__ __forceinline__ SyncRound sync_round(const lds_u32 *win, const lds_u32 *lut, uint32_t lroot, uint32_t lane, uint32_t rbp,
+                                                uint32_t zs, PF &pf) {
+  SyncRound r;
+  r.start = rbp + lane * zs, r.end = 0, r.stop = 0, r.nb = 0;
+  r.midp = 0xffffffffu, r.midcnt = 0;
+  r.limit = rbp + (lane + 1) * zs;
+  // the speculative pass starts a RUN-IN ahead of the zone (inside the zone before): all it has to deliver is the
+  // boundary at the zone's END, and the longer the walk, the likelier that it has synchronised by then - fewer lanes
+  // walk again in passes 2+, which cost a full pass each for a handful of lanes (the pass without counts is the
+  // cheap one: 24 instructions a step against 34)
+  const uint32_t runin_ = (zs * RUNIN_NUM) / RUNIN_DEN, runin = runin_ < lane * zs ? runin_ : lane * zs;  // (not before the round's start)
+  r.counted = false;
+  pf.count(C_PASSES);
+  sync_pass<false, BUDGET>(win, lut, lroot, true, r.start - runin, r.limit, r.end, r.stop, r.nb);
+  pf.tick(P_DECODE1);
+  r.np = 1;
+  const uint32_t passes = zs * PASSES >= PASS_BITS ? PASSES : PASS_BITS / zs > PASSES_MAX ? PASSES_MAX : PASS_BITS / zs;
+#pragma nounroll  // (with a constant zone size `passes` is a constant: one copy of the counting walk, not six)
+  for (uint32_t it = 0; it < passes; it++) {
+    const uint32_t pe = wave_shr1(r.end), ps = wave_shr1(r.stop);
+    const bool redo = lane == 0 ? !r.counted : (ps == 0 && (pe != r.start || !r.counted));
+    if (__ballot(redo) == 0) break;
+    if (redo && lane > 0) r.start = pe;
+    pf.count(C_PASSES);
+    r.np++;
+    if constexpr (MID) sync_pass<true, BUDGET, true>(win, lut, lroot, redo, r.start, r.limit, r.end, r.stop, r.nb, r.limit - (zs * MD_SPLIT_B) / 8, &r.midp, &r.midcnt);
+    else sync_pass<true, BUDGET>(win, lut, lroot, redo, r.start, r.limit, r.end, r.stop, r.nb);
+    r.counted = r.counted || redo;
+  }
+  r.nvalid = consistent_prefix(r, lane);
+  return r;
+}
+
+// How a round ends.  The first stopped lane (stream order) ends it: its reason, the bytes and records in front of its
+// failing token, and the lanes behind it are void; with no lane stopped, what the nvalid lanes produce together (all_*).
+// boff / roff: the bytes / records of the lanes before this one.
+struct Verdict {
+  uint32_t lstop, nvalid, total, nrec;
+};
+__device__ __forceinline__ Verdict round_verdict(bool mine, const LaneOut &lo, uint32_t boff, uint32_t roff, uint32_t nvalid,
+                                                 uint32_t all_bytes, uint32_t all_rec) {
+  Verdict v = {0, nvalid, all_bytes, all_rec};
+  const uint64_t fm = __ballot(mine && lo.stopc != 0);
+  if (fm) {
+    const uint32_t fl = __builtin_ctzll(fm);
+    v.lstop = rdlane(lo.stopc, fl);
+    v.total = rdlane(boff, fl) + rdlane(lo.bytes, fl);
+    v.nrec = rdlane(roff, fl) + rdlane(lo.nm, fl);  // later lanes are void
+    v.nvalid = fl + 1;
+  }
+  return v;
+}
+
+// ---- a stream from its first byte to its last block ---------------------------------------------------
+// What both kernels do first with a stream's descriptor: an input that 32-bit bit positions cannot address is refused
+// (rc = MD_E_INVALID_ARGUMENT: the descriptor is out of range, mdeflate.h; what is written then is the kernel's own), and
+// the zlib frame comes off (Zl.Inf.Ns.inflate, lib/zl.ml:400-417).  The DEFLATE body is src[body_off, body_off + body_len).
+struct Opened {
+  int rc;
+  uint32_t body_off, body_len;
+};
+__device__ __forceinline__ Opened open_stream(int format, const uint8_t *src, uint64_t slen64) {
+  Opened o = {MD_OK, 0, (uint32_t)slen64};
+  if (slen64 > MD_MAX_INFLATE_IN) {
+    o.rc = MD_E_INVALID_ARGUMENT;
+  } else if (format == MD_FORMAT_ZLIB) {
+    const uint32_t slen = (uint32_t)slen64;
+    if (slen < 2) o.rc = MD_UNEXPECTED_END_OF_INPUT;
+    else {
+      uint32_t cmf = src[0], flg = src[1];
+      if (((cmf << 8) + flg) % 31 != 0 || (cmf & 0xf) != 8) o.rc = MD_INVALID_HEADER;
+      else if (slen < 6) o.rc = MD_UNEXPECTED_END_OF_INPUT;
+      else {
+        o.body_off = 2;
+        o.body_len = slen - 6;
+      }
+    }
+  }
+  return o;
+}
+
+// A block header that still lies within this many bits of the window in LDS is read from there.  A stored block's LEN/NLEN
+// word is only ever met behind such a header (window bit <= kHeaderReuse + 3), so it lies in the window too:
+constexpr uint32_t kHeaderReuse = 4096;
+static_assert((kHeaderReuse + 3 + 7) / 8 + 4 <= (WIN_WORDS - 2) * 4, "a stored block's LEN/NLEN is read from the window in LDS");
+
+// All blocks of a body, from bit bp on: the block headers, the runs of empty fixed blocks, the stored headers, the table
+// builders; the status is that of the first failing check, in the reference's order.  The handler H has what differs between
+// the decoder and the size query:
+//   int stored(p, len)             the payload body[p, p + len) of a stored block (len may be 0)
+//   void fixed(&lroot)             fixed_tables: the root width
+//   int dynamic(rbp, tot, &hend, &lroot)   dynamic_tables: the window bit behind the header, the root width (| kLoopy)
+//   void header_done()             the tables are built (a profile tick)
+//   int huffman<BUDGET>(lroot, &bp)  all rounds of the Huffman block
+//   void block_done(&rc, bp, last)   a block is complete
+template <class H>
+__device__ __forceinline__ int block_loop(H &h, lds_smem *sm, const uint8_t *__restrict__ body, uint32_t body_len, uint32_t lane,
+                                          uint32_t &bp, Window &wnd) {
+  lds_u32 *win = (lds_u32 *)sm->win;
+  const uint32_t total_bits = body_len * 8;
+  int rc = MD_OK;
+  bool last = false;
+  uint32_t fixed_lroot = 0;         // != 0: the tables in LDS are the fixed ones (and this is their root width)
+  uint32_t lds_base = 0xffffffffu;  // the window in LDS begins at this byte of the body (nothing else has been loaded since)
+  while (!last && rc == MD_OK) {
+    // a block header that still lies in the first part of the window in LDS is read from there: runs of tiny blocks
+    // (flush points, empty blocks) would otherwise load 2 KiB from the input for every few bytes of it
+    uint32_t base = (bp >> 5) << 2;
+    if (lds_base != 0xffffffffu && bp >= lds_base * 8 && bp - lds_base * 8 <= kHeaderReuse) base = lds_base;
+    else {
+      wnd.ensure(win, body, body_len, base, lane);
+      lds_base = base;
+    }
+    uint32_t rbp = bp - base * 8;
+    const uint32_t tot = total_bits - base * 8;
+    if ((int32_t)(tot - rbp) < 3) {
+      rc = MD_UNEXPECTED_END_OF_INPUT;
+      break;
+    }
+    const uint32_t hdr = uni(peek(win, rbp));
+    last = hdr & 1;
+    const uint32_t type = (hdr >> 1) & 3;
+    bp += 3;
+    rbp += 3;
+    bool block_done = false;  // the block was dealt with here (an empty fixed one)
+    if (type == 1) {
+      // a run of EMPTY fixed blocks - header, then the 7-bit end-of-block code 0000000 (lib/de.ml:821-833) - is walked
+      // through right here: ten bits a block instead of a round each
+      for (;;) {
+        if (rbp + 7 > tot || rbp + 64 > WIN_WORDS * 32 - 64 || (uni(peek(win, rbp)) & 0x7fu) != 0) break;  // not one of them
+        rbp += 7;
+        bp += 7;
+        block_done = true;  // the block whose header was consumed last is complete
+        if (last || rbp + 3 > tot) break;
+        const uint32_t h3 = uni(peek(win, rbp)) & 7u;
+        if (((h3 >> 1) & 3) != 1) break;  // another kind of block: back to the loop above
+        last = h3 & 1;
+        rbp += 3;
+        bp += 3;
+        block_done = false;
+      }
+    }
+    if (block_done) {
+      // nothing to decode
+    } else if (type == 0) {
+      // flat, lib/de.ml:1613-1627
+      uint32_t p = (bp + 7) >> 3;
+      if (body_len - p < 4) {
+        rc = MD_UNEXPECTED_END_OF_INPUT;
+        break;
+      }
+      const uint32_t h4 = uni(peek(win, (p - base) * 8));
+      const uint32_t len = h4 & 0xffff, nlen = h4 >> 16;
+      p += 4;
+      if (nlen != 0xffff - len) rc = MD_INVALID_COMPLEMENT_OF_LENGTH;
+      else if (len > body_len - p) rc = MD_UNEXPECTED_END_OF_INPUT;
+      else {
+        rc = h.stored(p, len);
+        if (rc == MD_OK) bp = (p + len) * 8;
+      }
+    } else if (type == 3) {
+      rc = MD_INVALID_KIND_OF_BLOCK;
+    } else {
+      uint32_t lroot = 0;
+      if (type == 1) {
+        if (fixed_lroot == 0) {  // (a run of fixed blocks builds their tables once)
+          h.fixed(lroot);
+          fixed_lroot = uni(lroot);
+        }
+        lroot = fixed_lroot;
+      } else {
+        uint32_t hend = 0;
+        fixed_lroot = 0;
+        rc = h.dynamic(rbp, tot, hend, lroot);
+        bp = base * 8 + hend;
+      }
+      lroot = uni(lroot);
+      h.header_done();
+      if (rc == MD_OK) {
+        if (lroot & kLoopy) rc = h.template huffman<true>(lroot & 15, bp);
+        else rc = h.template huffman<false>(lroot, bp);
+        lds_base = 0xffffffffu;
+      }
+    }
+    h.block_done(rc, bp, last);
+  }
+  return rc;
 }
 
 }  // namespace wv

@@ -102,6 +102,24 @@ struct Cont {
   uint32_t *resume_adler, *resume_last;
 };
 
+// What one launch of the decoder (inflate_wave.hip) takes: md_launch_inflate_wave's argument, the kernel's too.
+struct InfArgs {
+  int format;
+  uint32_t n;
+  // the batch descriptors (device arrays of n entries, the blobs they index)
+  const uint8_t *in;
+  const uint64_t *in_off, *in_len;
+  uint8_t *out;
+  const uint64_t *out_off, *out_cap;
+  uint64_t *out_len, *consumed;
+  int32_t *status;
+  uint32_t *checksum;  // or null
+  uint64_t *dbg;       // the profile words of stream 0 (md_set_option "profile"), or null
+  uint32_t *order;     // n words of device scratch for the launch order (longest first), or null for index order
+  int waves;           // wavefronts per stream: 2, or 1 (the one-wavefront form of the kernel: same results)
+  Cont cont;           // every pointer null: whole streams
+};
+
 }  // namespace wv
 
 // One stream's row of piece_gather_kernel (gz_kernels.hip): its region of the new blob, at new_off, is old_len bytes
@@ -192,11 +210,7 @@ struct Round {
 extern "C" {
 
 // ---- inflate_wave.hip ----
-// `order` = n words of device scratch, or null for index order; waves = wavefronts per stream (2, or 1); cont = null
-// for whole streams
-int md_launch_inflate_wave(int format, uint32_t n, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len, uint8_t *out,
-                           const uint64_t *out_off, const uint64_t *out_cap, uint64_t *out_len, uint64_t *consumed, int32_t *status,
-                           uint32_t *checksum, uint64_t *dbg, uint32_t *order, int waves, const md::wv::Cont *cont, hipStream_t stream);
+int md_launch_inflate_wave(const md::wv::InfArgs *args, hipStream_t stream);
 int md_launch_stream_order(uint32_t n, const uint64_t *in_len, uint32_t *order, hipStream_t stream);
 // the size query (md_inflate_sizes_batch_device): the count kernel, `order` as above; dbg = null, or three u64 counters the
 // streams add to (rounds, passes, rounds that needed the checking walk)

@@ -1,6 +1,7 @@
 """Parity of the HIP inflate path (through the C ABI) with the CPU oracle and
 the reference's golden vectors.  Needs an MI355X: `pytest -m gpu`."""
 import ctypes
+import functools
 import random
 import zlib
 
@@ -179,13 +180,15 @@ def test_hand_over_between_block_kinds(eng_ring, oracle):
             assert out == plain
 
 
-def test_runs_of_tiny_blocks(eng_ring, oracle):
+@functools.lru_cache(None)
+def tiny_block_streams():
     """Runs of empty fixed blocks (zlib's Z_PARTIAL_FLUSH: header + end-of-block code, ten bits) and empty stored blocks
-    (Z_SYNC_FLUSH) between small data blocks: the kernel walks such runs through the window it has in LDS instead of
-    spending a round on each - whole, cut at every byte of a run, and with too little output room: status / count / bytes
-    as the oracle's."""
+    (Z_SYNC_FLUSH) between small data blocks.  Returns (wholes, cases): wholes = [(raw, plain)], the 24 seeded streams;
+    cases = [(src, cap, plain_len)], plain_len being that of the whole stream: each seeded stream whole with three output
+    rooms and cut inside its runs, then ten-bit blocks by hand.  The decode test below and the size query's
+    (tests/test_gpu_inflate_sizes.py) run them."""
     rng = random.Random(0xe3b)
-    srcs, caps = [], []
+    wholes, srcs, caps, plens = [], [], [], []
     for case in range(24):
         co = zlib.compressobj(6, zlib.DEFLATED, -15, 8, rng.choice((0, zlib.Z_FIXED)))
         body, plain = bytearray(), bytearray()
@@ -198,11 +201,13 @@ def test_runs_of_tiny_blocks(eng_ring, oracle):
         body += co.flush()
         raw, plain = bytes(body), bytes(plain)
         assert zlib.decompress(raw, -15) == plain
+        wholes.append((raw, plain))
         srcs += [raw, raw, raw]
         caps += [len(plain), len(plain) + 3, len(plain) // 2]
         for cut in sorted({rng.randrange(1, len(raw)) for _ in range(12)} | {len(raw) - 1, len(raw) - 2}):
             srcs.append(raw[:cut])
             caps.append(len(plain))
+        plens += [len(plain)] * (len(srcs) - len(plens))
     # ten-bit blocks by hand: a long run that ends the stream, one that ends without a final block, one followed by noise
     def bits_to_bytes(bits):
         b = bytearray((len(bits) + 7) // 8)
@@ -214,6 +219,15 @@ def test_runs_of_tiny_blocks(eng_ring, oracle):
         srcs += [bits_to_bytes(empty * run + final), bits_to_bytes(empty * run), bits_to_bytes(empty * run + [0, 1, 1]),
                  bits_to_bytes(empty * run + [0, 0, 0]) + b"\x05\x00\xfa\xffhello" + bits_to_bytes(final)]
         caps += [16, 16, 16, 16]
+        plens += [0, 0, 0, 5]
+    return wholes, list(zip(srcs, caps, plens))
+
+
+def test_runs_of_tiny_blocks(eng_ring, oracle):
+    """tiny_block_streams(): the kernel walks such runs through the window it has in LDS instead of spending a round on
+    each - whole, cut at every byte of a run, and with too little output room: status / count / bytes as the oracle's."""
+    _, cases = tiny_block_streams()
+    srcs, caps = [c[0] for c in cases], [c[1] for c in cases]
     res = eng_ring.inflate_many(srcs, caps)
     for src, cap, (st, used, out, _) in zip(srcs, caps, res):
         ost, oused, oout = oracle.de_inflate(src, cap)

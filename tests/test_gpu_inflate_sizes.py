@@ -16,6 +16,7 @@ from decompress_amd import workloads
 from tests.conftest import load_golden
 from tests.deflate_writer import Block, expand, write
 from tests.test_gpu_fuzz import _corrupt, _plain
+from tests.test_gpu_inflate import tiny_block_streams
 from tests.test_gpu_inflate_rounds import FAMILIES, _raw
 
 pytestmark = pytest.mark.gpu
@@ -95,6 +96,17 @@ def test_round_limits(eng, fam):
         est, eout = expand(blocks)
         assert (st, n) == (est, len(eout)), (name, st, n, est, len(eout))
         assert used == (len(_raw(blocks)) if est == OK else 0), name
+
+
+def test_runs_of_tiny_blocks(eng, oracle):
+    """2b. runs of empty fixed blocks and flush points (the decode test's streams, raw, one batch): the block loop walks them
+    through the window it has in LDS, past the window's end and the limit of its reuse in the runs of 1700, 1800 and 5000"""
+    _, cases = tiny_block_streams()
+    res = _sizes(eng, DE, [src for src, _, _ in cases])
+    assert len(res) == len(cases)
+    for (src, _, plain_len), r in zip(cases, res):
+        ost, oused, oout = oracle.de_inflate(src, plain_len + 16)  # room that never runs out
+        assert r == ((OK, oused, len(oout)) if ost == OK else (ost, 0, len(oout))), (len(src), plain_len, r, ost, oused, len(oout))
 
 
 def test_rounds_beyond_the_packed_count(eng):

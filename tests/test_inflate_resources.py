@@ -9,7 +9,7 @@ import subprocess
 from decompress_amd import _lib, build
 
 LLVM = "/opt/rocm/lib/llvm/bin"
-KERNEL = "_ZN2md2wv19inflate_wave_kernelILb0ELb1EEEvijPKhPKmS5_PhS5_S5_PmS7_PiPjS7_PKjNS0_4ContE"
+KERNEL = "inflate_wave_kernelILb0ELb1EE"  # <PROF = false, PAIR = true>, whatever its argument list
 
 
 def _kernel_metadata(so, tmp_path):
@@ -36,8 +36,9 @@ def _kernel_metadata(so, tmp_path):
 def test_inflate_pair_kernel_fits_nine_streams_per_cu(tmp_path):
     build.build()
     kernels = _kernel_metadata(_lib.SO, tmp_path)
-    assert KERNEL in kernels, sorted(k for k in kernels if "inflate" in k)
-    k = kernels[KERNEL]
+    names = [name for name in kernels if KERNEL in name]
+    assert len(names) == 1, sorted(k for k in kernels if "inflate" in k)
+    k = kernels[names[0]]
     assert k["group_segment_fixed_size"] <= 17920, k
     assert k["vgpr_count"] <= 96, k
     assert k["private_segment_fixed_size"] <= 40, k

@@ -27,6 +27,16 @@ def test_ns_vectors(oracle, case):
             assert out == bytes.fromhex(case["dst"])
 
 
+def test_tiny_block_streams(oracle):
+    """the GPU tests' runs of tiny blocks (tests/test_gpu_inflate.py): the whole streams are libz's, and the oracle's"""
+    from tests.test_gpu_inflate import tiny_block_streams
+    wholes, cases = tiny_block_streams()
+    assert len(wholes) == 24 and len(cases) > 24 * 5 + 28
+    for raw, plain in wholes:
+        assert zlib.decompress(raw, -15) == plain
+        assert oracle.de_inflate(raw, len(plain) + 16) == (0, len(raw), plain)
+
+
 @pytest.mark.parametrize("case", STREAM, ids=[c["name"] for c in STREAM])
 def test_stream_vectors(oracle, case):
     """De.Inf (streaming) cases: same bytes out, same error class."""
