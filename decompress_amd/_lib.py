@@ -141,6 +141,10 @@ SYMBOLS = [
     ("md_gz_members_last", ctypes.c_int, [c_vp, c_vp]),
     ("md_bgzf_compress_bound", c_sz, [c_sz, c_sz]),
     ("md_bgzf_compress", ctypes.c_int, [c_vp, ctypes.c_int, c_sz, c_vp, c_sz, c_vp, c_sz, c_szp]),
+    ("md_deflate_spans_bound", c_sz, [ctypes.c_int, c_sz, c_sz, ctypes.POINTER(GzHeader)]),
+    ("md_deflate_spans_host", ctypes.c_int, [c_vp, ctypes.c_int, c_pp, c_sz, c_vp, c_sz, c_vp, c_sz, c_szp, ctypes.POINTER(ctypes.c_uint32)]),
+    ("md_deflate_spans_device", ctypes.c_int, [c_vp, ctypes.c_int, c_pp, c_sz, c_vp, c_sz, c_vp, c_sz, c_vp, c_vp, c_vp]),
+    ("md_deflate_spans_last", ctypes.c_int, [c_vp, c_vp]),
     ("md_zip_directory", ctypes.c_int, [c_vp, c_sz, c_vp, c_vp, c_sz]),
     ("md_zip_uncompress", ctypes.c_int, [c_vp, c_vp, c_sz, c_vp, c_sz, c_vp, c_sz, c_vp, c_vp, c_vp]),
     ("md_zip_compress_bound", c_sz, [c_sz, c_vp]),
@@ -222,6 +226,11 @@ class GzMembersStats(ctypes.Structure):
     """md_gz_members_stats of include/mdeflate.h"""
     _fields_ = [("path", ctypes.c_int)] + [(k, c_sz) for k in ("candidates", "spans_decoded", "members_device", "members_host",
                                                                 "spans_long", "spans_no_room", "spans_implausible")]
+
+
+class DeflateSpansInfo(ctypes.Structure):
+    """md_deflate_spans_info of include/mdeflate.h"""
+    _fields_ = [(k, c_sz) for k in ("spans", "stored_spans", "span_bytes")]
 
 
 class GzMeta(ctypes.Structure):

@@ -1,13 +1,17 @@
 """`decompress` — the reference's command line tool (bin/decompress.ml:226-344) over the GPU engine.
 
-    python -m decompress_amd.cli [-d] [-f deflate|zlib|gzip|lzo] [-l <level>] [<input> [<output>]]
+    python -m decompress_amd.cli [-d] [-f deflate|zlib|gzip|lzo] [-l <level>] [--span <KiB>] [<input> [<output>]]
 
 Same flags, defaults and drivers as the reference: inflate unless `-d`; format `deflate` unless `-f`; level 4
 unless `-l`; stdin / stdout unless file names are given.  `-d` on raw DEFLATE is the CLI's own driver
 (`run_deflate`, bin/decompress.ml:47-75: a Dynamic block per queue flush, then a Fixed last block that holds only
 the end-of-block code — MD_DRIVER_CLI), zlib and gzip go through `Zl.Def` / `Gz.Def` (gzip: mtime = now, OS Unix,
 bin/decompress.ml:136-155), LZO through `Lzo.compress` / `Lzo.uncompress_with_buffer`.  A malformed input prints
-`decompress: <the reference's message>.` and exits with cmdliner's error status (124)."""
+`decompress: <the reference's message>.` and exits with cmdliner's error status (124).
+
+`--span <KiB>` is this tool's own: with `-d` and `-f deflate|zlib|gzip` the stream is written as joined spans of that
+many KiB by the whole chip (md_deflate_spans_host; same drivers and header); without `-d`, or with `-f lzo`, it
+is an error.  Without it the bytes are the reference's."""
 import sys
 import time
 
@@ -59,7 +63,29 @@ def parse(argv):
     return deflate, fmt, level, (pos[0] if pos else None), (pos[1] if len(pos) > 1 else None)
 
 
-def run(deflate, fmt, level, data, now=None):
+def take_span(argv):
+    """`--span <KiB>` / `--span=<KiB>` out of argv -> (the other arguments, span in bytes or None)"""
+    rest, span, i = [], None, 0
+    while i < len(argv):
+        a = argv[i]
+        if a == "--span" or a.startswith("--span="):
+            if a == "--span":
+                i += 1
+                if i >= len(argv):
+                    raise ValueError("option '--span' needs an argument")
+                v = argv[i]
+            else:
+                v = a[len("--span="):]
+            if not v.isdigit() or int(v) < 1:
+                raise ValueError("Invalid span")
+            span = int(v) << 10
+        else:
+            rest.append(a)
+        i += 1
+    return rest, span
+
+
+def run(deflate, fmt, level, data, now=None, span=None):
     """one run of the tool on `data` -> (exit status, output bytes, message for stderr)"""
     import decompress_amd
     from decompress_amd import de, engine, gz, lzo
@@ -67,6 +93,17 @@ def run(deflate, fmt, level, data, now=None):
     if deflate:
         if fmt == "lzo":
             return 0, lzo.compress(data), None
+        if span is not None:  # the same drivers and header as below, the stream in joined spans
+            f = {"deflate": decompress_amd.FORMAT_DEFLATE, "zlib": decompress_amd.FORMAT_ZLIB, "gzip": decompress_amd.FORMAT_GZIP}[fmt]
+            hdr = None
+            if fmt == "gzip":
+                mtime = int(time.time() if now is None else now) & 0xffffffff
+                hdr = dict(mtime=mtime, os=gz.OS["Unix"], hcrc=0, ascii=0, filename=None, comment=None)
+            st, out, _ = eng.deflate_spans(data, f, span=span, level=level, queue=QUEUE,
+                                           driver=engine.DRIVER_CLI if fmt == "deflate" else engine.DRIVER_ZL, header=hdr)
+            if st != 0:
+                return CLI_ERROR, b"", engine.STATUS_NAMES[st]
+            return 0, out, None
         if fmt == "deflate":
             st, out, _ = eng.deflate_one(data, decompress_amd.FORMAT_DEFLATE, level=level, queue=QUEUE,
                                          driver=engine.DRIVER_CLI)
@@ -100,12 +137,15 @@ def run(deflate, fmt, level, data, now=None):
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     try:
+        argv, span = take_span(argv)
         deflate, fmt, level, fin, fout = parse(argv)
+        if span is not None and (not deflate or fmt == "lzo"):
+            raise ValueError("option '--span' needs '-d' and a format of deflate, zlib or gzip")
     except ValueError as e:
         sys.stderr.write("decompress: %s\n" % e)
         return CLI_ERROR
     data = open(fin, "rb").read() if fin else sys.stdin.buffer.read()
-    status, out, msg = run(deflate, fmt, level, data)
+    status, out, msg = run(deflate, fmt, level, data, span=span)
     oc = open(fout, "wb") if fout else sys.stdout.buffer
     oc.write(out)
     oc.flush()

@@ -258,6 +258,11 @@ int md_set_option(md_ctx *ctx, const char *key, int value) {
     ctx->link_seg = (size_t)value << 10;
     return MD_OK;
   }
+  if (!strcmp(key, "deflate_span_kib")) {  // KiB of text per span of md_deflate_spans_* called with span = 0; 0 = the default
+    if (value < 0 || value > (int)(MD_MAX_STREAM >> 10)) return fail(ctx, MD_E_INVALID_ARGUMENT, "deflate_span_kib is 0 .. MD_MAX_STREAM / 1024");
+    ctx->span_bytes = value ? (size_t)value << 10 : md::kSpanDefault;
+    return MD_OK;
+  }
   if (!strcmp(key, "gz_members_speculate")) {  // md_gz_members_uncompress, a file without size fields: 1 = members found by speculation, one batch
     if (value != 0 && value != 1) return fail(ctx, MD_E_INVALID_ARGUMENT, "gz_members_speculate is 0 or 1");
     ctx->gzm_speculate = value != 0;

@@ -17,7 +17,7 @@ constexpr size_t kOrderFromDeflate = 257;  // the link kernel holds one stream p
 
 // The bytes Gz.Def writes in front of the body (lib/gz.ml:796-812) for the header fields of Gz.Def.encoder
 // (lib/gz.ml:859-918); returns the length, 0 when a field is out of range.
-static uint32_t gz_header_bytes(const md_gz_header *g, int level, uint8_t h[544]) {
+uint32_t gz_header_bytes(const md_gz_header *g, int level, uint8_t h[544]) {
   static const md_gz_header dflt = {0, 3, 0, 0, nullptr, nullptr};
   if (!g) g = &dflt;
   const size_t nl = g->filename ? strlen(g->filename) : 0, cl = g->comment ? strlen(g->comment) : 0;
@@ -100,12 +100,12 @@ static int front_workspace(md_ctx *ctx, size_t n, const uint64_t *d_len, int dri
   return MD_OK;
 }
 
-// total_in as in front_workspace.
+// total_in as in front_workspace.  d_tail: SeqArgs::tail (two words per stream), or null.
 static int deflate_launch(md_ctx *ctx, int format, int level, int queue_len, int driver, int dynamic, int matcher,
                           const md_gz_header *gz, size_t n, const uint8_t *d_in, const uint64_t *d_in_off,
                           const uint64_t *d_in_len, uint8_t *d_out, const uint64_t *d_out_off, const uint64_t *d_out_cap,
                           uint64_t *d_out_len, int32_t *d_status, uint32_t *d_checksum, uint32_t *d_hist, size_t total_in,
-                          const PieceArgs *pa = nullptr, const LinkSegs *ls = nullptr) {
+                          const PieceArgs *pa = nullptr, const LinkSegs *ls = nullptr, uint64_t *d_tail = nullptr) {
   int grc_ = MD_OK;
   // (the Lz77-alone / encode-alone / scripted drivers leave the kernel before it saves a piece's state)
   if (pa && driver >= md::defl::DRV_LZ77) return fail(ctx, MD_E_INVALID_ARGUMENT, "a stream in pieces needs one of the three public drivers");
@@ -175,6 +175,7 @@ static int deflate_launch(md_ctx *ctx, int format, int level, int queue_len, int
   args.hist = d_hist;
   args.order = order;
   if (pa) args.pcs = pa->piece;
+  args.tail = d_tail;
   MD_LAUNCH_TRY(ctx, md_launch_deflate(&args, ctx->stream));
   return MD_OK;
 }
@@ -295,7 +296,11 @@ struct SliceHooks {
 static int deflate_in_slices(md_ctx *ctx, int format, const md_deflate_params &q, size_t n, uint64_t S, const uint8_t *d_in,
                              const uint64_t *h_in_off, const uint64_t *h_in_len, uint8_t *d_out, const uint64_t *h_out_off,
                              const uint64_t *h_out_cap, uint64_t *h_out_len, int32_t *h_status, uint32_t *h_checksum,
-                             const uint32_t *h_crc, const SliceHooks *hooks = nullptr) {
+                             const uint32_t *h_crc, const SliceHooks *hooks = nullptr, uint64_t *d_tail = nullptr,
+                             uint64_t *h_tail = nullptr) {
+  // (d_tail / h_tail: SeqArgs::tail of the n streams.  The launch that ends a stream leaves its two words in d_tail, counted
+  // from that piece's output; h_tail gets them counted from the stream's first byte)
+  std::vector<uint64_t> tl(d_tail ? 2 * n : 0);
   // state slots for the streams that do not end in the first slice
   std::vector<uint64_t> slot(n, 0), used(n, 0);
   std::vector<uint8_t> done(n, 0);
@@ -361,7 +366,7 @@ static int deflate_in_slices(md_ctx *ctx, int format, const md_deflate_params &q
     // (every stream of a later slice stopped less than 262 + 64 short of the slice before's end)
     PieceArgs pa{d64 + n, ctx->scratch[kWs].p, {d32 + 2 * n, (uint8_t *)ctx->scratch[kSliceState].p, d64 + 6 * n, d32 + 3 * n}, k == 0 ? 0u : (uint32_t)kSliceKeep - 512u};
     rc = deflate_launch(ctx, format, q.level, q.queue_len, q.driver, q.dynamic, q.matcher, q.gz_header, n, d_in, d64, d64 + 2 * n,
-                        d_out, d64 + 3 * n, d64 + 4 * n, d64 + 5 * n, (int32_t *)d32, d32 + n, nullptr, total ? total : 1, &pa);
+                        d_out, d64 + 3 * n, d64 + 4 * n, d64 + 5 * n, (int32_t *)d32, d32 + n, nullptr, total ? total : 1, &pa, nullptr, d_tail);
     if (rc != MD_OK) return rc;
     if (hooks) {  // (in front of the read-backs: a copy to pageable memory keeps the calling thread until the kernels are done)
       rc = hooks->launched(k);
@@ -369,6 +374,7 @@ static int deflate_in_slices(md_ctx *ctx, int format, const md_deflate_params &q
     }
     HIP_TRY(ctx, hipMemcpyAsync(out_len, d64 + 5 * n, n * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(st, d32, 2 * n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (d_tail) HIP_TRY(ctx, hipMemcpyAsync(tl.data(), d_tail, 2 * n * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     for (size_t i = 0; i < n; i++) {
       if (flags[i] & 8) continue;
@@ -377,6 +383,7 @@ static int deflate_in_slices(md_ctx *ctx, int format, const md_deflate_params &q
         continue;
       }
       done[i] = 1;
+      if (h_tail) h_tail[2 * i] = 8 * used[i] + tl[2 * i], h_tail[2 * i + 1] = 8 * used[i] + tl[2 * i + 1];
       h_status[i] = (int32_t)st[i];
       h_checksum[i] = sum_out[i];
       h_out_len[i] = (int32_t)st[i] == MD_OK ? used[i] + out_len[i] : 0;
@@ -397,7 +404,8 @@ static int deflate_in_slices(md_ctx *ctx, int format, const md_deflate_params &q
 // slice of every stream at once would still be too much), results back to the caller's device arrays
 static int deflate_capped(md_ctx *ctx, int format, const md_deflate_params &q, size_t n, const uint8_t *d_in, const uint64_t *d_in_off,
                           const uint64_t *d_in_len, uint8_t *d_out, const uint64_t *d_out_off, const uint64_t *d_out_cap,
-                          uint64_t *d_out_len, int32_t *d_status, uint32_t *d_checksum, bool *whole, uint64_t *total_out) {
+                          uint64_t *d_out_len, int32_t *d_status, uint32_t *d_checksum, uint64_t *d_tail, bool *whole,
+                          uint64_t *total_out) {
   std::vector<uint64_t> h(4 * n);
   uint64_t *in_off = h.data(), *in_len = in_off + n, *out_off = in_len + n, *out_cap = out_off + n;
   HIP_TRY(ctx, hipMemcpyAsync(in_off, d_in_off, n * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -418,6 +426,7 @@ static int deflate_capped(md_ctx *ctx, int format, const md_deflate_params &q, s
   std::vector<uint64_t> r_len(n);
   std::vector<int32_t> r_st(n);
   std::vector<uint32_t> r_sum(n), crc;
+  std::vector<uint64_t> r_tail(d_tail ? 2 * n : 0);
   if (format == MD_FORMAT_GZIP) {  // the CRC-32 of every stream, once
     int grc = ctx->gz_tmp.reserve(ctx, n * 24, "hipMalloc(gzip scratch)");
     if (grc != MD_OK) return grc;
@@ -462,23 +471,25 @@ static int deflate_capped(md_ctx *ctx, int format, const md_deflate_params &q, s
       break;
     }
     int rc = deflate_in_slices(ctx, format, q, k, S, d_in, in_off + i0, in_len + i0, d_out, out_off + i0, out_cap + i0, r_len.data() + i0,
-                               r_st.data() + i0, r_sum.data() + i0, crc.empty() ? nullptr : crc.data() + i0);
+                               r_st.data() + i0, r_sum.data() + i0, crc.empty() ? nullptr : crc.data() + i0, nullptr,
+                               d_tail ? d_tail + 2 * i0 : nullptr, d_tail ? r_tail.data() + 2 * i0 : nullptr);
     if (rc != MD_OK) return rc;
     i0 += k;
   }
   HIP_TRY(ctx, hipMemcpyAsync(d_out_len, r_len.data(), n * 8, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(d_status, r_st.data(), n * 4, hipMemcpyHostToDevice, ctx->stream));
   if (d_checksum) HIP_TRY(ctx, hipMemcpyAsync(d_checksum, r_sum.data(), n * 4, hipMemcpyHostToDevice, ctx->stream));
+  if (d_tail) HIP_TRY(ctx, hipMemcpyAsync(d_tail, r_tail.data(), 2 * n * 8, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the host vectors go out of scope)
   *whole = false;
   return MD_OK;
 }
 
-// ls: ONE stream whose hash chains go in segments (md_deflate_batch_host), else null
+// ls: ONE stream whose hash chains go in segments (md_deflate_batch_host), else null; d_tail: SeqArgs::tail, or null
 static int deflate_batch_device(md_ctx *ctx, int format, const md_deflate_params *params, size_t n, const uint8_t *d_in,
                                 const uint64_t *d_in_off, const uint64_t *d_in_len, uint8_t *d_out, const uint64_t *d_out_off,
                                 const uint64_t *d_out_cap, uint64_t *d_out_len, int32_t *d_status, uint32_t *d_checksum,
-                                const LinkSegs *ls) {
+                                const LinkSegs *ls, uint64_t *d_tail = nullptr) {
   if (!ctx) return MD_E_INVALID_ARGUMENT;
   ctx->link_last_segments = 0;
   md_deflate_params q;
@@ -499,7 +510,8 @@ static int deflate_batch_device(md_ctx *ctx, int format, const md_deflate_params
         (!q.total_in_bytes || md_front_big_bytes((uint64_t)q.total_in_bytes + kSlotPad * n) > ctx->front_cap_bytes)) {
       bool whole = true;
       uint64_t total = 0;
-      rc = deflate_capped(ctx, format, q, n, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status, d_checksum, &whole, &total);
+      rc = deflate_capped(ctx, format, q, n, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status, d_checksum, d_tail, &whole,
+                          &total);
       if (rc != MD_OK || !whole) return rc;
       // the batch fits the cap after all: one launch, sized from the sum just read back (no second read-back in
       // deflate_launch, and a loose hint cannot make the workspace grow above the cap)
@@ -508,7 +520,14 @@ static int deflate_batch_device(md_ctx *ctx, int format, const md_deflate_params
   }
   return deflate_launch(ctx, format, q.level, q.queue_len, q.driver, q.dynamic, q.matcher, q.gz_header, n, d_in, d_in_off,
                         d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status, d_checksum, nullptr, q.total_in_bytes,
-                        nullptr, ls);
+                        nullptr, ls, d_tail);
+}
+
+int deflate_batch_tails(md_ctx *ctx, int format, const md_deflate_params *params, size_t n, const uint8_t *d_in, const uint64_t *d_in_off,
+                        const uint64_t *d_in_len, uint8_t *d_out, const uint64_t *d_out_off, const uint64_t *d_out_cap, uint64_t *d_out_len,
+                        int32_t *d_status, uint32_t *d_checksum, uint64_t *d_tail) {
+  return deflate_batch_device(ctx, format, params, n, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status,
+                              d_checksum, nullptr, d_tail);
 }
 
 int md_deflate_batch_device(md_ctx *ctx, int format, const md_deflate_params *params, size_t n, const uint8_t *d_in,

@@ -66,6 +66,10 @@ inline size_t blob_room(size_t need) { return need + need / 4 + 4096; }
 // 2 464 deflated ones (all five within 1 % of each other) - 4 096 wavefronts for 1 GiB, 16 a CU
 constexpr size_t kZipSegmentDefault = (size_t)256 << 10;
 
+// md_set_option "deflate_span_kib" = 0: text per span of md_deflate_spans_*.  The largest of 64 KiB .. 1 MiB whose time for
+// 64 MiB is within 10 % of the fastest, on text and on random bytes (51.9 ms; 128 KiB takes 57.4 ms on text)
+constexpr size_t kSpanDefault = (size_t)64 << 10;
+
 // One allocation of device (or pinned host) memory and its capacity.  It frees itself when its owner goes: whoever
 // deletes the owner sets the device and waits for the context's stream first.  Grow-only, and growing does not keep the
 // contents (reserve_keep does).
@@ -127,6 +131,7 @@ enum Scratch {
   // a GZip file of many members (md_gz_members_*, md_bgzf_compress): the member scan's bitmap and counts, its candidate
   // lists, the members' descriptors, and the writer's packed file (the reader of a file without size fields decodes its
   // batch into that one: its host steps go through kHostIn / kHostOut)
+  // (md_deflate_spans_*: descriptors in kGzmDesc, the joined stream of the host form in kGzmOut, slots in kHostOut)
   kGzmWs, kGzmCand, kGzmDesc, kGzmOut,
   // a ZIP archive (md_zip_*): rows, names, descriptors and the segment table; the writer's file image (archive bytes and
   // decoded entries / encoder slots go through kHostIn / kHostOut)
@@ -188,6 +193,12 @@ struct md_ctx {
   // round of md_bgzf_read; 0 = one member a round) and the counts of the last read (md_bgzf_read_last)
   size_t bgr_workspace = (size_t)256 << 20;
   md_bgzf_read_stats bgr_last = {};
+  // one stream written as joined spans: md_set_option "deflate_span_kib" (the span of a call that passes 0) and the counts of
+  // the last md_deflate_spans_* call (md_deflate_spans_last)
+  size_t span_bytes = md::kSpanDefault;
+  md_deflate_spans_info spans_last = {};
+  md::DevBuf spans_count;      // the device word that counts the stored spans of a call
+  bool spans_pending = false;  // spans_last.stored_spans is still in spans_count (the device form reads nothing back)
   std::string err;
 };
 
@@ -334,6 +345,14 @@ int md_get_profile(md_ctx *ctx, uint64_t *out32);
 }
 
 #pragma GCC visibility push(hidden)
+// ---- capi_deflate.cpp ----
+// The bytes Gz.Def writes in front of the body for the header fields g (null: the default header); returns the length, 0
+// when a field is out of range.
+uint32_t gz_header_bytes(const md_gz_header *g, int level, uint8_t h[544]);
+// md_deflate_batch_device that also leaves every stream's tail (SeqArgs::tail of internal.hpp: two words per stream) in d_tail
+int deflate_batch_tails(md_ctx *ctx, int format, const md_deflate_params *params, size_t n, const uint8_t *d_in, const uint64_t *d_in_off,
+                        const uint64_t *d_in_len, uint8_t *d_out, const uint64_t *d_out_off, const uint64_t *d_out_cap, uint64_t *d_out_len,
+                        int32_t *d_status, uint32_t *d_checksum, uint64_t *d_tail);
 // ---- capi_inflate.cpp ----
 // One piece of a raw DEFLATE stream through one pair of wavefronts, its output LEFT ON THE DEVICE: src[0, src_len) starts
 // start_bit bits into src[0], hist[0, hist_len) is the output in front of it and goes to the start of kContOut, the new

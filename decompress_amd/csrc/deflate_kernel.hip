@@ -120,6 +120,9 @@ struct DS {
   struct WCtl {
     uint64_t hold;
     uint32_t bits, o_pos, o_cap, qr, qw, qc, kind, last, overflow, rc, k, hdr;
+    // SeqArgs::tail, as o_pos * 8 + bits mod 2^32: where the closing block's header began (lane 0, emit_header), and
+    // where its end-of-block code ended (enc_write_wave)
+    uint32_t tail_h, tail_e;
     uint8_t *o;
     int *q;
   } w;
@@ -682,7 +685,8 @@ __device__ __forceinline__ void emit_eob(const DS *s, Enc *e) {
   lit_code(s, e, 256, &l, &c);
   put_bits(e, (unsigned)c, l);
 }
-__device__ __forceinline__ void emit_header(const DS *s, Enc *e) {  // lib/de.ml:2566-2633
+__device__ __forceinline__ void emit_header(DS *s, Enc *e) {  // lib/de.ml:2566-2633
+  if (e->last) s->w.tail_h = e->o_pos * 8 + (uint32_t)e->bits;
   put_bits(e, e->last ? 1 : 0, 1);
   if (e->kind == KIND_FIXED) put_bits(e, 1, 2);
   else if (e->kind == KIND_DYNAMIC) {
@@ -723,7 +727,7 @@ __device__ __forceinline__ void flat_len(Enc *e) {
 constexpr int W_PENDING = 2;  // enc_begin: the command loop (write, lib/de.ml:2708-2897) is still to run
 
 // block, lib/de.ml:2657-2684, up to the command loop
-__device__ __forceinline__ int enc_block_begin(const DS *s, Enc *e, int kind, int last) {
+__device__ __forceinline__ int enc_block_begin(DS *s, Enc *e, int kind, int last) {
   e->kind = kind;
   e->last = last;
   if (kind == KIND_FLAT) flat_len(e);
@@ -735,7 +739,7 @@ __device__ __forceinline__ int enc_block_begin(const DS *s, Enc *e, int kind, in
 // trees in DS — but force must close the OLD block first, whose EOB code comes from the old
 // trees; the caller passes it in.  Returns R_OK / R_BLOCK, or W_PENDING when the command
 // loop of a Fixed/Dynamic block has to run next (enc_write_wave, all lanes).
-__device__ __forceinline__ int enc_begin(const DS *s, Enc *e, int v, int kind, int last, int old_eob_len, int old_eob_code) {
+__device__ __forceinline__ int enc_begin(DS *s, Enc *e, int v, int kind, int last, int old_eob_len, int old_eob_code) {
   for (;;) {
     switch (e->k) {
     case K_FIRST_ENTRY:
@@ -770,7 +774,8 @@ struct Pack {
 // Appends one item of nb <= 48 bits per lane, in lane order: a wave prefix sum of the lengths
 // gives each item its bit offset, the items are OR-ed into an LDS bit buffer behind the bits
 // still held, and the finished bytes go out 4 per lane.  pad = pending_bits of the last block
-// (lib/de.ml:2635-2653): the final partial byte goes out too.
+// (lib/de.ml:2635-2653): the final partial byte goes out too.  Returns, for a padded step, the bit offset at which its
+// last item ended (mod 2^32, in a scalar register: no lane holds it while the step runs).
 // inclusive prefix sum over the wavefront in six data-parallel-primitive steps (row shifts inside the rows of 16 lanes,
 // then the two row broadcasts): no LDS round trip — a shuffle-based scan is six dependent ones
 __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
@@ -785,7 +790,7 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
 // (One wavefront owns the bit buffer, and a wavefront's LDS operations execute in program order: the phases need no
 // barrier.  A workgroup barrier here also waits for the step's global stores to complete — a microsecond per step.)
 __device__ __forceinline__ void lds_order() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); }
-__device__ void pack_step(DS *s, uint32_t lane, uint64_t v, uint32_t nb, uint64_t v1, uint32_t nb1, bool pad, Pack &p) {
+__device__ uint32_t pack_step(DS *s, uint32_t lane, uint64_t v, uint32_t nb, uint64_t v1, uint32_t nb1, bool pad, Pack &p) {
   // (two items per lane, the second right behind the first: a step of the command loop takes 128 commands - what a step
   // costs is its chain of dependent operations, hardly longer for two items than for one)
   const uint32_t incl = wave_incl_scan(nb + nb1);
@@ -826,6 +831,7 @@ __device__ void pack_step(DS *s, uint32_t lane, uint64_t v, uint32_t nb, uint64_
   p.bits = rem;
   p.o_pos += nbytes;
   lds_order();
+  return (uint32_t)__builtin_amdgcn_readfirstlane((int)(p.o_pos * 8 - (-total & 7u)));
 }
 
 // write, lib/de.ml:2708-2897, by the whole wave: 64 queue commands per step.  Every lane
@@ -838,7 +844,7 @@ __device__ void enc_write_wave(DS *s, uint32_t lane) {
   uint32_t qr = s->w.qr;
   const uint32_t qw = s->w.qw, qc = s->w.qc, kind = s->w.kind, last = s->w.last;
   const int *q = s->w.q;
-  uint32_t rc = R_OK, knew = K_ENCODE;
+  uint32_t rc = R_OK, knew = K_ENCODE, tail_e = 0;
   if (s->w.hdr) {
     const uint32_t h_len = (uint32_t)s->h_len, items = h_len + (uint32_t)s->nsymbols;
     for (uint32_t base = 0; base < items; base += kWave) {
@@ -926,7 +932,7 @@ __device__ void enc_write_wave(DS *s, uint32_t lane) {
     const bool stop = sp < kStep;
     const uint64_t e0 = __builtin_amdgcn_ballot_w64(a0.is_eob), e1 = __builtin_amdgcn_ballot_w64(a1.is_eob);
     const bool end_cmd = stop && ((((sp & 1) ? e1 : e0) >> (sp >> 1)) & 1) != 0;
-    pack_step(s, lane, v0, nb0, v1, nb1, end_cmd && last, p);
+    tail_e = pack_step(s, lane, v0, nb0, v1, nb1, end_cmd && last, p);
     qr += stop ? sp + (end_cmd ? 1u : 0u) : (avail < kStep ? avail : kStep);
     if (stop) {
       if (end_cmd && last) {
@@ -948,6 +954,7 @@ __device__ void enc_write_wave(DS *s, uint32_t lane) {
     s->w.rc = rc;
     s->w.k = knew;
     s->w.hdr = 0;
+    s->w.tail_e = tail_e;  // (it counts where this call ended the closing block: the last call of a stream)
   }
 }
 
@@ -1355,7 +1362,7 @@ bad:
 
 // Ask the encoder for a block of the kind the driver plans (`Block {kind; last}): its answer in rc.  When the kind
 // needs trees first, remember the mode and the phase to come back in and return false: the caller answers ACT_TREES.
-__device__ __forceinline__ bool block_begin(const DS *s, Run *r, int driver, int dynamic, int last, int trees_phase, int &rc) {
+__device__ __forceinline__ bool block_begin(DS *s, Run *r, int driver, int dynamic, int last, int trees_phase, int &rc) {
   const int kind = block_plan(driver, dynamic, r->z.level, last);
   if (kind < 0) {
     r->mode = -kind;
@@ -1752,6 +1759,10 @@ __device__ __forceinline__ void piece_resume(const SeqArgs &a, const Strm &t, co
 // the matcher waits for input the piece does not hold: the state goes out, nothing else
 __device__ __forceinline__ void piece_suspend(const SeqArgs &a, const Strm &t, DS &ds, Run &run, uint32_t hdr, uint32_t lane) {
   __syncthreads();
+  if (a.tail) {  // SeqArgs::tail: the header's note counts from where the next piece's output begins
+    if (lane == 0) ds.w.tail_h -= run.e.o_pos * 8;
+    __syncthreads();
+  }
   piece_state_move<true>(ds, run, reinterpret_cast<uint32_t *>(a.pcs.state + t.sslot * kPieceState), lane);
   if (lane == 0) report(a, t.sid, hdr + run.e.o_pos, run.e.overflow ? MD_UNEXPECTED_END_OF_OUTPUT : MD_PIECE_AWAIT, run.adler);
 }
@@ -2086,8 +2097,15 @@ __device__ __forceinline__ void lane0_publish(DS &ds, Run &run, int act, uint32_
 }
 
 // ---- exits (the LZ77-alone one is in the kernel).  The stream ended: its status, and the frame's trailer behind the body (lane 0)
-__device__ __forceinline__ void frame_trailer(const SeqArgs &a, const Strm &t, const Run &run, uint32_t hdr, bool room) {
+__device__ __forceinline__ void frame_trailer(const SeqArgs &a, const Strm &t, const DS &ds, const Run &run, uint32_t hdr, bool room) {
   const uint32_t adler = run.adler;
+  if (a.tail) {  // SeqArgs::tail.  The closing block is less than 2^32 bits long: the low words say how far back from the end
+    const uint64_t end = 8ull * run.e.o_pos;
+    // a stored closing block ends with its last byte; behind an end-of-block code come at most 7 bits of padding
+    const uint64_t e = run.e.kind == KIND_FLAT ? end : end - (uint32_t)((uint32_t)end - ds.w.tail_e);
+    a.tail[2 * (size_t)t.sid] = 8ull * hdr + e - (uint32_t)((uint32_t)e - ds.w.tail_h);
+    a.tail[2 * (size_t)t.sid + 1] = 8ull * hdr + e;
+  }
   // The output pointer and the input's length mod 2^32 for gzip's trailer (in pieces: the caller's count) are read from
   // the descriptors again here, where they are needed: carried through the loop they cost registers and a spill
   uint8_t *dst = a.out + a.out_off[t.sid];
@@ -2228,7 +2246,7 @@ __global__ __launch_bounds__(kWave, 4) void deflate_kernel(const SeqArgs a) {
     // on overflow: the size the caller needs (mdeflate.h)
     if (lane == 0) report(a, t.sid, room ? 4ull * run.ncmd : 0, room && !run.e.overflow ? MD_OK : MD_UNEXPECTED_END_OF_OUTPUT, run.adler);
   } else if (t.piece && ds.ctl[1] == 2) piece_suspend(a, t, ds, run, hdr, lane);
-  else if (lane == 0) frame_trailer(a, t, run, hdr, room);
+  else if (lane == 0) frame_trailer(a, t, ds, run, hdr, room);
 }
 
 }  // namespace defl

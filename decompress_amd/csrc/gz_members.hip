@@ -28,6 +28,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "copy_bytes.hpp"
 #include "gz_rfc.hpp"
 #include "internal.hpp"
 #include "mdeflate.h"
@@ -270,19 +271,6 @@ __global__ void bgzf_size_kernel(uint64_t nb, const uint64_t *__restrict__ in_le
   // (a body that did not fit its slot of n + 5 bytes is longer than the stored form)
   if (st != MD_OK && st != MD_UNEXPECTED_END_OF_OUTPUT) atomicMax(err, st);
   msize[i] = bgzf_deflated(st, out_len[i], in_len[i]) ? kBgzfFrame + out_len[i] : kBgzfFrame + 5 + in_len[i];
-}
-
-// n bytes a -> o, 256 threads: 16-byte stores on o's alignment, a read with unaligned 16-byte loads
-__device__ __forceinline__ void copy_bytes(uint8_t *__restrict__ o, const uint8_t *__restrict__ a, uint64_t n) {
-  const uint64_t head = (16 - ((uintptr_t)o & 15)) & 15, h1 = head < n ? head : n;
-  for (uint64_t k = threadIdx.x; k < h1; k += 256) o[k] = a[k];
-  const uint64_t body = (n - h1) & ~(uint64_t)15;
-  for (uint64_t k = h1 + (uint64_t)threadIdx.x * 16; k < h1 + body; k += 256 * 16) {
-    uint4 v;
-    __builtin_memcpy(&v, a + k, 16);
-    *reinterpret_cast<uint4 *>(o + k) = v;
-  }
-  for (uint64_t k = h1 + body + threadIdx.x; k < n; k += 256) o[k] = a[k];
 }
 
 __global__ __launch_bounds__(256) void bgzf_pack_kernel(uint64_t nb, const uint8_t *__restrict__ src, const uint64_t *__restrict__ in_off,

@@ -85,6 +85,14 @@ struct SeqArgs {
   uint32_t *hist;         // the partial drivers' second result (histograms / replies), or null
   const uint32_t *order;  // launch order (longest first), or null for index order
   Piece pcs;              // every pointer null: whole streams
+  // Each stream's tail (the writer of joined spans, deflate_spans.hip), or null: tail[2i] = h, the bit offset of the
+  // header of the stream's closing block (its BFINAL bit), tail[2i + 1] = e, the bit offset behind that block's last bit
+  // (behind its end-of-block code; a stored block: its byte-aligned end).  Both count from the first byte the launch
+  // wrote of the stream, the frame's header included; in pieces the launch that ends the stream writes them, and h is
+  // negative (two's complement) when the header went out with an earlier piece.  Garbage unless status[i] is MD_OK.
+  // (Null changes no byte and no result; the two notes the words are made from - one LDS store where a closing block's
+  // header is put, one scalar move per packing step - are taken either way: they cost less than asking.)
+  uint64_t *tail;
 };
 
 }  // namespace defl
@@ -144,6 +152,35 @@ constexpr uint64_t kLongShare = 1024;
 constexpr uint32_t kSpanVerified = 1;
 constexpr uint32_t kSpanAdmitted = 0, kSpanImplausible = 1, kSpanLong = 2, kSpanNoRoom = 3;
 }  // namespace gzs
+
+namespace spn {
+// One stream written as joined spans (deflate_spans.hip).  The stored form of a span of n bytes: stored blocks of at
+// most 65 535 bytes, all but the last full (the empty text: one empty block).
+constexpr uint64_t kStoredMax = 65535;
+constexpr uint64_t stored_blocks(uint64_t n) { return n ? (n + kStoredMax - 1) / kStoredMax : 1; }
+constexpr uint64_t stored_size(uint64_t n) { return n + 5 * stored_blocks(n); }
+// what stands around the body: the header's bytes (none, Zl.Def's two, Gz.Def's), and by the format the trailer
+struct Frame {
+  int format;
+  uint32_t hdr_len;
+  uint8_t hdr[544];
+};
+constexpr uint32_t trailer_len(int format) { return format == MD_FORMAT_ZLIB ? 4u : format == MD_FORMAT_GZIP ? 8u : 0u; }
+// The spans of a call: device arrays of n entries.  in_off .. tail are the deflate launch's descriptors and results (tail:
+// SeqArgs::tail, two words per span), adler its checksums, crc md_launch_crc32's (MD_FORMAT_GZIP, else null).  size[i]: the
+// bytes span i takes in the body, off (n + 1 entries): their scan.  err: two words preset to 0 - [0] the largest per-stream
+// status (positive) of the encoder that is neither MD_OK nor "no room", [1] the least call-level error (negative): a span's
+// own, or MD_E_HIP where a tail does not fit its body; stored: the count of stored spans.
+struct Spans {
+  uint64_t n, len;
+  const uint64_t *in_off, *in_len, *slot_off, *out_len, *tail;
+  const int32_t *status;
+  const uint32_t *adler, *crc;
+  uint64_t *size, *off;
+  int32_t *err;
+  uint64_t *stored;
+};
+}  // namespace spn
 
 namespace zip {
 // One selected entry of a ZIP archive as the host hands it to zip_kernels.hip: the directory's word on it.  name_pos: its
@@ -304,6 +341,19 @@ int md_launch_bgzf_sizes(uint64_t nb, const uint64_t *in_len, const uint64_t *ou
 int md_launch_bgzf_pack(uint64_t nb, const uint8_t *src, const uint64_t *in_off, const uint64_t *in_len, const uint8_t *slots,
                         const uint64_t *slot_off, const uint64_t *out_len, const int32_t *status, const uint64_t *moff, const uint32_t *crc,
                         uint8_t *dst, hipStream_t stream);
+
+// ---- deflate_spans.hip: one stream as joined spans (md_deflate_spans_*) ----
+// span i = text [i * span, + span) -> stream i of the deflate launch, its slot stored_size(in_len[i]) bytes at i * stride
+int md_launch_spans_plan(uint64_t n, uint64_t len, uint64_t span, uint64_t stride, uint64_t *in_off, uint64_t *in_len, uint64_t *out_off,
+                         uint64_t *out_cap, hipStream_t stream);
+// adler[i] = the Adler-32 of span i, from the text, for every span whose status is "no room" (the others' are left alone)
+int md_launch_spans_adler(const md::spn::Spans *s, const uint8_t *src, uint32_t *adler, hipStream_t stream);
+// size[i], err, stored; the scan of size into off is md_launch_gzm_scan64
+int md_launch_spans_sizes(const md::spn::Spans *s, hipStream_t stream);
+// The whole stream into dst (header, the spans at off[i], trailer) if it fits dst_cap, else nothing.  *written: its length
+// (what it needs); *status: MD_OK, MD_UNEXPECTED_END_OF_OUTPUT, or what err says; *checksum: Adler-32 (GZIP: CRC-32) of the text
+int md_launch_spans_join(const md::spn::Frame *f, const md::spn::Spans *s, const uint8_t *src, const uint8_t *slots, uint8_t *dst,
+                         uint64_t dst_cap, uint64_t *written, int32_t *status, uint32_t *checksum, hipStream_t stream);
 
 // ---- gz_spec.hip: the members of a file without size fields, by speculation (md_gz_members_uncompress) ----
 // bits / cnt as md_launch_gzm_mark's; the counts go through md_launch_gzm_scan32

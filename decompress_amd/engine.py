@@ -495,6 +495,50 @@ class Engine:
                                                             matcher, header)
         return int(status[0]), out[:int(out_len[0])].tobytes(), int(checksum[0])
 
+    def deflate_spans_bound(self, n, fmt=FORMAT_DEFLATE, span=None, header=None):
+        """md_deflate_spans_bound: room that always suffices for `deflate_spans` of n bytes (host arithmetic)"""
+        h = header if header is not None else getattr(self, "_gz", None)
+        gz = _lib.GzHeader(**h) if h and fmt == FORMAT_GZIP else None
+        return int(self.lib.md_deflate_spans_bound(fmt, n, int(span or 0), ctypes.byref(gz) if gz is not None else None))
+
+    def deflate_spans(self, data, fmt=FORMAT_DEFLATE, span=None, level=6, queue=4096, driver=DRIVER_ZL, dynamic=True,
+                      matcher=None, header=None, cap=None):
+        """ONE standard stream of `data` written as joined spans on the whole chip (md_deflate_spans_host):
+        `span` bytes of text per span (None: the option "deflate_span_kib") -> (status, stream bytes, checksum of the
+        input: Adler-32, CRC-32 for FORMAT_GZIP).  cap: room of the destination (default: the bound)."""
+        data = data if isinstance(data, bytes) else bytes(data)
+        params = self._params(level, queue, driver, dynamic, matcher, header)
+        if cap is None:
+            cap = self.deflate_spans_bound(len(data), fmt, span, header)
+            if cap == 0:  # (bad arguments: the call says which)
+                cap = 1
+        dst = ctypes.create_string_buffer(max(int(cap), 1))
+        wrote, sum_ = ctypes.c_size_t(), ctypes.c_uint32()
+        st = self.lib.md_deflate_spans_host(self.ctx, fmt, ctypes.byref(params), int(span or 0), data, len(data), dst, int(cap),
+                                            ctypes.byref(wrote), ctypes.byref(sum_))
+        if st < 0:
+            self._check(st)
+        return int(st), dst.raw[:wrote.value], int(sum_.value)
+
+    def deflate_spans_device(self, d_src, n, d_dst, fmt=FORMAT_DEFLATE, span=None, level=6, queue=4096, driver=DRIVER_ZL,
+                             dynamic=True, matcher=None, header=None):
+        """md_deflate_spans_device: the first n bytes of the CUDA uint8 tensor d_src into the CUDA uint8 tensor d_dst, nothing
+        read back -> (written, status, checksum) CUDA tensors of one element (async on the engine's stream)."""
+        torch = self.torch
+        written = torch.zeros(1, dtype=torch.int64, device=self.device)
+        status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        checksum = torch.zeros(1, dtype=torch.int32, device=self.device)
+        params = self._params(level, queue, driver, dynamic, matcher, header)
+        self._check(self.lib.md_deflate_spans_device(self.ctx, fmt, ctypes.byref(params), int(span or 0), _ptr(d_src), int(n),
+                                                     _ptr(d_dst), d_dst.numel(), _ptr(written), _ptr(status), _ptr(checksum)))
+        return written, status, checksum
+
+    def deflate_spans_last(self):
+        """md_deflate_spans_last -> dict: spans, stored_spans, span_bytes of the last deflate_spans* call"""
+        info = _lib.DeflateSpansInfo()
+        self._check(self.lib.md_deflate_spans_last(self.ctx, ctypes.byref(info)))
+        return {k: int(getattr(info, k)) for k, _ in _lib.DeflateSpansInfo._fields_}
+
     def link_segments(self):
         """segments the last deflate batch call built its hash chains in; 0 = one workgroup per stream"""
         return int(self.lib.md_i_link_segments(self.ctx))

@@ -72,3 +72,15 @@ def index(src, span=1 << 20, device=0):
     """The index of a long ZLIB stream (decompress_amd.index.Index.build): any byte range of its output as one batch."""
     from .index import Index
     return Index.build(src, _engine.FORMAT_ZLIB, span=span, device=device)
+
+
+def compress_spans(src, level=6, span=None, queue=4096, dynamic=True, matcher=None, device=0):
+    """ONE ZLIB stream of src written as joined spans on the whole chip (md_deflate_spans_host): the text
+    is cut into spans of `span` bytes (None: the option "deflate_span_kib"), the spans are compressed as one batch and
+    joined into a stream that every inflater reads to its end.  Not the bytes of `Higher.compress`: a span cannot refer
+    back across a joint, so the stream is a little longer - and takes milliseconds where the single stream takes seconds."""
+    eng = _engine.default_engine(device)
+    st, out, _ = eng.deflate_spans(src, _engine.FORMAT_ZLIB, span=span, level=level, queue=queue, dynamic=dynamic, matcher=matcher)
+    if st != 0:
+        raise _engine.Error(_engine.STATUS_NAMES[st])
+    return out

@@ -196,7 +196,9 @@ int md_synchronize(md_ctx *ctx);
  *   "bgzf_read_workspace"        MiB (0 .. 2^20; default 256): device memory for the members that ONE round of md_bgzf_read
  *                                decodes - their bytes packed back to back plus their output slots.  A read whose members
  *                                need more goes in several rounds, one inflate launch each.  0: one member a round.
- *   "debug_inflate_lds_pad", "debug_known_bounds"   measurement aids of tools/dbg (occupancy curve, known-boundaries floor).
+ *   "deflate_span_kib"           KiB (0 .. MD_MAX_STREAM / 1024; 0 = the default, 64): the text per span of md_deflate_spans_*
+ *                                called with span = 0.  Smaller spans are more parallel, larger ones keep more of the ratio.
+ *   "debug_inflate_lds_pad", "debug_known_bounds"  measurement aids of tools/dbg (occupancy curve, known-boundaries floor).
  *   "profile"                    0 / 1: in-kernel phase profile of stream 0 (md_get_profile, a debugging aid).
  * Unknown keys and values out of range: MD_E_INVALID_ARGUMENT. */
 int md_set_option(md_ctx *ctx, const char *key, int value);
@@ -698,6 +700,50 @@ int md_gz_members_last(const md_ctx *ctx, md_gz_members_stats *out);
 size_t md_bgzf_compress_bound(size_t src_len, size_t block);
 int md_bgzf_compress(md_ctx *ctx, int level, size_t block, const uint8_t *src, size_t src_len, uint8_t *dst, size_t dst_cap,
                      size_t *written);
+
+/* ---- One long stream written as joined spans ---------------------------------------------------------------------------
+ * md_zl_higher_compress and its kin write ONE stream byte for byte as the reference does, which is sequential work for one
+ * wavefront.  This writer is the whole chip's, the way pigz does it: the text is cut into n = max(1, ceil(src_len / span))
+ * spans, the spans are compressed independently by ONE deflate launch, and the bodies are joined into one standard stream
+ * that Zl.Inf / Gz.Inf / De.Inf and libz read to its end.  Exactly:
+ *   B_i   the raw body md_deflate_batch_device writes for span i under `params` (MD_FORMAT_GZIP: the Zl driver with dynamic
+ *         blocks, as for MD_FORMAT_GZIP everywhere); h_i the bit offset of its closing block's header, e_i the bit offset
+ *         behind that block's last bit (its end-of-block code; a stored block: its byte-aligned end)
+ *   J_i   the last span: B_i.  Any other: the first e_i bits of B_i with bit h_i (BFINAL) cleared, the three bits 0 00, zero
+ *         bits up to the byte, then 00 00 FF FF - an empty stored block, so the span ends on a byte
+ *   S_i   the span's bytes as stored blocks of at most 65 535 bytes, all but the last full (the empty text: one empty
+ *         block), BFINAL only on the last block of the last span
+ * Span i goes out as S_i exactly when J_i is strictly longer than S_i, else as J_i.  The body is the chosen forms end to
+ * end; MD_FORMAT_ZLIB puts Zl.Def's two header bytes in front and the big-endian Adler-32 of the text behind,
+ * MD_FORMAT_GZIP the header of params->gz_header in front and CRC-32 and length mod 2^32 behind.  With one span the bytes
+ * are md_deflate_batch_host's for that text (unless the stored form wins).  A span cannot refer back across a joint, so
+ * the stream is somewhat longer than the single stream (README); it depends on (text, params, span) alone.
+ *   span    bytes of text per span, 1 .. MD_MAX_STREAM; 0 = md_set_option "deflate_span_kib" (KiB; default 64)
+ *   params  as md_deflate_batch_device takes them (levels 0-9, the three drivers, both matchers, dynamic 0 / 1, wbits 0 / 15);
+ *           anything else is MD_E_INVALID_ARGUMENT.  total_in_bytes is ignored.  At most 0x7ffffff0 spans.
+ * md_deflate_spans_bound: room that always suffices (host arithmetic: every span stored, header, trailer; span 0: the bound
+ *   of the smallest span the option selects); 0 for bad arguments and for a sum that size_t does not hold.
+ * md_deflate_spans_host: host buffers; MD_UNEXPECTED_END_OF_OUTPUT when dst_cap is short (nothing is written then), a span's
+ *   MD_QUEUE_FULL is the call's status; *checksum (may be NULL): Adler-32 of the text, CRC-32 for MD_FORMAT_GZIP.
+ * md_deflate_spans_device: everything in device memory, asynchronous on the context's stream, nothing read back (unless the
+ *   spans' workspace is above md_set_option "deflate_workspace_cap_mib": the deflate launch then goes in slices of positions,
+ *   which waits for the stream and reads the slices' results back, as md_deflate_batch_device does): *d_written
+ *   = the stream's length (what it needs when *d_status is MD_UNEXPECTED_END_OF_OUTPUT: no byte of d_dst is written then),
+ *   *d_status and *d_checksum as above.  The per-position workspace and its cap are md_deflate_batch_device's.
+ * md_deflate_spans_last: spans, stored spans and span bytes of the context's last call (after the device form it waits for
+ *   the context's stream). */
+typedef struct md_deflate_spans_info {
+  size_t spans;        /* n */
+  size_t stored_spans; /* spans that went out in the stored form */
+  size_t span_bytes;   /* the span in bytes, the option resolved */
+} md_deflate_spans_info;
+size_t md_deflate_spans_bound(int format, size_t src_len, size_t span, const md_gz_header *hdr);
+int md_deflate_spans_host(md_ctx *ctx, int format, const md_deflate_params *params, size_t span, const uint8_t *src, size_t src_len,
+                          uint8_t *dst, size_t dst_cap, size_t *written, uint32_t *checksum);
+int md_deflate_spans_device(md_ctx *ctx, int format, const md_deflate_params *params, size_t span, const uint8_t *d_src,
+                            size_t src_len, uint8_t *d_dst, size_t dst_cap, uint64_t *d_written, int32_t *d_status,
+                            uint32_t *d_checksum);
+int md_deflate_spans_last(md_ctx *ctx, md_deflate_spans_info *info);
 
 /* ---- ZIP archives (PKWARE APPNOTE; .zip .jar .whl .npz .docx .apk .epub): every entry in one batch ----------------------
  * An entry is a raw RFC 1951 stream (method 8) or plain bytes (method 0), and the central directory states every entry's
