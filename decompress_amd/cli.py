@@ -1,6 +1,6 @@
 """`decompress` — the reference's command line tool (bin/decompress.ml:226-344) over the GPU engine.
 
-    python -m decompress_amd.cli [-d] [-f deflate|zlib|gzip|lzo] [-l <level>] [--span <KiB>] [<input> [<output>]]
+    python -m decompress_amd.cli [-d] [-f deflate|zlib|gzip|lzo] [-l <level>] [--span <KiB> [--prime]] [<input> [<output>]]
 
 Same flags, defaults and drivers as the reference: inflate unless `-d`; format `deflate` unless `-f`; level 4
 unless `-l`; stdin / stdout unless file names are given.  `-d` on raw DEFLATE is the CLI's own driver
@@ -11,7 +11,9 @@ bin/decompress.ml:136-155), LZO through `Lzo.compress` / `Lzo.uncompress_with_bu
 
 `--span <KiB>` is this tool's own: with `-d` and `-f deflate|zlib|gzip` the stream is written as joined spans of that
 many KiB by the whole chip (md_deflate_spans_host; same drivers and header); without `-d`, or with `-f lzo`, it
-is an error.  Without it the bytes are the reference's."""
+is an error.  `--prime` goes with `--span` alone: every span's matcher starts from the 32 KiB of text in front of it
+(md_set_option "deflate_span_prime"), and the stream is nearly as short as the single one.  Without `--span` the bytes are
+the reference's."""
 import sys
 import time
 
@@ -85,7 +87,7 @@ def take_span(argv):
     return rest, span
 
 
-def run(deflate, fmt, level, data, now=None, span=None):
+def run(deflate, fmt, level, data, now=None, span=None, prime=False):
     """one run of the tool on `data` -> (exit status, output bytes, message for stderr)"""
     import decompress_amd
     from decompress_amd import de, engine, gz, lzo
@@ -100,7 +102,8 @@ def run(deflate, fmt, level, data, now=None, span=None):
                 mtime = int(time.time() if now is None else now) & 0xffffffff
                 hdr = dict(mtime=mtime, os=gz.OS["Unix"], hcrc=0, ascii=0, filename=None, comment=None)
             st, out, _ = eng.deflate_spans(data, f, span=span, level=level, queue=QUEUE,
-                                           driver=engine.DRIVER_CLI if fmt == "deflate" else engine.DRIVER_ZL, header=hdr)
+                                           driver=engine.DRIVER_CLI if fmt == "deflate" else engine.DRIVER_ZL, header=hdr,
+                                           prime=bool(prime))
             if st != 0:
                 return CLI_ERROR, b"", engine.STATUS_NAMES[st]
             return 0, out, None
@@ -137,15 +140,18 @@ def run(deflate, fmt, level, data, now=None, span=None):
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     try:
-        argv, span = take_span(argv)
+        prime = "--prime" in argv
+        argv, span = take_span([a for a in argv if a != "--prime"])
         deflate, fmt, level, fin, fout = parse(argv)
         if span is not None and (not deflate or fmt == "lzo"):
             raise ValueError("option '--span' needs '-d' and a format of deflate, zlib or gzip")
+        if prime and span is None:
+            raise ValueError("option '--prime' needs '--span'")
     except ValueError as e:
         sys.stderr.write("decompress: %s\n" % e)
         return CLI_ERROR
     data = open(fin, "rb").read() if fin else sys.stdin.buffer.read()
-    status, out, msg = run(deflate, fmt, level, data, span=span)
+    status, out, msg = run(deflate, fmt, level, data, span=span, prime=prime)
     oc = open(fout, "wb") if fout else sys.stdout.buffer
     oc.write(out)
     oc.flush()

@@ -263,6 +263,11 @@ int md_set_option(md_ctx *ctx, const char *key, int value) {
     ctx->span_bytes = value ? (size_t)value << 10 : md::kSpanDefault;
     return MD_OK;
   }
+  if (!strcmp(key, "deflate_span_prime")) {  // md_deflate_spans_*: 1 = every span's matcher starts from the 32 KiB of text in front of it
+    if (value != 0 && value != 1) return fail(ctx, MD_E_INVALID_ARGUMENT, "deflate_span_prime is 0 or 1");
+    ctx->span_prime = value != 0;
+    return MD_OK;
+  }
   if (!strcmp(key, "gz_members_speculate")) {  // md_gz_members_uncompress, a file without size fields: 1 = members found by speculation, one batch
     if (value != 0 && value != 1) return fail(ctx, MD_E_INVALID_ARGUMENT, "gz_members_speculate is 0 or 1");
     ctx->gzm_speculate = value != 0;

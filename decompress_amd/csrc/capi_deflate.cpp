@@ -100,12 +100,15 @@ static int front_workspace(md_ctx *ctx, size_t n, const uint64_t *d_len, int dri
   return MD_OK;
 }
 
-// total_in as in front_workspace.  d_tail: SeqArgs::tail (two words per stream), or null.
+// total_in as in front_workspace.  d_tail: SeqArgs::tail (two words per stream), or null.  d_first: SeqArgs::first (where
+// each stream begins to emit), or null; the match kernel then leaves out the chunks below it (deflate_test_flags bit 5:
+// it does not - a measurement, the bytes are the same).
 static int deflate_launch(md_ctx *ctx, int format, int level, int queue_len, int driver, int dynamic, int matcher,
                           const md_gz_header *gz, size_t n, const uint8_t *d_in, const uint64_t *d_in_off,
                           const uint64_t *d_in_len, uint8_t *d_out, const uint64_t *d_out_off, const uint64_t *d_out_cap,
                           uint64_t *d_out_len, int32_t *d_status, uint32_t *d_checksum, uint32_t *d_hist, size_t total_in,
-                          const PieceArgs *pa = nullptr, const LinkSegs *ls = nullptr, uint64_t *d_tail = nullptr) {
+                          const PieceArgs *pa = nullptr, const LinkSegs *ls = nullptr, uint64_t *d_tail = nullptr,
+                          const uint32_t *d_first = nullptr) {
   int grc_ = MD_OK;
   // (the Lz77-alone / encode-alone / scripted drivers leave the kernel before it saves a piece's state)
   if (pa && driver >= md::defl::DRV_LZ77) return fail(ctx, MD_E_INVALID_ARGUMENT, "a stream in pieces needs one of the three public drivers");
@@ -158,6 +161,10 @@ static int deflate_launch(md_ctx *ctx, int format, int level, int queue_len, int
         (void)hipGetLastError();  // a launch that failed: the one-workgroup link kernel instead
       }
     }
+    if (d_first && !pa && !(ctx->test_flags & 32))
+      MD_LAUNCH_TRY(ctx, md_launch_deflate_front_first((uint32_t)n, chunks, d_in, d_in_off, d_front_len, matcher, max_chain, nice, &fr, order, d_first,
+                                                       ctx->stream));
+    else
     MD_LAUNCH_TRY(ctx, linked ? md_launch_deflate_match((uint32_t)n, chunks, d_in, d_in_off, d_front_len, max_chain, nice, &fr, 0u, ctx->stream)
                               : md_launch_deflate_front((uint32_t)n, chunks, d_in, d_in_off, d_front_len, matcher, max_chain, nice, &fr, order,
                                                         pa ? pa->match_skip : 0u, ctx->stream));
@@ -176,6 +183,7 @@ static int deflate_launch(md_ctx *ctx, int format, int level, int queue_len, int
   args.order = order;
   if (pa) args.pcs = pa->piece;
   args.tail = d_tail;
+  args.first = d_first;
   MD_LAUNCH_TRY(ctx, md_launch_deflate(&args, ctx->stream));
   return MD_OK;
 }
@@ -297,9 +305,10 @@ static int deflate_in_slices(md_ctx *ctx, int format, const md_deflate_params &q
                              const uint64_t *h_in_off, const uint64_t *h_in_len, uint8_t *d_out, const uint64_t *h_out_off,
                              const uint64_t *h_out_cap, uint64_t *h_out_len, int32_t *h_status, uint32_t *h_checksum,
                              const uint32_t *h_crc, const SliceHooks *hooks = nullptr, uint64_t *d_tail = nullptr,
-                             uint64_t *h_tail = nullptr) {
+                             uint64_t *h_tail = nullptr, const uint32_t *d_first = nullptr) {
   // (d_tail / h_tail: SeqArgs::tail of the n streams.  The launch that ends a stream leaves its two words in d_tail, counted
-  // from that piece's output; h_tail gets them counted from the stream's first byte)
+  // from that piece's output; h_tail gets them counted from the stream's first byte.  d_first: SeqArgs::first of the n
+  // streams; the first piece of a stream reads it, and S >= kSliceMin, so that piece holds all of [0, first))
   std::vector<uint64_t> tl(d_tail ? 2 * n : 0);
   // state slots for the streams that do not end in the first slice
   std::vector<uint64_t> slot(n, 0), used(n, 0);
@@ -366,7 +375,8 @@ static int deflate_in_slices(md_ctx *ctx, int format, const md_deflate_params &q
     // (every stream of a later slice stopped less than 262 + 64 short of the slice before's end)
     PieceArgs pa{d64 + n, ctx->scratch[kWs].p, {d32 + 2 * n, (uint8_t *)ctx->scratch[kSliceState].p, d64 + 6 * n, d32 + 3 * n}, k == 0 ? 0u : (uint32_t)kSliceKeep - 512u};
     rc = deflate_launch(ctx, format, q.level, q.queue_len, q.driver, q.dynamic, q.matcher, q.gz_header, n, d_in, d64, d64 + 2 * n,
-                        d_out, d64 + 3 * n, d64 + 4 * n, d64 + 5 * n, (int32_t *)d32, d32 + n, nullptr, total ? total : 1, &pa, nullptr, d_tail);
+                        d_out, d64 + 3 * n, d64 + 4 * n, d64 + 5 * n, (int32_t *)d32, d32 + n, nullptr, total ? total : 1, &pa, nullptr, d_tail,
+                        d_first);
     if (rc != MD_OK) return rc;
     if (hooks) {  // (in front of the read-backs: a copy to pageable memory keeps the calling thread until the kernels are done)
       rc = hooks->launched(k);
@@ -404,8 +414,8 @@ static int deflate_in_slices(md_ctx *ctx, int format, const md_deflate_params &q
 // slice of every stream at once would still be too much), results back to the caller's device arrays
 static int deflate_capped(md_ctx *ctx, int format, const md_deflate_params &q, size_t n, const uint8_t *d_in, const uint64_t *d_in_off,
                           const uint64_t *d_in_len, uint8_t *d_out, const uint64_t *d_out_off, const uint64_t *d_out_cap,
-                          uint64_t *d_out_len, int32_t *d_status, uint32_t *d_checksum, uint64_t *d_tail, bool *whole,
-                          uint64_t *total_out) {
+                          uint64_t *d_out_len, int32_t *d_status, uint32_t *d_checksum, uint64_t *d_tail, const uint32_t *d_first,
+                          bool *whole, uint64_t *total_out) {
   std::vector<uint64_t> h(4 * n);
   uint64_t *in_off = h.data(), *in_len = in_off + n, *out_off = in_len + n, *out_cap = out_off + n;
   HIP_TRY(ctx, hipMemcpyAsync(in_off, d_in_off, n * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -472,7 +482,7 @@ static int deflate_capped(md_ctx *ctx, int format, const md_deflate_params &q, s
     }
     int rc = deflate_in_slices(ctx, format, q, k, S, d_in, in_off + i0, in_len + i0, d_out, out_off + i0, out_cap + i0, r_len.data() + i0,
                                r_st.data() + i0, r_sum.data() + i0, crc.empty() ? nullptr : crc.data() + i0, nullptr,
-                               d_tail ? d_tail + 2 * i0 : nullptr, d_tail ? r_tail.data() + 2 * i0 : nullptr);
+                               d_tail ? d_tail + 2 * i0 : nullptr, d_tail ? r_tail.data() + 2 * i0 : nullptr, d_first ? d_first + i0 : nullptr);
     if (rc != MD_OK) return rc;
     i0 += k;
   }
@@ -485,11 +495,12 @@ static int deflate_capped(md_ctx *ctx, int format, const md_deflate_params &q, s
   return MD_OK;
 }
 
-// ls: ONE stream whose hash chains go in segments (md_deflate_batch_host), else null; d_tail: SeqArgs::tail, or null
+// ls: ONE stream whose hash chains go in segments (md_deflate_batch_host), else null; d_tail: SeqArgs::tail, or null;
+// d_first: SeqArgs::first, or null
 static int deflate_batch_device(md_ctx *ctx, int format, const md_deflate_params *params, size_t n, const uint8_t *d_in,
                                 const uint64_t *d_in_off, const uint64_t *d_in_len, uint8_t *d_out, const uint64_t *d_out_off,
                                 const uint64_t *d_out_cap, uint64_t *d_out_len, int32_t *d_status, uint32_t *d_checksum,
-                                const LinkSegs *ls, uint64_t *d_tail = nullptr) {
+                                const LinkSegs *ls, uint64_t *d_tail = nullptr, const uint32_t *d_first = nullptr) {
   if (!ctx) return MD_E_INVALID_ARGUMENT;
   ctx->link_last_segments = 0;
   md_deflate_params q;
@@ -510,8 +521,8 @@ static int deflate_batch_device(md_ctx *ctx, int format, const md_deflate_params
         (!q.total_in_bytes || md_front_big_bytes((uint64_t)q.total_in_bytes + kSlotPad * n) > ctx->front_cap_bytes)) {
       bool whole = true;
       uint64_t total = 0;
-      rc = deflate_capped(ctx, format, q, n, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status, d_checksum, d_tail, &whole,
-                          &total);
+      rc = deflate_capped(ctx, format, q, n, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status, d_checksum, d_tail, d_first,
+                          &whole, &total);
       if (rc != MD_OK || !whole) return rc;
       // the batch fits the cap after all: one launch, sized from the sum just read back (no second read-back in
       // deflate_launch, and a loose hint cannot make the workspace grow above the cap)
@@ -520,14 +531,14 @@ static int deflate_batch_device(md_ctx *ctx, int format, const md_deflate_params
   }
   return deflate_launch(ctx, format, q.level, q.queue_len, q.driver, q.dynamic, q.matcher, q.gz_header, n, d_in, d_in_off,
                         d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status, d_checksum, nullptr, q.total_in_bytes,
-                        nullptr, ls, d_tail);
+                        nullptr, ls, d_tail, d_first);
 }
 
 int deflate_batch_tails(md_ctx *ctx, int format, const md_deflate_params *params, size_t n, const uint8_t *d_in, const uint64_t *d_in_off,
                         const uint64_t *d_in_len, uint8_t *d_out, const uint64_t *d_out_off, const uint64_t *d_out_cap, uint64_t *d_out_len,
-                        int32_t *d_status, uint32_t *d_checksum, uint64_t *d_tail) {
+                        int32_t *d_status, uint32_t *d_checksum, uint64_t *d_tail, const uint32_t *d_first) {
   return deflate_batch_device(ctx, format, params, n, d_in, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_out_len, d_status,
-                              d_checksum, nullptr, d_tail);
+                              d_checksum, nullptr, d_tail, d_first);
 }
 
 int md_deflate_batch_device(md_ctx *ctx, int format, const md_deflate_params *params, size_t n, const uint8_t *d_in,

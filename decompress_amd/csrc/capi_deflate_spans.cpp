@@ -42,6 +42,9 @@ size_t md_deflate_spans_bound(int format, size_t src_len, size_t span, const md_
 // Plan, ONE deflate launch over the spans, the stored spans' Adler-32, sizes, scan, join: the stream goes to d_dst if it fits
 // dst_cap.  Everything is enqueued on the context's stream and nothing is read back - but by the deflate launch itself where
 // the workspace cap sends it through slices of positions.
+// Primed (md_set_option "deflate_span_prime"): the deflate launch alone takes a second set of descriptors - span i with the
+// w_i = min(i * span, 32 768) bytes in front of it as one stream that begins to emit at w_i.  The streams overlap in the
+// text, which is only read; the front workspace is 13 bytes per position of len + 32 768 (n - 1) positions at the most.
 static int spans_run(md_ctx *ctx, int format, const md_deflate_params *params, size_t span, const uint8_t *d_src, size_t len, uint8_t *d_dst,
                      size_t dst_cap, uint64_t *d_written, int32_t *d_status, uint32_t *d_checksum) {
   md_deflate_params q = *params;
@@ -61,7 +64,9 @@ static int spans_run(md_ctx *ctx, int format, const md_deflate_params *params, s
   if (rc != MD_OK) return rc;
   uint8_t *slots = (uint8_t *)ctx->scratch[kHostOut].p;
   uint64_t *in_off = nullptr, *in_len = nullptr, *out_off = nullptr, *out_cap = nullptr, *out_len = nullptr, *size = nullptr, *off = nullptr,
-           *tail = nullptr;
+           *tail = nullptr, *x_off = nullptr, *x_len = nullptr;
+  uint32_t *first = nullptr;
+  const bool prime = ctx->span_prime && n > 1;  // (one span has nothing in front of it)
   int32_t *status = nullptr, *err = nullptr;
   uint32_t *adler = nullptr, *crc = nullptr;
   md::Carver desc;
@@ -71,14 +76,22 @@ static int spans_run(md_ctx *ctx, int format, const md_deflate_params *params, s
     out_len = desc.take<uint64_t>(n), size = desc.take<uint64_t>(n), off = desc.take<uint64_t>(n + 1), tail = desc.take<uint64_t>(2 * n);
     status = desc.take<int32_t>(n), err = desc.take<int32_t>(2);
     adler = desc.take<uint32_t>(n), crc = desc.take<uint32_t>(n);
+    if (prime) x_off = desc.take<uint64_t>(n), x_len = desc.take<uint64_t>(n), first = desc.take<uint32_t>(n);
   }
   hipStream_t st = ctx->stream;
   HIP_TRY(ctx, hipMemsetAsync(err, 0, 8, st));
   HIP_TRY(ctx, hipMemsetAsync(ctx->spans_count.p, 0, 8, st));
-  MD_LAUNCH_TRY(ctx, md_launch_spans_plan(n, len, span, stride, in_off, in_len, out_off, out_cap, st));
-  q.total_in_bytes = len ? len : 1;
+  MD_LAUNCH_TRY(ctx, md_launch_spans_plan(n, len, span, stride, in_off, in_len, out_off, out_cap, x_off, x_len, first, st));
+  // (primed: span i brings min(i * span, kPrime) bytes along - summed exactly, the prefixes below kPrime first)
+  size_t primed = 0;
+  if (prime) {
+    const size_t growing = (size_t)(md::spn::kPrime / span) < n - 1 ? (size_t)(md::spn::kPrime / span) : n - 1;  // spans 1 .. growing: i * span
+    primed = span * (growing * (growing + 1) / 2) + (n - 1 - growing) * (size_t)md::spn::kPrime;
+  }
+  q.total_in_bytes = len ? len + primed : 1;
   q.gz_header = nullptr;
-  rc = deflate_batch_tails(ctx, MD_FORMAT_DEFLATE, &q, n, d_src, in_off, in_len, slots, out_off, out_cap, out_len, status, adler, tail);
+  rc = deflate_batch_tails(ctx, MD_FORMAT_DEFLATE, &q, n, d_src, prime ? x_off : in_off, prime ? x_len : in_len, slots, out_off, out_cap, out_len,
+                           status, adler, tail, first);
   if (rc != MD_OK) return rc;
   if (format == MD_FORMAT_GZIP) MD_LAUNCH_TRY(ctx, md_launch_crc32((uint32_t)n, d_src, in_off, in_len, crc, st));
   md::spn::Spans s = {};

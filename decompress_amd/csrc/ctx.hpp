@@ -163,7 +163,8 @@ struct md_ctx {
   size_t piece_bytes = (size_t)1 << 20;  // md_set_option "encoder_piece_bytes": input the md_def_* encoder gathers before a launch
   size_t front_cap_bytes = 0;  // md_set_option "deflate_workspace_cap_mib" (md_create: a sixth of the device's memory; 0 = none):
                                // batches whose per-position workspace would be larger go in slices of positions
-  int test_flags = 0;  // md_set_option "deflate_test_flags": bit 4 = the md_def_* encoder moves its origin every 128 KiB (tests)
+  int test_flags = 0;  // md_set_option "deflate_test_flags": bit 4 = the md_def_* encoder moves its origin every 128 KiB (tests),
+                       // bit 5 = the match kernel also takes the chunks below SeqArgs::first (primed spans; a measurement)
   md::DevBuf dbg;      // device buffer of the optional in-kernel profile (32 x u64)
   // the two copy streams of the host-buffer entry points, next to the context's stream (copy-in of slice k + 1 and
   // copy-out of slice k - 1 under the kernels of slice k)
@@ -196,6 +197,7 @@ struct md_ctx {
   // one stream written as joined spans: md_set_option "deflate_span_kib" (the span of a call that passes 0) and the counts of
   // the last md_deflate_spans_* call (md_deflate_spans_last)
   size_t span_bytes = md::kSpanDefault;
+  bool span_prime = false;  // md_set_option "deflate_span_prime": every span is primed with the 32 KiB of text in front of it
   md_deflate_spans_info spans_last = {};
   md::DevBuf spans_count;      // the device word that counts the stored spans of a call
   bool spans_pending = false;  // spans_last.stored_spans is still in spans_count (the device form reads nothing back)
@@ -349,10 +351,11 @@ int md_get_profile(md_ctx *ctx, uint64_t *out32);
 // The bytes Gz.Def writes in front of the body for the header fields g (null: the default header); returns the length, 0
 // when a field is out of range.
 uint32_t gz_header_bytes(const md_gz_header *g, int level, uint8_t h[544]);
-// md_deflate_batch_device that also leaves every stream's tail (SeqArgs::tail of internal.hpp: two words per stream) in d_tail
+// md_deflate_batch_device that also leaves every stream's tail (SeqArgs::tail of internal.hpp: two words per stream) in d_tail;
+// d_first: SeqArgs::first (where each stream begins to emit: the text in front of it only primes the matcher), or null
 int deflate_batch_tails(md_ctx *ctx, int format, const md_deflate_params *params, size_t n, const uint8_t *d_in, const uint64_t *d_in_off,
                         const uint64_t *d_in_len, uint8_t *d_out, const uint64_t *d_out_off, const uint64_t *d_out_cap, uint64_t *d_out_len,
-                        int32_t *d_status, uint32_t *d_checksum, uint64_t *d_tail);
+                        int32_t *d_status, uint32_t *d_checksum, uint64_t *d_tail, const uint32_t *d_first);
 // ---- capi_inflate.cpp ----
 // One piece of a raw DEFLATE stream through one pair of wavefronts, its output LEFT ON THE DEVICE: src[0, src_len) starts
 // start_bit bits into src[0], hist[0, hist_len) is the output in front of it and goes to the start of kContOut, the new

@@ -136,7 +136,8 @@ __global__ __launch_bounds__(kWave, MD_MATCH_WAVES) void deflate_match_kernel(ui
                                                               const uint32_t *__restrict__ link, uint8_t *__restrict__ flg,
                                                               uint32_t *__restrict__ m, uint32_t *__restrict__ mq,
                                                               const uint32_t *__restrict__ flags, uint32_t max_chain,
-                                                              uint32_t nice, uint32_t skip) {
+                                                              uint32_t nice, uint32_t skip,
+                                                              const uint32_t *__restrict__ first) {
   const uint32_t lane = threadIdx.x;
   if (flags[0]) return;
   // workgroup b runs on XCD b % 8: give every XCD one contiguous eighth of the chunks, so that the chunks that share
@@ -169,6 +170,8 @@ __global__ __launch_bounds__(kWave, MD_MATCH_WAVES) void deflate_match_kernel(ui
   // a stream in pieces: the first `skip` positions of the text are the window the piece brings along - the matcher is
   // past them, they only have to be in the chains
   if (pe + kChunk <= skip) return;
+  // a stream that begins to emit at first[sid] (SeqArgs::first): no verdict is read below it
+  if (first && pe + kChunk <= first[sid]) return;
   const uint32_t slen = (uint32_t)in_len[sid];
   const uint8_t *src = in + in_off[sid];
   const uint64_t so = slot[sid];
@@ -335,15 +338,20 @@ extern "C" int md_launch_deflate_plan(uint32_t n, const uint64_t *in_len, int dr
   return (int)hipGetLastError();
 }
 // flg[] / m[] / mq[] from link[]: nchunks_max >= chunk0[n]
-extern "C" int md_launch_deflate_match(uint32_t n, uint32_t nchunks_max, const uint8_t *in, const uint64_t *in_off,
-                                       const uint64_t *in_len, uint32_t max_chain, uint32_t nice, const md::defl::Front *f,
-                                       uint32_t match_skip, hipStream_t stream) {
+static int match_launch(uint32_t n, uint32_t nchunks_max, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len,
+                        uint32_t max_chain, uint32_t nice, const md::defl::Front *f, uint32_t match_skip, const uint32_t *first,
+                        hipStream_t stream) {
   using namespace md::defl;
   if (n == 0 || nchunks_max == 0) return 0;
   const uint32_t per = (nchunks_max + 7) / 8;
   hipLaunchKernelGGL(deflate_match_kernel, dim3(per * 8), dim3(kWave), 0, stream, n, nchunks_max, in, in_off, in_len, f->p_end,
-                     f->slot, f->chunk0, f->link, f->flg, f->m, f->mq, f->flags, max_chain, nice, match_skip);
+                     f->slot, f->chunk0, f->link, f->flg, f->m, f->mq, f->flags, max_chain, nice, match_skip, first);
   return (int)hipGetLastError();
+}
+extern "C" int md_launch_deflate_match(uint32_t n, uint32_t nchunks_max, const uint8_t *in, const uint64_t *in_off,
+                                       const uint64_t *in_len, uint32_t max_chain, uint32_t nice, const md::defl::Front *f,
+                                       uint32_t match_skip, hipStream_t stream) {
+  return match_launch(n, nchunks_max, in, in_off, in_len, max_chain, nice, f, match_skip, nullptr, stream);
 }
 // link[] / tail[], then flg[] / m[] / mq[]: nchunks_max >= chunk0[n]
 extern "C" int md_launch_deflate_front(uint32_t n, uint32_t nchunks_max, const uint8_t *in, const uint64_t *in_off,
@@ -354,6 +362,18 @@ extern "C" int md_launch_deflate_front(uint32_t n, uint32_t nchunks_max, const u
   hipLaunchKernelGGL(deflate_link_kernel<false>, dim3(n), dim3(LW * kWave), 0, stream, n, in, in_off, in_len, f->p_end, f->slot,
                      f->link, (uint32_t *)f->tail, f->flags, matcher, order);
   return md_launch_deflate_match(n, nchunks_max, in, in_off, in_len, max_chain, nice, f, match_skip, stream);
+}
+// the same for streams that begin to emit at first[i] (SeqArgs::first): the chains of the whole text, verdicts from the
+// chunk that holds first[i] on
+extern "C" int md_launch_deflate_front_first(uint32_t n, uint32_t nchunks_max, const uint8_t *in, const uint64_t *in_off,
+                                             const uint64_t *in_len, int matcher, uint32_t max_chain, uint32_t nice,
+                                             const md::defl::Front *f, const uint32_t *order, const uint32_t *first,
+                                             hipStream_t stream) {
+  using namespace md::defl;
+  if (n == 0 || nchunks_max == 0) return 0;
+  hipLaunchKernelGGL(deflate_link_kernel<false>, dim3(n), dim3(LW * kWave), 0, stream, n, in, in_off, in_len, f->p_end, f->slot,
+                     f->link, (uint32_t *)f->tail, f->flags, matcher, order);
+  return match_launch(n, nchunks_max, in, in_off, in_len, max_chain, nice, f, 0u, first, stream);
 }
 
 // the chains of De.Def.Ns's hc_matchfinder (deflate_ns.hip)

@@ -1083,7 +1083,9 @@ __device__ __forceinline__ bool lz_deflate(DS *s, Enc *e, Lz *z, const Ws *ws) {
     int ml;
     bool fast = false;
     ml = z->prev_length;
-    if (z->strstart < z->prepared_end && z->lookahead >= MIN_LOOKAHEAD) {
+    // (prev_length below MIN_MATCH - 1: De's first step alone, and with a candidate only in a stream that begins behind a
+    // prefix, SeqArgs::first - longest_match then also compares the byte in front, which no verdict knows of)
+    if (z->strstart < z->prepared_end && z->lookahead >= MIN_LOOKAHEAD && z->prev_length >= MIN_MATCH - 1) {
       // the wave has run this position's chain ahead (kernel main loop): FL_ENDED — no candidate
       // shares 3 bytes, nothing can beat prev_length; FL_MATCH — the best candidate of the full
       // and of the quartered chain (lib/de.ml:4117-4119) are in the match ring.  With prev_length
@@ -1235,7 +1237,9 @@ struct Run {  // the two state machines of one stream (lane 0's registers)
                    // exits only, so it waits here and not in a register of every lane; a piece's state carries it along
 };
 
-__device__ __forceinline__ void stream_begin(Run *r, const Ws *ws, const uint8_t *in, uint32_t n, uint8_t *out, uint32_t cap,
+// first (SeqArgs::first): the matcher has walked positions [0, first) inserting and emitting nothing - it stands at
+// strstart = first, nothing pending, the window filled as that walk's fills left it (fill_window tops up from `filled`)
+__device__ __forceinline__ void stream_begin(Run *r, const Ws *ws, const uint8_t *in, uint32_t n, uint32_t first, uint8_t *out, uint32_t cap,
                              int level, int qcap, int driver, int matcher) {
   // every cursor, count and flag of the two machines starts at zero; what follows is what does not
   static_assert(K_FIRST_ENTRY == 0 && LK_ENOUGH == 0 && PH_LZ == 0, "the states a stream begins in");
@@ -1257,7 +1261,8 @@ __device__ __forceinline__ void stream_begin(Run *r, const Ws *ws, const uint8_t
   z.n = n;
   z.p_end = stream_p_end(matcher, (uint32_t)z.level, n);
   z.match_length = z.prev_length = matcher == MD_MATCHER_LZ ? MIN_MATCH - 1 : 0;  // lib/lz.ml:563-566
-  z.eoi = n == 0;
+  z.strstart = z.filled = first;
+  z.eoi = n == first;
   r->first = true;
 }
 
@@ -1585,6 +1590,11 @@ struct Strm {
   uint32_t cap;
   uint32_t slot_len;            // positions [w0, slot_len) have a cell
 };
+// SeqArgs::first of a stream that begins in this launch: where it starts to emit.  Read from the descriptors where it is
+// needed (the checksum's start, the fresh state machines): carried along it costs a scalar register the kernel does not have
+__device__ __forceinline__ uint32_t stream_first(const SeqArgs &a, const Strm &t) {
+  return a.first && t.p_first ? __builtin_nontemporal_load(a.first + t.sid) : 0u;
+}
 // the one writer of a stream's three result words
 __device__ __forceinline__ void report(const SeqArgs &a, uint32_t sid, uint64_t len, int st, uint32_t sum) {
   a.out_len[sid] = len;
@@ -1615,7 +1625,7 @@ __device__ __forceinline__ bool stream_open(const SeqArgs &a, uint32_t lane, Str
   t.rebase = piece ? (uint32_t)pcs.pos[4 * sid + 1] : 0u;
   t.sslot = piece ? (size_t)pcs.pos[4 * sid + 2] : 0;
   t.src = a.in + a.in_off[sid] - w0;
-  if (a.in_len[sid] > MD_MAX_STREAM || fr.flags[0]) {  // 32-bit cursors: the descriptor is out of range (mdeflate.h);
+  if (a.in_len[sid] > MD_MAX_STREAM || fr.flags[0] || stream_first(a, t) > a.in_len[sid]) {  // 32-bit cursors: the descriptor is out of range (mdeflate.h);
                                                          // or the batch is larger than md_deflate_params.total_in_bytes said
     if (lane == 0) report(a, sid, 0, MD_E_INVALID_ARGUMENT, 0);
     return false;
@@ -2162,7 +2172,7 @@ __global__ __launch_bounds__(kWave, 4) void deflate_kernel(const SeqArgs a) {
   // range of `lane` on to trees_wave and enc_write_wave, and their code is what it was.  Without it tree_make_wave's
   // clearing loop is unrolled and trees + packing measured 2 % slower.  To re-check: hipcc --save-temps, and diff the ISA
   // of tree_make_wave / trees_wave / enc_write_wave against the build before the edit)
-  auto adler_from0 = [&]() { return adler_of(t.src, t.slen, lane, 0, 1u); };
+  auto adler_from0 = [&]() { return adler_of(t.src, t.slen, lane, stream_first(a, t), 1u); };
   const uint32_t sum = !t.piece ? adler_from0() : own_sum ? (t.p_first ? adler_from0() : 1u) : a.pcs.sum[2 * t.sid];
   __threadfence_block();
   __syncthreads();
@@ -2171,16 +2181,17 @@ __global__ __launch_bounds__(kWave, 4) void deflate_kernel(const SeqArgs a) {
   const bool room = t.cap >= hdr;
   if (t.piece && !t.p_first) piece_resume(a, t, ws, ds, run, own_sum, sum, lane);
   else if (lane == 0) {  // a stream (or its first piece) begins: the two state machines and what the wave reads of them
-    if (room) stream_begin(&run, &ws, t.src, t.slen, t.dst + hdr, t.cap - hdr, a.level, a.qcap, a.driver, a.matcher);
+    const uint32_t first = stream_first(a, t);
+    if (room) stream_begin(&run, &ws, t.src, t.slen, first, t.dst + hdr, t.cap - hdr, a.level, a.qcap, a.driver, a.matcher);
     if (room && t.piece && !t.p_last) {
       run.z.more = true;
       run.z.eoi = false;
     }
-    ds.ctl[0] = 0;
+    ds.ctl[0] = first;
     ds.ctl[1] = room ? 0 : 1;
     ds.ctl[2] = 0;
     ds.ctl[3] = ACT_PREP;
-    ds.ring_dead = 0;
+    ds.ring_dead = first != 0;  // (the ring's first fill begins at the pending literal's cell, as after a tree build)
     ds.zs.trivial = 0;
     ds.zs.bulked = 0;
     for (int i = 0; i < 8; i++) ds.tp[i] = 0;

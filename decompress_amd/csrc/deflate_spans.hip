@@ -3,7 +3,10 @@
 // launch, and the bodies are joined the way pigz joins them: the closing block of every span but the last loses its BFINAL
 // bit and is followed by an empty stored block (0 00, zero bits up to the byte, 00 00 FF FF), so a span ends on a byte.
 //   plan_kernel   span i of the text -> stream i of the deflate launch, slots of fixed stride; a slot holds exactly the
-//                 span's stored form, so a body that does not fit it has lost against that form already
+//                 span's stored form, so a body that does not fit it has lost against that form already.  Primed spans:
+//                 a second set of descriptors for the deflate launch alone - the stream is the span with the w = min(start,
+//                 32 768) bytes in front of it, and it begins to emit at w (SeqArgs::first); everything that handles the
+//                 text itself keeps the span's own offset and length
 //   adler_kernel  the Adler-32 of every span whose body did not fit its slot, from the text: the encoder's word for such a
 //                 span is not the whole span's when the batch went in slices of positions and the slot ran out early
 //   size_kernel   per span the joined form J or the stored form S (S exactly when J is strictly longer), its length, the
@@ -24,7 +27,8 @@ namespace md {
 namespace spn {
 
 __global__ void plan_kernel(uint64_t n, uint64_t len, uint64_t span, uint64_t stride, uint64_t *__restrict__ in_off,
-                            uint64_t *__restrict__ in_len, uint64_t *__restrict__ out_off, uint64_t *__restrict__ out_cap) {
+                            uint64_t *__restrict__ in_len, uint64_t *__restrict__ out_off, uint64_t *__restrict__ out_cap,
+                            uint64_t *__restrict__ x_off, uint64_t *__restrict__ x_len, uint32_t *__restrict__ first) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const uint64_t at = i * span, m = len - at < span ? len - at : span;
@@ -32,6 +36,12 @@ __global__ void plan_kernel(uint64_t n, uint64_t len, uint64_t span, uint64_t st
   in_len[i] = m;
   out_off[i] = i * stride;
   out_cap[i] = stored_size(m);
+  if (first) {  // primed: the stream of the deflate launch
+    const uint64_t w = at < kPrime ? at : kPrime;
+    x_off[i] = at - w;
+    x_len[i] = w + m;
+    first[i] = (uint32_t)w;
+  }
 }
 
 // bytes of the marker behind a joined span whose closing block ends at bit e: the three header bits 0 00 go into the last
@@ -201,8 +211,10 @@ using namespace md::spn;
 static inline uint32_t grid_of(uint64_t n, uint32_t threads) { return (uint32_t)((n + threads - 1) / threads); }
 
 extern "C" int md_launch_spans_plan(uint64_t n, uint64_t len, uint64_t span, uint64_t stride, uint64_t *in_off, uint64_t *in_len,
-                                    uint64_t *out_off, uint64_t *out_cap, hipStream_t stream) {
-  hipLaunchKernelGGL(plan_kernel, dim3(grid_of(n, 256)), dim3(256), 0, stream, n, len, span, stride, in_off, in_len, out_off, out_cap);
+                                    uint64_t *out_off, uint64_t *out_cap, uint64_t *x_off, uint64_t *x_len, uint32_t *first,
+                                    hipStream_t stream) {
+  hipLaunchKernelGGL(plan_kernel, dim3(grid_of(n, 256)), dim3(256), 0, stream, n, len, span, stride, in_off, in_len, out_off, out_cap, x_off,
+                     x_len, first);
   return (int)hipGetLastError();
 }
 extern "C" int md_launch_spans_adler(const Spans *s, const uint8_t *src, uint32_t *adler, hipStream_t stream) {

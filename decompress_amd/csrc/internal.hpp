@@ -93,6 +93,11 @@ struct SeqArgs {
   // (Null changes no byte and no result; the two notes the words are made from - one LDS store where a closing block's
   // header is put, one scalar move per packing step - are taken either way: they cost less than asking.)
   uint64_t *tail;
+  // Where each stream begins to emit (the writer of primed spans), or null: every stream from position 0.
+  // first[i] <= in_len[i].  The front kernels see the whole text as the stream it is; the matcher has walked [0, first[i])
+  // inserting every position and emitting nothing, and stands at first[i] with nothing pending and a fresh encoder.  The
+  // checksum (and a level-0 copy) covers [first[i], in_len[i]).  In pieces the first piece reads it.  Null changes nothing.
+  const uint32_t *first;
 };
 
 }  // namespace defl
@@ -159,6 +164,8 @@ namespace spn {
 constexpr uint64_t kStoredMax = 65535;
 constexpr uint64_t stored_blocks(uint64_t n) { return n ? (n + kStoredMax - 1) / kStoredMax : 1; }
 constexpr uint64_t stored_size(uint64_t n) { return n + 5 * stored_blocks(n); }
+// primed spans: a span's stream begins with at most this much of the text in front of it (De.Lz77's window)
+constexpr uint64_t kPrime = 32768;
 // what stands around the body: the header's bytes (none, Zl.Def's two, Gz.Def's), and by the format the trailer
 struct Frame {
   int format;
@@ -287,6 +294,10 @@ int md_launch_deflate_match(uint32_t n, uint32_t nchunks_max, const uint8_t *in,
 int md_launch_deflate_front(uint32_t n, uint32_t nchunks_max, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len,
                             int matcher, uint32_t max_chain, uint32_t nice, const md::defl::Front *f, const uint32_t *order,
                             uint32_t match_skip, hipStream_t stream);
+// streams that begin to emit at first[i] (SeqArgs::first): no verdicts for the chunks wholly below it
+int md_launch_deflate_front_first(uint32_t n, uint32_t nchunks_max, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len,
+                                  int matcher, uint32_t max_chain, uint32_t nice, const md::defl::Front *f, const uint32_t *order,
+                                  const uint32_t *first, hipStream_t stream);
 int md_launch_link_ns(uint32_t n, const uint8_t *in, const uint64_t *in_off, const uint64_t *in_len, const md::defl::Front *f,
                       hipStream_t stream);
 
@@ -343,9 +354,11 @@ int md_launch_bgzf_pack(uint64_t nb, const uint8_t *src, const uint64_t *in_off,
                         uint8_t *dst, hipStream_t stream);
 
 // ---- deflate_spans.hip: one stream as joined spans (md_deflate_spans_*) ----
-// span i = text [i * span, + span) -> stream i of the deflate launch, its slot stored_size(in_len[i]) bytes at i * stride
+// span i = text [i * span, + span) -> stream i of the deflate launch, its slot stored_size(in_len[i]) bytes at i * stride.
+// first != null (primed spans): the deflate launch's stream is x_off / x_len - the span and the w = min(i * span, kPrime)
+// bytes in front of it - and first[i] = w (SeqArgs::first); in_off / in_len stay the span's own
 int md_launch_spans_plan(uint64_t n, uint64_t len, uint64_t span, uint64_t stride, uint64_t *in_off, uint64_t *in_len, uint64_t *out_off,
-                         uint64_t *out_cap, hipStream_t stream);
+                         uint64_t *out_cap, uint64_t *x_off, uint64_t *x_len, uint32_t *first, hipStream_t stream);
 // adler[i] = the Adler-32 of span i, from the text, for every span whose status is "no room" (the others' are left alone)
 int md_launch_spans_adler(const md::spn::Spans *s, const uint8_t *src, uint32_t *adler, hipStream_t stream);
 // size[i], err, stored; the scan of size into off is md_launch_gzm_scan64

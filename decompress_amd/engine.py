@@ -1,5 +1,6 @@
 """Batch engine: device buffers in, device buffers out (torch is only the
 allocator / stream provider here; the work is done by libmdeflate.so)."""
+import contextlib
 import ctypes
 
 import numpy as _np
@@ -218,6 +219,22 @@ class Engine:
 
     def set_option(self, key, value):
         self._check(self.lib.md_set_option(self.ctx, key.encode(), int(value)))
+        if key == "deflate_span_prime":  # (the library has no query: `deflate_spans(prime=)` puts this back)
+            self._span_prime = int(value)
+
+    @contextlib.contextmanager
+    def _primed(self, prime):
+        """`prime` of deflate_spans*: None leaves the option "deflate_span_prime" as it is, True / False sets it for the
+        call and puts the old value back"""
+        old = getattr(self, "_span_prime", 0)
+        if prime is None or int(bool(prime)) == old:
+            yield
+            return
+        self.set_option("deflate_span_prime", int(bool(prime)))
+        try:
+            yield
+        finally:
+            self.set_option("deflate_span_prime", old)
 
     PROFILE_FIELDS = ["cyc_ensure", "cyc_decode1", "cyc_decode2", "cyc_emit_a", "cyc_far", "cyc_near",
                       "cyc_adler", "cyc_header", "cyc_near_fast", "cyc_near_slow", "cyc_near_upd", "cyc_near_load", "cyc_hdr_lens", "cyc_hdr_lit", "cyc_far_rec", "cyc_far_load", "cyc_wait_dec", "cyc_wait_copy", "rounds", "passes", "lanes", "tokens", "slots",
@@ -502,10 +519,12 @@ class Engine:
         return int(self.lib.md_deflate_spans_bound(fmt, n, int(span or 0), ctypes.byref(gz) if gz is not None else None))
 
     def deflate_spans(self, data, fmt=FORMAT_DEFLATE, span=None, level=6, queue=4096, driver=DRIVER_ZL, dynamic=True,
-                      matcher=None, header=None, cap=None):
+                      matcher=None, header=None, cap=None, prime=None):
         """ONE standard stream of `data` written as joined spans on the whole chip (md_deflate_spans_host):
         `span` bytes of text per span (None: the option "deflate_span_kib") -> (status, stream bytes, checksum of the
-        input: Adler-32, CRC-32 for FORMAT_GZIP).  cap: room of the destination (default: the bound)."""
+        input: Adler-32, CRC-32 for FORMAT_GZIP).  cap: room of the destination (default: the bound).  prime: every span's
+        matcher starts from the 32 KiB of text in front of it (None: the option "deflate_span_prime"; True / False: for
+        this call)."""
         data = data if isinstance(data, bytes) else bytes(data)
         params = self._params(level, queue, driver, dynamic, matcher, header)
         if cap is None:
@@ -514,23 +533,26 @@ class Engine:
                 cap = 1
         dst = ctypes.create_string_buffer(max(int(cap), 1))
         wrote, sum_ = ctypes.c_size_t(), ctypes.c_uint32()
-        st = self.lib.md_deflate_spans_host(self.ctx, fmt, ctypes.byref(params), int(span or 0), data, len(data), dst, int(cap),
-                                            ctypes.byref(wrote), ctypes.byref(sum_))
+        with self._primed(prime):
+            st = self.lib.md_deflate_spans_host(self.ctx, fmt, ctypes.byref(params), int(span or 0), data, len(data), dst, int(cap),
+                                                ctypes.byref(wrote), ctypes.byref(sum_))
         if st < 0:
             self._check(st)
         return int(st), dst.raw[:wrote.value], int(sum_.value)
 
     def deflate_spans_device(self, d_src, n, d_dst, fmt=FORMAT_DEFLATE, span=None, level=6, queue=4096, driver=DRIVER_ZL,
-                             dynamic=True, matcher=None, header=None):
+                             dynamic=True, matcher=None, header=None, prime=None):
         """md_deflate_spans_device: the first n bytes of the CUDA uint8 tensor d_src into the CUDA uint8 tensor d_dst, nothing
-        read back -> (written, status, checksum) CUDA tensors of one element (async on the engine's stream)."""
+        read back -> (written, status, checksum) CUDA tensors of one element (async on the engine's stream).  prime: as
+        `deflate_spans`'s."""
         torch = self.torch
         written = torch.zeros(1, dtype=torch.int64, device=self.device)
         status = torch.zeros(1, dtype=torch.int32, device=self.device)
         checksum = torch.zeros(1, dtype=torch.int32, device=self.device)
         params = self._params(level, queue, driver, dynamic, matcher, header)
-        self._check(self.lib.md_deflate_spans_device(self.ctx, fmt, ctypes.byref(params), int(span or 0), _ptr(d_src), int(n),
-                                                     _ptr(d_dst), d_dst.numel(), _ptr(written), _ptr(status), _ptr(checksum)))
+        with self._primed(prime):
+            self._check(self.lib.md_deflate_spans_device(self.ctx, fmt, ctypes.byref(params), int(span or 0), _ptr(d_src), int(n),
+                                                         _ptr(d_dst), d_dst.numel(), _ptr(written), _ptr(status), _ptr(checksum)))
         return written, status, checksum
 
     def deflate_spans_last(self):

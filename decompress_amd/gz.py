@@ -293,15 +293,17 @@ def index(src, span=1 << 20, device=0):
     return Index.build(src, _engine.FORMAT_GZIP, span=span, device=device)
 
 
-def compress_spans(src, level=6, span=None, filename=None, comment=None, mtime=0, os="Unix", ascii=False, hcrc=False, queue=4096, device=0):
+def compress_spans(src, level=6, span=None, filename=None, comment=None, mtime=0, os="Unix", ascii=False, hcrc=False, queue=4096, device=0,
+                   prime=None):
     """ONE GZip stream of src written as joined spans on the whole chip (md_deflate_spans_host): the text
     is cut into spans of `span` bytes (None: the option "deflate_span_kib"), the spans are compressed as one batch and
     joined into a stream that every inflater reads to its end.  Not the bytes of `Higher.compress`: a span cannot refer
-    back across a joint, so the stream is a little longer - and takes milliseconds where the single stream takes seconds."""
+    back across a joint, so the stream is a little longer - and takes milliseconds where the single stream takes seconds.  prime: every span's matcher starts from the 32 KiB
+    of text in front of it, which buys nearly all of that back (None: the option "deflate_span_prime")."""
     eng = _engine.default_engine(device)
     hdr = dict(mtime=int(mtime) & 0xffffffff, os=OS[os] if isinstance(os, str) else int(os), hcrc=int(bool(hcrc)),
                ascii=int(bool(ascii)), filename=filename, comment=comment)
-    st, out, _ = eng.deflate_spans(src, _engine.FORMAT_GZIP, span=span, level=level, queue=queue, header=hdr)
+    st, out, _ = eng.deflate_spans(src, _engine.FORMAT_GZIP, span=span, level=level, queue=queue, header=hdr, prime=prime)
     if st != 0:
         raise _engine.Error(_engine.STATUS_NAMES[st])
     return out

@@ -198,6 +198,9 @@ int md_synchronize(md_ctx *ctx);
  *                                need more goes in several rounds, one inflate launch each.  0: one member a round.
  *   "deflate_span_kib"           KiB (0 .. MD_MAX_STREAM / 1024; 0 = the default, 64): the text per span of md_deflate_spans_*
  *                                called with span = 0.  Smaller spans are more parallel, larger ones keep more of the ratio.
+ *   "deflate_span_prime"         0 or 1 (default 0; anything else is MD_E_INVALID_ARGUMENT): 1 = md_deflate_spans_* primes
+ *                                every span's matcher with the 32 KiB of text in front of it ("Primed spans" below).  Only
+ *                                md_deflate_spans_* read it.
  *   "debug_inflate_lds_pad", "debug_known_bounds"  measurement aids of tools/dbg (occupancy curve, known-boundaries floor).
  *   "profile"                    0 / 1: in-kernel phase profile of stream 0 (md_get_profile, a debugging aid).
  * Unknown keys and values out of range: MD_E_INVALID_ARGUMENT. */
@@ -718,6 +721,19 @@ int md_bgzf_compress(md_ctx *ctx, int level, size_t block, const uint8_t *src, s
  * MD_FORMAT_GZIP the header of params->gz_header in front and CRC-32 and length mod 2^32 behind.  With one span the bytes
  * are md_deflate_batch_host's for that text (unless the stored form wins).  A span cannot refer back across a joint, so
  * the stream is somewhat longer than the single stream (README); it depends on (text, params, span) alone.
+ * Primed spans (md_set_option "deflate_span_prime" = 1): span i is text [s_i, e_i) and has a prefix of
+ * w_i = min(s_i, 32768) bytes.  Its body B_i is defined over the stream X_i = text[s_i - w_i, e_i), whose position 0 is the
+ * prefix's first byte: B_i is what the reference's matcher (De.Lz77 or Lz) and De.Def write under `params` for X_i when the
+ * matcher has first walked positions [0, w_i) in this way - at each position it inserts the position if lookahead >=
+ * MIN_MATCH, then does strstart += 1, lookahead -= 1; it never calls longest_match and emits nothing; it then stands at
+ * strstart = w_i with match_available = false and match_length at its initial value (so De's first longest_match, entered
+ * with prev_length 0, also compares the byte in front of the span).  Everything else follows the reference in the positions
+ * of X_i: fill_window, the slide at strstart - base >= WSIZE + MAX_DIST, NIL at position 0, positions inserted ahead below
+ * the stream's end, the tail heads of its last string, the automatic end-of-block commands.  Histograms, queue and encoder
+ * start fresh; the input checksum covers [w_i, |X_i|) only; at level 0, or where the matcher only copies, the copy starts
+ * at w_i.  With w_i = 0 this is the unprimed B_i: span 0 and one-span calls keep their bytes.  h_i, e_i, J_i, S_i (chosen
+ * against the span's own bytes), marker, headers, trailers and checksums are as above.  The stream is nearly as short as the
+ * single stream; the per-position workspace covers src_len + 32768 (n - 1) positions at the most.
  *   span    bytes of text per span, 1 .. MD_MAX_STREAM; 0 = md_set_option "deflate_span_kib" (KiB; default 64)
  *   params  as md_deflate_batch_device takes them (levels 0-9, the three drivers, both matchers, dynamic 0 / 1, wbits 0 / 15);
  *           anything else is MD_E_INVALID_ARGUMENT.  total_in_bytes is ignored.  At most 0x7ffffff0 spans.

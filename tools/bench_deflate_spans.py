@@ -3,6 +3,8 @@
 sizes, against the single stream of Zl.Higher.compress's entry point (md_deflate_batch_host with n = 1) and against blocked
 gzip (md_bgzf_compress) on the same input, all in one process.  Same text generator as tools/bench_deflate_long.py.
     python tools/bench_deflate_spans.py --mib 64 --kinds text random --level 6 --spans 64 128 256 512 1024
+--prime adds primed rows ("deflate_span_prime") beside the unprimed ones, the variants of a span alternated run by run, and a
+third row per span with the prefix chunks kept in the match kernel ("deflate_test_flags" bit 5: same bytes, for the time).
 Prints one JSON line per (kind, writer): the median wall time of --reps runs in ms, the output size, and both relative to
 the single stream; every output is inflated back by libz and compared with the input after the timed region.  The last
 line per kind names the default the rule gives: the largest span whose time is within 10 % of the fastest."""
@@ -27,6 +29,7 @@ def main():
     ap.add_argument("--level", type=int, default=6)
     ap.add_argument("--spans", type=int, nargs="+", default=[64, 128, 256, 512, 1024], help="KiB")
     ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--prime", action="store_true", help="add primed rows beside the unprimed ones")
     ap.add_argument("--single-reps", type=int, default=3, help="runs of the single stream (seconds each)")
     args = ap.parse_args()
     import decompress_amd
@@ -58,13 +61,33 @@ def main():
         line("single", ms, out)
         ms, out = timed(lambda: gz.Bgzf.compress(data, level=args.level), args.reps)
         line("bgzf", ms, out, single)
-        rows = []
+        rows, primed_rows = [], []
+        variants = [("spans", False, 0)] + ([("spans-primed", True, 0), ("spans-primed-all-chunks", True, 32)] if args.prime else [])
         for kib in args.spans:
-            eng.deflate_spans(data, decompress_amd.FORMAT_ZLIB, span=kib << 10, level=args.level)  # (slots grow here, not in the timing)
-            ms, (st, out, _) = timed(lambda: eng.deflate_spans(data, decompress_amd.FORMAT_ZLIB, span=kib << 10, level=args.level), args.reps)
-            assert st == 0
-            line("spans", ms, out, single, span_kib=kib, **eng.deflate_spans_last())
-            rows.append((kib, ms))
+            def run(prime, flags):
+                eng.set_option("deflate_test_flags", flags)
+                try:
+                    return eng.deflate_spans(data, decompress_amd.FORMAT_ZLIB, span=kib << 10, level=args.level, prime=prime)
+                finally:
+                    eng.set_option("deflate_test_flags", 0)
+            ts, outs, last = {w: [] for w, _, _ in variants}, {}, {}
+            for w, prime, flags in variants:
+                run(prime, flags)  # (slots and workspace grow here, not in the timing)
+            for _ in range(args.reps):
+                for w, prime, flags in variants:
+                    t0 = time.perf_counter()
+                    st, outs[w], _ = run(prime, flags)
+                    ts[w].append((time.perf_counter() - t0) * 1e3)
+                    assert st == 0
+                    last[w] = eng.deflate_spans_last()
+            for w, _, _ in variants:
+                ms = statistics.median(ts[w])
+                line(w, ms, outs[w], single, span_kib=kib, min_ms=round(min(ts[w]), 1), max_ms=round(max(ts[w]), 1), **last[w])
+                (rows if w == "spans" else primed_rows if w == "spans-primed" else []).append((kib, ms))
+        if primed_rows:
+            fastest = min(ms for _, ms in primed_rows)
+            print(json.dumps({"kind": kind, "primed": True, "fastest_ms": round(fastest, 1),
+                              "default_by_rule_kib": max(kib for kib, ms in primed_rows if ms <= 1.1 * fastest)}), flush=True)
         fastest = min(ms for _, ms in rows)
         print(json.dumps({"kind": kind, "fastest_ms": round(fastest, 1),
                           "default_by_rule_kib": max(kib for kib, ms in rows if ms <= 1.1 * fastest)}), flush=True)
