@@ -168,6 +168,14 @@ SYMBOLS = [
     ("md_bgzf_read", ctypes.c_int, [c_vp, c_vp, c_vp, c_sz, c_sz, c_vp, c_vp, c_vp, c_vp, c_vp]),
     ("md_bgzf_read_virtual", ctypes.c_int, [c_vp, c_vp, c_vp, c_sz, c_sz, c_vp, c_vp, c_vp, c_vp, c_vp]),
     ("md_bgzf_read_last", ctypes.c_int, [c_vp, c_vp]),
+    ("md_pack_index", ctypes.c_int, [c_vp, c_sz, c_vp, c_vp, c_sz]),
+    ("md_pack_open", ctypes.c_int, [c_vp, c_vp, c_sz, c_vp, c_sz, ctypes.POINTER(c_vp)]),
+    ("md_pack_get", ctypes.c_int, [c_vp, c_vp]),
+    ("md_pack_objects", ctypes.c_int, [c_vp, c_vp, c_sz]),
+    ("md_pack_find", ctypes.c_int64, [c_vp, c_vp]),
+    ("md_pack_free", None, [c_vp]),
+    ("md_pack_read", ctypes.c_int, [c_vp, c_vp, c_vp, c_sz, c_vp, c_sz, ctypes.c_uint, c_vp, c_sz, c_vp, c_vp, c_vp]),
+    ("md_pack_last", ctypes.c_int, [c_vp, c_vp]),
 ]
 
 
@@ -190,6 +198,37 @@ class BgzfIndexInfo(ctypes.Structure):
 class BgzfReadStats(ctypes.Structure):
     """md_bgzf_read_stats of include/mdeflate.h"""
     _fields_ = [(k, ctypes.c_uint64) for k in ("members", "launches", "bytes_in", "bytes_scratch")]
+
+
+class PackIndexEntry(ctypes.Structure):
+    """md_pack_index_entry of include/mdeflate.h"""
+    _fields_ = [("offset", ctypes.c_uint64), ("crc32", ctypes.c_uint32), ("name", ctypes.c_uint8 * 20)]
+
+
+class PackIndexInfo(ctypes.Structure):
+    """md_pack_index_info of include/mdeflate.h"""
+    _fields_ = [("n", ctypes.c_uint64), ("has_64bit_table", ctypes.c_int), ("pack_checksum", ctypes.c_uint8 * 20)]
+
+
+class PackInfo(ctypes.Structure):
+    """md_pack_info of include/mdeflate.h"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("n", "deltas", "max_depth", "total_size", "failed")]
+
+
+class PackObject(ctypes.Structure):
+    """md_pack_object of include/mdeflate.h"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("size", "offset", "packed_len", "base")] + \
+               [("depth", ctypes.c_uint32), ("type", ctypes.c_uint32), ("status", ctypes.c_int32), ("name", ctypes.c_uint8 * 20)]
+
+
+class PackResult(ctypes.Structure):
+    """md_pack_result of include/mdeflate.h"""
+    _fields_ = [("entries", c_sz), ("failed", c_sz), ("written", ctypes.c_uint64)]
+
+
+class PackStats(ctypes.Structure):
+    """md_pack_stats of include/mdeflate.h"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("rounds", "inflate_launches", "apply_launches", "objects", "bytes_in", "apply_ns")]
 
 
 class ZipEntry(ctypes.Structure):

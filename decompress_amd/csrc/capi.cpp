@@ -78,6 +78,11 @@ const char *md_status_string(int s) {
   case MD_INVALID_ZIP_HEADER: return "Invalid ZIP local header";
   case MD_ZIP_UNSUPPORTED: return "Unsupported ZIP entry";
   case MD_INVALID_INDEX: return "Invalid index";
+  case MD_INVALID_PACK: return "Invalid pack";
+  case MD_INVALID_DELTA: return "Invalid delta";
+  case MD_INVALID_PACK_BASE: return "Invalid delta base";
+  case MD_PACK_MISSING_BASE: return "Missing delta base";
+  case MD_PACK_UNSUPPORTED: return "Unsupported pack";
   case MD_E_INVALID_ARGUMENT: return "Invalid argument";
   case MD_E_NO_DEVICE: return "No gfx950 device";
   case MD_E_HIP: return "HIP runtime error";
@@ -281,6 +286,11 @@ int md_set_option(md_ctx *ctx, const char *key, int value) {
   if (!strcmp(key, "index_read_workspace")) {  // MiB of piece scratch per round of md_inflate_index_read; 0 = one piece a round
     if (value < 0 || value > (1 << 20)) return fail(ctx, MD_E_INVALID_ARGUMENT, "index_read_workspace is 0 .. 2^20 (MiB)");
     ctx->zix_workspace = (size_t)value << 20;
+    return MD_OK;
+  }
+  if (!strcmp(key, "pack_workspace")) {  // MiB of scratch per round of md_pack_open / md_pack_read; 0 = one selected object a round
+    if (value < 0 || value > (1 << 20)) return fail(ctx, MD_E_INVALID_ARGUMENT, "pack_workspace is 0 .. 2^20 (MiB)");
+    ctx->pack_workspace = (size_t)value << 20;
     return MD_OK;
   }
   if (!strcmp(key, "bgzf_read_workspace")) {  // MiB of packed input and output slots per round of md_bgzf_read; 0 = one member a round

@@ -142,6 +142,9 @@ enum Scratch {
   // byte ranges of a blocked GZip file (md_bgzf_read): the touched members of a round packed back to back, their output
   // slots (tables and descriptors go through kGzmDesc, the ranges' bytes through kHostOut)
   kBgrIn, kBgrSlots,
+  // a git packfile (md_pack_*): the table of md_pack_open, the descriptors of a round, the delta payloads of md_pack_open (the
+  // pack goes through kHostIn; a read's output and its round's scratch are one block, kHostOut)
+  kPackDesc, kPackRound, kPackScratch,
   kScratchCount
 };
 
@@ -194,6 +197,10 @@ struct md_ctx {
   // round of md_bgzf_read; 0 = one member a round) and the counts of the last read (md_bgzf_read_last)
   size_t bgr_workspace = (size_t)256 << 20;
   md_bgzf_read_stats bgr_last = {};
+  // git packfiles: md_set_option "pack_workspace" (bytes of scratch per round of md_pack_open / md_pack_read; 0 = one selected
+  // object a round) and the counts of the last md_pack_read (md_pack_last)
+  size_t pack_workspace = (size_t)256 << 20;
+  md_pack_stats pack_last = {};
   // one stream written as joined spans: md_set_option "deflate_span_kib" (the span of a call that passes 0) and the counts of
   // the last md_deflate_spans_* call (md_deflate_spans_last)
   size_t span_bytes = md::kSpanDefault;

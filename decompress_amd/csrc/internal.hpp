@@ -249,6 +249,47 @@ struct Round {
   int32_t *verdict;  // 0 = good, else the status the ranges over this member get
 };
 }  // namespace bgr
+
+namespace pk {
+// git packfiles (pack_kernels.hip).  The objects of a pack in idx order: device arrays of n entries.
+constexpr uint32_t kNoBase = 0xffffffffu;
+// instruction bytes of a delta that one step of the apply kernel looks at: one per lane
+constexpr uint32_t kWindow = 64;
+// the table md_pack_open builds.  off / end: where the object lies in the pack (the idx's offsets, sorted on the host);
+// sorted_off / sorted_obj: the offsets ascending and whose they are; names: 20 bytes each, ascending.  The header
+// kernel leaves type (the object's own: 1-4, 6, 7), hsize (the size its header states), zoff (where its zlib stream
+// begins), base (kNoBase: none), status, and the chain's first state: jump = base, links = 1 for a delta with a base,
+// jump = itself, links = 0 for everything else.
+struct Table {
+  uint64_t n, pack_len;
+  const uint64_t *off, *end, *sorted_off;
+  const uint32_t *sorted_obj;
+  const uint8_t *names;
+  uint8_t *type;
+  uint64_t *hsize, *zoff;
+  uint32_t *base, *jump, *links;
+  int32_t *status;
+};
+// One needed zlib stream of a round: its packed bytes (header included) [off, off + packed) and the idx's CRC-32 of them,
+// the size its header states; in_len as the inflate launch got it.
+struct Stream {
+  uint64_t off, packed, in_len, hsize;
+  uint32_t crc, reserved;
+};
+static_assert(sizeof(Stream) == 40, "Stream is uploaded as is");
+// One delta of a level of a round.  All offsets count from the start of the round's buffer (the output, then the scratch):
+// the payload, the base's bytes, where the result goes.  self / base_slot: the delta's and its base's stream of the round,
+// whose statuses it reads and (self) writes.
+struct Delta {
+  uint64_t pay_off, pay_len, base_off, base_size, out_off, out_size;
+  uint32_t self, base_slot;
+};
+static_assert(sizeof(Delta) == 56, "Delta is uploaded as is");
+// a selected object that was selected before: len bytes from src_off to dst_off of the output
+struct Repeat {
+  uint64_t src_off, dst_off, len;
+};
+}  // namespace pk
 }  // namespace md
 
 extern "C" {
@@ -432,6 +473,25 @@ int md_launch_bgr_verdict(uint32_t count, const uint8_t *blob, const md::bgr::Ro
 int md_launch_bgr_gather(uint32_t count, const md::bgr::Round *r, uint32_t nr, const uint32_t *ids, uint64_t longest, const uint64_t *off,
                          const uint64_t *len, const uint8_t *slots, uint8_t *dst, const uint64_t *dst_off, int32_t *status,
                          hipStream_t stream);
+
+// ---- pack_kernels.hip: git packfiles (md_pack_open, md_pack_read) ----
+// one thread per object: the header's type / size varint, the base of a delta, Table's results
+int md_launch_pk_headers(const md::pk::Table *t, const uint8_t *pack, hipStream_t stream);
+// one round of pointer jumping: jump_out[i] = jump_in[jump_in[i]], links_out[i] = links_in[i] + links_in[jump_in[i]]
+int md_launch_pk_chain_step(uint64_t n, const uint32_t *jump_in, const uint32_t *links_in, uint32_t *jump_out, uint32_t *links_out,
+                            hipStream_t stream);
+// behind the last round: root[i] = jump[i] and depth[i] = links[i], or MD_INVALID_PACK where jump[i] is no root (a cycle)
+int md_launch_pk_chain_finish(uint64_t n, const uint32_t *jump, const uint32_t *links, uint32_t *root, uint32_t *depth, int32_t *status,
+                              hipStream_t stream);
+// behind the inflate launch of a round: every stream's final status (crc: md_launch_crc32's of the packed bytes, or null)
+int md_launch_pk_verdict(uint32_t count, const md::pk::Stream *s, const uint64_t *out_len, const uint64_t *consumed, const uint32_t *crc,
+                         int32_t *status, hipStream_t stream);
+// md_pack_open: the two varints in front of a delta payload's instructions (payload j = buf + pay_off[j], s[j].hsize bytes)
+int md_launch_pk_delta_sizes(uint32_t count, const md::pk::Stream *s, const uint8_t *buf, const uint64_t *pay_off, uint64_t *base_size,
+                             uint64_t *result_size, int32_t *status, hipStream_t stream);
+// one level of a round: one wavefront per delta
+int md_launch_pk_apply(uint32_t count, const md::pk::Delta *d, uint8_t *buf, int32_t *status, hipStream_t stream);
+int md_launch_pk_repeats(uint32_t count, const md::pk::Repeat *r, uint8_t *buf, hipStream_t stream);
 
 // ---- lzo_kernels.hip ----
 // resident workgroups of kind 0: the decoder, 1: the compressor, 2: the count kernel

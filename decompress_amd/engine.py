@@ -23,7 +23,8 @@ STATUS_NAMES = {
     13: "Queue.Full", 14: "Invalid input", 15: "No dictionary at offset 0 available",
     16: "Input is malformed or output is not large enough", 17: "Malformed input",
     18: "Invalid ZIP directory", 19: "Invalid ZIP local header", 20: "Unsupported ZIP entry",
-    21: "Invalid index",
+    21: "Invalid index", 22: "Invalid pack", 23: "Invalid delta", 24: "Invalid delta base", 25: "Missing delta base",
+    26: "Unsupported pack",
 }
 STATUS_CODES = {v: k for k, v in STATUS_NAMES.items()}
 

@@ -1,0 +1,111 @@
+"""git packfiles (pack v2 / v3 with an idx v2) through the C ABI's md_pack_* entry points: the idx is read on the host, the
+table of all objects - type, size, base, depth, status - is built once on the GPU, and a read decodes every selected object
+and the bases it hangs off in one inflate launch a round, then applies the deltas level by level."""
+import ctypes
+
+from . import engine as _engine
+from ._lib import PackIndexEntry, PackIndexInfo, PackInfo, PackObject, PackResult, PackStats
+from ._lib import load as _load
+
+TYPE_NAMES = {0: None, 1: "commit", 2: "tree", 3: "blob", 4: "tag"}
+VERIFY_CRC = 1
+NO_BASE = (1 << 64) - 1
+_INFO_KEYS = ("n", "deltas", "max_depth", "total_size", "failed")
+_OBJECT_KEYS = ("size", "offset", "packed_len", "base", "depth", "type", "status")
+_STATS_KEYS = ("rounds", "inflate_launches", "apply_launches", "objects", "bytes_in", "apply_ns")
+
+
+def _raw(src):
+    return src if isinstance(src, bytes) else bytes(src)
+
+
+def _status_name(st):
+    return _engine.STATUS_NAMES.get(st, _load().md_status_string(st).decode())
+
+
+def index(idx):
+    """md_pack_index (host arithmetic, no device needed) -> (entries, info): one dict per object in the idx's order - name
+    (20 bytes), offset, crc32 - and a dict of the idx's: n, has_64bit_table, pack_checksum.  Raises `Error` ("Invalid
+    index", "Unsupported pack") for what is no idx version 2."""
+    lib, idx = _load(), _raw(idx)
+    info = PackIndexInfo()
+    st = lib.md_pack_index(idx, len(idx), ctypes.byref(info), None, 0)
+    if st != 0:
+        raise _engine.Error(lib.md_status_string(st).decode())
+    ents = (PackIndexEntry * max(info.n, 1))()
+    st = lib.md_pack_index(idx, len(idx), ctypes.byref(info), ents, info.n)
+    if st != 0:
+        raise _engine.Error(lib.md_status_string(st).decode())
+    out = [{"name": bytes(e.name), "offset": e.offset, "crc32": e.crc32} for e in ents[:info.n]]
+    return out, {"n": info.n, "has_64bit_table": info.has_64bit_table, "pack_checksum": bytes(info.pack_checksum)}
+
+
+class Pack:
+    """md_pack_open: the table of a pack's objects.  `info`: n, deltas, max_depth, total_size, failed.  `objects`: one dict
+    per object in idx order - name, type (1 commit, 2 tree, 3 blob, 4 tag: the chain's root's), size, offset, packed_len,
+    base (an index, or None), depth, status (0 = Ok).  Raises `Error` for a pack or idx the call refuses."""
+
+    def __init__(self, pack, idx, device=0):
+        self._eng = _engine.default_engine(device)
+        self._pack = _raw(pack)
+        idx = _raw(idx)
+        h = ctypes.c_void_p()
+        st = self._eng.lib.md_pack_open(self._eng.ctx, self._pack, len(self._pack), idx, len(idx), ctypes.byref(h))
+        if st != 0:
+            self._eng._check(st)
+        self._h = h
+        lib = self._eng.lib
+        info = PackInfo()
+        lib.md_pack_get(self._h, ctypes.byref(info))
+        self.info = {k: getattr(info, k) for k in _INFO_KEYS}
+        objs = (PackObject * max(info.n, 1))()
+        lib.md_pack_objects(self._h, objs, info.n)
+        self.objects = []
+        for o in objs[:info.n]:
+            d = {k: getattr(o, k) for k in _OBJECT_KEYS}
+            d["name"] = bytes(o.name)
+            d["base"] = None if o.base == NO_BASE else o.base
+            self.objects.append(d)
+
+    def find(self, name):
+        """the index of the object named by 20 bytes (or 40 hex digits), or -1"""
+        name = bytes.fromhex(name) if isinstance(name, str) else bytes(name)
+        if len(name) != 20:
+            raise ValueError("a name has 20 bytes")
+        return self._eng.lib.md_pack_find(self._h, name)
+
+    def read_raw(self, select=None, verify_crc=False, dst_cap=None):
+        """md_pack_read as it is: (return value, statuses, out_off, bytes of dst, md_pack_result as a dict)"""
+        k = len(self.objects) if select is None else len(select)
+        sel = None if select is None else (ctypes.c_uint64 * max(k, 1))(*[int(i) for i in select])
+        need = sum(self.objects[i]["size"] for i in (range(k) if select is None else select) if 0 <= i < len(self.objects))
+        cap = need if dst_cap is None else dst_cap
+        dst = ctypes.create_string_buffer(max(cap, 1))
+        out_off, status, res = (ctypes.c_uint64 * (k + 1))(), (ctypes.c_int32 * max(k, 1))(), PackResult()
+        rc = self._eng.lib.md_pack_read(self._eng.ctx, self._h, self._pack, len(self._pack), sel, k, VERIFY_CRC if verify_crc else 0, dst, cap,
+                                        out_off, status, ctypes.byref(res))
+        return rc, list(status[:k]), list(out_off), dst.raw[:cap], {"entries": res.entries, "failed": res.failed, "written": res.written}
+
+    def read(self, select=None, verify_crc=False):
+        """md_pack_read: every object (or the indices in `select`, in idx order, repeats allowed) ->
+        [("Ok", (type, bytes)) | ("Error", status name)].  Objects are independent: a damaged one has its own status, and
+        so have the deltas that hang off it; the others are whole.  Raises `Error` for a selection out of range."""
+        rc, status, off, raw, _ = self.read_raw(select, verify_crc)
+        if rc != 0:
+            self._eng._check(rc)
+        idx = range(len(self.objects)) if select is None else select
+        return [("Ok", (self.objects[i]["type"], raw[off[j]:off[j + 1]])) if status[j] == 0 else ("Error", _status_name(status[j]))
+                for j, i in enumerate(idx)]
+
+    def last(self):
+        """md_pack_last: rounds, inflate_launches, apply_launches, objects, bytes_in, apply_ns of the engine's last read"""
+        s = PackStats()
+        self._eng._check(self._eng.lib.md_pack_last(self._eng.ctx, ctypes.byref(s)))
+        return {k: getattr(s, k) for k in _STATS_KEYS}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._eng.lib.md_pack_free(self._h)
+            self._h = None
+
+    __del__ = close

@@ -68,9 +68,16 @@ enum {
   MD_INVALID_ZIP_HEADER = 19,    /* "Invalid ZIP local header": an entry's local header or where its body lies */
   MD_ZIP_UNSUPPORTED = 20,       /* "Unsupported ZIP entry": encrypted, or a method other than 0 and 8 */
   /* the index of a long stream (md_inflate_index_* below) and of a blocked GZip file (md_bgzf_index_*) */
-  MD_INVALID_INDEX = 21          /* "Invalid index": a serialised index that breaks a rule of its layout, an index used with
+  MD_INVALID_INDEX = 21,         /* "Invalid index": a serialised index that breaks a rule of its layout, an index used with
                                   * another src than it was built from, a piece that does not end on the next point; a file
-                                  * without BC size fields, a virtual offset or a member that is not as the index says */
+                                  * without BC size fields, a virtual offset or a member that is not as the index says;
+                                  * a pack .idx that breaks a rule of its layout or belongs to another pack */
+  /* git packfiles (md_pack_* below) */
+  MD_INVALID_PACK = 22,      /* "Invalid pack": the pack's magic, an object's header, an OFS_DELTA offset, a REF_DELTA cycle */
+  MD_INVALID_DELTA = 23,     /* "Invalid delta": a delta's instructions or sizes */
+  MD_INVALID_PACK_BASE = 24, /* "Invalid delta base": the object is a delta and an object of its chain of bases failed */
+  MD_PACK_MISSING_BASE = 25, /* "Missing delta base": a REF_DELTA names an object the pack does not hold (a thin pack) */
+  MD_PACK_UNSUPPORTED = 26   /* "Unsupported pack": a pack version other than 2 and 3, an idx version other than 2 */
 };
 
 /* Call-level errors (negative): misuse raises Invalid_argument in the
@@ -196,6 +203,10 @@ int md_synchronize(md_ctx *ctx);
  *   "bgzf_read_workspace"        MiB (0 .. 2^20; default 256): device memory for the members that ONE round of md_bgzf_read
  *                                decodes - their bytes packed back to back plus their output slots.  A read whose members
  *                                need more goes in several rounds, one inflate launch each.  0: one member a round.
+ *   "pack_workspace"             MiB (0 .. 2^20; default 256): device memory for what ONE round of md_pack_open / md_pack_read
+ *                                keeps beside the caller's output - delta payloads, and the bases and intermediate results
+ *                                that were not asked for.  A call that needs more goes in several rounds, one inflate launch
+ *                                each.  0: one selected object (and its chain of bases) a round.
  *   "deflate_span_kib"           KiB (0 .. MD_MAX_STREAM / 1024; 0 = the default, 64): the text per span of md_deflate_spans_*
  *                                called with span = 0.  Smaller spans are more parallel, larger ones keep more of the ratio.
  *   "deflate_span_prime"         0 or 1 (default 0; anything else is MD_E_INVALID_ARGUMENT): 1 = md_deflate_spans_* primes
@@ -1013,6 +1024,113 @@ int md_bgzf_read(md_ctx *ctx, const md_bgzf_index *idx, const uint8_t *src, size
 int md_bgzf_read_virtual(md_ctx *ctx, const md_bgzf_index *idx, const uint8_t *src, size_t src_len, size_t n, const uint64_t *voff,
                          const uint64_t *len, uint8_t *dst, const uint64_t *dst_off, int32_t *status);
 int md_bgzf_read_last(const md_ctx *ctx, md_bgzf_read_stats *stats);
+
+/* ---- git packfiles (pack v2 / v3 with an idx v2 beside it): every object in one batch, deltas applied -------------------------
+ * A pack holds n objects, each a header and one zlib stream; most are deltas (copy / insert instructions against a base
+ * object that may itself be a delta).  The .idx beside the pack says where each object begins.
+ *
+ * md_pack_index reads an idx version 2 on the HOST: it takes no context and touches no device.  It is called twice, like
+ * md_zip_directory: first with cap = 0 for info->n, then with room for n entries (at most cap are written), in the idx's
+ * order - ascending by name.  Every read is checked against idx_len.  Layout: ff 74 4f 63, u32 version (big-endian, as all
+ * of it), 256 fan-out counts, n 20-byte names, n CRC-32s of the packed objects, n 31-bit offsets whose most significant
+ * bit marks an index into the table of m 64-bit offsets that follows, the pack's 20-byte checksum, the idx's own.
+ *   MD_PACK_UNSUPPORTED   no magic (idx version 1), or a version other than 2
+ *   MD_INVALID_INDEX      a file too short for its magic, its fan-out or what n implies; a fan-out that decreases; names
+ *                         that do not ascend strictly or do not lie where the fan-out says; an escape that points outside
+ *                         the 64-bit table; a length other than 8 + 1024 + 28 n + 8 m + 40, m = the number of escapes
+ * A SHA-256 repository's idx has 32-byte names and cannot be told apart from the idx alone: it ends as MD_INVALID_INDEX by
+ * the length rule.  MD_E_INVALID_ARGUMENT: NULL idx or info, NULL entries with cap != 0.
+ *
+ * md_pack_open builds the table of all n objects (host pointers; copy in, kernels, copy out, synchronise) and keeps it in
+ * the handle.  Call-level checks first: the pack begins with "PACK" (else MD_INVALID_PACK) and version 2 or 3 (else
+ * MD_PACK_UNSUPPORTED); its object count is the idx's n and its last 20 bytes are the idx's pack checksum (else
+ * MD_INVALID_INDEX: a 20-byte compare, nothing is hashed); every offset of the idx lies behind the pack's header and in
+ * front of its trailer, and no two are equal (else MD_INVALID_INDEX).  Then, with the idx's offsets sorted on the host - object i is
+ * pack[off_i, the next offset), the last one ends at pack_len - 20 -, per object:
+ *  - the header (one thread each): type and size varint.  Types 1-4, 6, 7; type 0 or 5, a size beyond 64 bits or a header
+ *    that passes the object's end: MD_INVALID_PACK.  OFS_DELTA: the offset varint v (+1 per continuation byte); the base is
+ *    the object at off_i - v; v = 0, v > off_i or no object there: MD_INVALID_PACK.  REF_DELTA: the base's name, looked up
+ *    in the idx; absent: MD_PACK_MISSING_BASE;
+ *  - depth and the chain's root by pointer jumping over the base links, ceil(log2 n) + 1 launches, no lane waits for
+ *    another: what has not reached a root by then is on a REF_DELTA cycle or hangs off one: MD_INVALID_PACK;
+ *  - a delta's final size: the delta payloads are inflated (rounds of "pack_workspace"; the status rules of md_pack_read's
+ *    inflate step apply) and the two varints in front of the instructions are read: base size and result size.  One that
+ *    does not fit 64 bits or passes the payload's end: MD_INVALID_DELTA; a base size that is not the base's final size:
+ *    MD_INVALID_DELTA.  The payloads are not kept;
+ *  - a delta with an object that failed above somewhere on its chain of bases: MD_INVALID_PACK_BASE (this last step walks
+ *    the table on the host, in order of depth).
+ * The type of a delta is its root's.  md_pack_get / md_pack_objects (idx order; objs may be NULL when cap is 0) / md_pack_find
+ * (host, by the fan-out; the index or -1) report the table; md_pack_free frees it.
+ *
+ * md_pack_read decodes the objects select[0 .. nselect) - indices in idx order, repeats allowed; select == NULL: all n -
+ * into dst, object j at out_off[j] (k + 1 words; sizes are the table's whatever the status).  If they need more than
+ * dst_cap the call returns MD_UNEXPECTED_END_OF_OUTPUT with res->written = the room needed and launches nothing.  Every
+ * object has its own status; a damaged object touches neither the bytes nor the status of another, except that a delta
+ * whose chain of bases holds a failed object gets MD_INVALID_PACK_BASE.  An object that failed in md_pack_open keeps that
+ * status and is not decoded.  pack must be the pack the table was built from: another length or trailer is MD_INVALID_INDEX
+ * as the call's return value; a selected index >= n or an unknown bit in flags is MD_E_INVALID_ARGUMENT.  Steps:
+ *  - plan (host, the table alone): the selected objects and the closure of their bases, each once a round;
+ *  - memory: a selected object that is no delta decodes straight into its place; a selected delta's result is applied
+ *    straight into its place; payloads, bases and intermediate results go to scratch.  Selected objects are taken into a
+ *    round while its scratch fits "pack_workspace"; an object whose own chain needs more gets MD_E_OUT_OF_MEMORY as its
+ *    status (with "pack_workspace" = 0 nothing is refused: one selected object a round);
+ *  - inflate: ONE launch per round over every needed zlib stream, each into exactly its header size.  MD_INVALID_SIZE: the
+ *    stream did not consume its whole packed length (git leaves no byte between objects), did not fill its size or holds
+ *    more; MD_INVALID_CHECKSUM: the zlib trailer; any other status is the decoder's;
+ *  - verify, with MD_PACK_VERIFY_CRC in flags: the idx's CRC-32 over each needed object's packed bytes, header included;
+ *    a mismatch is MD_INVALID_CHECKSUM;
+ *  - apply: one launch per depth 1, 2, .. of the round, ordered by the stream alone; one wavefront per delta.  An opcode
+ *    with bit 7 set copies from the base: its low 7 bits say which of 4 offset and 3 size bytes follow, size 0 means
+ *    0x10000; an opcode 1 .. 127 inserts that many bytes that follow it.  MD_INVALID_DELTA: opcode 0, a copy that leaves
+ *    the base, output beyond the result size, a payload that ends inside an instruction or with the result size not
+ *    reached, a base-size or result-size varint other than the table's.  A failing object leaves its bytes unspecified.
+ * md_pack_last: rounds, inflate launches, apply launches, objects decoded (a base decoded in two rounds counts twice) and
+ * bytes of the pack copied in, of the context's last md_pack_read, and the device time its apply launches took (two events
+ * a round around them, read when the call has synchronised).
+ * Limits per object: a packed length above MD_MAX_INFLATE_IN or a size above MD_MAX_STREAM is MD_E_INVALID_ARGUMENT as
+ * that object's status.
+ * Out of scope: hashing (names and the pack / idx trailers are not recomputed), writing packs, idx v1, .rev, multi-pack-index,
+ * bitmaps, the SHA-256 object format, completing a thin pack from another, objects above MD_MAX_STREAM, handing one very
+ * long object to the whole-chip decoder. */
+#define MD_PACK_VERIFY_CRC 1u
+#define MD_PACK_NO_BASE 0xffffffffffffffffull
+typedef struct md_pack_index_entry {
+  uint64_t offset;
+  uint32_t crc32;
+  uint8_t name[20];
+} md_pack_index_entry;
+typedef struct md_pack_index_info {
+  uint64_t n;
+  int has_64bit_table;
+  uint8_t pack_checksum[20];
+} md_pack_index_info;
+int md_pack_index(const uint8_t *idx, size_t idx_len, md_pack_index_info *info, md_pack_index_entry *entries, size_t cap);
+typedef struct md_pack md_pack;
+typedef struct md_pack_info {
+  uint64_t n, deltas, max_depth, total_size, failed;
+} md_pack_info;
+typedef struct md_pack_object {
+  uint64_t size, offset, packed_len, base; /* base: the index of the delta's base, MD_PACK_NO_BASE if none (or not found) */
+  uint32_t depth, type;                    /* type: 1 commit, 2 tree, 3 blob, 4 tag - the chain's root's; 0 if unknown */
+  int32_t status;
+  uint8_t name[20];
+} md_pack_object;
+typedef struct md_pack_result {
+  size_t entries, failed;
+  uint64_t written;
+} md_pack_result;
+typedef struct md_pack_stats {
+  uint64_t rounds, inflate_launches, apply_launches, objects, bytes_in;
+  uint64_t apply_ns; /* device time from the first apply launch of a round to the end of its last, summed over the rounds */
+} md_pack_stats;
+int md_pack_open(md_ctx *ctx, const uint8_t *pack, size_t pack_len, const uint8_t *idx, size_t idx_len, md_pack **p);
+int md_pack_get(const md_pack *p, md_pack_info *info);
+int md_pack_objects(const md_pack *p, md_pack_object *objs, size_t cap);
+int64_t md_pack_find(const md_pack *p, const uint8_t *name20);
+void md_pack_free(md_pack *p);
+int md_pack_read(md_ctx *ctx, const md_pack *p, const uint8_t *pack, size_t pack_len, const uint64_t *select, size_t nselect,
+                 unsigned flags, uint8_t *dst, size_t dst_cap, uint64_t *out_off, int32_t *status, md_pack_result *res);
+int md_pack_last(const md_ctx *ctx, md_pack_stats *stats);
 
 #ifdef __cplusplus
 }

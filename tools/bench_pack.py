@@ -1,0 +1,193 @@
+"""A git packfile read on one GPU, host to host, for DESIGN 4i.  The pack is written by tests/pack_writer.py from the
+corpus as version chains: `--objects` objects in chains of `--depth` deltas on a whole object, each version a small edit
+(a copy, an insert, a copy) of the one before it and stored as an OFS_DELTA against it; `--mib` is the total of the
+objects' sizes.
+
+  open        md_pack_open: idx, headers, chains, the deltas' sizes (their payloads inflated once)
+  read_all    md_pack_read of every object
+  read_1pct   md_pack_read of 1 % of the objects, chosen at random (and the bases they hang off)
+  payloads    md_inflate_batch_host over the same pack's zlib streams alone: what a caller could do before there was
+              md_pack_read - it yields the whole objects and the deltas' PAYLOADS, not the objects
+  git         `git cat-file --batch-all-objects --batch` over the same pack, one CPU process, if git is on the machine
+With read_all the share of its time that the apply launches take on the device (md_pack_last's apply_ns over the median).
+
+    python tools/bench_pack.py [--objects 16384] [--depth 8] [--mib 64] [--reps 7] [--warmup 1]
+
+The legs are alternated in one process; every leg reports the median and the spread (min .. max) of its repeats, host to
+host (perf_counter around a call that ends in a synchronise).  read_all's bytes are compared with the writer's."""
+import argparse
+import ctypes
+import json
+import os
+import random
+import shutil
+import statistics
+import subprocess
+import sys
+import tempfile
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import numpy as np  # noqa: E402
+
+from decompress_amd import _lib, workloads  # noqa: E402
+from decompress_amd import engine as _engine  # noqa: E402
+from decompress_amd import pack as mp  # noqa: E402
+from tests import pack_writer as pw  # noqa: E402
+
+
+def stats(v):
+    return {"median_ms": round(statistics.median(v), 3), "min_ms": round(min(v), 3), "max_ms": round(max(v), 3), "n": len(v)}
+
+
+def version_chains(objects, depth, size):
+    """entries for pack_writer: chains of a blob and `depth` deltas, each delta against the version before it"""
+    entries = []
+    chain = 0
+    while len(entries) < objects:
+        cur = workloads.corpus_slice(chain, size)
+        entries.append({"type": 3, "data": cur + b"%d" % chain})  # (the number: no two chains with one name)
+        cur = entries[-1]["data"]
+        for k in range(1, depth + 1):
+            if len(entries) == objects:
+                break
+            at = (37 * k + 101 * chain) % (len(cur) - 40) + 1
+            ins = [("copy", 0, at), ("insert", b"<%d.%d>" % (chain, k)), ("copy", at + 3, len(cur) - at - 3)]
+            entries.append({"delta": "ofs", "base": len(entries) - 1, "ins": ins})
+            cur = pw._result(cur, ins)
+        chain += 1
+    return entries
+
+
+def time_git(pack, idx, reps):
+    git = shutil.which("git")
+    if not git:
+        return None
+    env = dict(os.environ, GIT_CONFIG_GLOBAL="/dev/null", GIT_CONFIG_SYSTEM="/dev/null")
+    with tempfile.TemporaryDirectory() as tmp:
+        repo = os.path.join(tmp, "r.git")
+        subprocess.run([git, "init", "-q", "--bare", repo], check=True, env=env, capture_output=True)
+        stem = os.path.join(repo, "objects", "pack", "pack-" + pack[-20:].hex())
+        for ext, data in ((".pack", pack), (".idx", idx)):
+            with open(stem + ext, "wb") as f:
+                f.write(data)
+        times = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            r = subprocess.run([git, "-C", repo, "cat-file", "--batch-all-objects", "--batch"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+            times.append((time.perf_counter() - t0) * 1e3)
+            assert r.returncode == 0, r.stderr
+        return times
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--objects", type=int, default=16384)
+    ap.add_argument("--depth", type=int, default=8)
+    ap.add_argument("--mib", type=int, default=64)
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--warmup", type=int, default=1)
+    a = ap.parse_args()
+    eng = _engine.default_engine(0)
+    lib = eng.lib
+    size = max(64, (a.mib << 20) // a.objects)
+    pack, idx, layout = pw.write_pack(version_chains(a.objects, a.depth, size))
+    order = pw.idx_order(layout)
+    p = mp.Pack(pack, idx)
+    n = p.info["n"]
+    assert n == a.objects and p.info["failed"] == 0 and p.info["max_depth"] == min(a.depth, n - 1)
+    total = p.info["total_size"]
+
+    def opened():
+        h = ctypes.c_void_p()
+        eng._check(lib.md_pack_open(eng.ctx, pack, len(pack), idx, len(idx), ctypes.byref(h)))
+        lib.md_pack_free(h)
+
+    rng = random.Random(3)
+    some = sorted(rng.sample(range(n), max(1, n // 100)))
+    last = {}
+    calls = {}
+    for name, sel in (("read_all", None), ("read_1pct", some)):
+        k = n if sel is None else len(sel)
+        sizes = [p.objects[i]["size"] for i in (range(n) if sel is None else sel)]
+        dst = np.empty(max(sum(sizes), 1), dtype=np.uint8)  # (a buffer that exists: no first-touch page faults timed)
+        arr = None if sel is None else np.array(sel, dtype=np.uint64)
+        out_off, status, res = np.zeros(k + 1, dtype=np.uint64), np.zeros(k, dtype=np.int32), _lib.PackResult()
+
+        def read(arr=arr, k=k, dst=dst, out_off=out_off, status=status, res=res, name=name):
+            eng._check(lib.md_pack_read(eng.ctx, p._h, pack, len(pack), arr.ctypes.data if arr is not None else None, k, 0, dst.ctypes.data, dst.size,
+                                        out_off.ctypes.data, status.ctypes.data, ctypes.byref(res)))
+            last[name] = p.last()
+
+        calls[name] = (read, dst, out_off, status)
+    # the same streams through the batch decoder alone
+    objs = p.objects
+    in_off = np.array([o["offset"] + o["packed_len"] - len(_zlib_of(pack, o)) for o in objs], dtype=np.uint64)
+    in_len = np.array([len(_zlib_of(pack, o)) for o in objs], dtype=np.uint64)
+    caps = np.array([_header_size(pack, o) for o in objs], dtype=np.uint64)
+    p_off = np.concatenate(([0], np.cumsum(caps)[:-1])).astype(np.uint64)
+    h_in = np.frombuffer(pack, dtype=np.uint8)
+    h_out = np.empty(int(caps.sum()) + 1, dtype=np.uint8)
+    out_len, consumed, pst = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.int32)
+
+    def payloads():
+        eng._check(lib.md_inflate_batch_host(eng.ctx, _engine.FORMAT_ZLIB, n, h_in.ctypes.data, h_in.size, in_off.ctypes.data, in_len.ctypes.data,
+                                             h_out.ctypes.data, h_out.size, p_off.ctypes.data, caps.ctypes.data, out_len.ctypes.data,
+                                             consumed.ctypes.data, pst.ctypes.data, None))
+
+    legs = {"open": opened, "payloads": payloads}
+    legs.update({k: v[0] for k, v in calls.items()})
+    times = {k: [] for k in legs}
+    for r in range(a.warmup + a.reps):
+        for k, fn in legs.items():
+            t0 = time.perf_counter()
+            fn()
+            if r >= a.warmup:
+                times[k].append((time.perf_counter() - t0) * 1e3)
+    assert not pst.any() and np.array_equal(out_len, caps) and np.array_equal(consumed, in_len)
+    _, dst, out_off, status = calls["read_all"]
+    assert not status.any() and not calls["read_1pct"][3].any()
+    raw = dst.tobytes()
+    for k, lay in enumerate(layout):
+        i = order[k]
+        assert raw[int(out_off[i]):int(out_off[i + 1])] == lay["data"], k
+    res = {"objects": n, "depth": a.depth, "object_bytes": size, "pack_bytes": len(pack), "total_size": total, "deltas": p.info["deltas"],
+           "payload_bytes": int(caps.sum()), "reps": a.reps, "warmup": a.warmup, "times": {k: stats(v) for k, v in times.items()}, "last_stats": last}
+    med = res["times"]["read_all"]["median_ms"]
+    res["read_all_gib_s"] = round(total / 2**30 / (med / 1e3), 3)
+    res["apply_share_of_read_all"] = round(last["read_all"]["apply_ns"] / 1e6 / med, 4)
+    git = time_git(pack, idx, a.reps)
+    res["git_cat_file"] = stats(git) if git else "git is not on this machine: no CPU figure"
+    print(json.dumps(res))
+
+
+def _header_size(pack, o):
+    """the size the object's header states"""
+    at = o["offset"]
+    c = pack[at]
+    size, shift = c & 15, 4
+    while c & 0x80:
+        at += 1
+        c = pack[at]
+        size |= (c & 0x7f) << shift
+        shift += 7
+    return size
+
+
+def _zlib_of(pack, o):
+    """the object's zlib stream: what follows its header and, for an OFS_DELTA, its distance (the pack holds no REF_DELTA)"""
+    at = o["offset"]
+    kind = (pack[at] >> 4) & 7
+    while pack[at] & 0x80:
+        at += 1
+    at += 1
+    if kind == 6:
+        while pack[at] & 0x80:
+            at += 1
+        at += 1
+    return memoryview(pack)[at:o["offset"] + o["packed_len"]]
+
+
+if __name__ == "__main__":
+    main()
