@@ -176,6 +176,11 @@ SYMBOLS = [
     ("md_pack_free", None, [c_vp]),
     ("md_pack_read", ctypes.c_int, [c_vp, c_vp, c_vp, c_sz, c_vp, c_sz, ctypes.c_uint, c_vp, c_sz, c_vp, c_vp, c_vp]),
     ("md_pack_last", ctypes.c_int, [c_vp, c_vp]),
+    ("md_pack_verify", ctypes.c_int, [c_vp, c_vp, c_vp, c_sz, c_vp, c_sz, ctypes.c_uint, c_vp, c_vp]),
+    ("md_pack_check_trailers", ctypes.c_int, [c_vp, c_sz, c_vp, c_sz, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
+    ("md_sha1_batch_device", ctypes.c_int, [c_vp, c_sz, c_vp, c_vp, c_vp, c_vp, ctypes.c_uint64, c_vp]),
+    ("md_sha1_batch_host", ctypes.c_int, [c_vp, c_sz, c_vp, c_sz, c_vp, c_vp, c_vp, c_vp]),
+    ("md_sha1_last", ctypes.c_int, [c_vp, c_vp]),
 ]
 
 
@@ -229,6 +234,11 @@ class PackResult(ctypes.Structure):
 class PackStats(ctypes.Structure):
     """md_pack_stats of include/mdeflate.h"""
     _fields_ = [(k, ctypes.c_uint64) for k in ("rounds", "inflate_launches", "apply_launches", "objects", "bytes_in", "apply_ns")]
+
+
+class Sha1Stats(ctypes.Structure):
+    """md_sha1_stats of include/mdeflate.h"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("messages", "blocks", "launches", "device_ns")]
 
 
 class ZipEntry(ctypes.Structure):

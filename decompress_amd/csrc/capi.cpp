@@ -1,5 +1,6 @@
 // capi.cpp — host side of the C ABI declared in include/mdeflate.h: contexts, options, timing, status strings.  The
-// entry points of each area are in capi_inflate / capi_long_stream / capi_deflate / capi_gz_members / capi_zip / capi_zindex / capi_lzo.cpp.
+// entry points of each area are in capi_inflate / capi_long_stream / capi_deflate / capi_gz_members / capi_zip / capi_zindex / capi_lzo / capi_pack /
+// capi_sha1.cpp.
 // Plain HIP runtime calls; no torch types anywhere in this library.
 #include <string.h>
 
@@ -134,7 +135,8 @@ md_ctx *md_create(int device, void *hip_stream) {
     }
     ctx->own_stream = true;
   }
-  if (hipEventCreate(&ctx->ev0) != hipSuccess || hipEventCreate(&ctx->ev1) != hipSuccess) {
+  if (hipEventCreate(&ctx->ev0) != hipSuccess || hipEventCreate(&ctx->ev1) != hipSuccess || hipEventCreate(&ctx->sha_ev0) != hipSuccess ||
+      hipEventCreate(&ctx->sha_ev1) != hipSuccess) {
     md_destroy(ctx);
     fail(nullptr, MD_E_HIP, "hipEventCreate");
     return nullptr;
@@ -159,6 +161,8 @@ void md_destroy(md_ctx *ctx) {
   md::DeviceGuard guard(ctx->device);
   if (ctx->ev0) hipEventDestroy(ctx->ev0);
   if (ctx->ev1) hipEventDestroy(ctx->ev1);
+  if (ctx->sha_ev0) hipEventDestroy(ctx->sha_ev0);
+  if (ctx->sha_ev1) hipEventDestroy(ctx->sha_ev1);
   if (ctx->s_in) hipStreamDestroy(ctx->s_in);
   if (ctx->s_out) hipStreamDestroy(ctx->s_out);
   if (ctx->own_stream && ctx->stream) hipStreamDestroy(ctx->stream);
@@ -291,6 +295,11 @@ int md_set_option(md_ctx *ctx, const char *key, int value) {
   if (!strcmp(key, "pack_workspace")) {  // MiB of scratch per round of md_pack_open / md_pack_read; 0 = one selected object a round
     if (value < 0 || value > (1 << 20)) return fail(ctx, MD_E_INVALID_ARGUMENT, "pack_workspace is 0 .. 2^20 (MiB)");
     ctx->pack_workspace = (size_t)value << 20;
+    return MD_OK;
+  }
+  if (!strcmp(key, "sha1_launch_blocks")) {  // blocks of 64 bytes by which one launch of the SHA-1 kernel advances a message
+    if (value < 1 || value > (int)md::sha::kLaunchBlocksMax) return fail(ctx, MD_E_INVALID_ARGUMENT, "sha1_launch_blocks is 1 .. 2^24");
+    ctx->sha1_launch_blocks = (uint32_t)value;
     return MD_OK;
   }
   if (!strcmp(key, "bgzf_read_workspace")) {  // MiB of packed input and output slots per round of md_bgzf_read; 0 = one member a round

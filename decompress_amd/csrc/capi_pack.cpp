@@ -1,7 +1,8 @@
 // capi_pack.cpp — git packfiles (mdeflate.h: md_pack_index, md_pack_open, md_pack_get, md_pack_objects, md_pack_find,
-// md_pack_free, md_pack_read, md_pack_last).  The idx is the host's (pack_index.hpp), and so are the sort of its offsets,
-// the plan of a read and the last walk over the table in order of depth; headers, chains, sizes, statuses and the
-// deltas' instructions are the device's (pack_kernels.hip), the zlib streams the batch decoder's.
+// md_pack_free, md_pack_read, md_pack_verify, md_pack_last).  The idx is the host's (pack_index.hpp), and so are the sort
+// of its offsets, the plan of a read and the last walk over the table in order of depth; headers, chains, sizes, statuses
+// and the deltas' instructions are the device's (pack_kernels.hip), the zlib streams the batch decoder's, the names'
+// SHA-1s capi_sha1.cpp's (sha1_enqueue).
 #include <string.h>
 
 #include <algorithm>
@@ -264,9 +265,9 @@ int pack_open(md_ctx *ctx, const uint8_t *pack, size_t pack_len, const uint8_t *
   return MD_OK;
 }
 
-// pairs of events around the apply launches of the rounds of a read (md_pack_stats::apply_ns); an event that cannot be had
-// leaves the time 0, never fails the read
-struct ApplyTimers {
+// pairs of events around a step of the rounds of a read - the apply launches (md_pack_stats::apply_ns), the hash passes
+// (md_sha1_stats::device_ns); an event that cannot be had leaves the time 0, never fails the read
+struct PairTimers {
   std::vector<hipEvent_t> ev;
   void mark(hipStream_t st) {
     hipEvent_t e = nullptr;
@@ -283,7 +284,7 @@ struct ApplyTimers {
     }
     return (uint64_t)(ms * 1e6);
   }
-  ~ApplyTimers() {
+  ~PairTimers() {
     for (hipEvent_t e : ev)
       if (e) (void)hipEventDestroy(e);
   }
@@ -301,29 +302,39 @@ struct ReadRound {
   std::vector<int32_t> status;
   uint64_t scratch = 0;
   size_t selected = 0;
+  // MD_PACK_VERIFY_NAME: the hash pass's messages (every object of the round where its bytes stand, its size and its root's
+  // type), the idx's names, and what comes back: differs[slot] != 0, the SHA-1 is not the name
+  std::vector<uint64_t> size;
+  std::vector<uint8_t> type, names;
+  std::vector<uint32_t> differs;
+  Sha1Batch sha;
 };
 
-int pack_read(md_ctx *ctx, const md_pack *P, const uint8_t *pack, const uint64_t *select, size_t k, unsigned flags, uint8_t *dst, size_t dst_cap,
-              uint64_t *out_off, int32_t *status, md_pack_result *res) {
+// md_pack_read (keep: the selected objects stand in dst, out_off[k + 1] says where) and md_pack_verify (!keep: they stand in
+// the round's scratch like the bases, dst and out_off are null, nothing but the statuses comes back)
+int pack_read(md_ctx *ctx, const md_pack *P, const uint8_t *pack, const uint64_t *select, size_t k, unsigned flags, bool keep, uint8_t *dst,
+              size_t dst_cap, uint64_t *out_off, int32_t *status, md_pack_result *res) {
   const size_t n = P->objs.size();
   for (size_t j = 0; select && j < k; j++)
     if (select[j] >= n) return fail(ctx, MD_E_INVALID_ARGUMENT, "selected object out of range");
   const auto sel = [&](size_t j) { return select ? (size_t)select[j] : j; };
   uint64_t need = 0;
-  for (size_t j = 0; j < k; j++) {
+  for (size_t j = 0; keep && j < k; j++) {
     out_off[j] = need;
     const uint64_t sz = P->objs[sel(j)].size;
     need = need + sz < need ? UINT64_MAX : need + sz;
   }
-  out_off[k] = need;
+  if (keep) out_off[k] = need;
   res->entries = k;
   res->written = need;
   if (need > dst_cap) return MD_UNEXPECTED_END_OF_OUTPUT;
   ctx->pack_last = {};
+  const bool names = (flags & MD_PACK_VERIFY_NAME) != 0;
+  if (names) ctx->sha1_last = {}, ctx->sha1_pending = false;
   if (k == 0) return MD_OK;
 
   // -- the plan, from the table alone.  The buffer of a round: the output as it lies in dst, then the round's scratch.
-  const uint64_t scratch0 = slot_stride(need), ws = ctx->pack_workspace;
+  const uint64_t scratch0 = keep ? slot_stride(need) : 0, ws = ctx->pack_workspace;
   std::vector<uint32_t> stamp(n, kNone), slot_of(n, 0), sel_round(n, kNone), sel_slot(n, 0), first_at(n, kNone);
   std::vector<uint8_t> refused(n, 0);
   std::vector<ReadRound> rounds;
@@ -335,7 +346,7 @@ int pack_read(md_ctx *ctx, const md_pack *P, const uint8_t *pack, const uint64_t
       if (stamp[o] == round) break;
       chain.push_back(o);
       if (P->delta[o]) cost += slot_stride(P->hsize[o]);
-      if (o != s) cost += slot_stride(P->objs[o].size);
+      if (o != s || !keep) cost += slot_stride(P->objs[o].size);
       if (!P->delta[o]) break;
     }
     return cost;
@@ -344,7 +355,7 @@ int pack_read(md_ctx *ctx, const md_pack *P, const uint8_t *pack, const uint64_t
     const uint32_t s = (uint32_t)sel(j);
     if (P->objs[s].status != MD_OK || refused[s]) continue;
     if (first_at[s] != kNone) {  // selected before: copied from its first place when that round is through
-      rounds[sel_round[s]].repeats.push_back(Repeat{rounds[sel_round[s]].res_off[sel_slot[s]], out_off[j], P->objs[s].size});
+      if (keep) rounds[sel_round[s]].repeats.push_back(Repeat{rounds[sel_round[s]].res_off[sel_slot[s]], out_off[j], P->objs[s].size});
       continue;
     }
     first_at[s] = (uint32_t)j;
@@ -352,7 +363,7 @@ int pack_read(md_ctx *ctx, const md_pack *P, const uint8_t *pack, const uint64_t
     uint32_t r = (uint32_t)rounds.size() - 1;
     if (stamp[s] == r) {  // it is in this round's scratch, as another's base
       sel_round[s] = r, sel_slot[s] = slot_of[s];
-      rounds[r].repeats.push_back(Repeat{rounds[r].res_off[slot_of[s]], out_off[j], P->objs[s].size});
+      if (keep) rounds[r].repeats.push_back(Repeat{rounds[r].res_off[slot_of[s]], out_off[j], P->objs[s].size});
       continue;
     }
     uint64_t cost = cost_of(s, r);
@@ -374,7 +385,7 @@ int pack_read(md_ctx *ctx, const md_pack *P, const uint8_t *pack, const uint64_t
       const uint32_t slot = (uint32_t)R.obj.size();
       stamp[o] = r, slot_of[o] = slot;
       uint64_t place;  // of the object's bytes
-      if (o == s) place = out_off[j];
+      if (o == s && keep) place = out_off[j];
       else place = scratch0 + R.scratch, R.scratch += slot_stride(ob.size);
       uint64_t inflated = place;
       if (P->delta[o]) inflated = scratch0 + R.scratch, R.scratch += slot_stride(P->hsize[o]);
@@ -408,6 +419,14 @@ int pack_read(md_ctx *ctx, const md_pack *P, const uint8_t *pack, const uint64_t
     for (size_t q = 0; q < perm.size(); q++) dl[q] = R.deltas[perm[q]], dd[q] = R.delta_depth[perm[q]];
     R.deltas.swap(dl), R.delta_depth.swap(dd);
     R.status.assign(R.obj.size(), 0);
+    if (names) {
+      R.differs.assign(R.obj.size(), 0);
+      for (uint32_t o : R.obj) {
+        R.size.push_back(P->objs[o].size);
+        R.type.push_back((uint8_t)P->objs[o].type);
+        R.names.insert(R.names.end(), P->objs[o].name, P->objs[o].name + 20);
+      }
+    }
     max_scratch = std::max(max_scratch, R.scratch);
     max_count = std::max(max_count, R.obj.size());
     max_deltas = std::max(max_deltas, R.deltas.size());
@@ -432,7 +451,8 @@ int pack_read(md_ctx *ctx, const md_pack *P, const uint8_t *pack, const uint64_t
   md_pack_stats &stats = ctx->pack_last;
   stats.bytes_in = P->pack_len;
   const bool verify = (flags & MD_PACK_VERIFY_CRC) != 0;
-  ApplyTimers timers;
+  PairTimers timers, hash_timers;
+  md_sha1_stats &hashed = ctx->sha1_last;
   // -- the rounds, one behind the other on the context's stream: only the statuses come back
   for (ReadRound &R : rounds) {
     const size_t count = R.obj.size();
@@ -449,6 +469,14 @@ int pack_read(md_ctx *ctx, const md_pack *P, const uint8_t *pack, const uint64_t
       a = b;
     }
     if (!R.deltas.empty()) timers.mark(st);
+    if (names) {  // behind the round's last apply launch: every object where it stands; the verdicts are the host's, below
+      hash_timers.mark(st);
+      if ((rc = sha1_enqueue(ctx, count, d_buf, R.res_off.data(), R.size.data(), R.type.data(), &R.sha, &hashed)) != MD_OK) return rc;
+      if ((rc = upload(ctx, R.sha.expect, R.names.data(), count * 20)) != MD_OK) return rc;
+      MD_LAUNCH_TRY(ctx, md_launch_sha1_names((uint32_t)count, R.sha.digest, R.sha.expect, R.sha.differs, st));
+      hash_timers.mark(st);
+      if ((rc = download(ctx, R.differs.data(), R.sha.differs, count)) != MD_OK) return rc;
+    }
     if (!R.repeats.empty()) {
       if ((rc = upload(ctx, d.repeats, R.repeats.data(), R.repeats.size())) != MD_OK) return rc;
       MD_LAUNCH_TRY(ctx, md_launch_pk_repeats((uint32_t)R.repeats.size(), d.repeats, d_buf, st));
@@ -460,7 +488,21 @@ int pack_read(md_ctx *ctx, const md_pack *P, const uint8_t *pack, const uint64_t
   }
   HIP_TRY(ctx, hipStreamSynchronize(st));
   stats.apply_ns = timers.total_ns();
-  if (need) HIP_TRY(ctx, hipMemcpy(dst, d_buf, (size_t)need, hipMemcpyDeviceToHost));
+  if (names) {
+    hashed.device_ns = hash_timers.total_ns();
+    // The names' verdicts, in the order of the header's rules: a status of its own stays; else a failed base; else the
+    // name.  The deltas of a round are sorted by depth, so a base has its final status when its deltas are looked at.
+    for (ReadRound &R : rounds) {
+      for (size_t q = 0; q < R.obj.size(); q++)
+        if (!P->delta[R.obj[q]] && R.status[q] == MD_OK && R.differs[q]) R.status[q] = MD_INVALID_CHECKSUM;
+      for (const Delta &dl : R.deltas)
+        if (R.status[dl.self] == MD_OK) {
+          if (R.status[dl.base_slot] != MD_OK) R.status[dl.self] = MD_INVALID_PACK_BASE;
+          else if (R.differs[dl.self]) R.status[dl.self] = MD_INVALID_CHECKSUM;
+        }
+    }
+  }
+  if (keep && need) HIP_TRY(ctx, hipMemcpy(dst, d_buf, (size_t)need, hipMemcpyDeviceToHost));
   for (size_t j = 0; j < k; j++) {
     const uint32_t s = (uint32_t)sel(j);
     status[j] = P->objs[s].status != MD_OK ? P->objs[s].status : refused[s] ? MD_E_OUT_OF_MEMORY : rounds[sel_round[s]].status[sel_slot[s]];
@@ -527,15 +569,33 @@ int md_pack_read(md_ctx *ctx, const md_pack *p, const uint8_t *pack, size_t pack
   if (!ctx) return MD_E_INVALID_ARGUMENT;
   if (!p || !pack || !res || !out_off || (!dst && dst_cap)) return fail(ctx, MD_E_INVALID_ARGUMENT, "null pointer");
   memset(res, 0, sizeof *res);
-  if (flags & ~MD_PACK_VERIFY_CRC) return fail(ctx, MD_E_INVALID_ARGUMENT, "md_pack_read: unknown flag");
+  if (flags & ~(MD_PACK_VERIFY_CRC | MD_PACK_VERIFY_NAME)) return fail(ctx, MD_E_INVALID_ARGUMENT, "md_pack_read: unknown flag");
   if (pack_len != p->pack_len || memcmp(pack + pack_len - 20, p->pack_checksum, 20) != 0)
     return fail(ctx, MD_INVALID_INDEX, "md_pack_read: the table belongs to another pack");
   const size_t k = select ? nselect : p->objs.size();
   if (k > 0x7fffffffull) return fail(ctx, MD_E_INVALID_ARGUMENT, "too many objects in one call");
   if (k && !status) return fail(ctx, MD_E_INVALID_ARGUMENT, "null pointer");
   try {
-    return pack_read(ctx, p, pack, select, k, flags, dst, dst_cap, out_off, status, res);
+    return pack_read(ctx, p, pack, select, k, flags, true, dst, dst_cap, out_off, status, res);
   } catch (const std::bad_alloc &) {
     return fail(ctx, MD_E_OUT_OF_MEMORY, "host memory for the read's plan");
+  }
+}
+
+int md_pack_verify(md_ctx *ctx, const md_pack *p, const uint8_t *pack, size_t pack_len, const uint64_t *select, size_t nselect, unsigned flags,
+                   int32_t *status, md_pack_result *res) {
+  if (!ctx) return MD_E_INVALID_ARGUMENT;
+  if (!p || !pack || !res) return fail(ctx, MD_E_INVALID_ARGUMENT, "null pointer");
+  memset(res, 0, sizeof *res);
+  if (flags & ~(MD_PACK_VERIFY_CRC | MD_PACK_VERIFY_NAME)) return fail(ctx, MD_E_INVALID_ARGUMENT, "md_pack_verify: unknown flag");
+  if (pack_len != p->pack_len || memcmp(pack + pack_len - 20, p->pack_checksum, 20) != 0)
+    return fail(ctx, MD_INVALID_INDEX, "md_pack_verify: the table belongs to another pack");
+  const size_t k = select ? nselect : p->objs.size();
+  if (k > 0x7fffffffull) return fail(ctx, MD_E_INVALID_ARGUMENT, "too many objects in one call");
+  if (k && !status) return fail(ctx, MD_E_INVALID_ARGUMENT, "null pointer");
+  try {
+    return pack_read(ctx, p, pack, select, k, flags, false, nullptr, 0, nullptr, status, res);
+  } catch (const std::bad_alloc &) {
+    return fail(ctx, MD_E_OUT_OF_MEMORY, "host memory for the verification's plan");
   }
 }

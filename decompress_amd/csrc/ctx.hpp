@@ -145,6 +145,9 @@ enum Scratch {
   // a git packfile (md_pack_*): the table of md_pack_open, the descriptors of a round, the delta payloads of md_pack_open (the
   // pack goes through kHostIn; a read's output and its round's scratch are one block, kHostOut)
   kPackDesc, kPackRound, kPackScratch,
+  // SHA-1 of many messages (md_sha1_batch_*, the names of a round of md_pack_read / md_pack_verify): descriptors, states
+  // and digests (the host form's bytes go through kHostIn)
+  kShaDesc,
   kScratchCount
 };
 
@@ -201,6 +204,12 @@ struct md_ctx {
   // object a round) and the counts of the last md_pack_read (md_pack_last)
   size_t pack_workspace = (size_t)256 << 20;
   md_pack_stats pack_last = {};
+  // SHA-1 batches: md_set_option "sha1_launch_blocks" (blocks of 64 bytes by which one launch advances a message) and the
+  // counts of the last batch (md_sha1_last).  The device form reads nothing back: its two events are asked when the counts are
+  uint32_t sha1_launch_blocks = md::sha::kLaunchBlocksDefault;
+  md_sha1_stats sha1_last = {};
+  hipEvent_t sha_ev0 = nullptr, sha_ev1 = nullptr;
+  bool sha1_pending = false;
   // one stream written as joined spans: md_set_option "deflate_span_kib" (the span of a call that passes 0) and the counts of
   // the last md_deflate_spans_* call (md_deflate_spans_last)
   size_t span_bytes = md::kSpanDefault;
@@ -390,6 +399,25 @@ struct GzmIndex {
 // leads from offset 0 to the end of the file; then ix holds the members, their headers parsed and their output offsets
 // scanned (md_gz_members_scan, md_gz_members_uncompress, md_bgzf_index_build).
 int gzm_index(md_ctx *ctx, const uint8_t *d_src, uint64_t len, bool *indexed, GzmIndex *ix);
+// ---- capi_sha1.cpp ----
+// What a batch of n messages keeps on the device, carved from kShaDesc: the descriptors and states of md::sha::Args, the
+// digests (20 bytes a message, message order), and for the names of a pack the 20 bytes expected of each and the verdicts
+// of md_launch_sha1_names.
+struct Sha1Batch {
+  uint64_t *off = nullptr, *len = nullptr;
+  uint8_t *type = nullptr;
+  uint32_t *index = nullptr;
+  md::sha::State *state = nullptr;
+  uint8_t *digest = nullptr, *expect = nullptr;
+  uint32_t *differs = nullptr;
+  std::vector<uint32_t> order;  // the host's copy of index: it is uploaded from here, so it lives as long as the batch
+};
+// SHA-1 of n messages of the buffer at d_data whose lengths the host knows (host arrays; type null: the bytes as they
+// are): orders them longest first, uploads, and launches ceil(longest in blocks / "sha1_launch_blocks") times over a
+// shrinking prefix.  Nothing is read back and nothing waited for: off, len, type and *b live until the stream has been.
+// Adds messages, blocks and launches to *stats.
+int sha1_enqueue(md_ctx *ctx, size_t n, const uint8_t *d_data, const uint64_t *off, const uint64_t *len, const uint8_t *type, Sha1Batch *b,
+                 md_sha1_stats *stats);
 // ---- capi_long_stream.cpp: both return MD_NOT_HANDLED for what the serial path has to answer ----
 int continue_parallel(md_ctx *ctx, const uint8_t *src, size_t src_len, unsigned start_bit, uint8_t *dst, size_t hist_len,
                       size_t dst_cap, uint32_t adler_in, unsigned flags, size_t *dst_len, int *status, md_inf_resume *resume);

@@ -290,6 +290,30 @@ struct Repeat {
   uint64_t src_off, dst_off, len;
 };
 }  // namespace pk
+
+namespace sha {
+// SHA-1 of many messages, one a lane (sha1_kernels.hip).  Message m is data[off[m], off[m] + len[m]) with the header of
+// a git object of type[m] in front (1 commit, 2 tree, 3 blob, 4 tag; 0, or type == null: the bytes as they are), len[m] at
+// most MD_MAX_STREAM.  Its state between two launches: h[5] and the blocks of 64 bytes done.
+struct State {
+  uint32_t h[5], done;
+};
+// md_set_option "sha1_launch_blocks": its range, and the default (DESIGN 4j has the launch time measured for it)
+constexpr uint32_t kLaunchBlocksMax = 1u << 24, kLaunchBlocksDefault = 4096;
+static_assert(sizeof(State) == 24, "State is six words");
+// What one launch takes: md_launch_sha1's argument, the kernel's too.  Lane i of the launch has message index[i] (index ==
+// null: message i) and advances it by at most `blocks` blocks; fresh != 0: the first launch of the batch, the states are
+// the kernel's to begin.  The launch that ends message m leaves its 20 bytes at digest + 20 m.
+struct Args {
+  uint32_t count, blocks, fresh;
+  const uint8_t *data;
+  const uint64_t *off, *len;
+  const uint8_t *type;
+  const uint32_t *index;
+  State *state;
+  uint8_t *digest;
+};
+}  // namespace sha
 }  // namespace md
 
 extern "C" {
@@ -492,6 +516,11 @@ int md_launch_pk_delta_sizes(uint32_t count, const md::pk::Stream *s, const uint
 // one level of a round: one wavefront per delta
 int md_launch_pk_apply(uint32_t count, const md::pk::Delta *d, uint8_t *buf, int32_t *status, hipStream_t stream);
 int md_launch_pk_repeats(uint32_t count, const md::pk::Repeat *r, uint8_t *buf, hipStream_t stream);
+
+// ---- sha1_kernels.hip: SHA-1 of many messages (md_sha1_batch_*, MD_PACK_VERIFY_NAME) ----
+int md_launch_sha1(const md::sha::Args *args, hipStream_t stream);
+// differs[j] = the 20 bytes at digest + 20 j are not those at expect + 20 j
+int md_launch_sha1_names(uint32_t count, const uint8_t *digest, const uint8_t *expect, uint32_t *differs, hipStream_t stream);
 
 // ---- lzo_kernels.hip ----
 // resident workgroups of kind 0: the decoder, 1: the compressor, 2: the count kernel

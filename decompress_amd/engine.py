@@ -12,6 +12,7 @@ FORMAT_ZLIB = 1
 FORMAT_GZIP = 2
 MATCHER_DE, MATCHER_LZ = 0, 1
 DRIVER_ZL, DRIVER_HIGHER, DRIVER_CLI = 0, 1, 2
+SHA1_LAUNCH_BLOCKS = 4096  # the default of set_option("sha1_launch_blocks") (mdeflate.h)
 
 # variant names of De.Inf.Ns.error (lib/de.ml:1548-1555) + Zl.Inf.Ns.error (lib/zl.ml:383)
 STATUS_NAMES = {
@@ -217,6 +218,40 @@ class Engine:
         crc = self.torch.empty(n, dtype=self.torch.int32, device=self.device)
         self._check(self.lib.md_crc32_batch_device(self.ctx, n, _ptr(d_data), _ptr(d_off), _ptr(d_len), _ptr(crc)))
         return crc
+
+    def sha1_batch(self, bufs, types=None):
+        """md_sha1_batch_host on a list of bytes -> [20-byte digest]: SHA-1 of each buffer as it is, or with types[i] in
+        1 .. 4 its name as a git commit / tree / blob / tag.  Synchronous."""
+        n = len(bufs)
+        if types is not None and len(types) != n:
+            raise Error("Invalid argument: one type per buffer")
+        in_len = _np.array([len(b) for b in bufs], dtype=_np.uint64)
+        in_off = _np.zeros(max(n, 1), dtype=_np.uint64)
+        if n > 1:
+            _np.cumsum(in_len[:-1], out=in_off[1:])
+        blob = _np.frombuffer(b"".join(bytes(b) for b in bufs), dtype=_np.uint8)
+        if types is not None and any(not 0 <= int(t) <= 255 for t in types):
+            raise Error("Invalid argument: a type is 0 .. 4")
+        typ = None if types is None else _np.array([int(t) for t in types] or [0], dtype=_np.uint8)
+        digest = _np.zeros(20 * max(n, 1), dtype=_np.uint8)
+        self._check(self.lib.md_sha1_batch_host(self.ctx, n, blob.ctypes.data if blob.size else None, blob.size, in_off.ctypes.data,
+                                                in_len.ctypes.data if n else None, typ.ctypes.data if typ is not None else None,
+                                                digest.ctypes.data))
+        return [digest[20 * i:20 * i + 20].tobytes() for i in range(n)]
+
+    def sha1_batch_device(self, d_data, d_off, d_len, d_type, max_len):
+        """md_sha1_batch_device: n device-resident buffers -> uint8 tensor of 20 n bytes (device, async).  d_type may be None;
+        max_len bounds every length (it sets the number of launches)."""
+        n = d_off.numel()
+        digest = self.torch.empty(20 * n, dtype=self.torch.uint8, device=self.device)
+        self._check(self.lib.md_sha1_batch_device(self.ctx, n, _ptr(d_data), _ptr(d_off), _ptr(d_len), _ptr(d_type), int(max_len), _ptr(digest)))
+        return digest
+
+    def sha1_last(self):
+        """md_sha1_last: messages, blocks, launches, device_ns of the last SHA-1 batch (a pack read's hash passes included)"""
+        s = _lib.Sha1Stats()
+        self._check(self.lib.md_sha1_last(self.ctx, ctypes.byref(s)))
+        return {k: getattr(s, k) for k in ("messages", "blocks", "launches", "device_ns")}
 
     def set_option(self, key, value):
         self._check(self.lib.md_set_option(self.ctx, key.encode(), int(value)))

@@ -9,6 +9,7 @@ from ._lib import load as _load
 
 TYPE_NAMES = {0: None, 1: "commit", 2: "tree", 3: "blob", 4: "tag"}
 VERIFY_CRC = 1
+VERIFY_NAMES = 2
 NO_BASE = (1 << 64) - 1
 _INFO_KEYS = ("n", "deltas", "max_depth", "total_size", "failed")
 _OBJECT_KEYS = ("size", "offset", "packed_len", "base", "depth", "type", "status")
@@ -21,6 +22,10 @@ def _raw(src):
 
 def _status_name(st):
     return _engine.STATUS_NAMES.get(st, _load().md_status_string(st).decode())
+
+
+def _flags(crc, names):
+    return (VERIFY_CRC if crc else 0) | (VERIFY_NAMES if names else 0)
 
 
 def index(idx):
@@ -38,6 +43,27 @@ def index(idx):
         raise _engine.Error(lib.md_status_string(st).decode())
     out = [{"name": bytes(e.name), "offset": e.offset, "crc32": e.crc32} for e in ents[:info.n]]
     return out, {"n": info.n, "has_64bit_table": info.has_64bit_table, "pack_checksum": bytes(info.pack_checksum)}
+
+
+def hash_objects(types, bufs, device=0):
+    """`git hash-object` for a batch: the 20-byte names of the objects whose contents are `bufs` and whose types are `types`
+    (1 commit, 2 tree, 3 blob, 4 tag, or those words), hashed on the GPU (md_sha1_batch_host)"""
+    by_name = {v: k for k, v in TYPE_NAMES.items() if v}
+    types = [by_name[t] if isinstance(t, str) else int(t) for t in types]
+    if any(not 1 <= t <= 4 for t in types):
+        raise ValueError("a git object is a commit, a tree, a blob or a tag")
+    return _engine.default_engine(device).sha1_batch(bufs, types)
+
+
+def check_trailers(pack, idx):
+    """md_pack_check_trailers (host, no device needed) -> (pack_ok, idx_ok): each file's last 20 bytes are the SHA-1 of what
+    is in front of them.  Raises `Error` ("Invalid pack", "Invalid index") for a file too short to be one."""
+    lib, pack, idx = _load(), _raw(pack), _raw(idx)
+    pack_ok, idx_ok = ctypes.c_int(0), ctypes.c_int(0)
+    st = lib.md_pack_check_trailers(pack, len(pack), idx, len(idx), ctypes.byref(pack_ok), ctypes.byref(idx_ok))
+    if st != 0:
+        raise _engine.Error(lib.md_status_string(st).decode())
+    return bool(pack_ok.value), bool(idx_ok.value)
 
 
 class Pack:
@@ -74,7 +100,7 @@ class Pack:
             raise ValueError("a name has 20 bytes")
         return self._eng.lib.md_pack_find(self._h, name)
 
-    def read_raw(self, select=None, verify_crc=False, dst_cap=None):
+    def read_raw(self, select=None, verify_crc=False, dst_cap=None, verify_names=False):
         """md_pack_read as it is: (return value, statuses, out_off, bytes of dst, md_pack_result as a dict)"""
         k = len(self.objects) if select is None else len(select)
         sel = None if select is None else (ctypes.c_uint64 * max(k, 1))(*[int(i) for i in select])
@@ -82,20 +108,38 @@ class Pack:
         cap = need if dst_cap is None else dst_cap
         dst = ctypes.create_string_buffer(max(cap, 1))
         out_off, status, res = (ctypes.c_uint64 * (k + 1))(), (ctypes.c_int32 * max(k, 1))(), PackResult()
-        rc = self._eng.lib.md_pack_read(self._eng.ctx, self._h, self._pack, len(self._pack), sel, k, VERIFY_CRC if verify_crc else 0, dst, cap,
+        rc = self._eng.lib.md_pack_read(self._eng.ctx, self._h, self._pack, len(self._pack), sel, k, _flags(verify_crc, verify_names), dst, cap,
                                         out_off, status, ctypes.byref(res))
         return rc, list(status[:k]), list(out_off), dst.raw[:cap], {"entries": res.entries, "failed": res.failed, "written": res.written}
 
-    def read(self, select=None, verify_crc=False):
+    def read(self, select=None, verify_crc=False, verify_names=False):
         """md_pack_read: every object (or the indices in `select`, in idx order, repeats allowed) ->
         [("Ok", (type, bytes)) | ("Error", status name)].  Objects are independent: a damaged one has its own status, and
-        so have the deltas that hang off it; the others are whole.  Raises `Error` for a selection out of range."""
-        rc, status, off, raw, _ = self.read_raw(select, verify_crc)
+        so have the deltas that hang off it; the others are whole.  verify_names: every decoded object's SHA-1 is held
+        against its name in the idx ("Invalid_checksum" where it differs).  Raises `Error` for a selection out of range."""
+        rc, status, off, raw, _ = self.read_raw(select, verify_crc, None, verify_names)
         if rc != 0:
             self._eng._check(rc)
         idx = range(len(self.objects)) if select is None else select
         return [("Ok", (self.objects[i]["type"], raw[off[j]:off[j + 1]])) if status[j] == 0 else ("Error", _status_name(status[j]))
                 for j, i in enumerate(idx)]
+
+    def verify_raw(self, select=None, flags=VERIFY_CRC | VERIFY_NAMES):
+        """md_pack_verify as it is: (return value, statuses, md_pack_result as a dict)"""
+        k = len(self.objects) if select is None else len(select)
+        sel = None if select is None else (ctypes.c_uint64 * max(k, 1))(*[int(i) for i in select])
+        status, res = (ctypes.c_int32 * max(k, 1))(), PackResult()
+        rc = self._eng.lib.md_pack_verify(self._eng.ctx, self._h, self._pack, len(self._pack), sel, k, flags, status, ctypes.byref(res))
+        return rc, list(status[:k]), {"entries": res.entries, "failed": res.failed, "written": res.written}
+
+    def verify(self, select=None, crc=True, names=True):
+        """md_pack_verify: every object (or those in `select`) decoded and checked on the device - the idx's CRC-32 of its
+        packed bytes, the SHA-1 of its content against its name - with nothing copied back -> [status name], "Ok" for a
+        sound object.  Raises `Error` for a selection out of range."""
+        rc, status, _ = self.verify_raw(select, _flags(crc, names))
+        if rc != 0:
+            self._eng._check(rc)
+        return [_status_name(st) for st in status]
 
     def last(self):
         """md_pack_last: rounds, inflate_launches, apply_launches, objects, bytes_in, apply_ns of the engine's last read"""

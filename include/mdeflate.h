@@ -207,6 +207,9 @@ int md_synchronize(md_ctx *ctx);
  *                                keeps beside the caller's output - delta payloads, and the bases and intermediate results
  *                                that were not asked for.  A call that needs more goes in several rounds, one inflate launch
  *                                each.  0: one selected object (and its chain of bases) a round.
+ *   "sha1_launch_blocks"         1 .. 2^24 (default 4096): blocks of 64 bytes by which ONE launch of the SHA-1 kernel advances
+ *                                a message (md_sha1_batch_*, MD_PACK_VERIFY_NAME).  Longer messages take further launches, the
+ *                                state kept on the device.  Digests do not depend on it.
  *   "deflate_span_kib"           KiB (0 .. MD_MAX_STREAM / 1024; 0 = the default, 64): the text per span of md_deflate_spans_*
  *                                called with span = 0.  Smaller spans are more parallel, larger ones keep more of the ratio.
  *   "deflate_span_prime"         0 or 1 (default 0; anything else is MD_E_INVALID_ARGUMENT): 1 = md_deflate_spans_* primes
@@ -1068,7 +1071,8 @@ int md_bgzf_read_last(const md_ctx *ctx, md_bgzf_read_stats *stats);
  * object has its own status; a damaged object touches neither the bytes nor the status of another, except that a delta
  * whose chain of bases holds a failed object gets MD_INVALID_PACK_BASE.  An object that failed in md_pack_open keeps that
  * status and is not decoded.  pack must be the pack the table was built from: another length or trailer is MD_INVALID_INDEX
- * as the call's return value; a selected index >= n or an unknown bit in flags is MD_E_INVALID_ARGUMENT.  Steps:
+ * as the call's return value; a selected index >= n or an unknown bit in flags (one that is neither MD_PACK_VERIFY_CRC
+ * nor MD_PACK_VERIFY_NAME) is MD_E_INVALID_ARGUMENT.  Steps:
  *  - plan (host, the table alone): the selected objects and the closure of their bases, each once a round;
  *  - memory: a selected object that is no delta decodes straight into its place; a selected delta's result is applied
  *    straight into its place; payloads, bases and intermediate results go to scratch.  Selected objects are taken into a
@@ -1089,10 +1093,31 @@ int md_bgzf_read_last(const md_ctx *ctx, md_bgzf_read_stats *stats);
  * a round around them, read when the call has synchronised).
  * Limits per object: a packed length above MD_MAX_INFLATE_IN or a size above MD_MAX_STREAM is MD_E_INVALID_ARGUMENT as
  * that object's status.
- * Out of scope: hashing (names and the pack / idx trailers are not recomputed), writing packs, idx v1, .rev, multi-pack-index,
- * bitmaps, the SHA-256 object format, completing a thin pack from another, objects above MD_MAX_STREAM, handing one very
- * long object to the whole-chip decoder. */
+ *
+ * Names.  An object's name is SHA-1("<type> <size>\0" + content), type being "commit", "tree", "blob" or "tag" - a delta's is
+ * its root's - and size the content's length in decimal.  With MD_PACK_VERIFY_NAME in flags a hash pass (md_sha1_batch_*'s
+ * kernel) runs in every round behind the round's last apply launch, over every object of the round - the selected ones and
+ * the bases alike - where its bytes stand, and the 20 bytes are compared with the idx's name on the device.  The rules, per
+ * object and in this order: a status of its own from the steps above stays (with both flags a CRC failure comes first, as
+ * without names); else a failed object anywhere on its chain of bases - failed by name included - is MD_INVALID_PACK_BASE;
+ * else a name other than the idx's is MD_INVALID_CHECKSUM (the CRC rule's status for "the idx says otherwise": there is no
+ * status of its own).  A failing object's bytes are unspecified; every other object's bytes are what they are without the
+ * flag.  md_sha1_last has the hash passes' counts and device time, summed over the rounds of the call.
+ *
+ * md_pack_verify is md_pack_read without output: the same plan, rounds and statuses for the same flags, but the selected
+ * objects stand in the round's scratch, so "pack_workspace" cuts the rounds with a selected object's own size counted (and
+ * an object may get MD_E_OUT_OF_MEMORY here that a read has room for), a repeated selection costs no copy, and nothing
+ * comes back but the statuses: res->written is 0.  With flags = 0 it still says which objects decode.
+ *
+ * md_pack_check_trailers runs on the HOST, without a context: *pack_ok = the pack's last 20 bytes are the SHA-1 of all that
+ * is in front of them, *idx_ok the same for the idx (one serial message each: not a shape for the device).  An idx shorter
+ * than an empty idx (8 + 1024 + 40 bytes) is MD_INVALID_INDEX, a pack shorter than an empty pack (32) MD_INVALID_PACK, and
+ * neither flag is written; NULL pointers are MD_E_INVALID_ARGUMENT.
+ * Out of scope: building an idx from a pack alone, writing packs, idx v1, .rev, multi-pack-index, bitmaps, the SHA-256 object
+ * format, SHA-1 collision detection, hashing the trailers on the device, completing a thin pack from another, objects above
+ * MD_MAX_STREAM, handing one very long object to the whole-chip decoder. */
 #define MD_PACK_VERIFY_CRC 1u
+#define MD_PACK_VERIFY_NAME 2u
 #define MD_PACK_NO_BASE 0xffffffffffffffffull
 typedef struct md_pack_index_entry {
   uint64_t offset;
@@ -1131,6 +1156,43 @@ void md_pack_free(md_pack *p);
 int md_pack_read(md_ctx *ctx, const md_pack *p, const uint8_t *pack, size_t pack_len, const uint64_t *select, size_t nselect,
                  unsigned flags, uint8_t *dst, size_t dst_cap, uint64_t *out_off, int32_t *status, md_pack_result *res);
 int md_pack_last(const md_ctx *ctx, md_pack_stats *stats);
+int md_pack_verify(md_ctx *ctx, const md_pack *p, const uint8_t *pack, size_t pack_len, const uint64_t *select, size_t nselect,
+                   unsigned flags, int32_t *status, md_pack_result *res);
+int md_pack_check_trailers(const uint8_t *pack, size_t pack_len, const uint8_t *idx, size_t idx_len, int *pack_ok, int *idx_ok);
+
+/* ---- SHA-1 of many buffers: one message a lane, 64 a wavefront (csrc/sha1_kernels.hip) ---------------------------------------
+ * SHA-1 is serial inside a message, so one long message is hashed by one lane, at tens of MB/s; the batch is what is fast.
+ * Message i is data[off[i], off[i] + len[i]), at any byte address; the kernel reads no dword that holds no byte of a
+ * message, so the buffer may end with the last one.  type == NULL or type[i] == 0: the SHA-1 of the bytes as they are;
+ * type[i] = 1 .. 4: the git object name of a commit / tree / blob / tag with that content (the header "<type> <size>\0" is
+ * the kernel's own).  digest receives 20 bytes a message.  n == 0 is MD_OK and launches nothing.
+ *
+ * One launch advances every message by at most "sha1_launch_blocks" blocks of 64 bytes (md_set_option; 1 .. 2^24), the
+ * state waits in device memory between launches: no launch runs longer than that many blocks take, whatever the lengths.
+ *
+ * md_sha1_batch_host (host pointers; copy in, kernels, copy out, synchronise): every range is checked against data_len and
+ * every length against MD_MAX_STREAM, a type above 4 is refused: MD_E_INVALID_ARGUMENT, as are NULL data (with data_len
+ * != 0), off, len or digest.  The host knows the lengths: it orders the messages longest first, so that the lanes of a
+ * wavefront are of similar length, and launches ceil(blocks of the longest / "sha1_launch_blocks") times over a shrinking
+ * prefix of that order, nothing read back in between.
+ *
+ * md_sha1_batch_device (device pointers, asynchronous on the context's stream like md_crc32_batch_device): the lengths
+ * live on the device, so the launch count comes from an extra argument, max_len: the caller's bound on the longest
+ * len[i], at most MD_MAX_STREAM.  Every launch covers all n messages, in index order; a message that is through drops out
+ * at once.  The caller's duties, which the host cannot check: len[i] <= max_len (a longer message is not finished and its
+ * digest is not written; no byte outside its range is read whatever it says) and type[i] <= 4 (a larger one is hashed as 0).
+ *
+ * md_sha1_last: messages, blocks of 64 bytes (header and padding included), launches and the device time between two
+ * events around them, of the context's last batch - that of md_sha1_batch_*, or the hash passes of the last md_pack_read /
+ * md_pack_verify with MD_PACK_VERIFY_NAME, summed over its rounds.  After the device form it waits for the second event. */
+typedef struct md_sha1_stats {
+  uint64_t messages, blocks, launches, device_ns;
+} md_sha1_stats;
+int md_sha1_batch_device(md_ctx *ctx, size_t n, const uint8_t *d_data, const uint64_t *d_off, const uint64_t *d_len,
+                         const uint8_t *d_type, uint64_t max_len, uint8_t *d_digest);
+int md_sha1_batch_host(md_ctx *ctx, size_t n, const uint8_t *data, size_t data_len, const uint64_t *off, const uint64_t *len,
+                       const uint8_t *type, uint8_t *digest);
+int md_sha1_last(const md_ctx *ctx, md_sha1_stats *stats);
 
 #ifdef __cplusplus
 }

@@ -11,12 +11,20 @@ objects' sizes.
   git         `git cat-file --batch-all-objects --batch` over the same pack, one CPU process, if git is on the machine
 With read_all the share of its time that the apply launches take on the device (md_pack_last's apply_ns over the median).
 
-    python tools/bench_pack.py [--objects 16384] [--depth 8] [--mib 64] [--reps 7] [--warmup 1]
+With --names, for DESIGN 4j, further legs on the same pack:
+  read_names    md_pack_read of every object with MD_PACK_VERIFY_NAME (beside read_all, which is the same call without)
+  verify        md_pack_verify of every object with MD_PACK_VERIFY_CRC | MD_PACK_VERIFY_NAME: nothing comes back but statuses
+  hashlib       hashlib.sha1 over "<type> <size>\0" + content of the same objects, one CPU thread of this machine
+  git verify-pack, git fsck   over the same pack, if git is on the machine
+and with read_names and verify the device time of their hash passes (md_sha1_last's device_ns) and its counts.
+
+    python tools/bench_pack.py [--objects 16384] [--depth 8] [--mib 64] [--reps 7] [--warmup 1] [--names]
 
 The legs are alternated in one process; every leg reports the median and the spread (min .. max) of its repeats, host to
 host (perf_counter around a call that ends in a synchronise).  read_all's bytes are compared with the writer's."""
 import argparse
 import ctypes
+import hashlib
 import json
 import os
 import random
@@ -81,6 +89,30 @@ def time_git(pack, idx, reps):
         return times
 
 
+def time_git_checks(pack, idx, reps):
+    """git verify-pack and git fsck over the pack -> {name: times} or None"""
+    git = shutil.which("git")
+    if not git:
+        return None
+    env = dict(os.environ, GIT_CONFIG_GLOBAL="/dev/null", GIT_CONFIG_SYSTEM="/dev/null")
+    with tempfile.TemporaryDirectory() as tmp:
+        repo = os.path.join(tmp, "r.git")
+        subprocess.run([git, "init", "-q", "--bare", repo], check=True, env=env, capture_output=True)
+        stem = os.path.join(repo, "objects", "pack", "pack-" + pack[-20:].hex())
+        for ext, data in ((".pack", pack), (".idx", idx)):
+            with open(stem + ext, "wb") as f:
+                f.write(data)
+        out = {}
+        for name, cmd in (("git_verify_pack", ["verify-pack", stem + ".idx"]), ("git_fsck", ["fsck", "--no-dangling", "--no-progress"])):
+            out[name] = []
+            for _ in range(reps):
+                t0 = time.perf_counter()
+                r = subprocess.run([git, "-C", repo] + cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+                out[name].append((time.perf_counter() - t0) * 1e3)
+                assert r.returncode == 0, r.stderr
+        return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--objects", type=int, default=16384)
@@ -88,6 +120,7 @@ def main():
     ap.add_argument("--mib", type=int, default=64)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--names", action="store_true")
     a = ap.parse_args()
     eng = _engine.default_engine(0)
     lib = eng.lib
@@ -138,6 +171,22 @@ def main():
 
     legs = {"open": opened, "payloads": payloads}
     legs.update({k: v[0] for k, v in calls.items()})
+    hashed = {}
+    if a.names:
+        _, dst_all, off_all, _ = calls["read_all"]
+        st_names, st_verify, res_n, res_v = np.ones(n, dtype=np.int32), np.ones(n, dtype=np.int32), _lib.PackResult(), _lib.PackResult()
+
+        def read_names():
+            eng._check(lib.md_pack_read(eng.ctx, p._h, pack, len(pack), None, n, mp.VERIFY_NAMES, dst_all.ctypes.data, dst_all.size,
+                                        off_all.ctypes.data, st_names.ctypes.data, ctypes.byref(res_n)))
+            hashed["read_names"] = eng.sha1_last()
+
+        def verify():
+            eng._check(lib.md_pack_verify(eng.ctx, p._h, pack, len(pack), None, n, mp.VERIFY_CRC | mp.VERIFY_NAMES, st_verify.ctypes.data,
+                                          ctypes.byref(res_v)))
+            hashed["verify"] = eng.sha1_last()
+
+        legs.update({"read_names": read_names, "verify": verify})
     times = {k: [] for k in legs}
     for r in range(a.warmup + a.reps):
         for k, fn in legs.items():
@@ -159,6 +208,24 @@ def main():
     res["apply_share_of_read_all"] = round(last["read_all"]["apply_ns"] / 1e6 / med, 4)
     git = time_git(pack, idx, a.reps)
     res["git_cat_file"] = stats(git) if git else "git is not on this machine: no CPU figure"
+    if a.names:
+        assert not st_names.any() and not st_verify.any() and res_v.written == 0 and res_v.failed == 0
+        heads = [pw.TYPE_NAMES[lay["type"]] + b" %d\0" % len(lay["data"]) for lay in layout]
+        cpu = []
+        for _ in range(a.reps):
+            t0 = time.perf_counter()
+            got = [hashlib.sha1(h + lay["data"]).digest() for h, lay in zip(heads, layout)]
+            cpu.append((time.perf_counter() - t0) * 1e3)
+        assert got == [lay["name"] for lay in layout]
+        t = res["times"]
+        res["names"] = {
+            "hash_pass": hashed, "hashlib": stats(cpu),
+            "read_names_over_read_all": round(t["read_names"]["median_ms"] / t["read_all"]["median_ms"], 3),
+            "verify_over_read_all": round(t["verify"]["median_ms"] / t["read_all"]["median_ms"], 3),
+            "hashlib_over_read_names_extra": round(statistics.median(cpu) / max(t["read_names"]["median_ms"] - t["read_all"]["median_ms"], 1e-3), 1),
+            "hashlib_over_verify": round(statistics.median(cpu) / t["verify"]["median_ms"], 1)}
+        checks = time_git_checks(pack, idx, min(a.reps, 3))
+        res["names"]["git"] = {k: stats(v) for k, v in checks.items()} if checks else "git is not on this machine: no CPU figure"
     print(json.dumps(res))
 
 
