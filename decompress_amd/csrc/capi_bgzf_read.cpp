@@ -15,7 +15,7 @@ int md_bgzf_index_build(md_ctx *ctx, const uint8_t *src, size_t src_len, md_bgzf
   if (idx) *idx = nullptr;
   if (!ctx) return MD_E_INVALID_ARGUMENT;
   if (!idx || (!src && src_len)) return fail(ctx, MD_E_INVALID_ARGUMENT, "md_bgzf_index_build: null pointer");
-  try {
+  return no_bad_alloc(ctx, "md_bgzf_index_build", [&]() -> int {
     md_bgzf_index *x = new md_bgzf_index();
     std::unique_ptr<md_bgzf_index> hold(x);
     x->src_len = src_len;
@@ -32,17 +32,15 @@ int md_bgzf_index_build(md_ctx *ctx, const uint8_t *src, size_t src_len, md_bgzf
       uint64_t last_len = 0;
       x->c_off.assign(M + 1, 0);
       x->u_off.assign(M + 1, 0);
-      HIP_TRY(ctx, hipMemcpyAsync(x->c_off.data(), ix.mpos, M * 8, hipMemcpyDeviceToHost, ctx->stream));
-      HIP_TRY(ctx, hipMemcpyAsync(x->u_off.data(), ix.out_off, (M + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-      HIP_TRY(ctx, hipMemcpyAsync(&last_len, ix.mlen + (M - 1), 8, hipMemcpyDeviceToHost, ctx->stream));
+      HIP_TRY(ctx, md::to_host(x->c_off.data(), ix.mpos, M, ctx->stream));
+      HIP_TRY(ctx, md::to_host(x->u_off.data(), ix.out_off, M + 1, ctx->stream));
+      HIP_TRY(ctx, md::to_host(&last_len, ix.mlen + (M - 1), 1, ctx->stream));
       HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
       x->c_off[M] = x->c_off[M - 1] + last_len;
     }
     *idx = hold.release();
     return MD_OK;
-  } catch (const std::bad_alloc &) {
-    return fail(ctx, MD_E_OUT_OF_MEMORY, "md_bgzf_index_build");
-  }
+  });
 }
 
 int md_bgzf_index_from_gzi(const uint8_t *gzi, size_t gzi_len, const uint8_t *src, size_t src_len, md_bgzf_index **idx) {
@@ -186,9 +184,7 @@ static int bgzf_read_ranges(md_ctx *ctx, const md_bgzf_index *idx, const uint8_t
            *d_dst_off = nullptr;
   int32_t *d_hstatus = nullptr, *d_status = nullptr, *d_inf_status = nullptr, *d_verdict = nullptr, *d_rstatus = nullptr;
   uint32_t *d_ids = nullptr;
-  md::Carver c;
-  for (int pass = 0; pass < 2; pass++) {
-    if (pass && (rc = carve_from(ctx, ctx->scratch[kGzmDesc], &c, "hipMalloc(member descriptors)", 64)) != MD_OK) return rc;
+  rc = carve(ctx, ctx->scratch[kGzmDesc], "hipMalloc(member descriptors)", [&](md::Carver &c) {
     uint64_t **m64[11] = {&d_mpos, &d_mlen, &d_slot, &d_cap, &d_u0, &d_body_off, &d_body_len, &d_isize, &d_out_len, &d_consumed, &d_inf_consumed};
     for (uint64_t **p : m64) *p = c.take<uint64_t>(T);
     d_off = c.take<uint64_t>(n), d_len = c.take<uint64_t>(n), d_dst_off = c.take<uint64_t>(n);
@@ -196,17 +192,18 @@ static int bgzf_read_ranges(md_ctx *ctx, const md_bgzf_index *idx, const uint8_t
     for (int32_t **p : m32) *p = c.take<int32_t>(T);
     d_rstatus = c.take<int32_t>(n);
     d_ids = c.take<uint32_t>(h_ids.size());
-  }
-  HIP_TRY(ctx, hipMemcpyAsync(d_mpos, h_mpos.data(), T * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(d_mlen, h_mlen.data(), T * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(d_slot, h_slot.data(), T * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(d_cap, h_cap.data(), T * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(d_u0, h_u0.data(), T * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(d_off, off, n * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(d_len, len, n * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(d_dst_off, dst_off, n * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(d_ids, h_ids.data(), h_ids.size() * 4, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemsetAsync(d_rstatus, 0, n * 4, st));
+  }, 64);
+  if (rc != MD_OK) return rc;
+  HIP_TRY(ctx, md::to_device(d_mpos, h_mpos, st));
+  HIP_TRY(ctx, md::to_device(d_mlen, h_mlen, st));
+  HIP_TRY(ctx, md::to_device(d_slot, h_slot, st));
+  HIP_TRY(ctx, md::to_device(d_cap, h_cap, st));
+  HIP_TRY(ctx, md::to_device(d_u0, h_u0, st));
+  HIP_TRY(ctx, md::to_device(d_off, off, n, st));
+  HIP_TRY(ctx, md::to_device(d_len, len, n, st));
+  HIP_TRY(ctx, md::to_device(d_dst_off, dst_off, n, st));
+  HIP_TRY(ctx, md::to_device(d_ids, h_ids, st));
+  HIP_TRY(ctx, md::zero(d_rstatus, n, st));
   uint8_t *d_in = ctx->scratch[kBgrIn].as<uint8_t>(), *d_slots = ctx->scratch[kBgrSlots].as<uint8_t>(), *d_dst = ctx->scratch[kHostOut].as<uint8_t>();
   // -- the rounds, one behind the other on the context's stream: nothing comes back in between
   for (const RoundPlan &r : rounds) {
@@ -215,7 +212,7 @@ static int bgzf_read_ranges(md_ctx *ctx, const md_bgzf_index *idx, const uint8_t
       size_t e = t + 1;
       while (e < r.t1 && touched[e] == touched[e - 1] + 1) e++;
       const uint64_t b0 = c_off[touched[t]], b1 = c_off[touched[e - 1] + 1];
-      HIP_TRY(ctx, hipMemcpyAsync(d_in + h_mpos[t], src + b0, b1 - b0, hipMemcpyHostToDevice, st));
+      HIP_TRY(ctx, md::to_device(d_in + h_mpos[t], src + b0, b1 - b0, st));
       t = e;
     }
     MD_LAUNCH_TRY(ctx, md_launch_gzm_headers(count, d_in, d_mpos + t0, d_mlen + t0, d_body_off + t0, d_body_len + t0, d_isize + t0, d_hstatus + t0, st));
@@ -223,8 +220,8 @@ static int bgzf_read_ranges(md_ctx *ctx, const md_bgzf_index *idx, const uint8_t
                                  d_out_len + t0, d_consumed + t0, d_status + t0, nullptr);
     if (rc != MD_OK) return rc;
     // (md_launch_gz_finish replaces the decoder's status and count by the member's: the verdict wants both)
-    HIP_TRY(ctx, hipMemcpyAsync(d_inf_consumed + t0, d_consumed + t0, count * 8, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(d_inf_status + t0, d_status + t0, count * 4, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d_inf_consumed + t0, d_consumed + t0, count * sizeof *d_consumed, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d_inf_status + t0, d_status + t0, count * sizeof *d_status, hipMemcpyDeviceToDevice, st));
     MD_LAUNCH_TRY(ctx, md_launch_gz_finish((uint32_t)count, d_in, d_mpos + t0, d_mlen + t0, d_body_off + t0, d_hstatus + t0, d_slots, d_slot + t0,
                                            d_out_len + t0, d_consumed + t0, d_status + t0, nullptr, st));
     const md::bgr::Round dr{d_mpos + t0,     d_mlen + t0,         d_slot + t0,    d_cap + t0,        d_u0 + t0,     d_body_len + t0,
@@ -239,21 +236,15 @@ static int bgzf_read_ranges(md_ctx *ctx, const md_bgzf_index *idx, const uint8_t
   }
   // -- the statuses first: a range that failed is not copied out; what is adjacent in dst leaves by one copy
   std::vector<int32_t> got(n);
-  HIP_TRY(ctx, hipMemcpyAsync(got.data(), d_rstatus, n * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, md::to_host(got.data(), d_rstatus, n, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
   for (size_t i = 0; i < n; i++)
     if (status[i] == MD_OK) status[i] = got[i];
-  for (size_t i = 0; i < n;) {
-    if (status[i] != MD_OK || len[i] == 0) {
-      i++;
-      continue;
-    }
-    size_t e = i + 1;
-    uint64_t bytes = len[i];
-    while (e < n && status[e] == MD_OK && len[e] && dst_off[e] == dst_off[i] + bytes) bytes += len[e++];
-    HIP_TRY(ctx, hipMemcpyAsync(dst + dst_off[i], d_dst + dst_off[i], bytes, hipMemcpyDeviceToHost, st));
-    i = e;
-  }
+  rc = md::adjacent_runs(n, status, len, dst_off, [&](size_t i, uint64_t bytes) -> int {
+    HIP_TRY(ctx, md::to_host(dst + dst_off[i], d_dst + dst_off[i], bytes, st));
+    return MD_OK;
+  });
+  if (rc != MD_OK) return rc;
   HIP_TRY(ctx, hipStreamSynchronize(st));
   return MD_OK;
 }
@@ -280,11 +271,7 @@ static int bgzf_read_checked(md_ctx *ctx, const md_bgzf_index *idx, const uint8_
   if (bytes && !dst) return fail(ctx, MD_E_INVALID_ARGUMENT, "md_bgzf_read: null pointer");
   ctx->bgr_last = {};
   if (!bytes) return MD_OK;
-  try {
-    return bgzf_read_ranges(ctx, idx, src, n, off, len, dst, dst_off, status);
-  } catch (const std::bad_alloc &) {
-    return fail(ctx, MD_E_OUT_OF_MEMORY, "md_bgzf_read");
-  }
+  return no_bad_alloc(ctx, "md_bgzf_read", [&] { return bgzf_read_ranges(ctx, idx, src, n, off, len, dst, dst_off, status); });
 }
 
 int md_bgzf_read(md_ctx *ctx, const md_bgzf_index *idx, const uint8_t *src, size_t src_len, size_t n, const uint64_t *off, const uint64_t *len,
@@ -301,7 +288,7 @@ int md_bgzf_read_virtual(md_ctx *ctx, const md_bgzf_index *idx, const uint8_t *s
   if (!ctx) return MD_E_INVALID_ARGUMENT;
   const int rc = bgzf_read_checks(ctx, idx, src, src_len, n, voff, len, dst_off, status);
   if (rc != MD_OK) return rc;
-  try {
+  return no_bad_alloc(ctx, "md_bgzf_read_virtual", [&] {
     // voff = the member's offset in src << 16 | an offset in its output: the member by binary search over c_off
     std::vector<uint64_t> off(n, 0);
     const size_t M = idx->members();
@@ -313,7 +300,5 @@ int md_bgzf_read_virtual(md_ctx *ctx, const md_bgzf_index *idx, const uint8_t *s
       if (known) off[i] = idx->u_off[k] + in;
     }
     return bgzf_read_checked(ctx, idx, src, n, off.data(), len, dst, dst_off, status);
-  } catch (const std::bad_alloc &) {
-    return fail(ctx, MD_E_OUT_OF_MEMORY, "md_bgzf_read_virtual");
-  }
+  });
 }

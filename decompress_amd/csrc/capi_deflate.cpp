@@ -382,9 +382,9 @@ static int deflate_in_slices(md_ctx *ctx, int format, const md_deflate_params &q
       rc = hooks->launched(k);
       if (rc != MD_OK) return rc;
     }
-    HIP_TRY(ctx, hipMemcpyAsync(out_len, d64 + 5 * n, n * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(st, d32, 2 * n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (d_tail) HIP_TRY(ctx, hipMemcpyAsync(tl.data(), d_tail, 2 * n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, md::to_host(out_len, d64 + 5 * n, n, ctx->stream));
+    HIP_TRY(ctx, md::to_host(st, d32, 2 * n, ctx->stream));
+    if (d_tail) HIP_TRY(ctx, md::to_host(tl.data(), d_tail, 2 * n, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     for (size_t i = 0; i < n; i++) {
       if (flags[i] & 8) continue;
@@ -418,10 +418,10 @@ static int deflate_capped(md_ctx *ctx, int format, const md_deflate_params &q, s
                           bool *whole, uint64_t *total_out) {
   std::vector<uint64_t> h(4 * n);
   uint64_t *in_off = h.data(), *in_len = in_off + n, *out_off = in_len + n, *out_cap = out_off + n;
-  HIP_TRY(ctx, hipMemcpyAsync(in_off, d_in_off, n * 8, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(in_len, d_in_len, n * 8, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(out_off, d_out_off, n * 8, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(out_cap, d_out_cap, n * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, md::to_host(in_off, d_in_off, n, ctx->stream));
+  HIP_TRY(ctx, md::to_host(in_len, d_in_len, n, ctx->stream));
+  HIP_TRY(ctx, md::to_host(out_off, d_out_off, n, ctx->stream));
+  HIP_TRY(ctx, md::to_host(out_cap, d_out_cap, n, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   uint64_t total = 0, longest = 0;
   for (size_t i = 0; i < n; i++) {
@@ -443,7 +443,7 @@ static int deflate_capped(md_ctx *ctx, int format, const md_deflate_params &q, s
     uint32_t *d_crc = (uint32_t *)((uint8_t *)ctx->gz_tmp.p + n * 20);
     MD_LAUNCH_TRY(ctx, md_launch_crc32((uint32_t)n, d_in, d_in_off, d_in_len, d_crc, ctx->stream));
     crc.resize(n);
-    HIP_TRY(ctx, hipMemcpyAsync(crc.data(), d_crc, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, md::to_host(crc.data(), d_crc, n, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   }
   // First in groups of consecutive streams, as long as a group still fills the device several times over (16 streams
@@ -486,10 +486,10 @@ static int deflate_capped(md_ctx *ctx, int format, const md_deflate_params &q, s
     if (rc != MD_OK) return rc;
     i0 += k;
   }
-  HIP_TRY(ctx, hipMemcpyAsync(d_out_len, r_len.data(), n * 8, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(d_status, r_st.data(), n * 4, hipMemcpyHostToDevice, ctx->stream));
-  if (d_checksum) HIP_TRY(ctx, hipMemcpyAsync(d_checksum, r_sum.data(), n * 4, hipMemcpyHostToDevice, ctx->stream));
-  if (d_tail) HIP_TRY(ctx, hipMemcpyAsync(d_tail, r_tail.data(), 2 * n * 8, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, md::to_device(d_out_len, r_len.data(), n, ctx->stream));
+  HIP_TRY(ctx, md::to_device(d_status, r_st.data(), n, ctx->stream));
+  if (d_checksum) HIP_TRY(ctx, md::to_device(d_checksum, r_sum.data(), n, ctx->stream));
+  if (d_tail) HIP_TRY(ctx, md::to_device(d_tail, r_tail.data(), 2 * n, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the host vectors go out of scope)
   *whole = false;
   return MD_OK;
@@ -662,8 +662,8 @@ int md_i_pieces_run(md_ctx *ctx, int format, const md_deflate_params *params, si
   rc = deflate_launch(ctx, format, q.level, q.queue_len, q.driver, q.dynamic, q.matcher, q.gz_header, n, d_text, d64, d64 + 2 * n,
                       d_out, d64 + 3 * n, d64 + 4 * n, d64 + 5 * n, (int32_t *)d32, d32 + n, nullptr, total ? total : 1, &pa);
   if (rc != MD_OK) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(io->out_len, d64 + 5 * n, n * 8, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(io->status, d32, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, md::to_host(io->out_len, d64 + 5 * n, n, ctx->stream));
+  HIP_TRY(ctx, md::to_host(io->status, (const int32_t *)d32, n, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return MD_OK;
 }
@@ -827,19 +827,18 @@ static int deflate_batch_host(md_ctx *ctx, int format, const md_deflate_params *
   uint64_t *d_in_off = nullptr, *d_in_len = nullptr, *d_out_off = nullptr, *d_out_cap = nullptr, *d_out_len = nullptr;
   int32_t *dstatus = nullptr;
   uint32_t *dsum = nullptr;
-  md::Carver c;
-  for (int pass = 0; pass < 2; pass++) {
-    if (pass && (rc = carve_from(ctx, ctx->scratch[kHostDesc], &c, "hipMalloc(host path descriptors)")) != MD_OK) return rc;
+  rc = carve(ctx, ctx->scratch[kHostDesc], "hipMalloc(host path descriptors)", [&](md::Carver &c) {
     d_in_off = c.take<uint64_t>(n), d_in_len = c.take<uint64_t>(n), d_out_off = c.take<uint64_t>(n), d_out_cap = c.take<uint64_t>(n);
     d_out_len = c.take<uint64_t>(n);
     dstatus = c.take<int32_t>(n);
     dsum = c.take<uint32_t>(n);
-  }
+  });
+  if (rc != MD_OK) return rc;
   hipStream_t st = ctx->stream;
-  HIP_TRY(ctx, hipMemcpyAsync(d_in_off, in_off, n * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(d_in_len, in_len, n * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(d_out_off, out_off, n * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(d_out_cap, out_cap, n * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, md::to_device(d_in_off, in_off, n, st));
+  HIP_TRY(ctx, md::to_device(d_in_len, in_len, n, st));
+  HIP_TRY(ctx, md::to_device(d_out_off, out_off, n, st));
+  HIP_TRY(ctx, md::to_device(d_out_cap, out_cap, n, st));
   {  // long streams in a regular layout: slices of POSITIONS, input arriving and output leaving under the kernels
     const int prc = deflate_host_positions(ctx, format, params, n, h_in, in_bytes, in_off, in_len, h_out, out_bytes, out_off, out_cap,
                                            out_len, status, checksum, din, dout);
@@ -857,9 +856,9 @@ static int deflate_batch_host(md_ctx *ctx, int format, const md_deflate_params *
                                 dstatus + i0, dsum + i0, cnt == 1 ? ls : nullptr);
   });
   if (rc != MD_OK) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(out_len, d_out_len, n * 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipMemcpyAsync(status, dstatus, n * 4, hipMemcpyDeviceToHost, st));
-  if (checksum) HIP_TRY(ctx, hipMemcpyAsync(checksum, dsum, n * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, md::to_host(out_len, d_out_len, n, st));
+  HIP_TRY(ctx, md::to_host(status, dstatus, n, st));
+  if (checksum) HIP_TRY(ctx, md::to_host(checksum, dsum, n, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
   return MD_OK;
 }

@@ -60,7 +60,7 @@ static int spans_run(md_ctx *ctx, int format, const md_deflate_params *params, s
   // says MD_UNEXPECTED_END_OF_OUTPUT for the slot, and the join kernel writes the span stored)
   const size_t stride = ((size_t)stored_size(span < len ? span : len) + 15) & ~(size_t)15;
   int rc = ctx->scratch[kHostOut].reserve(ctx, n * stride + 64, "hipMalloc(span slots)");
-  if (rc == MD_OK) rc = ctx->spans_count.reserve(ctx, 8, "hipMalloc(span count)");
+  if (rc == MD_OK) rc = ctx->spans_count.reserve(ctx, sizeof(uint64_t), "hipMalloc(span count)");
   if (rc != MD_OK) return rc;
   uint8_t *slots = (uint8_t *)ctx->scratch[kHostOut].p;
   uint64_t *in_off = nullptr, *in_len = nullptr, *out_off = nullptr, *out_cap = nullptr, *out_len = nullptr, *size = nullptr, *off = nullptr,
@@ -69,18 +69,17 @@ static int spans_run(md_ctx *ctx, int format, const md_deflate_params *params, s
   const bool prime = ctx->span_prime && n > 1;  // (one span has nothing in front of it)
   int32_t *status = nullptr, *err = nullptr;
   uint32_t *adler = nullptr, *crc = nullptr;
-  md::Carver desc;
-  for (int pass = 0; pass < 2; pass++) {
-    if (pass && (rc = carve_from(ctx, ctx->scratch[kGzmDesc], &desc, "hipMalloc(span descriptors)")) != MD_OK) return rc;
+  rc = carve(ctx, ctx->scratch[kGzmDesc], "hipMalloc(span descriptors)", [&](md::Carver &desc) {
     in_off = desc.take<uint64_t>(n), in_len = desc.take<uint64_t>(n), out_off = desc.take<uint64_t>(n), out_cap = desc.take<uint64_t>(n);
     out_len = desc.take<uint64_t>(n), size = desc.take<uint64_t>(n), off = desc.take<uint64_t>(n + 1), tail = desc.take<uint64_t>(2 * n);
     status = desc.take<int32_t>(n), err = desc.take<int32_t>(2);
     adler = desc.take<uint32_t>(n), crc = desc.take<uint32_t>(n);
     if (prime) x_off = desc.take<uint64_t>(n), x_len = desc.take<uint64_t>(n), first = desc.take<uint32_t>(n);
-  }
+  });
+  if (rc != MD_OK) return rc;
   hipStream_t st = ctx->stream;
-  HIP_TRY(ctx, hipMemsetAsync(err, 0, 8, st));
-  HIP_TRY(ctx, hipMemsetAsync(ctx->spans_count.p, 0, 8, st));
+  HIP_TRY(ctx, md::zero(err, 2, st));
+  HIP_TRY(ctx, md::zero(ctx->spans_count.as<uint64_t>(), 1, st));
   MD_LAUNCH_TRY(ctx, md_launch_spans_plan(n, len, span, stride, in_off, in_len, out_off, out_cap, x_off, x_len, first, st));
   // (primed: span i brings min(i * span, kPrime) bytes along - summed exactly, the prefixes below kPrime first)
   size_t primed = 0;
@@ -147,8 +146,8 @@ int md_deflate_spans_host(md_ctx *ctx, int format, const md_deflate_params *para
                  (uint32_t *)(d_res + 1) + 1);
   if (rc != MD_OK) return rc;
   uint64_t res[2] = {0, 0}, stored = 0;
-  HIP_TRY(ctx, hipMemcpyAsync(res, d_res, 16, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(&stored, ctx->spans_count.p, 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, md::to_host(res, d_res, 2, ctx->stream));
+  HIP_TRY(ctx, md::to_host(&stored, ctx->spans_count.as<uint64_t>(), 1, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   ctx->spans_last.stored_spans = (size_t)stored;
   ctx->spans_pending = false;
@@ -172,7 +171,7 @@ int md_deflate_spans_last(md_ctx *ctx, md_deflate_spans_info *info) {
   if (ctx->spans_pending) {  // the device form reads nothing back: the count of stored spans is fetched when it is asked for
     MD_ON_DEVICE(ctx);
     uint64_t stored = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&stored, ctx->spans_count.p, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, md::to_host(&stored, ctx->spans_count.as<uint64_t>(), 1, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->spans_last.stored_spans = (size_t)stored;
     ctx->spans_pending = false;

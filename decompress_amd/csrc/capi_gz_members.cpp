@@ -17,51 +17,47 @@ int gzm_index(md_ctx *ctx, const uint8_t *d_src, uint64_t len, bool *indexed, Gz
   if (len < 28) return MD_OK;  // (shorter than any indexed member)
   hipStream_t st = ctx->stream;
   const uint64_t nspans = (len + md::gzm::kMarkSpanBytes - 1) / md::gzm::kMarkSpanBytes, nwords = (len + 31) / 32;
-  int rc = MD_OK;
   uint32_t *bits = nullptr, *cnt = nullptr;  // the bitmap of marks, the marks per span
   uint64_t *base = nullptr, *last_nz = nullptr;
-  md::Carver ws;
-  for (int pass = 0; pass < 2; pass++) {
-    if (pass && (rc = carve_from(ctx, ctx->scratch[kGzmWs], &ws, "hipMalloc(member scan)")) != MD_OK) return rc;
+  int rc = carve(ctx, ctx->scratch[kGzmWs], "hipMalloc(member scan)", [&](md::Carver &ws) {
     bits = ws.take<uint32_t>(nwords), cnt = ws.take<uint32_t>(nspans);
     base = ws.take<uint64_t>(nspans + 1), last_nz = ws.take<uint64_t>(1);
-  }
+  });
+  if (rc != MD_OK) return rc;
   MD_LAUNCH_TRY(ctx, md_launch_gzm_mark(d_src, len, bits, cnt, last_nz, st));
   MD_LAUNCH_TRY(ctx, md_launch_gzm_scan32(cnt, nspans, base, st));
   uint64_t C = 0;
-  HIP_TRY(ctx, hipMemcpyAsync(&C, base + nspans, 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, md::to_host(&C, base + nspans, 1, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
   if (C == 0 || C > 0x7ffffff0ull) return MD_OK;
   uint64_t *cpos = nullptr, *cnext = nullptr, *ridx = nullptr;
   uint32_t *jump_a = nullptr, *jump_b = nullptr, *reach = nullptr;
-  md::Carver cand;
-  for (int pass = 0; pass < 2; pass++) {
-    if (pass && (rc = carve_from(ctx, ctx->scratch[kGzmCand], &cand, "hipMalloc(member candidates)")) != MD_OK) return rc;
+  rc = carve(ctx, ctx->scratch[kGzmCand], "hipMalloc(member candidates)", [&](md::Carver &cand) {
     cpos = cand.take<uint64_t>(C), cnext = cand.take<uint64_t>(C), ridx = cand.take<uint64_t>(C + 1);
     jump_a = cand.take<uint32_t>(C + 2), jump_b = cand.take<uint32_t>(C + 2), reach = cand.take<uint32_t>(C + 2);
-  }
+  });
+  if (rc != MD_OK) return rc;
   MD_LAUNCH_TRY(ctx, md_launch_gzm_compact(d_src, len, bits, base, cpos, cnext, st));
   MD_LAUNCH_TRY(ctx, md_launch_gzm_chain(C, cpos, cnext, last_nz, jump_a, jump_b, reach, st));
   MD_LAUNCH_TRY(ctx, md_launch_gzm_scan32(reach, C, ridx, st));
   uint64_t M = 0;
   uint32_t at_end = 0;
-  HIP_TRY(ctx, hipMemcpyAsync(&M, ridx + C, 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipMemcpyAsync(&at_end, reach + C, 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, md::to_host(&M, ridx + C, 1, st));
+  HIP_TRY(ctx, md::to_host(&at_end, reach + C, 1, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
   if (!at_end || M == 0) return MD_OK;
   ix->M = M;
-  md::Carver desc;
-  for (int pass = 0; pass < 2; pass++) {
-    if (pass && (rc = carve_from(ctx, ctx->scratch[kGzmDesc], &desc, "hipMalloc(member descriptors)")) != MD_OK) return rc;
+  rc = carve(ctx, ctx->scratch[kGzmDesc], "hipMalloc(member descriptors)", [&](md::Carver &desc) {
     ix->mpos = desc.take<uint64_t>(M), ix->mlen = desc.take<uint64_t>(M), ix->body_off = desc.take<uint64_t>(M), ix->body_len = desc.take<uint64_t>(M);
     ix->isize = desc.take<uint64_t>(M), ix->out_len = desc.take<uint64_t>(M), ix->consumed = desc.take<uint64_t>(M);
     ix->out_off = desc.take<uint64_t>(M + 1), ix->first = desc.take<uint64_t>(1);
     ix->hstatus = desc.take<int32_t>(M), ix->status = desc.take<int32_t>(M);
-  }
+  });
+  if (rc != MD_OK) return rc;
   MD_LAUNCH_TRY(ctx, md_launch_gzm_select(C, reach, ridx, cpos, cnext, ix->mpos, ix->mlen, st));
   MD_LAUNCH_TRY(ctx, md_launch_gzm_headers(M, d_src, ix->mpos, ix->mlen, ix->body_off, ix->body_len, ix->isize, ix->hstatus, st));
   MD_LAUNCH_TRY(ctx, md_launch_gzm_scan64(ix->isize, M, ix->out_off, st));
-  HIP_TRY(ctx, hipMemcpyAsync(&ix->total, ix->out_off + M, 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, md::to_host(&ix->total, ix->out_off + M, 1, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
   *indexed = true;
   return MD_OK;
@@ -86,8 +82,8 @@ int md_gz_members_scan(md_ctx *ctx, const uint8_t *src, size_t src_len, md_gz_me
   info->written = (size_t)ix.total;
   const size_t k = cap < ix.M ? cap : (size_t)ix.M;
   if (k) {
-    HIP_TRY(ctx, hipMemcpyAsync(c_off, ix.mpos, k * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipMemcpyAsync(u_off, ix.out_off, k * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, md::to_host(c_off, ix.mpos, k, ctx->stream));
+    HIP_TRY(ctx, md::to_host(u_off, ix.out_off, k, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   }
   return MD_OK;
@@ -162,39 +158,36 @@ struct SpecBatch {
 static int gzm_spec_batch(md_ctx *ctx, const uint8_t *d_src, uint64_t len, uint64_t dst_cap, SpecBatch *b) {
   hipStream_t st = ctx->stream;
   const uint64_t nspans = (len + md::gzm::kMarkSpanBytes - 1) / md::gzm::kMarkSpanBytes, nwords = (len + 31) / 32;
-  int rc = MD_OK;
   uint32_t *bits = nullptr, *cnt = nullptr;  // (as gzm_index)
   uint64_t *base = nullptr;
-  md::Carver ws;
-  for (int pass = 0; pass < 2; pass++) {
-    if (pass && (rc = carve_from(ctx, ctx->scratch[kGzmWs], &ws, nullptr)) != MD_OK) return rc;
+  int rc = carve(ctx, ctx->scratch[kGzmWs], nullptr, [&](md::Carver &ws) {
     bits = ws.take<uint32_t>(nwords), cnt = ws.take<uint32_t>(nspans);
     base = ws.take<uint64_t>(nspans + 1);
-  }
+  });
+  if (rc != MD_OK) return rc;
   SPEC_TRY(md_launch_gzs_mark(d_src, len, bits, cnt, st));
   SPEC_TRY(md_launch_gzm_scan32(cnt, nspans, base, st));
   uint64_t C = 0;
   uint32_t word0 = 0;
-  SPEC_TRY(hipMemcpyAsync(&C, base + nspans, 8, hipMemcpyDeviceToHost, st));
-  SPEC_TRY(hipMemcpyAsync(&word0, bits, 4, hipMemcpyDeviceToHost, st));
+  SPEC_TRY(md::to_host(&C, base + nspans, 1, st));
+  SPEC_TRY(md::to_host(&word0, bits, 1, st));
   SPEC_TRY(hipStreamSynchronize(st));
   if (C < kSpecMinCandidates || !(word0 & 1) || C > 0x7ffffff0ull) return MD_NOT_HANDLED;
-  rc = ctx->scratch[kGzmCand].reserve(ctx, (size_t)C * 8, nullptr);
+  rc = ctx->scratch[kGzmCand].reserve(ctx, (size_t)C * sizeof(uint64_t), nullptr);
   if (rc != MD_OK) return rc;
-  uint64_t *cpos = (uint64_t *)ctx->scratch[kGzmCand].p;
+  uint64_t *cpos = ctx->scratch[kGzmCand].as<uint64_t>();
   uint64_t *mlen = nullptr, *body_off = nullptr, *body_len = nullptr, *guess = nullptr, *pass = nullptr, *dec_len = nullptr, *out_cap = nullptr,
            *out_len = nullptr, *consumed = nullptr, *out_off = nullptr;
   int32_t *hstatus = nullptr, *status = nullptr;
   uint8_t *flag = nullptr;
-  md::Carver desc;
-  for (int second = 0; second < 2; second++) {
-    if (second && (rc = carve_from(ctx, ctx->scratch[kGzmDesc], &desc, nullptr)) != MD_OK) return rc;
+  rc = carve(ctx, ctx->scratch[kGzmDesc], nullptr, [&](md::Carver &desc) {
     mlen = desc.take<uint64_t>(C), body_off = desc.take<uint64_t>(C), body_len = desc.take<uint64_t>(C), guess = desc.take<uint64_t>(C);
     pass = desc.take<uint64_t>(C), dec_len = desc.take<uint64_t>(C), out_cap = desc.take<uint64_t>(C), out_len = desc.take<uint64_t>(C);
     consumed = desc.take<uint64_t>(C), out_off = desc.take<uint64_t>(C + 1);
     hstatus = desc.take<int32_t>(C), status = desc.take<int32_t>(C);
     flag = desc.take<uint8_t>(C);
-  }
+  });
+  if (rc != MD_OK) return rc;
   SPEC_TRY(md_launch_gzs_compact(len, bits, base, cpos, st));
   SPEC_TRY(md_launch_gzs_spans(C, cpos, len, mlen, st));
   SPEC_TRY(md_launch_gzm_headers(C, d_src, cpos, mlen, body_off, body_len, guess, hstatus, st));
@@ -202,7 +195,7 @@ static int gzm_spec_batch(md_ctx *ctx, const uint8_t *d_src, uint64_t len, uint6
   SPEC_TRY(md_launch_gzs_classify(C, hstatus, body_len, guess, out_off + C, ctx->par_min, pass, flag, st));
   SPEC_TRY(md_launch_gzm_scan64(pass, C, out_off, st));
   uint64_t total = 0;
-  SPEC_TRY(hipMemcpyAsync(&total, out_off + C, 8, hipMemcpyDeviceToHost, st));
+  SPEC_TRY(md::to_host(&total, out_off + C, 1, st));
   SPEC_TRY(md_launch_gzs_room(C, body_len, pass, dst_cap, out_off, dec_len, out_cap, flag, st));
   SPEC_TRY(hipStreamSynchronize(st));
   // no admitted span ends behind dst_cap (rule (d)), and none behind the sum
@@ -216,9 +209,9 @@ static int gzm_spec_batch(md_ctx *ctx, const uint8_t *d_src, uint64_t len, uint6
   b->cpos.resize((size_t)C);
   b->pass.resize((size_t)C);
   b->flag.resize((size_t)C);
-  SPEC_TRY(hipMemcpyAsync(b->cpos.data(), cpos, (size_t)C * 8, hipMemcpyDeviceToHost, st));
-  SPEC_TRY(hipMemcpyAsync(b->pass.data(), pass, (size_t)C * 8, hipMemcpyDeviceToHost, st));
-  SPEC_TRY(hipMemcpyAsync(b->flag.data(), flag, (size_t)C, hipMemcpyDeviceToHost, st));
+  SPEC_TRY(md::to_host(b->cpos.data(), cpos, (size_t)C, st));
+  SPEC_TRY(md::to_host(b->pass.data(), pass, (size_t)C, st));
+  SPEC_TRY(md::to_host(b->flag.data(), flag, (size_t)C, st));
   SPEC_TRY(hipStreamSynchronize(st));
   b->d_out = d_out;
   return MD_OK;
@@ -341,9 +334,9 @@ int md_gz_members_uncompress(md_ctx *ctx, const uint8_t *src, size_t src_len, ui
   MD_LAUNCH_TRY(ctx, md_launch_gz_finish((uint32_t)ix.M, d_src, ix.mpos, ix.mlen, ix.body_off, ix.hstatus, d_out, ix.out_off, ix.out_len,
                                          ix.consumed, ix.status, nullptr, st));
   uint64_t first = ix.M;
-  HIP_TRY(ctx, hipMemcpyAsync(ix.first, &first, 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, md::to_device(ix.first, &first, 1, st));
   MD_LAUNCH_TRY(ctx, md_launch_gzm_verdict(ix.M, ix.mlen, ix.consumed, ix.status, ix.first, st));
-  HIP_TRY(ctx, hipMemcpyAsync(&first, ix.first, 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, md::to_host(&first, ix.first, 1, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
   if (first == ix.M) {
     if (ix.total) HIP_TRY(ctx, hipMemcpy(dst, d_out, (size_t)ix.total, hipMemcpyDeviceToHost));
@@ -356,8 +349,8 @@ int md_gz_members_uncompress(md_ctx *ctx, const uint8_t *src, size_t src_len, ui
   // a member failed: the members in front of it are good and go out; from the failing one on the host loop speaks, so the
   // status is the one the same bytes get without a size index
   uint64_t at[2] = {0, 0};
-  HIP_TRY(ctx, hipMemcpyAsync(&at[0], ix.mpos + first, 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipMemcpyAsync(&at[1], ix.out_off + first, 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, md::to_host(&at[0], ix.mpos + first, 1, st));
+  HIP_TRY(ctx, md::to_host(&at[1], ix.out_off + first, 1, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
   if (at[1]) HIP_TRY(ctx, hipMemcpy(dst, d_out, (size_t)at[1], hipMemcpyDeviceToHost));
   rc = gzm_general(ctx, src, src_len, dst, dst_cap, (size_t)at[0], (size_t)at[1], (size_t)first, info);
@@ -399,16 +392,15 @@ int md_bgzf_compress(md_ctx *ctx, int level, size_t block, const uint8_t *src, s
   uint64_t *in_off = nullptr, *in_len = nullptr, *out_off = nullptr, *out_cap = nullptr, *out_len = nullptr, *msize = nullptr, *moff = nullptr;
   int32_t *status = nullptr, *err = nullptr;
   uint32_t *crc = nullptr;
-  md::Carver desc;
-  for (int pass = 0; pass < 2; pass++) {
-    if (pass && (rc = carve_from(ctx, ctx->scratch[kGzmDesc], &desc, "hipMalloc(member descriptors)")) != MD_OK) return rc;
+  rc = carve(ctx, ctx->scratch[kGzmDesc], "hipMalloc(member descriptors)", [&](md::Carver &desc) {
     in_off = desc.take<uint64_t>(nb), in_len = desc.take<uint64_t>(nb), out_off = desc.take<uint64_t>(nb), out_cap = desc.take<uint64_t>(nb);
     out_len = desc.take<uint64_t>(nb), msize = desc.take<uint64_t>(nb), moff = desc.take<uint64_t>(nb + 1);
     status = desc.take<int32_t>(nb), err = desc.take<int32_t>(1);
     crc = desc.take<uint32_t>(nb);
-  }
+  });
+  if (rc != MD_OK) return rc;
   hipStream_t st = ctx->stream;
-  HIP_TRY(ctx, hipMemsetAsync(err, 0, 4, st));
+  HIP_TRY(ctx, md::zero(err, 1, st));
   if (nb) {
     MD_LAUNCH_TRY(ctx, md_launch_bgzf_plan(nb, src_len, block, stride, in_off, in_len, out_off, out_cap, st));
     const md_deflate_params p = gzip_body_params(level, src_len);
@@ -421,8 +413,8 @@ int md_bgzf_compress(md_ctx *ctx, int level, size_t block, const uint8_t *src, s
   MD_LAUNCH_TRY(ctx, md_launch_bgzf_pack(nb, d_in, in_off, in_len, slots, out_off, out_len, status, moff, crc, d_file, st));
   uint64_t total = 0;
   int32_t bad = 0;
-  HIP_TRY(ctx, hipMemcpyAsync(&total, moff + nb, 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipMemcpyAsync(&bad, err, 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, md::to_host(&total, moff + nb, 1, st));
+  HIP_TRY(ctx, md::to_host(&bad, err, 1, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
   if (bad != 0) return bad;  // (MD_QUEUE_FULL: not with this queue, said all the same)
   if (total + 28 > bound) return fail(ctx, MD_E_HIP, "blocked gzip: member sizes above the bound");

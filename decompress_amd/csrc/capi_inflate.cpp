@@ -25,15 +25,13 @@ int md_inflate_batch_device(md_ctx *ctx, int format, size_t n, const uint8_t *d_
   MD_ON_DEVICE(ctx);
   if (format == MD_FORMAT_GZIP) {
     // Gz.Inf = header, De.Inf on the body, checksum (lib/gz.ml:463-531, :344-356)
-    int rc = MD_OK;
     uint64_t *body_off = nullptr, *body_len = nullptr;
     int32_t *hstatus = nullptr;
-    md::Carver c;
-    for (int pass = 0; pass < 2; pass++) {
-      if (pass && (rc = carve_from(ctx, ctx->gz_tmp, &c, "hipMalloc(gzip scratch)")) != MD_OK) return rc;
+    int rc = carve(ctx, ctx->gz_tmp, "hipMalloc(gzip scratch)", [&](md::Carver &c) {
       body_off = c.take<uint64_t>(n), body_len = c.take<uint64_t>(n);
       hstatus = c.take<int32_t>(n);
-    }
+    });
+    if (rc != MD_OK) return rc;
     MD_LAUNCH_TRY(ctx, md_launch_gz_header((uint32_t)n, d_in, d_in_off, d_in_len, body_off, body_len, hstatus, ctx->stream));
     rc = md_inflate_batch_device(ctx, MD_FORMAT_DEFLATE, n, d_in, body_off, body_len, d_out, d_out_off, d_out_cap,
                                  d_out_len, d_consumed, d_status, nullptr);
@@ -148,19 +146,18 @@ int md_inflate_batch_host(md_ctx *ctx, int format, size_t n, const uint8_t *h_in
   uint64_t *d_in_off = nullptr, *d_in_len = nullptr, *d_out_off = nullptr, *d_out_cap = nullptr, *d_out_len = nullptr, *d_consumed = nullptr;
   int32_t *dstatus = nullptr;
   uint32_t *dsum = nullptr;
-  md::Carver c;
-  for (int pass = 0; pass < 2; pass++) {
-    if (pass && (rc = carve_from(ctx, ctx->scratch[kHostDesc], &c, "hipMalloc(host path descriptors)")) != MD_OK) return rc;
+  rc = carve(ctx, ctx->scratch[kHostDesc], "hipMalloc(host path descriptors)", [&](md::Carver &c) {
     d_in_off = c.take<uint64_t>(n), d_in_len = c.take<uint64_t>(n), d_out_off = c.take<uint64_t>(n), d_out_cap = c.take<uint64_t>(n);
     d_out_len = c.take<uint64_t>(n), d_consumed = c.take<uint64_t>(n);
     dstatus = c.take<int32_t>(n);
     dsum = c.take<uint32_t>(n);
-  }
+  });
+  if (rc != MD_OK) return rc;
   hipStream_t st = ctx->stream;
-  HIP_TRY(ctx, hipMemcpyAsync(d_in_off, in_off, n * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(d_in_len, in_len, n * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(d_out_off, out_off, n * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(d_out_cap, out_cap, n * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, md::to_device(d_in_off, in_off, n, st));
+  HIP_TRY(ctx, md::to_device(d_in_len, in_len, n, st));
+  HIP_TRY(ctx, md::to_device(d_out_off, out_off, n, st));
+  HIP_TRY(ctx, md::to_device(d_out_cap, out_cap, n, st));
   // a slice of 1 024 streams (4 per CU) runs at half the batch's rate per stream - still several times what the link to
   // the host moves (57 GB/s each way measured), so the copies stay the longer leg and more slices hide more of the kernels
   const std::vector<HostSlice> sl = host_slices(n, in_off, in_len, out_off, out_cap, 1024, (size_t)ctx->host_slices_max, in_bytes, out_bytes);
@@ -169,10 +166,10 @@ int md_inflate_batch_host(md_ctx *ctx, int format, size_t n, const uint8_t *h_in
                                    d_consumed + i0, dstatus + i0, dsum + i0);
   });
   if (rc != MD_OK) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(out_len, d_out_len, n * 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipMemcpyAsync(consumed, d_consumed, n * 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipMemcpyAsync(status, dstatus, n * 4, hipMemcpyDeviceToHost, st));
-  if (checksum) HIP_TRY(ctx, hipMemcpyAsync(checksum, dsum, n * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, md::to_host(out_len, d_out_len, n, st));
+  HIP_TRY(ctx, md::to_host(consumed, d_consumed, n, st));
+  HIP_TRY(ctx, md::to_host(status, dstatus, n, st));
+  if (checksum) HIP_TRY(ctx, md::to_host(checksum, dsum, n, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
   return MD_OK;
 }
@@ -238,12 +235,11 @@ int inflate_piece(md_ctx *ctx, const uint8_t *src, size_t src_len, unsigned star
   uint32_t h32[7] = {0, 0, start_bit, (uint32_t)hist_len, adler_in, 0, 0};
   uint64_t *d64 = nullptr;
   uint32_t *d32 = nullptr;
-  md::Carver c;
-  for (int pass = 0; pass < 2; pass++) {
-    if (pass && (rc = carve_from(ctx, ctx->scratch[kContDesc], &c, "hipMalloc(decoder piece descriptors)")) != MD_OK) return rc;
+  rc = carve(ctx, ctx->scratch[kContDesc], "hipMalloc(decoder piece descriptors)", [&](md::Carver &c) {
     d64 = c.take<uint64_t>(8);
     d32 = c.take<uint32_t>(7);
-  }
+  });
+  if (rc != MD_OK) return rc;
   hipStream_t st = ctx->stream;
   if (src_len) HIP_TRY(ctx, hipMemcpyAsync(din.p, src, src_len, hipMemcpyHostToDevice, st));
   if (hist_len) HIP_TRY(ctx, hipMemcpyAsync(dout.p, hist, hist_len, hipMemcpyHostToDevice, st));
@@ -287,12 +283,11 @@ int continue_serial(md_ctx *ctx, const uint8_t *src, size_t src_len, unsigned st
     // (the piece's descriptors have been read: their block serves again)
     uint64_t *c64 = nullptr;
     uint32_t *c32 = nullptr;
-    md::Carver c;
-    for (int pass = 0; pass < 2; pass++) {
-      if (pass && (rc = carve_from(ctx, ctx->scratch[kContDesc], &c, "hipMalloc(decoder piece descriptors)")) != MD_OK) return rc;
+    rc = carve(ctx, ctx->scratch[kContDesc], "hipMalloc(decoder piece descriptors)", [&](md::Carver &c) {
       c64 = c.take<uint64_t>(4);  // two offsets, two lengths
       c32 = c.take<uint32_t>(2);
-    }
+    });
+    if (rc != MD_OK) return rc;
     const uint64_t to_out = resume->out > hist_len ? resume->out - hist_len : 0, to_end = produced > hist_len ? produced - hist_len : 0;
     const uint64_t hc[4] = {(uint64_t)hist_len, (uint64_t)hist_len, to_out, to_end};
     uint32_t crc[2] = {0, 0};

@@ -64,12 +64,10 @@ static int par_decode(md_ctx *ctx, const ParIn &in, ParOut *out, std::vector<Par
   // (the slack: room for the descriptors of the rounds below, 93 bytes a row and about two rows a chunk, so that the block
   // does not grow between the rounds)
   uint64_t *d_cand = nullptr;
-  md::Carver cd;
-  for (int pass = 0; pass < 2; pass++) {
-    if (pass && (rc = carve_from(ctx, ctx->scratch[kParDesc], &cd, "hipMalloc(parallel inflate descriptors)", (size_t)nchunks * 2 * 160 + 4096)) != MD_OK)
-      return rc;
+  rc = carve(ctx, ctx->scratch[kParDesc], "hipMalloc(parallel inflate descriptors)", [&](md::Carver &cd) {
     d_cand = cd.take<uint64_t>(nchunks - 1);
-  }
+  }, (size_t)nchunks * 2 * 160 + 4096);
+  if (rc != MD_OK) return rc;
   uint8_t *d_body = (uint8_t *)ctx->scratch[kParIn].p;
   HIP_TRY(ctx, hipMemcpyAsync(d_body, body, body_len, hipMemcpyHostToDevice, st));
   if (dbg_t) {
@@ -78,7 +76,7 @@ static int par_decode(md_ctx *ctx, const ParIn &in, ParOut *out, std::vector<Par
   }
   MD_LAUNCH_TRY(ctx, md_launch_find_blocks(d_body, body_len, K, nchunks - 1, d_cand, st));
   std::vector<uint64_t> cand(nchunks - 1);
-  HIP_TRY(ctx, hipMemcpyAsync(cand.data(), d_cand, (nchunks - 1) * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, md::to_host(cand.data(), d_cand, cand.size(), st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
   stamp("candidates found");
   // A run of STORED blocks from bit `pos` on is followed on the host, a read per block (lib/de.ml:1613-1627: header, padding,
@@ -168,25 +166,24 @@ static int par_decode(md_ctx *ctx, const ParIn &in, ParOut *out, std::vector<Par
     uint32_t *d_start_bit = nullptr, *d_hist = nullptr, *d_adler_in = nullptr, *d_checksum = nullptr, *d_resume_adler = nullptr, *d_resume_last = nullptr;
     int32_t *d_status = nullptr;
     uint8_t *d_variant = nullptr;
-    md::Carver c;
-    for (int pass = 0; pass < 2; pass++) {
-      if (pass && (rc = carve_from(ctx, ctx->scratch[kParDesc], &c, "hipMalloc(parallel inflate descriptors)", 256)) != MD_OK) return rc;
+    rc = carve(ctx, ctx->scratch[kParDesc], "hipMalloc(parallel inflate descriptors)", [&](md::Carver &c) {
       d_in_off = c.take<uint64_t>(n), d_in_len = c.take<uint64_t>(n), d_out_off = c.take<uint64_t>(n), d_out_cap = c.take<uint64_t>(n);
       d_out_len = c.take<uint64_t>(n), d_consumed = c.take<uint64_t>(n), d_resume_bits = c.take<uint64_t>(n), d_resume_out = c.take<uint64_t>(n);
       d_start_bit = c.take<uint32_t>(n), d_hist = c.take<uint32_t>(n), d_adler_in = c.take<uint32_t>(n);
       d_status = c.take<int32_t>(n);
       d_checksum = c.take<uint32_t>(n), d_resume_adler = c.take<uint32_t>(n), d_resume_last = c.take<uint32_t>(n);
       d_variant = c.take<uint8_t>(n);
-    }
+    }, 256);
+    if (rc != MD_OK) return rc;
     uint8_t *d_out = (uint8_t *)ctx->scratch[kParOut].p;
     if (hl) HIP_TRY(ctx, hipMemcpyAsync(d_out, in.hist, hl, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(d_in_off, in_off.data(), n * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(d_in_len, in_len.data(), n * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(d_out_off, out_off.data(), n * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(d_out_cap, out_cap.data(), n * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(d_start_bit, start_bit.data(), n * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(d_hist, hist.data(), n * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(d_adler_in, adler_in.data(), n * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, md::to_device(d_in_off, in_off.data(), n, st));
+    HIP_TRY(ctx, md::to_device(d_in_len, in_len.data(), n, st));
+    HIP_TRY(ctx, md::to_device(d_out_off, out_off.data(), n, st));
+    HIP_TRY(ctx, md::to_device(d_out_cap, out_cap.data(), n, st));
+    HIP_TRY(ctx, md::to_device(d_start_bit, start_bit.data(), n, st));
+    HIP_TRY(ctx, md::to_device(d_hist, hist.data(), n, st));
+    HIP_TRY(ctx, md::to_device(d_adler_in, adler_in.data(), n, st));
     HIP_TRY(ctx, hipMemcpyAsync(d_variant, variant.data(), n, hipMemcpyHostToDevice, st));
     MD_LAUNCH_TRY(ctx, md_launch_fill_windows((uint32_t)n, d_out, d_out_off, d_variant, st));
     rc = md_inflate_continue_batch_device(ctx, n, d_body, d_in_off, d_in_len, d_out, d_out_off, d_out_cap, d_start_bit, d_hist, d_adler_in, d_out_len,
@@ -195,11 +192,11 @@ static int par_decode(md_ctx *ctx, const ParIn &in, ParOut *out, std::vector<Par
     std::vector<uint64_t> r_used(n), r_bits(n), r_out(n);
     std::vector<int32_t> r_st(n);
     std::vector<uint32_t> r_last(n);
-    HIP_TRY(ctx, hipMemcpyAsync(r_used.data(), d_consumed, n * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(r_bits.data(), d_resume_bits, n * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(r_out.data(), d_resume_out, n * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(r_st.data(), d_status, n * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(r_last.data(), d_resume_last, n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, md::to_host(r_used.data(), d_consumed, n, st));
+    HIP_TRY(ctx, md::to_host(r_bits.data(), d_resume_bits, n, st));
+    HIP_TRY(ctx, md::to_host(r_out.data(), d_resume_out, n, st));
+    HIP_TRY(ctx, md::to_host(r_st.data(), d_status, n, st));
+    HIP_TRY(ctx, md::to_host(r_last.data(), d_resume_last, n, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     stamp("pieces decoded");
     // The pieces in order: piece p must end - its last complete block - exactly where piece p + 1 starts ("links").  From
@@ -313,17 +310,16 @@ static int par_decode(md_ctx *ctx, const ParIn &in, ParOut *out, std::vector<Par
     if (rc != MD_OK) return rc;
     uint64_t *d_offa = nullptr, *d_offb = nullptr, *d_u = nullptr, *d_pos = nullptr;
     uint32_t *d_flag = nullptr;
-    md::Carver c;
-    for (int pass = 0; pass < 2; pass++) {
-      if (pass && (rc = carve_from(ctx, ctx->scratch[kParDesc], &c, "hipMalloc(parallel inflate descriptors)", 256)) != MD_OK) return rc;
+    rc = carve(ctx, ctx->scratch[kParDesc], "hipMalloc(parallel inflate descriptors)", [&](md::Carver &c) {
       d_offa = c.take<uint64_t>(np), d_offb = c.take<uint64_t>(np), d_u = c.take<uint64_t>(np), d_pos = c.take<uint64_t>(np);
       d_flag = c.take<uint32_t>(16);
-    }
+    }, 256);
+    if (rc != MD_OK) return rc;
     uint8_t *d_out = (uint8_t *)ctx->scratch[kParOut].p, *d_win = (uint8_t *)ctx->scratch[kParWin].p;
-    HIP_TRY(ctx, hipMemcpyAsync(d_offa, offa.data(), np * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(d_offb, offb.data(), np * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(d_u, u.data(), np * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(d_pos, pos.data(), np * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, md::to_device(d_offa, offa.data(), np, st));
+    HIP_TRY(ctx, md::to_device(d_offb, offb.data(), np, st));
+    HIP_TRY(ctx, md::to_device(d_u, u.data(), np, st));
+    HIP_TRY(ctx, md::to_device(d_pos, pos.data(), np, st));
     HIP_TRY(ctx, hipMemsetAsync(d_flag, 0, 64, st));
     if (jumping)
       MD_LAUNCH_TRY(ctx, md_launch_windows_parallel((uint32_t)np, kGroup, d_out, u[0], d_out, d_offa, d_offb, d_u, d_pos, d_win, (uint32_t *)(d_win + win_bytes),
@@ -375,16 +371,14 @@ int par_adler(md_ctx *ctx, const uint8_t *d, uint64_t n, uint32_t adler, uint32_
   *res = adler;
   if (n == 0) return MD_OK;
   const size_t nseg = (size_t)((n + 65535) / 65536);
-  int rc = MD_OK;
   uint32_t *d_sums = nullptr;  // a pair of sums per segment
-  md::Carver c;
-  for (int pass = 0; pass < 2; pass++) {
-    if (pass && (rc = carve_from(ctx, ctx->scratch[kParDesc], &c, "hipMalloc(parallel inflate descriptors)", 64)) != MD_OK) return rc;
+  const int rc = carve(ctx, ctx->scratch[kParDesc], "hipMalloc(parallel inflate descriptors)", [&](md::Carver &c) {
     d_sums = c.take<uint32_t>(2 * nseg);
-  }
+  }, 64);
+  if (rc != MD_OK) return rc;
   MD_LAUNCH_TRY(ctx, md_launch_adler_segments(d, n, 65536, d_sums, ctx->stream));
   std::vector<uint32_t> sums(2 * nseg);
-  HIP_TRY(ctx, hipMemcpyAsync(sums.data(), d_sums, nseg * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, md::to_host(sums.data(), d_sums, sums.size(), ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   uint64_t a = adler & 0xffffu, b = adler >> 16;
   for (size_t s = 0; s < nseg; s++) {
@@ -399,25 +393,23 @@ int par_crc(md_ctx *ctx, const uint8_t *d_base, uint64_t off, uint64_t n, uint32
   *res = 0;
   if (n == 0) return MD_OK;
   const size_t ncrc = (size_t)((n + ((1u << 20) - 1)) >> 20);
-  int rc = MD_OK;
   uint64_t *d_off = nullptr, *d_len = nullptr;
   uint32_t *d_crc = nullptr;
-  md::Carver c;
-  for (int pass = 0; pass < 2; pass++) {
-    if (pass && (rc = carve_from(ctx, ctx->scratch[kParDesc], &c, "hipMalloc(parallel inflate descriptors)", 64)) != MD_OK) return rc;
+  const int rc = carve(ctx, ctx->scratch[kParDesc], "hipMalloc(parallel inflate descriptors)", [&](md::Carver &c) {
     d_off = c.take<uint64_t>(ncrc), d_len = c.take<uint64_t>(ncrc);
     d_crc = c.take<uint32_t>(ncrc);
-  }
+  }, 64);
+  if (rc != MD_OK) return rc;
   std::vector<uint64_t> co(ncrc), cl(ncrc);
   for (size_t s = 0; s < ncrc; s++) {
     co[s] = off + ((uint64_t)s << 20);
     cl[s] = s + 1 < ncrc ? (uint64_t)1 << 20 : n - ((uint64_t)s << 20);
   }
-  HIP_TRY(ctx, hipMemcpyAsync(d_off, co.data(), ncrc * 8, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(d_len, cl.data(), ncrc * 8, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, md::to_device(d_off, co.data(), ncrc, ctx->stream));
+  HIP_TRY(ctx, md::to_device(d_len, cl.data(), ncrc, ctx->stream));
   MD_LAUNCH_TRY(ctx, md_launch_crc32((uint32_t)ncrc, d_base, d_off, d_len, d_crc, ctx->stream));
   std::vector<uint32_t> crcs(ncrc);
-  HIP_TRY(ctx, hipMemcpyAsync(crcs.data(), d_crc, ncrc * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, md::to_host(crcs.data(), d_crc, ncrc, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   uint32_t crc = crcs[0];
   for (size_t s = 1; s < ncrc; s++) crc = md::crc32_concat(crc, crcs[s], cl[s]);

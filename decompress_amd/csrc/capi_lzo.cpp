@@ -91,20 +91,19 @@ int md_lzo_sizes_batch_host(md_ctx *ctx, size_t n, const uint8_t *h_in, size_t i
   uint8_t *din = (uint8_t *)ctx->scratch[kHostIn].p;
   uint64_t *d_in_off = nullptr, *d_in_len = nullptr, *d_out_len = nullptr;
   int32_t *dstatus = nullptr;
-  md::Carver c;
-  for (int pass = 0; pass < 2; pass++) {
-    if (pass && (rc = carve_from(ctx, ctx->scratch[kHostDesc], &c, "hipMalloc(host path descriptors)")) != MD_OK) return rc;
+  rc = carve(ctx, ctx->scratch[kHostDesc], "hipMalloc(host path descriptors)", [&](md::Carver &c) {
     d_in_off = c.take<uint64_t>(n), d_in_len = c.take<uint64_t>(n), d_out_len = c.take<uint64_t>(n);
     dstatus = c.take<int32_t>(n);
-  }
+  });
+  if (rc != MD_OK) return rc;
   hipStream_t st = ctx->stream;
   if (hi > lo) HIP_TRY(ctx, hipMemcpyAsync(din + lo, h_in + lo, hi - lo, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(d_in_off, in_off, n * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(d_in_len, in_len, n * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, md::to_device(d_in_off, in_off, n, st));
+  HIP_TRY(ctx, md::to_device(d_in_len, in_len, n, st));
   rc = md_lzo_sizes_batch_device(ctx, n, din, d_in_off, d_in_len, d_out_len, dstatus);
   if (rc != MD_OK) return rc;
-  HIP_TRY(ctx, hipMemcpyAsync(out_len, d_out_len, n * 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipMemcpyAsync(status, dstatus, n * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, md::to_host(out_len, d_out_len, n, st));
+  HIP_TRY(ctx, md::to_host(status, dstatus, n, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
   return MD_OK;
 }

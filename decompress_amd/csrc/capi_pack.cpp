@@ -33,17 +33,6 @@ constexpr uint32_t kNone = 0xffffffffu;
 // a slot of scratch: the bytes and room for the copy loops' 16-byte reads, on 64 bytes
 inline uint64_t slot_stride(uint64_t cap) { return ((cap + 63) & ~(uint64_t)63) + 64; }
 
-template <class T>
-int upload(md_ctx *ctx, T *d, const T *h, size_t count) {
-  if (count) HIP_TRY(ctx, hipMemcpyAsync(d, h, count * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-  return MD_OK;
-}
-template <class T>
-int download(md_ctx *ctx, T *h, const T *d, size_t count) {
-  if (count) HIP_TRY(ctx, hipMemcpyAsync(h, d, count * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-  return MD_OK;
-}
-
 // the inflate launch's descriptors of `count` streams and what comes behind it, carved from one block
 struct RoundDesc {
   Stream *rows = nullptr;
@@ -64,24 +53,39 @@ struct RoundDesc {
   }
 };
 
-// The streams h_rows[0, count) of the pack at d_pack, stream j into d_buf + h_out_off[j]: one inflate launch, the CRC-32s
-// of the packed bytes if asked for, and the verdicts (left in d.status).
-int inflate_round(md_ctx *ctx, const RoundDesc &d, const uint8_t *d_pack, uint8_t *d_buf, size_t count, const Stream *h_rows,
-                  const std::vector<uint64_t> &h_in_off, const std::vector<uint64_t> &h_in_len, const std::vector<uint64_t> &h_out_off,
-                  const std::vector<uint64_t> &h_out_cap, const std::vector<uint64_t> &h_p_off, const std::vector<uint64_t> &h_p_len, bool verify) {
-  int rc;
-  if ((rc = upload(ctx, d.rows, h_rows, count)) != MD_OK || (rc = upload(ctx, d.in_off, h_in_off.data(), count)) != MD_OK ||
-      (rc = upload(ctx, d.in_len, h_in_len.data(), count)) != MD_OK || (rc = upload(ctx, d.out_off, h_out_off.data(), count)) != MD_OK ||
-      (rc = upload(ctx, d.out_cap, h_out_cap.data(), count)) != MD_OK)
-    return rc;
-  rc = md_inflate_batch_device(ctx, MD_FORMAT_ZLIB, count, d_pack, d.in_off, d.in_len, d_buf, d.out_off, d.out_cap, d.out_len, d.consumed, d.status,
+// the host side of a round's streams: the rows, the inflate launch's descriptors and the CRC launch's (p_off and p_len:
+// inflate_round reads them with `verify` alone, so md_pack_open's rounds fill them for nothing)
+struct RoundStreams {
+  std::vector<Stream> rows;
+  std::vector<uint64_t> in_off, in_len, out_off, out_cap, p_off, p_len;
+  // the object at pack[off, off + packed) whose zlib stream begins at zoff and inflates to hsize bytes at `out`
+  void add(uint64_t off, uint64_t packed, uint64_t zoff, uint64_t hsize, uint32_t crc, uint64_t out) {
+    const uint64_t zlen = off + packed - zoff;
+    rows.push_back(Stream{off, packed, zlen, hsize, crc, 0});
+    in_off.push_back(zoff), in_len.push_back(zlen), out_off.push_back(out), out_cap.push_back(hsize);
+    p_off.push_back(off), p_len.push_back(packed);
+  }
+};
+
+// The streams of h (it lives until the stream has been waited for) of the pack at d_pack, stream j into d_buf + h.out_off[j]:
+// one inflate launch, the CRC-32s of the packed bytes if asked for, and the verdicts (left in d.status).
+int inflate_round(md_ctx *ctx, const RoundDesc &d, const uint8_t *d_pack, uint8_t *d_buf, const RoundStreams &h, bool verify) {
+  hipStream_t st = ctx->stream;
+  const size_t count = h.rows.size();
+  HIP_TRY(ctx, md::to_device(d.rows, h.rows, st));
+  HIP_TRY(ctx, md::to_device(d.in_off, h.in_off, st));
+  HIP_TRY(ctx, md::to_device(d.in_len, h.in_len, st));
+  HIP_TRY(ctx, md::to_device(d.out_off, h.out_off, st));
+  HIP_TRY(ctx, md::to_device(d.out_cap, h.out_cap, st));
+  int rc = md_inflate_batch_device(ctx, MD_FORMAT_ZLIB, count, d_pack, d.in_off, d.in_len, d_buf, d.out_off, d.out_cap, d.out_len, d.consumed, d.status,
                                nullptr);
   if (rc != MD_OK) return rc;
   if (verify) {
-    if ((rc = upload(ctx, d.p_off, h_p_off.data(), count)) != MD_OK || (rc = upload(ctx, d.p_len, h_p_len.data(), count)) != MD_OK) return rc;
-    MD_LAUNCH_TRY(ctx, md_launch_crc32((uint32_t)count, d_pack, d.p_off, d.p_len, d.crc, ctx->stream));
+    HIP_TRY(ctx, md::to_device(d.p_off, h.p_off, st));
+    HIP_TRY(ctx, md::to_device(d.p_len, h.p_len, st));
+    MD_LAUNCH_TRY(ctx, md_launch_crc32((uint32_t)count, d_pack, d.p_off, d.p_len, d.crc, st));
   }
-  MD_LAUNCH_TRY(ctx, md_launch_pk_verdict((uint32_t)count, d.rows, d.out_len, d.consumed, verify ? d.crc : nullptr, d.status, ctx->stream));
+  MD_LAUNCH_TRY(ctx, md_launch_pk_verdict((uint32_t)count, d.rows, d.out_len, d.consumed, verify ? d.crc : nullptr, d.status, st));
   return MD_OK;
 }
 
@@ -133,13 +137,11 @@ int pack_open(md_ctx *ctx, const uint8_t *pack, size_t pack_len, const uint8_t *
 
   MD_ON_DEVICE(ctx);
   hipStream_t st = ctx->stream;
-  md::Carver c;
   md::pk::Table t = {};
   uint64_t *d_off = nullptr, *d_end = nullptr, *d_sorted = nullptr;
   uint32_t *d_sorted_obj = nullptr, *jump_b = nullptr, *links_b = nullptr, *d_root = nullptr, *d_depth = nullptr;
   uint8_t *d_names = nullptr;
-  for (int pass = 0; pass < 2; pass++) {  // (once for the size, once for the pointers)
-    if (pass && (rc = carve_from(ctx, ctx->scratch[kPackDesc], &c, "hipMalloc(pack table)")) != MD_OK) return rc;
+  rc = carve(ctx, ctx->scratch[kPackDesc], "hipMalloc(pack table)", [&](md::Carver &c) {
     d_off = c.take<uint64_t>(n), d_end = c.take<uint64_t>(n), d_sorted = c.take<uint64_t>(n);
     t.hsize = c.take<uint64_t>(n), t.zoff = c.take<uint64_t>(n);
     d_sorted_obj = c.take<uint32_t>(n);
@@ -148,15 +150,17 @@ int pack_open(md_ctx *ctx, const uint8_t *pack, size_t pack_len, const uint8_t *
     t.status = c.take<int32_t>(n);
     t.type = c.take<uint8_t>(n);
     d_names = c.take<uint8_t>(n * 20);
-  }
+  });
+  if (rc != MD_OK) return rc;
   t.n = n, t.pack_len = pack_len;
   t.off = d_off, t.end = d_end, t.sorted_off = d_sorted, t.sorted_obj = d_sorted_obj, t.names = d_names;
   if ((rc = upload_host_in(ctx, pack, pack_len)) != MD_OK) return rc;
   const uint8_t *d_pack = ctx->scratch[kHostIn].as<uint8_t>();
-  if ((rc = upload(ctx, d_off, h_off.data(), n)) != MD_OK || (rc = upload(ctx, d_end, h_end.data(), n)) != MD_OK ||
-      (rc = upload(ctx, d_sorted, h_sorted.data(), n)) != MD_OK || (rc = upload(ctx, d_sorted_obj, h_sorted_obj.data(), n)) != MD_OK ||
-      (rc = upload(ctx, d_names, h_names.data(), n * 20)) != MD_OK)
-    return rc;
+  HIP_TRY(ctx, md::to_device(d_off, h_off, st));
+  HIP_TRY(ctx, md::to_device(d_end, h_end, st));
+  HIP_TRY(ctx, md::to_device(d_sorted, h_sorted, st));
+  HIP_TRY(ctx, md::to_device(d_sorted_obj, h_sorted_obj, st));
+  HIP_TRY(ctx, md::to_device(d_names, h_names, st));
   MD_LAUNCH_TRY(ctx, md_launch_pk_headers(&t, d_pack, st));
   // chains of at most n - 1 links: 2^rounds >= n brings every one to its root
   uint32_t *ja = t.jump, *la = t.links, *jb = jump_b, *lb = links_b;
@@ -169,11 +173,13 @@ int pack_open(md_ctx *ctx, const uint8_t *pack, size_t pack_len, const uint8_t *
   std::vector<uint32_t> base(n), root(n), depth(n);
   std::vector<int32_t> status(n);
   std::vector<uint8_t> type(n);
-  if ((rc = download(ctx, P->hsize.data(), t.hsize, n)) != MD_OK || (rc = download(ctx, P->zoff.data(), t.zoff, n)) != MD_OK ||
-      (rc = download(ctx, base.data(), t.base, n)) != MD_OK || (rc = download(ctx, root.data(), d_root, n)) != MD_OK ||
-      (rc = download(ctx, depth.data(), d_depth, n)) != MD_OK || (rc = download(ctx, status.data(), t.status, n)) != MD_OK ||
-      (rc = download(ctx, type.data(), t.type, n)) != MD_OK)
-    return rc;
+  HIP_TRY(ctx, md::to_host(P->hsize.data(), t.hsize, n, st));
+  HIP_TRY(ctx, md::to_host(P->zoff.data(), t.zoff, n, st));
+  HIP_TRY(ctx, md::to_host(base.data(), t.base, n, st));
+  HIP_TRY(ctx, md::to_host(root.data(), d_root, n, st));
+  HIP_TRY(ctx, md::to_host(depth.data(), d_depth, n, st));
+  HIP_TRY(ctx, md::to_host(status.data(), t.status, n, st));
+  HIP_TRY(ctx, md::to_host(type.data(), t.type, n, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
 
   // -- the deltas' own sizes: their payloads through the decoder, in rounds of the workspace
@@ -186,34 +192,26 @@ int pack_open(md_ctx *ctx, const uint8_t *pack, size_t pack_len, const uint8_t *
   for (size_t t0 = 0; t0 < todo.size();) {
     size_t t1 = t0;
     uint64_t room = 0;
-    std::vector<Stream> rows;
-    std::vector<uint64_t> in_off, in_len, out_off, out_cap, none;
+    RoundStreams h;
     for (; t1 < todo.size(); t1++) {
       const uint32_t i = todo[t1];
       if (t1 > t0 && room + slot_stride(P->hsize[i]) > ctx->pack_workspace) break;
-      rows.push_back(Stream{h_off[i], h_end[i] - h_off[i], h_end[i] - P->zoff[i], P->hsize[i], ent[i].crc32, 0});
-      in_off.push_back(P->zoff[i]);
-      in_len.push_back(h_end[i] - P->zoff[i]);
-      out_off.push_back(room);
-      out_cap.push_back(P->hsize[i]);
+      h.add(h_off[i], h_end[i] - h_off[i], P->zoff[i], P->hsize[i], ent[i].crc32, room);
       room += slot_stride(P->hsize[i]);
     }
     const size_t count = t1 - t0;
     RoundDesc d;
-    md::Carver cc;
-    for (int pass = 0; pass < 2; pass++) {
-      if (pass && (rc = carve_from(ctx, ctx->scratch[kPackRound], &cc, "hipMalloc(pack round descriptors)")) != MD_OK) return rc;
-      d.carve(&cc, count, 0, 0);
-    }
+    rc = carve(ctx, ctx->scratch[kPackRound], "hipMalloc(pack round descriptors)", [&](md::Carver &c) { d.carve(&c, count, 0, 0); });
+    if (rc != MD_OK) return rc;
     if ((rc = ctx->scratch[kPackScratch].reserve(ctx, room + 64, "hipMalloc(pack scratch)")) != MD_OK) return rc;
     uint8_t *d_buf = ctx->scratch[kPackScratch].as<uint8_t>();
-    if ((rc = inflate_round(ctx, d, d_pack, d_buf, count, rows.data(), in_off, in_len, out_off, out_cap, none, none, false)) != MD_OK) return rc;
+    if ((rc = inflate_round(ctx, d, d_pack, d_buf, h, false)) != MD_OK) return rc;
     MD_LAUNCH_TRY(ctx, md_launch_pk_delta_sizes((uint32_t)count, d.rows, d_buf, d.out_off, d.base_size, d.result_size, d.status, st));
     std::vector<uint64_t> bs(count), rs(count);
     std::vector<int32_t> stt(count);
-    if ((rc = download(ctx, bs.data(), d.base_size, count)) != MD_OK || (rc = download(ctx, rs.data(), d.result_size, count)) != MD_OK ||
-        (rc = download(ctx, stt.data(), d.status, count)) != MD_OK)
-      return rc;
+    HIP_TRY(ctx, md::to_host(bs.data(), d.base_size, count, st));
+    HIP_TRY(ctx, md::to_host(rs.data(), d.result_size, count, st));
+    HIP_TRY(ctx, md::to_host(stt.data(), d.status, count, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     for (size_t j = 0; j < count; j++) {
       const uint32_t i = todo[t0 + j];
@@ -291,12 +289,10 @@ struct PairTimers {
 };
 
 // one round of a read
-struct ReadRound {
-  std::vector<uint32_t> obj;                                          // stream -> object
-  std::vector<Stream> rows;
-  std::vector<uint64_t> in_off, in_len, out_off, out_cap, p_off, p_len;  // the inflate launch's and the CRC launch's
-  std::vector<uint64_t> res_off;                                         // where the object's bytes stand in the end
-  std::vector<Delta> deltas;                                             // sorted by depth
+struct ReadRound : RoundStreams {
+  std::vector<uint32_t> obj;      // stream -> object
+  std::vector<uint64_t> res_off;  // where the object's bytes stand in the end
+  std::vector<Delta> deltas;      // sorted by depth
   std::vector<uint32_t> delta_depth;
   std::vector<Repeat> repeats;
   std::vector<int32_t> status;
@@ -318,13 +314,7 @@ int pack_read(md_ctx *ctx, const md_pack *P, const uint8_t *pack, const uint64_t
   for (size_t j = 0; select && j < k; j++)
     if (select[j] >= n) return fail(ctx, MD_E_INVALID_ARGUMENT, "selected object out of range");
   const auto sel = [&](size_t j) { return select ? (size_t)select[j] : j; };
-  uint64_t need = 0;
-  for (size_t j = 0; keep && j < k; j++) {
-    out_off[j] = need;
-    const uint64_t sz = P->objs[sel(j)].size;
-    need = need + sz < need ? UINT64_MAX : need + sz;
-  }
-  if (keep) out_off[k] = need;
+  const uint64_t need = keep ? md::running_offsets(k, out_off, [&](size_t j) { return P->objs[sel(j)].size; }) : 0;
   res->entries = k;
   res->written = need;
   if (need > dst_cap) return MD_UNEXPECTED_END_OF_OUTPUT;
@@ -389,15 +379,8 @@ int pack_read(md_ctx *ctx, const md_pack *P, const uint8_t *pack, const uint64_t
       else place = scratch0 + R.scratch, R.scratch += slot_stride(ob.size);
       uint64_t inflated = place;
       if (P->delta[o]) inflated = scratch0 + R.scratch, R.scratch += slot_stride(P->hsize[o]);
-      const uint64_t end = ob.offset + ob.packed_len;
       R.obj.push_back(o);
-      R.rows.push_back(Stream{ob.offset, ob.packed_len, end - P->zoff[o], P->hsize[o], P->crc[o], 0});
-      R.in_off.push_back(P->zoff[o]);
-      R.in_len.push_back(end - P->zoff[o]);
-      R.out_off.push_back(inflated);
-      R.out_cap.push_back(P->hsize[o]);
-      R.p_off.push_back(ob.offset);
-      R.p_len.push_back(ob.packed_len);
+      R.add(ob.offset, ob.packed_len, P->zoff[o], P->hsize[o], P->crc[o], inflated);
       R.res_off.push_back(place);
       if (P->delta[o]) {
         const uint32_t b = (uint32_t)ob.base;
@@ -441,11 +424,8 @@ int pack_read(md_ctx *ctx, const md_pack *P, const uint8_t *pack, const uint64_t
   if (rc == MD_OK) rc = ctx->scratch[kHostOut].reserve(ctx, scratch0 + max_scratch + 64, "hipMalloc(pack output and scratch)");
   if (rc != MD_OK) return rc;
   RoundDesc d;
-  md::Carver c;
-  for (int pass = 0; pass < 2; pass++) {
-    if (pass && (rc = carve_from(ctx, ctx->scratch[kPackRound], &c, "hipMalloc(pack round descriptors)")) != MD_OK) return rc;
-    d.carve(&c, max_count, max_deltas, max_repeats);
-  }
+  rc = carve(ctx, ctx->scratch[kPackRound], "hipMalloc(pack round descriptors)", [&](md::Carver &c) { d.carve(&c, max_count, max_deltas, max_repeats); });
+  if (rc != MD_OK) return rc;
   const uint8_t *d_pack = ctx->scratch[kHostIn].as<uint8_t>();
   uint8_t *d_buf = ctx->scratch[kHostOut].as<uint8_t>();
   md_pack_stats &stats = ctx->pack_last;
@@ -457,9 +437,8 @@ int pack_read(md_ctx *ctx, const md_pack *P, const uint8_t *pack, const uint64_t
   for (ReadRound &R : rounds) {
     const size_t count = R.obj.size();
     if (count == 0) continue;
-    if ((rc = inflate_round(ctx, d, d_pack, d_buf, count, R.rows.data(), R.in_off, R.in_len, R.out_off, R.out_cap, R.p_off, R.p_len, verify)) != MD_OK)
-      return rc;
-    if ((rc = upload(ctx, d.deltas, R.deltas.data(), R.deltas.size())) != MD_OK) return rc;
+    if ((rc = inflate_round(ctx, d, d_pack, d_buf, R, verify)) != MD_OK) return rc;
+    HIP_TRY(ctx, md::to_device(d.deltas, R.deltas, st));
     if (!R.deltas.empty()) timers.mark(st);
     for (size_t a = 0; a < R.deltas.size();) {  // one launch per level: the stream orders them
       size_t b = a + 1;
@@ -472,16 +451,16 @@ int pack_read(md_ctx *ctx, const md_pack *P, const uint8_t *pack, const uint64_t
     if (names) {  // behind the round's last apply launch: every object where it stands; the verdicts are the host's, below
       hash_timers.mark(st);
       if ((rc = sha1_enqueue(ctx, count, d_buf, R.res_off.data(), R.size.data(), R.type.data(), &R.sha, &hashed)) != MD_OK) return rc;
-      if ((rc = upload(ctx, R.sha.expect, R.names.data(), count * 20)) != MD_OK) return rc;
+      HIP_TRY(ctx, md::to_device(R.sha.expect, R.names, st));
       MD_LAUNCH_TRY(ctx, md_launch_sha1_names((uint32_t)count, R.sha.digest, R.sha.expect, R.sha.differs, st));
       hash_timers.mark(st);
-      if ((rc = download(ctx, R.differs.data(), R.sha.differs, count)) != MD_OK) return rc;
+      HIP_TRY(ctx, md::to_host(R.differs.data(), R.sha.differs, count, st));
     }
     if (!R.repeats.empty()) {
-      if ((rc = upload(ctx, d.repeats, R.repeats.data(), R.repeats.size())) != MD_OK) return rc;
+      HIP_TRY(ctx, md::to_device(d.repeats, R.repeats, st));
       MD_LAUNCH_TRY(ctx, md_launch_pk_repeats((uint32_t)R.repeats.size(), d.repeats, d_buf, st));
     }
-    if ((rc = download(ctx, R.status.data(), d.status, count)) != MD_OK) return rc;
+    HIP_TRY(ctx, md::to_host(R.status.data(), d.status, count, st));
     stats.rounds++;
     stats.inflate_launches++;
     stats.objects += count;
@@ -524,12 +503,7 @@ int md_pack_open(md_ctx *ctx, const uint8_t *pack, size_t pack_len, const uint8_
   if (!pack || !idx) return fail(ctx, MD_E_INVALID_ARGUMENT, "null pointer");
   md_pack *P = new (std::nothrow) md_pack();
   if (!P) return fail(ctx, MD_E_OUT_OF_MEMORY, "host memory for the pack's table");
-  int rc;
-  try {
-    rc = pack_open(ctx, pack, pack_len, idx, idx_len, P);
-  } catch (const std::bad_alloc &) {
-    rc = fail(ctx, MD_E_OUT_OF_MEMORY, "host memory for the pack's table");
-  }
+  const int rc = no_bad_alloc(ctx, "host memory for the pack's table", [&] { return pack_open(ctx, pack, pack_len, idx, idx_len, P); });
   if (rc != MD_OK) {
     delete P;
     return rc;
@@ -564,38 +538,37 @@ int md_pack_last(const md_ctx *ctx, md_pack_stats *stats) {
   return MD_OK;
 }
 
+// the checks md_pack_read and md_pack_verify share (pointers: those of the caller's own are there); *k = the objects of the call
+static int pack_checks(md_ctx *ctx, bool verify, bool pointers, const md_pack *p, const uint8_t *pack, size_t pack_len, const uint64_t *select,
+                       size_t nselect, unsigned flags, const int32_t *status, md_pack_result *res, size_t *k) {
+  if (!p || !pack || !res || !pointers) return fail(ctx, MD_E_INVALID_ARGUMENT, "null pointer");
+  memset(res, 0, sizeof *res);
+  if (flags & ~(MD_PACK_VERIFY_CRC | MD_PACK_VERIFY_NAME))
+    return fail(ctx, MD_E_INVALID_ARGUMENT, verify ? "md_pack_verify: unknown flag" : "md_pack_read: unknown flag");
+  if (pack_len != p->pack_len || memcmp(pack + pack_len - 20, p->pack_checksum, 20) != 0)
+    return fail(ctx, MD_INVALID_INDEX, verify ? "md_pack_verify: the table belongs to another pack" : "md_pack_read: the table belongs to another pack");
+  *k = select ? nselect : p->objs.size();
+  if (*k > 0x7fffffffull) return fail(ctx, MD_E_INVALID_ARGUMENT, "too many objects in one call");
+  if (*k && !status) return fail(ctx, MD_E_INVALID_ARGUMENT, "null pointer");
+  return MD_OK;
+}
+
 int md_pack_read(md_ctx *ctx, const md_pack *p, const uint8_t *pack, size_t pack_len, const uint64_t *select, size_t nselect, unsigned flags,
                  uint8_t *dst, size_t dst_cap, uint64_t *out_off, int32_t *status, md_pack_result *res) {
   if (!ctx) return MD_E_INVALID_ARGUMENT;
-  if (!p || !pack || !res || !out_off || (!dst && dst_cap)) return fail(ctx, MD_E_INVALID_ARGUMENT, "null pointer");
-  memset(res, 0, sizeof *res);
-  if (flags & ~(MD_PACK_VERIFY_CRC | MD_PACK_VERIFY_NAME)) return fail(ctx, MD_E_INVALID_ARGUMENT, "md_pack_read: unknown flag");
-  if (pack_len != p->pack_len || memcmp(pack + pack_len - 20, p->pack_checksum, 20) != 0)
-    return fail(ctx, MD_INVALID_INDEX, "md_pack_read: the table belongs to another pack");
-  const size_t k = select ? nselect : p->objs.size();
-  if (k > 0x7fffffffull) return fail(ctx, MD_E_INVALID_ARGUMENT, "too many objects in one call");
-  if (k && !status) return fail(ctx, MD_E_INVALID_ARGUMENT, "null pointer");
-  try {
-    return pack_read(ctx, p, pack, select, k, flags, true, dst, dst_cap, out_off, status, res);
-  } catch (const std::bad_alloc &) {
-    return fail(ctx, MD_E_OUT_OF_MEMORY, "host memory for the read's plan");
-  }
+  size_t k = 0;
+  const int rc = pack_checks(ctx, false, out_off && (dst || !dst_cap), p, pack, pack_len, select, nselect, flags, status, res, &k);
+  if (rc != MD_OK) return rc;
+  return no_bad_alloc(ctx, "host memory for the read's plan",
+                      [&] { return pack_read(ctx, p, pack, select, k, flags, true, dst, dst_cap, out_off, status, res); });
 }
 
 int md_pack_verify(md_ctx *ctx, const md_pack *p, const uint8_t *pack, size_t pack_len, const uint64_t *select, size_t nselect, unsigned flags,
                    int32_t *status, md_pack_result *res) {
   if (!ctx) return MD_E_INVALID_ARGUMENT;
-  if (!p || !pack || !res) return fail(ctx, MD_E_INVALID_ARGUMENT, "null pointer");
-  memset(res, 0, sizeof *res);
-  if (flags & ~(MD_PACK_VERIFY_CRC | MD_PACK_VERIFY_NAME)) return fail(ctx, MD_E_INVALID_ARGUMENT, "md_pack_verify: unknown flag");
-  if (pack_len != p->pack_len || memcmp(pack + pack_len - 20, p->pack_checksum, 20) != 0)
-    return fail(ctx, MD_INVALID_INDEX, "md_pack_verify: the table belongs to another pack");
-  const size_t k = select ? nselect : p->objs.size();
-  if (k > 0x7fffffffull) return fail(ctx, MD_E_INVALID_ARGUMENT, "too many objects in one call");
-  if (k && !status) return fail(ctx, MD_E_INVALID_ARGUMENT, "null pointer");
-  try {
-    return pack_read(ctx, p, pack, select, k, flags, false, nullptr, 0, nullptr, status, res);
-  } catch (const std::bad_alloc &) {
-    return fail(ctx, MD_E_OUT_OF_MEMORY, "host memory for the verification's plan");
-  }
+  size_t k = 0;
+  const int rc = pack_checks(ctx, true, true, p, pack, pack_len, select, nselect, flags, status, res, &k);
+  if (rc != MD_OK) return rc;
+  return no_bad_alloc(ctx, "host memory for the verification's plan",
+                      [&] { return pack_read(ctx, p, pack, select, k, flags, false, nullptr, 0, nullptr, status, res); });
 }

@@ -20,19 +20,13 @@ uint64_t blocks_of(uint32_t type, uint64_t len) {
 }
 
 int carve_batch(md_ctx *ctx, size_t n, Sha1Batch *b) {
-  md::Carver c;
-  for (int pass = 0; pass < 2; pass++) {
-    if (pass) {
-      const int rc = carve_from(ctx, ctx->scratch[kShaDesc], &c, "hipMalloc(SHA-1 descriptors)");
-      if (rc != MD_OK) return rc;
-    }
+  return carve(ctx, ctx->scratch[kShaDesc], "hipMalloc(SHA-1 descriptors)", [&](md::Carver &c) {
     b->off = c.take<uint64_t>(n), b->len = c.take<uint64_t>(n);
     b->state = c.take<md::sha::State>(n);
     b->index = c.take<uint32_t>(n), b->differs = c.take<uint32_t>(n);
     b->type = c.take<uint8_t>(n);
-    b->digest = c.take<uint8_t>(n * 20), b->expect = c.take<uint8_t>(n * 20);
-  }
-  return MD_OK;
+    b->digest = c.take<uint8_t>(n * kSha1Bytes), b->expect = c.take<uint8_t>(n * kSha1Bytes);
+  });
 }
 
 // the time between the context's two SHA-1 events, behind a synchronise (an event that cannot be read leaves 0)
@@ -60,10 +54,10 @@ int sha1_enqueue(md_ctx *ctx, size_t n, const uint8_t *d_data, const uint64_t *o
   }
   std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return blocks[x] > blocks[y]; });
   hipStream_t st = ctx->stream;
-  HIP_TRY(ctx, hipMemcpyAsync(b->off, off, n * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(b->len, len, n * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(b->index, order.data(), n * 4, hipMemcpyHostToDevice, st));
-  if (type) HIP_TRY(ctx, hipMemcpyAsync(b->type, type, n, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, md::to_device(b->off, off, n, st));
+  HIP_TRY(ctx, md::to_device(b->len, len, n, st));
+  HIP_TRY(ctx, md::to_device(b->index, order, st));
+  if (type) HIP_TRY(ctx, md::to_device(b->type, type, n, st));
   md::sha::Args a = {};
   a.blocks = ctx->sha1_launch_blocks;
   a.data = d_data, a.off = b->off, a.len = b->len, a.type = type ? b->type : nullptr, a.index = b->index;
@@ -102,15 +96,12 @@ int md_sha1_batch_host(md_ctx *ctx, size_t n, const uint8_t *data, size_t data_l
   if (rc != MD_OK) return rc;
   Sha1Batch b;
   md_sha1_stats stats = {};
-  try {
-    HIP_TRY(ctx, hipEventRecord(ctx->sha_ev0, st));
-    rc = sha1_enqueue(ctx, n, ctx->scratch[kHostIn].as<uint8_t>(), off, len, type, &b, &stats);
-    if (rc != MD_OK) return rc;
-    HIP_TRY(ctx, hipEventRecord(ctx->sha_ev1, st));
-  } catch (const std::bad_alloc &) {
-    return fail(ctx, MD_E_OUT_OF_MEMORY, "host memory for the batch's order");
-  }
-  HIP_TRY(ctx, hipMemcpyAsync(digest, b.digest, n * 20, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipEventRecord(ctx->sha_ev0, st));
+  rc = no_bad_alloc(ctx, "host memory for the batch's order",
+                    [&] { return sha1_enqueue(ctx, n, ctx->scratch[kHostIn].as<uint8_t>(), off, len, type, &b, &stats); });
+  if (rc != MD_OK) return rc;
+  HIP_TRY(ctx, hipEventRecord(ctx->sha_ev1, st));
+  HIP_TRY(ctx, md::to_host(digest, b.digest, n * kSha1Bytes, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
   stats.device_ns = event_ns(ctx);
   ctx->sha1_last = stats;
@@ -129,15 +120,9 @@ int md_sha1_batch_device(md_ctx *ctx, size_t n, const uint8_t *d_data, const uin
   if (n > 0x7fffffffull || !d_off || !d_len || !d_digest || max_len > MD_MAX_STREAM) return fail(ctx, MD_E_INVALID_ARGUMENT, "bad sha1 batch");
   MD_ON_DEVICE(ctx);
   hipStream_t st = ctx->stream;
-  md::Carver c;
   md::sha::State *state = nullptr;
-  for (int pass = 0; pass < 2; pass++) {
-    if (pass) {
-      const int rc = carve_from(ctx, ctx->scratch[kShaDesc], &c, "hipMalloc(SHA-1 states)");
-      if (rc != MD_OK) return rc;
-    }
-    state = c.take<md::sha::State>(n);
-  }
+  const int rc = carve(ctx, ctx->scratch[kShaDesc], "hipMalloc(SHA-1 states)", [&](md::Carver &c) { state = c.take<md::sha::State>(n); });
+  if (rc != MD_OK) return rc;
   md::sha::Args a = {};
   a.count = (uint32_t)n, a.blocks = ctx->sha1_launch_blocks;
   a.data = d_data, a.off = d_off, a.len = d_len, a.type = d_type, a.state = state, a.digest = d_digest;

@@ -183,18 +183,15 @@ int build_index(md_ctx *ctx, int format, const uint8_t *src, size_t src_len, uin
       if (rc != MD_OK) return rc;
       uint64_t *d_src = nullptr;
       uint32_t *d_len = nullptr;
-      md::Carver c;
-      for (int pass = 0; pass < 2; pass++) {
-        if (pass && (rc = carve_from(ctx, ctx->scratch[kZixDesc], &c, "hipMalloc(index descriptors)", 64)) != MD_OK) return rc;
-        d_src = c.take<uint64_t>(m);
-        d_len = c.take<uint32_t>(m);
-      }
+      const auto takes = [&](md::Carver &c) { d_src = c.take<uint64_t>(m), d_len = c.take<uint32_t>(m); };
+      rc = carve(ctx, ctx->scratch[kZixDesc], "hipMalloc(index descriptors)", takes, 64);
+      if (rc != MD_OK) return rc;
       uint8_t *d_wins = ctx->scratch[kZixWin].as<uint8_t>();
-      HIP_TRY(ctx, hipMemcpyAsync(d_src, k_src.data(), m * 8, hipMemcpyHostToDevice, stream));
-      HIP_TRY(ctx, hipMemcpyAsync(d_len, k_len.data(), m * 4, hipMemcpyHostToDevice, stream));
+      HIP_TRY(ctx, md::to_device(d_src, k_src, stream));
+      HIP_TRY(ctx, md::to_device(d_len, k_len, stream));
       MD_LAUNCH_TRY(ctx, md_launch_zix_windows_take((uint32_t)m, d_base, d_src, d_len, d_wins, stream));
       taken.resize(m * kWindow);
-      HIP_TRY(ctx, hipMemcpyAsync(taken.data(), d_wins, m * kWindow, hipMemcpyDeviceToHost, stream));
+      HIP_TRY(ctx, md::to_host(taken.data(), d_wins, taken.size(), stream));
       HIP_TRY(ctx, hipStreamSynchronize(stream));
       for (size_t p = 0; p < m; p++) md::zix::add_point(x, k_bit[p], k_out[p], taken.data() + p * kWindow);
     }
@@ -257,12 +254,7 @@ int md_inflate_index_build(md_ctx *ctx, int format, const uint8_t *src, size_t s
   MD_ON_DEVICE(ctx);
   md_inflate_index *x = new (std::nothrow) md_inflate_index();
   if (!x) return fail(ctx, MD_E_OUT_OF_MEMORY, "md_inflate_index_build");
-  int rc;
-  try {
-    rc = build_index(ctx, format, src, src_len, span, dst, dst ? dst_cap : 0, x);
-  } catch (const std::bad_alloc &) {
-    rc = fail(ctx, MD_E_OUT_OF_MEMORY, "md_inflate_index_build");
-  }
+  const int rc = no_bad_alloc(ctx, "md_inflate_index_build", [&] { return build_index(ctx, format, src, src_len, span, dst, dst ? dst_cap : 0, x); });
   if (rc != MD_OK) {
     delete x;
     return rc;
@@ -344,13 +336,7 @@ int md_inflate_index_read(md_ctx *ctx, const md_inflate_index *idx, const uint8_
   uint64_t *d_off = nullptr, *d_len = nullptr, *d_pack = nullptr, *d_plan = nullptr;
   int32_t *d_status = nullptr;
   uint64_t *d_bit = nullptr, *d_outs = nullptr;
-  md::Carver c;
-  for (int pass = 0; pass < 2; pass++) {  // (sizes first, then the pointers)
-    if (pass) {
-      int rc = carve_from(ctx, ctx->scratch[kZixDesc], &c, "hipMalloc(index descriptors)", 64);
-      if (rc == MD_OK) rc = ctx->scratch[kZixOut].reserve(ctx, total + 64, "hipMalloc(index ranges)");
-      if (rc != MD_OK) return rc;
-    }
+  int rc = carve(ctx, ctx->scratch[kZixDesc], "hipMalloc(index descriptors)", [&](md::Carver &c) {
     d_plan = c.take<uint64_t>(md::zix::kPlanWords);
     d_bit = c.take<uint64_t>(P);
     d_outs = c.take<uint64_t>(P);
@@ -367,20 +353,22 @@ int md_inflate_index_read(md_ctx *ctx, const md_inflate_index *idx, const uint8_
     t.round_of = c.take<uint32_t>(P);
     t.verdict = c.take<int32_t>(P);
     d_status = c.take<int32_t>(n);
-  }
+  }, 64);
+  if (rc == MD_OK) rc = ctx->scratch[kZixOut].reserve(ctx, total + 64, "hipMalloc(index ranges)");
+  if (rc != MD_OK) return rc;
   t.points = P;
   t.size = f.size;
   t.body_end = f.consumed - md::zix::trailer_len(f.format);
   t.bit = d_bit;
   t.out = d_outs;
-  HIP_TRY(ctx, hipMemcpyAsync(d_bit, idx->bit.data(), P * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(d_outs, idx->out.data(), P * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(d_off, off, n * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(d_len, len, n * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(d_pack, pack.data(), n * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemsetAsync(t.marked, 0, words * 4, st));
-  HIP_TRY(ctx, hipMemsetAsync(t.round_of, 0xff, P * 4, st));
-  HIP_TRY(ctx, hipMemsetAsync(d_status, 0, n * 4, st));
+  HIP_TRY(ctx, md::to_device(d_bit, idx->bit.data(), P, st));
+  HIP_TRY(ctx, md::to_device(d_outs, idx->out.data(), P, st));
+  HIP_TRY(ctx, md::to_device(d_off, off, n, st));
+  HIP_TRY(ctx, md::to_device(d_len, len, n, st));
+  HIP_TRY(ctx, md::to_device(d_pack, pack, st));
+  HIP_TRY(ctx, md::zero(t.marked, words, st));
+  HIP_TRY(ctx, hipMemsetAsync(t.round_of, 0xff, P * sizeof *t.round_of, st));
+  HIP_TRY(ctx, md::zero(d_status, n, st));
   uint8_t *d_dst = ctx->scratch[kZixOut].as<uint8_t>();
   md_inflate_index_stats &stats = ctx->zix_last;
   std::vector<uint32_t> ids;
@@ -392,8 +380,8 @@ int md_inflate_index_read(md_ctx *ctx, const md_inflate_index *idx, const uint8_
     // (the pieces' numbers ride along with the four words: up to kIdsAhead of them, so a round costs one wait unless it is larger)
     const size_t ahead = (size_t)std::min<uint64_t>(P - first, kIdsAhead);
     ids.resize(ahead);
-    HIP_TRY(ctx, hipMemcpyAsync(plan, d_plan, sizeof plan, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(ids.data(), r.piece, ahead * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, md::to_host(plan, d_plan, md::zix::kPlanWords, st));
+    HIP_TRY(ctx, md::to_host(ids.data(), r.piece, ahead, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     const size_t count = (size_t)plan[md::zix::kPlanCount];
     first = plan[md::zix::kPlanNext];
@@ -401,10 +389,10 @@ int md_inflate_index_read(md_ctx *ctx, const md_inflate_index *idx, const uint8_
     if (count > P || first > P) return fail(ctx, MD_E_HIP, "md_inflate_index_read: plan");
     ids.resize(count);
     if (count > ahead) {
-      HIP_TRY(ctx, hipMemcpyAsync(ids.data() + ahead, r.piece + ahead, (count - ahead) * 4, hipMemcpyDeviceToHost, st));
+      HIP_TRY(ctx, md::to_host(ids.data() + ahead, r.piece + ahead, count - ahead, st));
       HIP_TRY(ctx, hipStreamSynchronize(st));
     }
-    int rc = ctx->scratch[kZixIn].reserve(ctx, plan[md::zix::kPlanIn] + 64, "hipMalloc(index input)");
+    rc = ctx->scratch[kZixIn].reserve(ctx, plan[md::zix::kPlanIn] + 64, "hipMalloc(index input)");
     if (rc == MD_OK) rc = ctx->scratch[kZixSlots].reserve(ctx, plan[md::zix::kPlanScratch] + 64, "hipMalloc(index slots)");
     if (rc == MD_OK) rc = ctx->scratch[kZixWin].reserve(ctx, count * kWindow, "hipMalloc(index windows)");
     if (rc != MD_OK) return rc;
@@ -416,7 +404,7 @@ int md_inflate_index_read(md_ctx *ctx, const md_inflate_index *idx, const uint8_
       if (k >= P || (j && k <= ids[j - 1])) return fail(ctx, MD_E_HIP, "md_inflate_index_read: plan");
       const uint64_t b0 = idx->bit[k] >> 3, b1 = k + 1 < P ? (idx->bit[k + 1] + 7) >> 3 : t.body_end, in_len = b1 - b0;
       if (at + in_len > plan[md::zix::kPlanIn] || b1 > src_len) return fail(ctx, MD_E_HIP, "md_inflate_index_read: plan");
-      HIP_TRY(ctx, hipMemcpyAsync(d_in + at, src + b0, in_len, hipMemcpyHostToDevice, st));
+      HIP_TRY(ctx, md::to_device(d_in + at, src + b0, in_len, st));
       at += md::zix::in_stride(in_len);
       stats.bytes_in += in_len;
     }
@@ -425,7 +413,7 @@ int md_inflate_index_read(md_ctx *ctx, const md_inflate_index *idx, const uint8_
       const auto full = [&](size_t q) { return idx->win_off[ids[q] + 1] - idx->win_off[ids[q]] == kWindow; };
       while (e < count && ids[e] == ids[e - 1] + 1 && full(e - 1)) e++;
       const uint64_t w0 = idx->win_off[ids[j]], w1 = idx->win_off[ids[e - 1] + 1];
-      if (w1 > w0) HIP_TRY(ctx, hipMemcpyAsync(d_wins + j * kWindow, idx->wins.data() + w0, w1 - w0, hipMemcpyHostToDevice, st));
+      HIP_TRY(ctx, md::to_device(d_wins + j * kWindow, idx->wins.data() + w0, w1 - w0, st));
       stats.bytes_windows += w1 - w0;
       j = e;
     }
@@ -441,19 +429,13 @@ int md_inflate_index_read(md_ctx *ctx, const md_inflate_index *idx, const uint8_
     stats.bytes_scratch += plan[md::zix::kPlanScratch];
   }
   // the statuses first: a range that failed is not copied out (its part of the block holds what an earlier call left)
-  HIP_TRY(ctx, hipMemcpyAsync(status, d_status, n * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, md::to_host(status, d_status, n, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
-  for (size_t i = 0; i < n;) {
-    if (status[i] != MD_OK) {
-      i++;
-      continue;
-    }
-    size_t e = i + 1;
-    uint64_t bytes = len[i];
-    while (e < n && status[e] == MD_OK && dst_off[e] == dst_off[i] + bytes) bytes += len[e++];
-    if (bytes) HIP_TRY(ctx, hipMemcpyAsync(dst + dst_off[i], d_dst + pack[i], bytes, hipMemcpyDeviceToHost, st));
-    i = e;
-  }
+  rc = md::adjacent_runs(n, status, len, dst_off, [&](size_t i, uint64_t bytes) -> int {
+    HIP_TRY(ctx, md::to_host(dst + dst_off[i], d_dst + pack[i], bytes, st));
+    return MD_OK;
+  });
+  if (rc != MD_OK) return rc;
   HIP_TRY(ctx, hipStreamSynchronize(st));
   return MD_OK;
 }

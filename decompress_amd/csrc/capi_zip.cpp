@@ -24,12 +24,6 @@ void segment_table(const std::vector<uint64_t> &len, uint64_t seg, std::vector<u
   for (size_t j = 0; j < k; j++)
     for (uint64_t s = (*first)[j]; s < (*first)[j + 1]; s++) (*seg_entry)[(size_t)s] = (uint32_t)j;
 }
-
-template <class T>
-int upload(md_ctx *ctx, T *d, const std::vector<T> &h) {
-  if (!h.empty()) HIP_TRY(ctx, hipMemcpyAsync(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-  return MD_OK;
-}
 }  // namespace
 
 int md_zip_directory(const uint8_t *src, size_t src_len, md_zip_info *info, md_zip_entry *entries, size_t cap) {
@@ -52,10 +46,10 @@ static int zip_uncompress(md_ctx *ctx, const uint8_t *src, size_t src_len, const
     if (select[j] >= info.entries) return fail(ctx, MD_E_INVALID_ARGUMENT, "selected entry out of range");
   // the rows, the names and the room: the directory's word alone
   std::vector<md::zip::Row> rows(k);
-  std::vector<uint64_t> usize(k), offs(k + 1);
+  std::vector<uint64_t> usize(k);
   std::vector<uint8_t> names;
   const uint64_t dir_at = info.prefix + info.dir_off;  // where the directory begins: no header or body reaches it
-  uint64_t need = 0, lo = dir_at, hi = 0;
+  uint64_t lo = dir_at, hi = 0;
   for (size_t j = 0; j < k; j++) {
     const md_zip_entry &e = dir[select ? (size_t)select[j] : j];
     md::zip::Row &r = rows[j];
@@ -69,8 +63,6 @@ static int zip_uncompress(md_ctx *ctx, const uint8_t *src, size_t src_len, const
     r.method = e.method;
     r.flags = e.flags;
     names.insert(names.end(), src + e.name_off, src + e.name_off + e.name_len);
-    offs[j] = out_off[j] = need;
-    need = need + e.usize < need ? UINT64_MAX : need + e.usize;
     if (e.header_off < dir_at) {
       // the body ends at most 30 + name + 65 535 (the local extra field, unknown here) + csize behind the header
       const uint64_t room = dir_at - e.header_off, frame = 30 + (uint64_t)e.name_len + 0xffff;
@@ -79,7 +71,7 @@ static int zip_uncompress(md_ctx *ctx, const uint8_t *src, size_t src_len, const
       if (end > hi) hi = end;
     }
   }
-  offs[k] = out_off[k] = need;
+  const uint64_t need = md::running_offsets(k, out_off, [&](size_t j) { return usize[j]; });
   res->entries = k;
   res->written = need;
   if (need > dst_cap) return MD_UNEXPECTED_END_OF_OUTPUT;
@@ -93,15 +85,13 @@ static int zip_uncompress(md_ctx *ctx, const uint8_t *src, size_t src_len, const
 
   MD_ON_DEVICE(ctx);
   hipStream_t st = ctx->stream;
-  md::Carver c;
   md::zip::Row *d_rows = nullptr;
   uint64_t *d_usize = nullptr, *d_out_off = nullptr, *d_first = nullptr, *in_off = nullptr, *in_len = nullptr, *out_cap = nullptr, *body_off = nullptr,
            *out_len = nullptr, *consumed = nullptr, *failed = nullptr;
   int32_t *hstatus = nullptr, *d_status = nullptr;
   uint32_t *d_seg_entry = nullptr, *crc = nullptr;
   uint8_t *kind = nullptr, *d_names = nullptr;
-  for (int pass = 0; pass < 2; pass++) {  // (once for the size, once for the pointers)
-    if (pass && (rc = carve_from(ctx, ctx->scratch[kZipDesc], &c, "hipMalloc(zip descriptors)")) != MD_OK) return rc;
+  rc = carve(ctx, ctx->scratch[kZipDesc], "hipMalloc(zip descriptors)", [&](md::Carver &c) {
     d_rows = c.take<md::zip::Row>(k);
     d_usize = c.take<uint64_t>(k);
     d_out_off = c.take<uint64_t>(k + 1);
@@ -119,16 +109,18 @@ static int zip_uncompress(md_ctx *ctx, const uint8_t *src, size_t src_len, const
     crc = c.take<uint32_t>(nseg);
     kind = c.take<uint8_t>(k);
     d_names = c.take<uint8_t>(names.size());
-  }
-  const size_t span = (size_t)(hi - lo);
-  rc = upload_host_in(ctx, src + lo, span);
+  });
+  if (rc == MD_OK) rc = upload_host_in(ctx, src + lo, (size_t)(hi - lo));
   if (rc == MD_OK) rc = ctx->scratch[kHostOut].reserve(ctx, (size_t)need + 64, "hipMalloc(host path output)");
   if (rc != MD_OK) return rc;
   uint8_t *d_src = (uint8_t *)ctx->scratch[kHostIn].p, *d_out = (uint8_t *)ctx->scratch[kHostOut].p;
-  if ((rc = upload(ctx, d_rows, rows)) != MD_OK || (rc = upload(ctx, d_usize, usize)) != MD_OK || (rc = upload(ctx, d_out_off, offs)) != MD_OK ||
-      (rc = upload(ctx, d_first, first)) != MD_OK || (rc = upload(ctx, d_seg_entry, seg_entry)) != MD_OK || (rc = upload(ctx, d_names, names)) != MD_OK)
-    return rc;
-  HIP_TRY(ctx, hipMemsetAsync(failed, 0, 8, st));
+  HIP_TRY(ctx, md::to_device(d_rows, rows, st));
+  HIP_TRY(ctx, md::to_device(d_usize, usize, st));
+  HIP_TRY(ctx, md::to_device(d_out_off, out_off, k + 1, st));
+  HIP_TRY(ctx, md::to_device(d_first, first, st));
+  HIP_TRY(ctx, md::to_device(d_seg_entry, seg_entry, st));
+  HIP_TRY(ctx, md::to_device(d_names, names, st));
+  HIP_TRY(ctx, md::zero(failed, 1, st));
   MD_LAUNCH_TRY(ctx, md_launch_zip_local(k, d_rows, d_src, lo, hi, d_names, in_off, in_len, out_cap, body_off, hstatus, kind, st));
   // every deflated entry at once, each into the usize bytes the directory promises: an entry that lies about its size
   // cannot write into its neighbour (stored entries and those without a good header are streams of no input and no room)
@@ -137,8 +129,8 @@ static int zip_uncompress(md_ctx *ctx, const uint8_t *src, size_t src_len, const
   MD_LAUNCH_TRY(ctx, md_launch_zip_segments(nseg, seg, d_seg_entry, d_first, d_usize, kind, d_src, body_off, d_out, d_out_off, crc, st));
   MD_LAUNCH_TRY(ctx, md_launch_zip_verdict(k, d_rows, d_first, seg, crc, hstatus, out_len, consumed, d_status, failed, st));
   uint64_t nfailed = 0;
-  HIP_TRY(ctx, hipMemcpyAsync(status, d_status, k * 4, hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipMemcpyAsync(&nfailed, failed, 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, md::to_host(status, d_status, k, st));
+  HIP_TRY(ctx, md::to_host(&nfailed, failed, 1, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
   if (need) HIP_TRY(ctx, hipMemcpy(dst, d_out, (size_t)need, hipMemcpyDeviceToHost));
   res->failed = (size_t)nfailed;
@@ -150,11 +142,8 @@ int md_zip_uncompress(md_ctx *ctx, const uint8_t *src, size_t src_len, const uin
   if (!ctx) return MD_E_INVALID_ARGUMENT;
   if (!src || !res || !out_off || (!dst && dst_cap)) return fail(ctx, MD_E_INVALID_ARGUMENT, "null pointer");
   memset(res, 0, sizeof *res);
-  try {
-    return zip_uncompress(ctx, src, src_len, select, nselect, dst, dst_cap, out_off, status, res);
-  } catch (const std::bad_alloc &) {
-    return fail(ctx, MD_E_OUT_OF_MEMORY, "host memory for the archive's directory");
-  }
+  return no_bad_alloc(ctx, "host memory for the archive's directory",
+                      [&] { return zip_uncompress(ctx, src, src_len, select, nselect, dst, dst_cap, out_off, status, res); });
 }
 
 // ---- the writer ----
@@ -222,15 +211,12 @@ static int zip_compress(md_ctx *ctx, int level, size_t n, const md_zip_source *f
 
   MD_ON_DEVICE(ctx);
   hipStream_t st = ctx->stream;
-  md::Carver c;
   uint64_t *in_off = nullptr, *in_len = nullptr, *slot_off = nullptr, *out_len = nullptr, *name_pos = nullptr, *lsize = nullptr, *loff = nullptr,
            *d_first = nullptr;
   int32_t *status = nullptr, *err = nullptr;
   uint32_t *name_len = nullptr, *dos = nullptr, *rec = nullptr, *d_seg_entry = nullptr, *crc = nullptr;
   uint8_t *kind = nullptr, *d_names = nullptr;
-  int rc = MD_OK;
-  for (int pass = 0; pass < 2; pass++) {  // (once for the size, once for the pointers)
-    if (pass && (rc = carve_from(ctx, ctx->scratch[kZipDesc], &c, "hipMalloc(zip descriptors)")) != MD_OK) return rc;
+  int rc = carve(ctx, ctx->scratch[kZipDesc], "hipMalloc(zip descriptors)", [&](md::Carver &c) {
     in_off = c.take<uint64_t>(n);
     in_len = c.take<uint64_t>(n);
     slot_off = c.take<uint64_t>(n);
@@ -248,18 +234,23 @@ static int zip_compress(md_ctx *ctx, int level, size_t n, const md_zip_source *f
     crc = c.take<uint32_t>(nseg);
     kind = c.take<uint8_t>(n);
     d_names = c.take<uint8_t>(names.size());
-  }
-  rc = upload_host_in(ctx, src + lo, span);
+  });
+  if (rc == MD_OK) rc = upload_host_in(ctx, src + lo, span);
   if (rc == MD_OK) rc = ctx->scratch[kHostOut].reserve(ctx, (size_t)slots_bytes + 64, "hipMalloc(host path output)");
   if (rc == MD_OK) rc = ctx->scratch[kZipOut].reserve(ctx, (size_t)image_max + 64, "hipMalloc(zip file image)");
   if (rc != MD_OK) return rc;
   const uint8_t *d_in = (const uint8_t *)ctx->scratch[kHostIn].p;
   uint8_t *slots = (uint8_t *)ctx->scratch[kHostOut].p, *d_file = (uint8_t *)ctx->scratch[kZipOut].p;
-  if ((rc = upload(ctx, in_off, h_in_off)) != MD_OK || (rc = upload(ctx, in_len, h_in_len)) != MD_OK || (rc = upload(ctx, slot_off, h_slot_off)) != MD_OK ||
-      (rc = upload(ctx, name_pos, h_name_pos)) != MD_OK || (rc = upload(ctx, name_len, h_name_len)) != MD_OK || (rc = upload(ctx, dos, h_dos)) != MD_OK ||
-      (rc = upload(ctx, d_first, first)) != MD_OK || (rc = upload(ctx, d_seg_entry, seg_entry)) != MD_OK || (rc = upload(ctx, d_names, names)) != MD_OK)
-    return rc;
-  HIP_TRY(ctx, hipMemsetAsync(err, 0, 4, st));
+  HIP_TRY(ctx, md::to_device(in_off, h_in_off, st));
+  HIP_TRY(ctx, md::to_device(in_len, h_in_len, st));
+  HIP_TRY(ctx, md::to_device(slot_off, h_slot_off, st));
+  HIP_TRY(ctx, md::to_device(name_pos, h_name_pos, st));
+  HIP_TRY(ctx, md::to_device(name_len, h_name_len, st));
+  HIP_TRY(ctx, md::to_device(dos, h_dos, st));
+  HIP_TRY(ctx, md::to_device(d_first, first, st));
+  HIP_TRY(ctx, md::to_device(d_seg_entry, seg_entry, st));
+  HIP_TRY(ctx, md::to_device(d_names, names, st));
+  HIP_TRY(ctx, md::zero(err, 1, st));
   if (n) HIP_TRY(ctx, hipMemsetAsync(kind, md::zip::kStored, n, st));
   if (n && level != 0) {
     // the room of a file is its own length (in_len serves as out_cap): a body that is not shorter loses against stored
@@ -274,9 +265,9 @@ static int zip_compress(md_ctx *ctx, int level, size_t n, const md_zip_source *f
   std::vector<uint32_t> h_rec(4 * n);
   uint64_t image = 0;
   int32_t bad = 0;
-  if (n) HIP_TRY(ctx, hipMemcpyAsync(h_rec.data(), rec, 16 * n, hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipMemcpyAsync(&image, loff + n, 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipMemcpyAsync(&bad, err, 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, md::to_host(h_rec.data(), rec, h_rec.size(), st));
+  HIP_TRY(ctx, md::to_host(&image, loff + n, 1, st));
+  HIP_TRY(ctx, md::to_host(&bad, err, 1, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
   if (bad != 0) return bad;  // (MD_QUEUE_FULL: not with this queue, said all the same)
   if (image > image_max) return fail(ctx, MD_E_HIP, "zip: local sizes above the bound");
@@ -352,9 +343,5 @@ int md_zip_compress(md_ctx *ctx, int level, size_t n, const md_zip_source *files
   }
   const size_t bound = md_zip_compress_bound(n, files);
   if (bound == 0 || bound >= ((uint64_t)1 << 32)) return fail(ctx, MD_E_INVALID_ARGUMENT, "the archive could reach 4 GiB: the writer has no 64-bit offsets");
-  try {
-    return zip_compress(ctx, level, n, files, src, dst, dst_cap, written);
-  } catch (const std::bad_alloc &) {
-    return fail(ctx, MD_E_OUT_OF_MEMORY, "host memory for the archive's descriptors");
-  }
+  return no_bad_alloc(ctx, "host memory for the archive's descriptors", [&] { return zip_compress(ctx, level, n, files, src, dst, dst_cap, written); });
 }

@@ -1,12 +1,13 @@
 // ctx.hpp — what the host translation units (capi*.cpp, stream_*.cpp) share and no kernel sees: the context, the one
 // type that owns device or pinned memory, the error helpers (fail, HIP_TRY, MD_LAUNCH_TRY), the device guard of the entry
-// points, the carving of a scratch block into arrays (md::Carver of host_util.hpp, carve_from), and every function that
+// points, the carving of a scratch block into arrays (md::Carver of host_util.hpp, carve), and every function that
 // one of those files defines and another calls.  The defining file and every caller include it, as with internal.hpp.
 // Plain host C++.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <new>
 #include <string>
 #include <utility>
 #include <vector>
@@ -267,24 +268,57 @@ inline int launch_order(md_ctx *ctx, size_t n, size_t from, uint32_t **order) {
   return rc;
 }
 
-// A block carved in two passes, the takes written once: the first pass counts over a null base, then `buf` is reserved
-// for what it counted and `slack` bytes more, and c starts again over the block.
-//   md::Carver c;
-//   for (int pass = 0; pass < 2; pass++) {
-//     if (pass && (rc = carve_from(ctx, buf, &c, "hipMalloc(..)")) != MD_OK) return rc;
-//     a = c.take<uint64_t>(n), b = c.take<int32_t>(n);
-//   }
-inline int carve_from(md_ctx *ctx, md::DevBuf &buf, md::Carver *c, const char *what, size_t slack = 0) {
-  const int rc = buf.reserve(ctx, c->at + slack, what);
-  if (rc == MD_OK) *c = md::Carver(buf.p);
-  return rc;
+// A block carved in two passes, the takes written once: `takes` runs over a carver that only counts (null pointers), then
+// `buf` is reserved for what it counted and `slack` bytes more, and `takes` runs again over the block.  what == nullptr: no
+// error text (Buffer::reserve).
+//   rc = carve(ctx, buf, "hipMalloc(..)", [&](md::Carver &c) { a = c.take<uint64_t>(n), b = c.take<int32_t>(n); });
+template <class Takes>
+int carve(md_ctx *ctx, md::DevBuf &buf, const char *what, Takes takes, size_t slack = 0) {
+  md::Carver c;
+  takes(c);
+  const int rc = buf.reserve(ctx, c.at + slack, what);
+  if (rc != MD_OK) return rc;
+  c = md::Carver(buf.p);
+  takes(c);
+  return MD_OK;
+}
+
+namespace md {
+// count elements between host and device (or count zeroed elements) on st; nothing for a count of 0.  The byte count is
+// the type's: HIP_TRY(ctx, md::to_device(d_off, off, n, st)).
+template <class T>
+hipError_t to_device(T *d, const T *h, size_t count, hipStream_t st) {
+  return count ? hipMemcpyAsync(d, h, count * sizeof(T), hipMemcpyHostToDevice, st) : hipSuccess;
+}
+template <class T>
+hipError_t to_device(T *d, const std::vector<T> &h, hipStream_t st) {
+  return to_device(d, h.data(), h.size(), st);
+}
+template <class T>
+hipError_t to_host(T *h, const T *d, size_t count, hipStream_t st) {
+  return count ? hipMemcpyAsync(h, d, count * sizeof(T), hipMemcpyDeviceToHost, st) : hipSuccess;
+}
+template <class T>
+hipError_t zero(T *d, size_t count, hipStream_t st) {
+  return count ? hipMemsetAsync(d, 0, count * sizeof(T), st) : hipSuccess;
+}
+}  // namespace md
+
+// f() with the host running out of memory inside it as the context's error `what`
+template <class F>
+int no_bad_alloc(md_ctx *ctx, const char *what, F f) {
+  try {
+    return f();
+  } catch (const std::bad_alloc &) {
+    return fail(ctx, MD_E_OUT_OF_MEMORY, what);
+  }
 }
 
 // the caller's bytes into kHostIn, on the context's stream
 inline int upload_host_in(md_ctx *ctx, const uint8_t *src, size_t len) {
   const int rc = ctx->scratch[kHostIn].reserve(ctx, len + 64, "hipMalloc(host path input)");
   if (rc != MD_OK) return rc;
-  if (len) HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[kHostIn].p, src, len, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, md::to_device(ctx->scratch[kHostIn].as<uint8_t>(), src, len, ctx->stream));
   return MD_OK;
 }
 
@@ -403,6 +437,7 @@ int gzm_index(md_ctx *ctx, const uint8_t *d_src, uint64_t len, bool *indexed, Gz
 // What a batch of n messages keeps on the device, carved from kShaDesc: the descriptors and states of md::sha::Args, the
 // digests (20 bytes a message, message order), and for the names of a pack the 20 bytes expected of each and the verdicts
 // of md_launch_sha1_names.
+constexpr size_t kSha1Bytes = 20;  // a digest
 struct Sha1Batch {
   uint64_t *off = nullptr, *len = nullptr;
   uint8_t *type = nullptr;

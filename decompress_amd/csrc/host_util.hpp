@@ -1,6 +1,7 @@
 // host_util.hpp — small host-side helpers of capi*.cpp and stream_*.cpp: checksums of the few bytes the host
-// handles itself, 32-bit reads of header and trailer fields, and the carver that splits one block of memory into
-// arrays.  Plain C++ without HIP: a host compiler alone takes it (gz_frame.hpp and the sanitizer programs of tests/ do).
+// handles itself, 32-bit reads of header and trailer fields, the carver that splits one block of memory into arrays, the
+// running sum of output offsets and the walk over the ranges that leave by one copy.  Plain C++ without HIP: a host
+// compiler alone takes it (gz_frame.hpp and the sanitizer programs of tests/ do).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -92,5 +93,38 @@ struct Carver {
     return r;
   }
 };
+
+// out_off[0 .. k] = the running sum of size_of(0 .. k - 1); returns the total.  A sum above 64 bits stays UINT64_MAX from
+// there on, which no buffer holds.
+template <class SizeOf>
+uint64_t running_offsets(size_t k, uint64_t *out_off, SizeOf size_of) {
+  uint64_t at = 0;
+  for (size_t j = 0; j < k; j++) {
+    out_off[j] = at;
+    const uint64_t sz = size_of(j);
+    at = at + sz < at ? UINT64_MAX : at + sz;
+  }
+  return out_off[k] = at;
+}
+
+// The copy-out of n ranges: f(first, bytes) once per longest run of consecutive ranges that succeeded (status 0), have
+// bytes and are adjacent in dst - what is adjacent there leaves by one copy.  A failed range and a range of no bytes are
+// skipped and end the run in front of them.  Stops at the first f that does not return 0 and returns that.
+template <class F>
+int adjacent_runs(size_t n, const int32_t *status, const uint64_t *len, const uint64_t *dst_off, F f) {
+  for (size_t i = 0; i < n;) {
+    if (status[i] != 0 || len[i] == 0) {
+      i++;
+      continue;
+    }
+    size_t e = i + 1;
+    uint64_t bytes = len[i];
+    while (e < n && status[e] == 0 && len[e] && dst_off[e] == dst_off[i] + bytes) bytes += len[e++];
+    const int rc = f(i, bytes);
+    if (rc != 0) return rc;
+    i = e;
+  }
+  return 0;
+}
 
 }  // namespace md
