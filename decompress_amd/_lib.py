@@ -178,6 +178,9 @@ SYMBOLS = [
     ("md_pack_last", ctypes.c_int, [c_vp, c_vp]),
     ("md_pack_verify", ctypes.c_int, [c_vp, c_vp, c_vp, c_sz, c_vp, c_sz, ctypes.c_uint, c_vp, c_vp]),
     ("md_pack_check_trailers", ctypes.c_int, [c_vp, c_sz, c_vp, c_sz, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
+    ("md_pack_index_write", ctypes.c_int, [c_vp, c_sz, c_vp, c_vp, c_sz, c_szp]),
+    ("md_pack_index_build", ctypes.c_int, [c_vp, c_vp, c_sz, ctypes.c_uint, c_vp, c_sz, c_vp, c_vp, c_sz, c_vp]),
+    ("md_pack_build_last", ctypes.c_int, [c_vp, c_vp]),
     ("md_sha1_batch_device", ctypes.c_int, [c_vp, c_sz, c_vp, c_vp, c_vp, c_vp, ctypes.c_uint64, c_vp]),
     ("md_sha1_batch_host", ctypes.c_int, [c_vp, c_sz, c_vp, c_sz, c_vp, c_vp, c_vp, c_vp]),
     ("md_sha1_last", ctypes.c_int, [c_vp, c_vp]),
@@ -234,6 +237,16 @@ class PackResult(ctypes.Structure):
 class PackStats(ctypes.Structure):
     """md_pack_stats of include/mdeflate.h"""
     _fields_ = [(k, ctypes.c_uint64) for k in ("rounds", "inflate_launches", "apply_launches", "objects", "bytes_in", "apply_ns")]
+
+
+class PackBuildResult(ctypes.Structure):
+    """md_pack_build_result of include/mdeflate.h"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("n", "failed", "idx_len", "bad_offset")] + [("bad_status", ctypes.c_int32)]
+
+
+class PackBuildStats(ctypes.Structure):
+    """md_pack_build_stats of include/mdeflate.h"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("candidates", "generations", "rounds", "inflate_launches", "apply_launches", "objects", "bytes_in")]
 
 
 class Sha1Stats(ctypes.Structure):

@@ -2,7 +2,8 @@
 // md_pack_free, md_pack_read, md_pack_verify, md_pack_last).  The idx is the host's (pack_index.hpp), and so are the sort
 // of its offsets, the plan of a read and the last walk over the table in order of depth; headers, chains, sizes, statuses
 // and the deltas' instructions are the device's (pack_kernels.hip), the zlib streams the batch decoder's, the names'
-// SHA-1s capi_sha1.cpp's (sha1_enqueue).
+// SHA-1s capi_sha1.cpp's (sha1_enqueue).  The table builder behind the idx (pack_table) and the rounds of a verification
+// with a hash pass that writes names (pack_verify_names) are also md_pack_index_build's (capi_pack_build.cpp; ctx.hpp).
 #include <string.h>
 
 #include <algorithm>
@@ -11,18 +12,6 @@
 
 #include "ctx.hpp"
 #include "pack_index.hpp"
-
-// The table of a pack, all of it on the host: a read uploads the rows of the objects it needs.
-struct md_pack {
-  uint64_t pack_len = 0;
-  md_pack_info info = {};
-  uint8_t pack_checksum[20] = {0};
-  uint32_t fan[256] = {0};
-  std::vector<md_pack_object> objs;  // idx order
-  std::vector<uint64_t> zoff, hsize;  // where an object's zlib stream begins, the size its header states
-  std::vector<uint32_t> crc;          // the idx's CRC-32 of the packed object
-  std::vector<uint8_t> delta;         // 1: the object is a delta (with a base in the pack)
-};
 
 namespace {
 using md::pk::Delta;
@@ -112,7 +101,7 @@ int pack_open(md_ctx *ctx, const uint8_t *pack, size_t pack_len, const uint8_t *
   }
   std::sort(order.begin(), order.end());
   std::vector<uint64_t> h_off(n), h_end(n), h_sorted(n);
-  std::vector<uint32_t> h_sorted_obj(n);
+  std::vector<uint32_t> h_sorted_obj(n), h_crc(n);
   std::vector<uint8_t> h_names(n * 20);
   for (size_t s = 0; s < n; s++) {
     if (s && order[s].first == order[s - 1].first) return fail(ctx, MD_INVALID_INDEX, "md_pack_open: two objects at one offset");
@@ -121,11 +110,21 @@ int pack_open(md_ctx *ctx, const uint8_t *pack, size_t pack_len, const uint8_t *
     h_sorted_obj[s] = i;
     h_end[i] = s + 1 < n ? order[s + 1].first : body_end;
   }
-  for (size_t i = 0; i < n; i++) memcpy(&h_names[i * 20], ent[i].name, 20);
+  for (size_t i = 0; i < n; i++) memcpy(&h_names[i * 20], ent[i].name, 20), h_crc[i] = ent[i].crc32;
   for (int b = 0; b < 256; b++) P->fan[b] = md::pack::be32(idx + 8 + 4 * b);
-
-  P->pack_len = pack_len;
   memcpy(P->pack_checksum, ii.pack_checksum, 20);
+  PackTableIn in;
+  in.n = n, in.off = h_off.data(), in.end = h_end.data(), in.sorted_off = h_sorted.data(), in.sorted_obj = h_sorted_obj.data();
+  in.names = in.obj_names = h_names.data(), in.n_names = n, in.crc = h_crc.data();  // (the idx's order is the names')
+  return pack_table(ctx, pack, pack_len, in, false, P);
+}
+}  // namespace
+
+int pack_table(md_ctx *ctx, const uint8_t *pack, size_t pack_len, const PackTableIn &in, bool resident, md_pack *P) {
+  const size_t n = in.n;
+  const uint64_t *h_off = in.off, *h_end = in.end;
+  int rc = MD_OK;
+  P->pack_len = pack_len;
   P->info = {};
   P->info.n = n;
   P->objs.assign(n, md_pack_object{});
@@ -141,6 +140,7 @@ int pack_open(md_ctx *ctx, const uint8_t *pack, size_t pack_len, const uint8_t *
   uint64_t *d_off = nullptr, *d_end = nullptr, *d_sorted = nullptr;
   uint32_t *d_sorted_obj = nullptr, *jump_b = nullptr, *links_b = nullptr, *d_root = nullptr, *d_depth = nullptr;
   uint8_t *d_names = nullptr;
+  uint32_t *d_name_obj = nullptr;
   rc = carve(ctx, ctx->scratch[kPackDesc], "hipMalloc(pack table)", [&](md::Carver &c) {
     d_off = c.take<uint64_t>(n), d_end = c.take<uint64_t>(n), d_sorted = c.take<uint64_t>(n);
     t.hsize = c.take<uint64_t>(n), t.zoff = c.take<uint64_t>(n);
@@ -149,18 +149,21 @@ int pack_open(md_ctx *ctx, const uint8_t *pack, size_t pack_len, const uint8_t *
     jump_b = c.take<uint32_t>(n), links_b = c.take<uint32_t>(n), d_root = c.take<uint32_t>(n), d_depth = c.take<uint32_t>(n);
     t.status = c.take<int32_t>(n);
     t.type = c.take<uint8_t>(n);
-    d_names = c.take<uint8_t>(n * 20);
+    d_names = c.take<uint8_t>(in.n_names * 20);
+    d_name_obj = c.take<uint32_t>(in.name_obj ? in.n_names : 0);
   });
   if (rc != MD_OK) return rc;
   t.n = n, t.pack_len = pack_len;
   t.off = d_off, t.end = d_end, t.sorted_off = d_sorted, t.sorted_obj = d_sorted_obj, t.names = d_names;
-  if ((rc = upload_host_in(ctx, pack, pack_len)) != MD_OK) return rc;
+  t.n_names = in.n_names, t.name_obj = in.name_obj ? d_name_obj : nullptr;
+  if (!resident && (rc = upload_host_in(ctx, pack, pack_len)) != MD_OK) return rc;
   const uint8_t *d_pack = ctx->scratch[kHostIn].as<uint8_t>();
-  HIP_TRY(ctx, md::to_device(d_off, h_off, st));
-  HIP_TRY(ctx, md::to_device(d_end, h_end, st));
-  HIP_TRY(ctx, md::to_device(d_sorted, h_sorted, st));
-  HIP_TRY(ctx, md::to_device(d_sorted_obj, h_sorted_obj, st));
-  HIP_TRY(ctx, md::to_device(d_names, h_names, st));
+  HIP_TRY(ctx, md::to_device(d_off, h_off, n, st));
+  HIP_TRY(ctx, md::to_device(d_end, h_end, n, st));
+  HIP_TRY(ctx, md::to_device(d_sorted, in.sorted_off, n, st));
+  HIP_TRY(ctx, md::to_device(d_sorted_obj, in.sorted_obj, n, st));
+  HIP_TRY(ctx, md::to_device(d_names, in.names, in.n_names * 20, st));
+  if (in.name_obj) HIP_TRY(ctx, md::to_device(d_name_obj, in.name_obj, in.n_names, st));
   MD_LAUNCH_TRY(ctx, md_launch_pk_headers(&t, d_pack, st));
   // chains of at most n - 1 links: 2^rounds >= n brings every one to its root
   uint32_t *ja = t.jump, *la = t.links, *jb = jump_b, *lb = links_b;
@@ -196,7 +199,7 @@ int pack_open(md_ctx *ctx, const uint8_t *pack, size_t pack_len, const uint8_t *
     for (; t1 < todo.size(); t1++) {
       const uint32_t i = todo[t1];
       if (t1 > t0 && room + slot_stride(P->hsize[i]) > ctx->pack_workspace) break;
-      h.add(h_off[i], h_end[i] - h_off[i], P->zoff[i], P->hsize[i], ent[i].crc32, room);
+      h.add(h_off[i], h_end[i] - h_off[i], P->zoff[i], P->hsize[i], in.crc ? in.crc[i] : 0, room);
       room += slot_stride(P->hsize[i]);
     }
     const size_t count = t1 - t0;
@@ -252,8 +255,8 @@ int pack_open(md_ctx *ctx, const uint8_t *pack, size_t pack_len, const uint8_t *
     o.depth = depth[i];
     o.type = rt >= 1 && rt <= 4 ? rt : 0;
     o.status = status[i];
-    memcpy(o.name, ent[i].name, 20);
-    P->crc[i] = ent[i].crc32;
+    if (in.obj_names) memcpy(o.name, in.obj_names + i * 20, 20);
+    P->crc[i] = in.crc ? in.crc[i] : 0;
     P->delta[i] = base[i] != kNone && depth[i] != 0;
     P->info.deltas += P->delta[i];
     P->info.max_depth = std::max<uint64_t>(P->info.max_depth, depth[i]);
@@ -263,6 +266,7 @@ int pack_open(md_ctx *ctx, const uint8_t *pack, size_t pack_len, const uint8_t *
   return MD_OK;
 }
 
+namespace {
 // pairs of events around a step of the rounds of a read - the apply launches (md_pack_stats::apply_ns), the hash passes
 // (md_sha1_stats::device_ns); an event that cannot be had leaves the time 0, never fails the read
 struct PairTimers {
@@ -303,13 +307,16 @@ struct ReadRound : RoundStreams {
   std::vector<uint64_t> size;
   std::vector<uint8_t> type, names;
   std::vector<uint32_t> differs;
+  std::vector<uint8_t> digest;  // md_pack_index_build: what the hash pass found, 20 bytes a slot
   Sha1Batch sha;
 };
 
 // md_pack_read (keep: the selected objects stand in dst, out_off[k + 1] says where) and md_pack_verify (!keep: they stand in
-// the round's scratch like the bases, dst and out_off are null, nothing but the statuses comes back)
+// the round's scratch like the bases, dst and out_off are null, nothing but the statuses comes back).  sink (with !keep:
+// md_pack_index_build): the hash pass runs, an object whose name is not known yet gets what the pass found written to
+// sink->names, one that has a name is compared as MD_PACK_VERIFY_NAME compares it; the pack is on the device already.
 int pack_read(md_ctx *ctx, const md_pack *P, const uint8_t *pack, const uint64_t *select, size_t k, unsigned flags, bool keep, uint8_t *dst,
-              size_t dst_cap, uint64_t *out_off, int32_t *status, md_pack_result *res) {
+              size_t dst_cap, uint64_t *out_off, int32_t *status, md_pack_result *res, const PackNameSink *sink) {
   const size_t n = P->objs.size();
   for (size_t j = 0; select && j < k; j++)
     if (select[j] >= n) return fail(ctx, MD_E_INVALID_ARGUMENT, "selected object out of range");
@@ -319,7 +326,7 @@ int pack_read(md_ctx *ctx, const md_pack *P, const uint8_t *pack, const uint64_t
   res->written = need;
   if (need > dst_cap) return MD_UNEXPECTED_END_OF_OUTPUT;
   ctx->pack_last = {};
-  const bool names = (flags & MD_PACK_VERIFY_NAME) != 0;
+  const bool names = (flags & MD_PACK_VERIFY_NAME) != 0 || sink;
   if (names) ctx->sha1_last = {}, ctx->sha1_pending = false;
   if (k == 0) return MD_OK;
 
@@ -420,7 +427,7 @@ int pack_read(md_ctx *ctx, const md_pack *P, const uint8_t *pack, const uint64_t
   // -- device memory: the pack, the buffer, one block of descriptors for the largest round
   MD_ON_DEVICE(ctx);
   hipStream_t st = ctx->stream;
-  int rc = upload_host_in(ctx, pack, P->pack_len);
+  int rc = sink ? MD_OK : upload_host_in(ctx, pack, P->pack_len);
   if (rc == MD_OK) rc = ctx->scratch[kHostOut].reserve(ctx, scratch0 + max_scratch + 64, "hipMalloc(pack output and scratch)");
   if (rc != MD_OK) return rc;
   RoundDesc d;
@@ -455,6 +462,10 @@ int pack_read(md_ctx *ctx, const md_pack *P, const uint8_t *pack, const uint64_t
       MD_LAUNCH_TRY(ctx, md_launch_sha1_names((uint32_t)count, R.sha.digest, R.sha.expect, R.sha.differs, st));
       hash_timers.mark(st);
       HIP_TRY(ctx, md::to_host(R.differs.data(), R.sha.differs, count, st));
+      if (sink) {
+        R.digest.resize(count * kSha1Bytes);
+        HIP_TRY(ctx, md::to_host(R.digest.data(), R.sha.digest, count * kSha1Bytes, st));
+      }
     }
     if (!R.repeats.empty()) {
       HIP_TRY(ctx, md::to_device(d.repeats, R.repeats, st));
@@ -472,6 +483,9 @@ int pack_read(md_ctx *ctx, const md_pack *P, const uint8_t *pack, const uint64_t
     // The names' verdicts, in the order of the header's rules: a status of its own stays; else a failed base; else the
     // name.  The deltas of a round are sorted by depth, so a base has its final status when its deltas are looked at.
     for (ReadRound &R : rounds) {
+      if (sink)  // a name that is not known yet cannot differ
+        for (size_t q = 0; q < R.obj.size(); q++)
+          if (!sink->known[R.obj[q]]) R.differs[q] = 0;
       for (size_t q = 0; q < R.obj.size(); q++)
         if (!P->delta[R.obj[q]] && R.status[q] == MD_OK && R.differs[q]) R.status[q] = MD_INVALID_CHECKSUM;
       for (const Delta &dl : R.deltas)
@@ -481,6 +495,10 @@ int pack_read(md_ctx *ctx, const md_pack *P, const uint8_t *pack, const uint64_t
         }
     }
   }
+  if (sink)
+    for (const ReadRound &R : rounds)
+      for (size_t q = 0; q < R.obj.size(); q++)
+        if (R.status[q] == MD_OK && !sink->known[R.obj[q]]) memcpy(sink->names + (size_t)R.obj[q] * kSha1Bytes, &R.digest[q * kSha1Bytes], kSha1Bytes), sink->named[R.obj[q]] = 1;
   if (keep && need) HIP_TRY(ctx, hipMemcpy(dst, d_buf, (size_t)need, hipMemcpyDeviceToHost));
   for (size_t j = 0; j < k; j++) {
     const uint32_t s = (uint32_t)sel(j);
@@ -490,6 +508,10 @@ int pack_read(md_ctx *ctx, const md_pack *P, const uint8_t *pack, const uint64_t
   return MD_OK;
 }
 }  // namespace
+
+int pack_verify_names(md_ctx *ctx, const md_pack *P, const uint64_t *select, size_t k, int32_t *status, md_pack_result *res, const PackNameSink *sink) {
+  return pack_read(ctx, P, nullptr, select, k, 0, false, nullptr, 0, nullptr, status, res, sink);
+}
 
 int md_pack_index(const uint8_t *idx, size_t idx_len, md_pack_index_info *info, md_pack_index_entry *entries, size_t cap) {
   if (!idx || !info || (cap && !entries)) return MD_E_INVALID_ARGUMENT;
@@ -560,7 +582,7 @@ int md_pack_read(md_ctx *ctx, const md_pack *p, const uint8_t *pack, size_t pack
   const int rc = pack_checks(ctx, false, out_off && (dst || !dst_cap), p, pack, pack_len, select, nselect, flags, status, res, &k);
   if (rc != MD_OK) return rc;
   return no_bad_alloc(ctx, "host memory for the read's plan",
-                      [&] { return pack_read(ctx, p, pack, select, k, flags, true, dst, dst_cap, out_off, status, res); });
+                      [&] { return pack_read(ctx, p, pack, select, k, flags, true, dst, dst_cap, out_off, status, res, nullptr); });
 }
 
 int md_pack_verify(md_ctx *ctx, const md_pack *p, const uint8_t *pack, size_t pack_len, const uint64_t *select, size_t nselect, unsigned flags,
@@ -570,5 +592,5 @@ int md_pack_verify(md_ctx *ctx, const md_pack *p, const uint8_t *pack, size_t pa
   const int rc = pack_checks(ctx, true, true, p, pack, pack_len, select, nselect, flags, status, res, &k);
   if (rc != MD_OK) return rc;
   return no_bad_alloc(ctx, "host memory for the verification's plan",
-                      [&] { return pack_read(ctx, p, pack, select, k, flags, false, nullptr, 0, nullptr, status, res); });
+                      [&] { return pack_read(ctx, p, pack, select, k, flags, false, nullptr, 0, nullptr, status, res, nullptr); });
 }

@@ -133,6 +133,7 @@ enum Scratch {
   // lists, the members' descriptors, and the writer's packed file (the reader of a file without size fields decodes its
   // batch into that one: its host steps go through kHostIn / kHostOut)
   // (md_deflate_spans_*: descriptors in kGzmDesc, the joined stream of the host form in kGzmOut, slots in kHostOut)
+  // (md_pack_index_build: the candidates' bitmap and counts in kGzmWs, their list in kGzmCand, the size query's arrays in kGzmDesc)
   kGzmWs, kGzmCand, kGzmDesc, kGzmOut,
   // a ZIP archive (md_zip_*): rows, names, descriptors and the segment table; the writer's file image (archive bytes and
   // decoded entries / encoder slots go through kHostIn / kHostOut)
@@ -150,6 +151,18 @@ enum Scratch {
   // and digests (the host form's bytes go through kHostIn)
   kShaDesc,
   kScratchCount
+};
+
+// The table of a pack, all of it on the host: a read uploads the rows of the objects it needs.
+struct md_pack {
+  uint64_t pack_len = 0;
+  md_pack_info info = {};
+  uint8_t pack_checksum[20] = {0};
+  uint32_t fan[256] = {0};
+  std::vector<md_pack_object> objs;  // idx order (md_pack_index_build's own tables: pack order)
+  std::vector<uint64_t> zoff, hsize;  // where an object's zlib stream begins, the size its header states
+  std::vector<uint32_t> crc;          // the idx's CRC-32 of the packed object
+  std::vector<uint8_t> delta;         // 1: the object is a delta (with a base in the pack)
 };
 
 struct md_ctx {
@@ -205,6 +218,7 @@ struct md_ctx {
   // object a round) and the counts of the last md_pack_read (md_pack_last)
   size_t pack_workspace = (size_t)256 << 20;
   md_pack_stats pack_last = {};
+  md_pack_build_stats pack_build_last = {};  // of the last md_pack_index_build (md_pack_build_last)
   // SHA-1 batches: md_set_option "sha1_launch_blocks" (blocks of 64 bytes by which one launch advances a message) and the
   // counts of the last batch (md_sha1_last).  The device form reads nothing back: its two events are asked when the counts are
   uint32_t sha1_launch_blocks = md::sha::kLaunchBlocksDefault;
@@ -453,6 +467,29 @@ struct Sha1Batch {
 // Adds messages, blocks and launches to *stats.
 int sha1_enqueue(md_ctx *ctx, size_t n, const uint8_t *d_data, const uint64_t *off, const uint64_t *len, const uint8_t *type, Sha1Batch *b,
                  md_sha1_stats *stats);
+// ---- capi_pack.cpp: what md_pack_index_build (capi_pack_build.cpp) shares with md_pack_open and md_pack_verify ----
+// The objects' offsets as the table builder takes them - object i is pack[off[i], end[i]), sorted_off / sorted_obj the
+// offsets ascending and whose they are - and the names that are known: n_names names ascending, name k being object
+// name_obj[k]'s (null: object k's - the idx's order, every name known).  obj_names (20 bytes an object, or null) and crc
+// (or null) go into the table as they are.
+struct PackTableIn {
+  size_t n = 0, n_names = 0;
+  const uint64_t *off = nullptr, *end = nullptr, *sorted_off = nullptr;
+  const uint32_t *sorted_obj = nullptr, *name_obj = nullptr, *crc = nullptr;
+  const uint8_t *names = nullptr, *obj_names = nullptr;
+};
+// md_pack_open behind the idx: headers, chains, the deltas' sizes, the last walk.  A REF_DELTA whose base's name is not
+// among `names` is MD_PACK_MISSING_BASE and what hangs off it MD_INVALID_PACK_BASE, as ever.  resident: the pack is in
+// kHostIn already.  P's checksum and fan-out are the caller's.
+int pack_table(md_ctx *ctx, const uint8_t *pack, size_t pack_len, const PackTableIn &in, bool resident, md_pack *P);
+// md_pack_verify's rounds with the hash pass, over a pack that is in kHostIn: an object with known[o] is compared with its
+// name in the table, one without gets its 20 bytes written to names + 20 o and named[o] = 1 if it decoded
+struct PackNameSink {
+  const uint8_t *known = nullptr;
+  uint8_t *names = nullptr, *named = nullptr;
+};
+int pack_verify_names(md_ctx *ctx, const md_pack *P, const uint64_t *select, size_t k, int32_t *status, md_pack_result *res,
+                      const PackNameSink *sink);
 // ---- capi_long_stream.cpp: both return MD_NOT_HANDLED for what the serial path has to answer ----
 int continue_parallel(md_ctx *ctx, const uint8_t *src, size_t src_len, unsigned start_bit, uint8_t *dst, size_t hist_len,
                       size_t dst_cap, uint32_t adler_in, unsigned flags, size_t *dst_len, int *status, md_inf_resume *resume);

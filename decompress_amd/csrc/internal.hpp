@@ -256,10 +256,11 @@ constexpr uint32_t kNoBase = 0xffffffffu;
 // instruction bytes of a delta that one step of the apply kernel looks at: one per lane
 constexpr uint32_t kWindow = 64;
 // the table md_pack_open builds.  off / end: where the object lies in the pack (the idx's offsets, sorted on the host);
-// sorted_off / sorted_obj: the offsets ascending and whose they are; names: 20 bytes each, ascending.  The header
-// kernel leaves type (the object's own: 1-4, 6, 7), hsize (the size its header states), zoff (where its zlib stream
-// begins), base (kNoBase: none), status, and the chain's first state: jump = base, links = 1 for a delta with a base,
-// jump = itself, links = 0 for everything else.
+// sorted_off / sorted_obj: the offsets ascending and whose they are; names: n_names names of 20 bytes each, ascending,
+// name k being object name_obj[k]'s (name_obj == null: object k's, the idx's order; md_pack_index_build knows only some of
+// the names and has its objects in pack order).  The header kernel leaves type (the object's own: 1-4, 6, 7), hsize (the
+// size its header states), zoff (where its zlib stream begins), base (kNoBase: none), status, and the chain's first
+// state: jump = base, links = 1 for a delta with a base, jump = itself, links = 0 for everything else.
 struct Table {
   uint64_t n, pack_len;
   const uint64_t *off, *end, *sorted_off;
@@ -269,6 +270,8 @@ struct Table {
   uint64_t *hsize, *zoff;
   uint32_t *base, *jump, *links;
   int32_t *status;
+  uint64_t n_names;
+  const uint32_t *name_obj;
 };
 // One needed zlib stream of a round: its packed bytes (header included) [off, off + packed) and the idx's CRC-32 of them,
 // the size its header states; in_len as the inflate launch got it.
@@ -516,6 +519,14 @@ int md_launch_pk_delta_sizes(uint32_t count, const md::pk::Stream *s, const uint
 // one level of a round: one wavefront per delta
 int md_launch_pk_apply(uint32_t count, const md::pk::Delta *d, uint8_t *buf, int32_t *status, hipStream_t stream);
 int md_launch_pk_repeats(uint32_t count, const md::pk::Repeat *r, uint8_t *buf, hipStream_t stream);
+
+// ---- pack_build_kernels.hip: the candidates of md_pack_index_build ----
+// bits / cnt as md_launch_gzs_mark's (every word of bits is written: no memset), for the positions of [lo, hi] whose two
+// bytes pass the decoder's test of a zlib header; pack is 16-byte aligned and hi + 1 < len.  The counts go through
+// md_launch_gzm_scan32, the bits through md_launch_gzs_compact
+int md_launch_pkb_mark(const uint8_t *pack, uint64_t len, uint64_t lo, uint64_t hi, uint32_t *bits, uint32_t *cnt, hipStream_t stream);
+// in_len[k] = min(end - cpos[k], MD_MAX_INFLATE_IN): the size query's input of candidate k
+int md_launch_pkb_inputs(uint64_t C, const uint64_t *cpos, uint64_t end, uint64_t *in_len, hipStream_t stream);
 
 // ---- sha1_kernels.hip: SHA-1 of many messages (md_sha1_batch_*, MD_PACK_VERIFY_NAME) ----
 int md_launch_sha1(const md::sha::Args *args, hipStream_t stream);

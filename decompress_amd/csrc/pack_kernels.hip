@@ -89,14 +89,14 @@ __global__ void headers_kernel(Table t, const uint8_t *__restrict__ pack) {
     if (e - p < 20) st = MD_INVALID_PACK;
     else {
       const uint8_t *want = pack + p;
-      uint64_t lo = 0, hi = t.n;
+      uint64_t lo = 0, hi = t.n_names;
       bool found = false;
       while (lo < hi && !found) {
         const uint64_t mid = lo + (hi - lo) / 2;
         const uint8_t *nm = t.names + mid * 20;
         int c = 0;
         for (uint32_t k = 0; k < 20 && c == 0; k++) c = (int)nm[k] - (int)want[k];
-        if (c == 0) found = true, base = (uint32_t)mid;
+        if (c == 0) found = true, base = t.name_obj ? t.name_obj[mid] : (uint32_t)mid;
         else if (c < 0) lo = mid + 1;
         else hi = mid;
       }

@@ -1,19 +1,23 @@
 """git packfiles (pack v2 / v3 with an idx v2) through the C ABI's md_pack_* entry points: the idx is read on the host, the
 table of all objects - type, size, base, depth, status - is built once on the GPU, and a read decodes every selected object
-and the bases it hangs off in one inflate launch a round, then applies the deltas level by level."""
+and the bases it hangs off in one inflate launch a round, then applies the deltas level by level.  A pack without an idx
+gets one from the GPU (`build_index`, git index-pack's bytes)."""
 import ctypes
 
 from . import engine as _engine
-from ._lib import PackIndexEntry, PackIndexInfo, PackInfo, PackObject, PackResult, PackStats
+from ._lib import PackBuildResult, PackBuildStats, PackIndexEntry, PackIndexInfo, PackInfo, PackObject, PackResult, PackStats
 from ._lib import load as _load
 
 TYPE_NAMES = {0: None, 1: "commit", 2: "tree", 3: "blob", 4: "tag"}
 VERIFY_CRC = 1
 VERIFY_NAMES = 2
 NO_BASE = (1 << 64) - 1
+BUILD_CHECK_TRAILER = 1
 _INFO_KEYS = ("n", "deltas", "max_depth", "total_size", "failed")
 _OBJECT_KEYS = ("size", "offset", "packed_len", "base", "depth", "type", "status")
 _STATS_KEYS = ("rounds", "inflate_launches", "apply_launches", "objects", "bytes_in", "apply_ns")
+_BUILD_RESULT_KEYS = ("n", "failed", "idx_len", "bad_offset", "bad_status")
+_BUILD_STATS_KEYS = ("candidates", "generations", "rounds", "inflate_launches", "apply_launches", "objects", "bytes_in")
 
 
 def _raw(src):
@@ -66,15 +70,77 @@ def check_trailers(pack, idx):
     return bool(pack_ok.value), bool(idx_ok.value)
 
 
+def write_index(entries, pack_checksum):
+    """md_pack_index_write (host arithmetic, no device needed), the inverse of `index`: entries - dicts with name (20 bytes),
+    offset, crc32, in any order - and the pack's 20-byte checksum -> the idx version 2.  Raises `Error` ("Invalid index")
+    for two entries with one name."""
+    lib, n = _load(), len(entries)
+    ents = (PackIndexEntry * max(n, 1))()
+    for e, d in zip(ents, entries):
+        e.offset, e.crc32 = d["offset"], d["crc32"]
+        e.name[:] = bytes(d["name"])
+    need = ctypes.c_size_t(0)
+    st = lib.md_pack_index_write(ents, n, bytes(pack_checksum), None, 0, ctypes.byref(need))
+    if st != 2:  # (no idx fits 0 bytes: MD_UNEXPECTED_END_OF_OUTPUT says how long it is)
+        raise _engine.Error(lib.md_status_string(st).decode())
+    idx = ctypes.create_string_buffer(need.value)
+    st = lib.md_pack_index_write(ents, n, bytes(pack_checksum), idx, need.value, ctypes.byref(need))
+    if st != 0:
+        raise _engine.Error(lib.md_status_string(st).decode())
+    return idx.raw[:need.value]
+
+
+def build_index_raw(pack, flags=BUILD_CHECK_TRAILER, idx_cap=None, cap=None, device=0):
+    """md_pack_index_build as it is: (return value, the bytes of idx, offsets, statuses, md_pack_build_result as a dict).
+    idx_cap None: room for the idx of as many objects as the pack's header states (bounded by the pack's length: no object
+    has fewer than 9 bytes), and what comes back is the idx alone; a given idx_cap: those bytes, NUL where nothing was
+    written.  cap None: every object."""
+    eng, pack = _engine.default_engine(device), _raw(pack)
+    res = PackBuildResult()
+    count = min(int.from_bytes(pack[8:12], "big"), len(pack) // 8) if len(pack) >= 12 else 0
+    room = 8 + 1024 + 36 * count + 40 if idx_cap is None else idx_cap
+    cap = count if cap is None else cap
+    idx = ctypes.create_string_buffer(max(room, 1))
+    off, status = (ctypes.c_uint64 * max(cap, 1))(), (ctypes.c_int32 * max(cap, 1))()
+    rc = eng.lib.md_pack_index_build(eng.ctx, pack, len(pack), flags, idx if room else None, room, off if cap else None, status if cap else None, cap,
+                                     ctypes.byref(res))
+    k = min(cap, res.n)
+    got = idx.raw[:room] if idx_cap is not None else idx.raw[:res.idx_len] if rc == 0 else b""
+    return rc, got, list(off[:k]), list(status[:k]) if rc != 2 else [], {k: getattr(res, k) for k in _BUILD_RESULT_KEYS}
+
+
+def build_index(pack, check_trailer=True, device=0):
+    """md_pack_index_build: the idx version 2 of a pack that has none - what `git index-pack` writes, byte for byte - with
+    the objects found, decoded, hashed and checksummed on the GPU.  Raises `Error` with the status name and the offset
+    where the pack or one of its objects fails."""
+    rc, idx, _, _, res = build_index_raw(pack, BUILD_CHECK_TRAILER if check_trailer else 0, device=device)
+    if rc != 0:
+        where = "" if res["bad_offset"] == NO_BASE else " at offset %d" % res["bad_offset"]
+        raise _engine.Error(_status_name(rc) + where)
+    return idx[:res["idx_len"]]
+
+
+def build_last(device=0):
+    """md_pack_build_last: candidates, generations, rounds, inflate_launches, apply_launches, objects, bytes_in of the
+    engine's last `build_index`"""
+    eng = _engine.default_engine(device)
+    s = PackBuildStats()
+    eng._check(eng.lib.md_pack_build_last(eng.ctx, ctypes.byref(s)))
+    return {k: getattr(s, k) for k in _BUILD_STATS_KEYS}
+
+
 class Pack:
     """md_pack_open: the table of a pack's objects.  `info`: n, deltas, max_depth, total_size, failed.  `objects`: one dict
     per object in idx order - name, type (1 commit, 2 tree, 3 blob, 4 tag: the chain's root's), size, offset, packed_len,
-    base (an index, or None), depth, status (0 = Ok).  Raises `Error` for a pack or idx the call refuses."""
+    base (an index, or None), depth, status (0 = Ok).  Raises `Error` for a pack or idx the call refuses.  idx None: the pack
+    came without one and `build_index` makes it (`self.idx` keeps its bytes)."""
 
-    def __init__(self, pack, idx, device=0):
+    def __init__(self, pack, idx=None, device=0):
         self._eng = _engine.default_engine(device)
         self._pack = _raw(pack)
-        idx = _raw(idx)
+        self._device = device
+        idx = build_index(self._pack, device=device) if idx is None else _raw(idx)
+        self.idx = idx
         h = ctypes.c_void_p()
         st = self._eng.lib.md_pack_open(self._eng.ctx, self._pack, len(self._pack), idx, len(idx), ctypes.byref(h))
         if st != 0:
@@ -146,6 +212,10 @@ class Pack:
         s = PackStats()
         self._eng._check(self._eng.lib.md_pack_last(self._eng.ctx, ctypes.byref(s)))
         return {k: getattr(s, k) for k in _STATS_KEYS}
+
+    def build_last(self):
+        """md_pack_build_last of this pack's engine"""
+        return build_last(self._device)
 
     def close(self):
         if getattr(self, "_h", None):

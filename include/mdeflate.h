@@ -1113,7 +1113,7 @@ int md_bgzf_read_last(const md_ctx *ctx, md_bgzf_read_stats *stats);
  * is in front of them, *idx_ok the same for the idx (one serial message each: not a shape for the device).  An idx shorter
  * than an empty idx (8 + 1024 + 40 bytes) is MD_INVALID_INDEX, a pack shorter than an empty pack (32) MD_INVALID_PACK, and
  * neither flag is written; NULL pointers are MD_E_INVALID_ARGUMENT.
- * Out of scope: building an idx from a pack alone, writing packs, idx v1, .rev, multi-pack-index, bitmaps, the SHA-256 object
+ * Out of scope: writing packs, idx v1, .rev, multi-pack-index, bitmaps, the SHA-256 object
  * format, SHA-1 collision detection, hashing the trailers on the device, completing a thin pack from another, objects above
  * MD_MAX_STREAM, handing one very long object to the whole-chip decoder. */
 #define MD_PACK_VERIFY_CRC 1u
@@ -1159,6 +1159,81 @@ int md_pack_last(const md_ctx *ctx, md_pack_stats *stats);
 int md_pack_verify(md_ctx *ctx, const md_pack *p, const uint8_t *pack, size_t pack_len, const uint64_t *select, size_t nselect,
                    unsigned flags, int32_t *status, md_pack_result *res);
 int md_pack_check_trailers(const uint8_t *pack, size_t pack_len, const uint8_t *idx, size_t idx_len, int *pack_ok, int *idx_ok);
+
+/* ---- git packs: the idx from the pack alone (index-pack; csrc/pack_build_kernels.hip, csrc/pack_build.hpp) ------------------
+ * A pack that came over the wire (git fetch, a bundle, git pack-objects --stdout) has no idx.  md_pack_index_build writes
+ * the idx version 2 that git index-pack writes for it, byte for byte, so that md_pack_open can follow with no git in between.
+ *
+ * Call-level checks, as md_pack_open's: "PACK" and at least 32 bytes, else MD_INVALID_PACK; version 2 or 3, else
+ * MD_PACK_UNSUPPORTED; a flag other than MD_PACK_BUILD_CHECK_TRAILER is MD_E_INVALID_ARGUMENT.  With that flag the HOST hashes
+ * pack[0, pack_len - 20) (one serial message, under the device's count pass) and compares it with the trailer: a mismatch
+ * is MD_INVALID_CHECKSUM as the call's return value, res->bad_offset = pack_len - 20.  Without it the trailer is copied into
+ * the idx as it is.
+ *
+ * Where the objects begin.  Object k + 1 begins where the zlib stream of object k ends, which only a decoder knows.  So
+ * every position z of [12, pack_len - 20 - 6] whose two bytes pass the decoder's own test of a zlib header
+ * (((cmf << 8) + flg) % 31 == 0 and (cmf & 15) == 8) is a CANDIDATE; they are marked and compacted on the device and ONE
+ * md_inflate_sizes_batch_device launch (MD_FORMAT_ZLIB, in_len = min(pack_len - 20 - z, MD_MAX_INFLATE_IN)) says of every one
+ * what a stream that began there would consume and inflate to.  Candidates are stream starts, not header starts: a size
+ * varint of two or more bytes almost always has a second start one byte in that parses and leads to the same stream.
+ * In compressed bytes about one position in 496 is a candidate (132 of the 65 536 pairs of bytes pass).  The host then walks from byte 12: it parses the header it
+ * stands on (type, size varint, an OFS_DELTA's distance or a REF_DELTA's 20 bytes; the bound is pack_len - 20), finds the
+ * stream's z among the candidates and steps to z + consumed.  A false candidate is never on this chain - the chain is a
+ * function of the pack's bytes - it only costs time.  The walk stops, and the call returns MD_INVALID_PACK with
+ * res->bad_offset = where it stood, when no z can be told (type 0 or 5, a size varint beyond 64 bits, an OFS_DELTA distance
+ * beyond 2^63, a header that passes the end), z is no candidate, z's count did not end MD_OK (res->bad_status has its
+ * status), the chain ends anywhere but on pack_len - 20 (bad_offset = the first byte that is no object's), or it finds
+ * fewer objects than the pack's header states (bad_offset = pack_len - 20).  It goes on past an object whose stream
+ * inflates to another size than its header states and past an OFS_DELTA whose distance is 0, beyond its own offset or to
+ * no object's start: those get statuses of their own below.
+ * After the walk res->n and res->idx_len are known and offsets[0 .. min(cap, n)) are written, in pack order.  An idx_cap
+ * below res->idx_len returns MD_UNEXPECTED_END_OF_OUTPUT before anything further is launched.
+ *
+ * Names, CRCs and bases.  The CRC-32 of every object's packed bytes is one md_crc32 launch.  The names come in GENERATIONS,
+ * as in git index-pack, because a REF_DELTA names its base by the SHA-1 nobody knows yet.  A generation builds md_pack_open's
+ * table from the offsets and the names known so far - a REF_DELTA whose base is not among them is MD_PACK_MISSING_BASE for
+ * now and what hangs off it MD_INVALID_PACK_BASE - and then runs md_pack_verify's rounds ("pack_workspace") over every object
+ * that table calls sound and that has no verdict yet, with the hash pass behind each round's last apply launch.  The pass
+ * writes the name of an object that has none and compares the name of one that has (a base decoded again).  The next
+ * generation looks the pending REF_DELTAs up among the new names.  The loop ends when a generation names nothing or
+ * nothing is pending.  A pack as git writes it to disk has no REF_DELTA and takes ONE generation; every REF link along a
+ * chain costs one more (a fan of REF_DELTAs on one base: 2; a chain of 64 alternating OFS and REF: 33).  That is accepted.
+ * Per object, in this order: MD_INVALID_SIZE (the stream does not inflate to the header's size), MD_INVALID_CHECKSUM (the
+ * Adler-32) and the decoder's own statuses by md_pack_read's rules; MD_INVALID_PACK for the OFS_DELTA faults above;
+ * MD_INVALID_DELTA by the apply kernel's rules; MD_PACK_MISSING_BASE for a REF_DELTA whose base never got a name - a thin
+ * pack, and also a REF_DELTA cycle, which cannot be told from one here - and MD_INVALID_PACK_BASE for what hangs off a failed
+ * object; MD_E_INVALID_ARGUMENT for the size limits (MD_MAX_INFLATE_IN / MD_MAX_STREAM); MD_INVALID_PACK for the later, by
+ * offset, of two objects with one name (git index-pack --strict refuses those, and md_pack_index an idx whose names do not
+ * ascend strictly: no idx is written here that is not read here).
+ * status[0 .. min(cap, n)) is written in pack order (offsets and status may be NULL with cap 0).  If any object failed the
+ * call returns the status of the first failing one in pack order, res->failed counts them, res->bad_offset is that object's
+ * offset and no byte of idx is written.  Otherwise MD_OK and idx[0, res->idx_len).  An empty pack gives the idx of 1 072 bytes.
+ *
+ * md_pack_index_write (HOST, no context) is the inverse of md_pack_index: entries in any order are sorted by name (two equal
+ * names: MD_INVALID_INDEX; more than 2^32 - 1 entries: MD_E_INVALID_ARGUMENT), then magic, version 2, fan-out, names, CRCs,
+ * 31-bit offsets - one above 0x7fffffff escapes into the 64-bit table, in idx order, as git does -, the pack's checksum
+ * and the idx's own SHA-1.  *idx_len = 8 + 1024 + 28 n + 8 m + 40; an idx_cap below it returns MD_UNEXPECTED_END_OF_OUTPUT
+ * with *idx_len set and nothing written.  For any valid idx, writing what md_pack_index read gives the same bytes.
+ *
+ * md_pack_build_last: of the context's last md_pack_index_build the candidates, the generations, and summed over their
+ * reads the rounds, inflate launches, apply launches and objects decoded; bytes of the pack copied in.
+ * Known limit: a crafted pack can make the count pass slow - a stored blob full of nested zlib streams makes every one of
+ * them a candidate that is walked to its end - never wrong.  There is no defence.
+ * Out of scope: completing a thin pack (--fix-thin), .rev, idx v1, SHA-256, objects beyond MD_MAX_INFLATE_IN /
+ * MD_MAX_STREAM, the slow crafted pack. */
+#define MD_PACK_BUILD_CHECK_TRAILER 1u
+typedef struct md_pack_build_result {
+  uint64_t n, failed, idx_len, bad_offset; /* bad_offset: MD_PACK_NO_BASE if none */
+  int32_t bad_status;
+} md_pack_build_result;
+typedef struct md_pack_build_stats {
+  uint64_t candidates, generations, rounds, inflate_launches, apply_launches, objects, bytes_in;
+} md_pack_build_stats;
+int md_pack_index_write(const md_pack_index_entry *entries, size_t n, const uint8_t pack_checksum[20], uint8_t *idx, size_t idx_cap,
+                        size_t *idx_len);
+int md_pack_index_build(md_ctx *ctx, const uint8_t *pack, size_t pack_len, unsigned flags, uint8_t *idx, size_t idx_cap,
+                        uint64_t *offsets, int32_t *status, size_t cap, md_pack_build_result *res);
+int md_pack_build_last(const md_ctx *ctx, md_pack_build_stats *stats);
 
 /* ---- SHA-1 of many buffers: one message a lane, 64 a wavefront (csrc/sha1_kernels.hip) ---------------------------------------
  * SHA-1 is serial inside a message, so one long message is hashed by one lane, at tens of MB/s; the batch is what is fast.

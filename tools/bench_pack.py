@@ -18,7 +18,16 @@ With --names, for DESIGN 4j, further legs on the same pack:
   git verify-pack, git fsck   over the same pack, if git is on the machine
 and with read_names and verify the device time of their hash passes (md_sha1_last's device_ns) and its counts.
 
-    python tools/bench_pack.py [--objects 16384] [--depth 8] [--mib 64] [--reps 7] [--warmup 1] [--names]
+With --build, for DESIGN 4k, the idx from the pack alone:
+  build, build_no_trailer   md_pack_index_build with and without MD_PACK_BUILD_CHECK_TRAILER; the idx is compared with the writer's
+  verify                    what it cannot beat: md_pack_verify with both flags, given the idx (beside open)
+  count                     md_inflate_sizes_batch_host over the same candidates (found here with numpy): the count pass, with
+                            its own copy of the pack to the device
+  trailer_hash, idx_write   md_pack_check_trailers (the host's SHA-1 over the pack and the idx) and md_pack_index_write alone
+  git index-pack            over the same pack, one CPU process, if git is on the machine
+and md_pack_build_last's counts (candidates against n, generations).
+
+    python tools/bench_pack.py [--objects 16384] [--depth 8] [--mib 64] [--reps 7] [--warmup 1] [--names] [--build]
 
 The legs are alternated in one process; every leg reports the median and the spread (min .. max) of its repeats, host to
 host (perf_counter around a call that ends in a synchronise).  read_all's bytes are compared with the writer's."""
@@ -113,6 +122,25 @@ def time_git_checks(pack, idx, reps):
         return out
 
 
+def time_git_index_pack(pack, reps):
+    git = shutil.which("git")
+    if not git:
+        return None
+    env = dict(os.environ, GIT_CONFIG_GLOBAL="/dev/null", GIT_CONFIG_SYSTEM="/dev/null")
+    with tempfile.TemporaryDirectory() as tmp:
+        path = os.path.join(tmp, "x.pack")
+        with open(path, "wb") as f:
+            f.write(pack)
+        times = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            r = subprocess.run([git, "index-pack", "-o", os.path.join(tmp, "x.idx"), path], env=env, cwd=tmp, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+            times.append((time.perf_counter() - t0) * 1e3)
+            assert r.returncode == 0, r.stderr
+        with open(os.path.join(tmp, "x.idx"), "rb") as f:
+            return times, f.read()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--objects", type=int, default=16384)
@@ -121,6 +149,7 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--names", action="store_true")
+    ap.add_argument("--build", action="store_true")
     a = ap.parse_args()
     eng = _engine.default_engine(0)
     lib = eng.lib
@@ -187,6 +216,51 @@ def main():
             hashed["verify"] = eng.sha1_last()
 
         legs.update({"read_names": read_names, "verify": verify})
+    built = {}
+    if a.build:
+        b = np.frombuffer(pack, dtype=np.uint8)
+        hi = len(pack) - 20 - 6
+        cmf, flg = b[12:hi + 1].astype(np.uint32), b[13:hi + 2].astype(np.uint32)
+        cand = (np.nonzero(((cmf & 15) == 8) & (((cmf << 8) + flg) % 31 == 0))[0] + 12).astype(np.uint64)
+        c_len = np.minimum(np.uint64(len(pack) - 20) - cand, np.uint64(0x1ffffff0)).astype(np.uint64)
+        c_out, c_used, c_st = np.zeros(cand.size, dtype=np.uint64), np.zeros(cand.size, dtype=np.uint64), np.zeros(cand.size, dtype=np.int32)
+        idx_buf = np.zeros(len(idx), dtype=np.uint8)
+        b_off, b_st, b_res = np.zeros(n, dtype=np.uint64), np.ones(n, dtype=np.int32), _lib.PackBuildResult()
+
+        def build_with(flags):
+            def run():
+                eng._check(lib.md_pack_index_build(eng.ctx, pack, len(pack), flags, idx_buf.ctypes.data, idx_buf.size, b_off.ctypes.data,
+                                                   b_st.ctypes.data, n, ctypes.byref(b_res)))
+                built["last"] = mp.build_last()
+            return run
+
+        def count():
+            eng._check(lib.md_inflate_sizes_batch_host(eng.ctx, _engine.FORMAT_ZLIB, cand.size, h_in.ctypes.data, h_in.size, cand.ctypes.data,
+                                                       c_len.ctypes.data, c_out.ctypes.data, c_used.ctypes.data, c_st.ctypes.data))
+
+        ents, info = mp.index(idx)
+        c_ents = (_lib.PackIndexEntry * max(n, 1))()
+        for e, d in zip(c_ents, ents):
+            e.offset, e.crc32 = d["offset"], d["crc32"]
+            e.name[:] = d["name"]
+        w_buf, w_len, ok = ctypes.create_string_buffer(len(idx)), ctypes.c_size_t(0), (ctypes.c_int(0), ctypes.c_int(0))
+
+        def idx_write():
+            assert lib.md_pack_index_write(c_ents, n, info["pack_checksum"], w_buf, len(idx), ctypes.byref(w_len)) == 0
+
+        def trailer_hash():
+            assert lib.md_pack_check_trailers(pack, len(pack), idx, len(idx), ctypes.byref(ok[0]), ctypes.byref(ok[1])) == 0
+
+        legs.update({"build": build_with(mp.BUILD_CHECK_TRAILER), "build_no_trailer": build_with(0), "count": count, "idx_write": idx_write,
+                     "trailer_hash": trailer_hash})
+        if not a.names:
+            st_v, res_b = np.ones(n, dtype=np.int32), _lib.PackResult()
+
+            def verify_both():
+                eng._check(lib.md_pack_verify(eng.ctx, p._h, pack, len(pack), None, n, mp.VERIFY_CRC | mp.VERIFY_NAMES, st_v.ctypes.data,
+                                              ctypes.byref(res_b)))
+
+            legs["verify"] = verify_both
     times = {k: [] for k in legs}
     for r in range(a.warmup + a.reps):
         for k, fn in legs.items():
@@ -226,6 +300,20 @@ def main():
             "hashlib_over_verify": round(statistics.median(cpu) / t["verify"]["median_ms"], 1)}
         checks = time_git_checks(pack, idx, min(a.reps, 3))
         res["names"]["git"] = {k: stats(v) for k, v in checks.items()} if checks else "git is not on this machine: no CPU figure"
+    if a.build:
+        assert idx_buf.tobytes() == idx == w_buf.raw and not b_st.any() and ok[0].value and ok[1].value
+        assert c_used.size == cand.size and int((c_st == 0).sum()) >= n
+        t = res["times"]
+        res["build"] = {"last": built["last"], "candidates_over_objects": round(cand.size / n, 3),
+                        "candidates_that_count_ok": int((c_st == 0).sum()),
+                        "build_over_open_plus_verify": round(t["build"]["median_ms"] / (t["open"]["median_ms"] + t["verify"]["median_ms"]), 3)}
+        git = time_git_index_pack(pack, min(a.reps, 3))
+        if git:
+            assert git[1] == idx
+            res["build"]["git_index_pack"] = stats(git[0])
+            res["build"]["git_index_pack_over_build"] = round(statistics.median(git[0]) / t["build"]["median_ms"], 1)
+        else:
+            res["build"]["git_index_pack"] = "git is not on this machine: no CPU figure"
     print(json.dumps(res))
 
 
