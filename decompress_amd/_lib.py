@@ -184,6 +184,11 @@ SYMBOLS = [
     ("md_sha1_batch_device", ctypes.c_int, [c_vp, c_sz, c_vp, c_vp, c_vp, c_vp, ctypes.c_uint64, c_vp]),
     ("md_sha1_batch_host", ctypes.c_int, [c_vp, c_sz, c_vp, c_sz, c_vp, c_vp, c_vp, c_vp]),
     ("md_sha1_last", ctypes.c_int, [c_vp, c_vp]),
+    ("md_pack_delta_batch_device", ctypes.c_int, [c_vp, c_sz, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    ("md_pack_delta_batch_host", ctypes.c_int, [c_vp, c_sz, c_vp, c_vp, c_sz, c_vp, c_sz, c_vp, c_vp]),
+    ("md_pack_write_bound", c_sz, [c_sz, c_vp]),
+    ("md_pack_write", ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_uint, ctypes.c_uint32, c_sz, c_vp, c_vp, c_sz, c_vp, c_sz, c_szp, c_vp, c_vp]),
+    ("md_pack_write_last", ctypes.c_int, [c_vp, c_vp]),
 ]
 
 
@@ -252,6 +257,27 @@ class PackBuildStats(ctypes.Structure):
 class Sha1Stats(ctypes.Structure):
     """md_sha1_stats of include/mdeflate.h"""
     _fields_ = [(k, ctypes.c_uint64) for k in ("messages", "blocks", "launches", "device_ns")]
+
+
+class PackDeltaPair(ctypes.Structure):
+    """md_pack_delta_pair of include/mdeflate.h"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("base_off", "base_len", "tgt_off", "tgt_len", "out_off", "out_cap")]
+
+
+class PackSource(ctypes.Structure):
+    """md_pack_source of include/mdeflate.h"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("off", "len", "base")] + [("type", ctypes.c_uint32)]
+
+
+class PackWriteResult(ctypes.Structure):
+    """md_pack_write_result of include/mdeflate.h"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("n", "deltas", "max_depth")]
+
+
+class PackWriteStats(ctypes.Structure):
+    """md_pack_write_stats of include/mdeflate.h"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("pairs", "kept", "dropped_size", "dropped_depth", "payload_before", "payload_after", "launches",
+                                                "delta_ns")]
 
 
 class ZipEntry(ctypes.Structure):

@@ -136,7 +136,7 @@ md_ctx *md_create(int device, void *hip_stream) {
     ctx->own_stream = true;
   }
   if (hipEventCreate(&ctx->ev0) != hipSuccess || hipEventCreate(&ctx->ev1) != hipSuccess || hipEventCreate(&ctx->sha_ev0) != hipSuccess ||
-      hipEventCreate(&ctx->sha_ev1) != hipSuccess) {
+      hipEventCreate(&ctx->sha_ev1) != hipSuccess || hipEventCreate(&ctx->pkw_ev0) != hipSuccess || hipEventCreate(&ctx->pkw_ev1) != hipSuccess) {
     md_destroy(ctx);
     fail(nullptr, MD_E_HIP, "hipEventCreate");
     return nullptr;
@@ -163,6 +163,8 @@ void md_destroy(md_ctx *ctx) {
   if (ctx->ev1) hipEventDestroy(ctx->ev1);
   if (ctx->sha_ev0) hipEventDestroy(ctx->sha_ev0);
   if (ctx->sha_ev1) hipEventDestroy(ctx->sha_ev1);
+  if (ctx->pkw_ev0) hipEventDestroy(ctx->pkw_ev0);
+  if (ctx->pkw_ev1) hipEventDestroy(ctx->pkw_ev1);
   if (ctx->s_in) hipStreamDestroy(ctx->s_in);
   if (ctx->s_out) hipStreamDestroy(ctx->s_out);
   if (ctx->own_stream && ctx->stream) hipStreamDestroy(ctx->stream);

@@ -150,6 +150,10 @@ enum Scratch {
   // SHA-1 of many messages (md_sha1_batch_*, the names of a round of md_pack_read / md_pack_verify): descriptors, states
   // and digests (the host form's bytes go through kHostIn)
   kShaDesc,
+  // making deltas (md_pack_delta_batch_*): pairs, bases and the host form's results; the bases' tables.  Writing a pack
+  // (md_pack_write): the per-object arrays, the compressed payloads (the objects and behind them the deltas stand in kHostIn,
+  // the pack in kHostOut)
+  kPkwDesc, kPkwTables, kPkwObjs, kPkwSlots,
   kScratchCount
 };
 
@@ -225,6 +229,11 @@ struct md_ctx {
   md_sha1_stats sha1_last = {};
   hipEvent_t sha_ev0 = nullptr, sha_ev1 = nullptr;
   bool sha1_pending = false;
+  // making deltas and writing packs: the counts of the last md_pack_delta_batch_* / md_pack_write (md_pack_write_last) and the two
+  // events around the index and delta launches; the device form of the delta batch reads nothing back (pkw_pending)
+  md_pack_write_stats pack_write_last = {};
+  hipEvent_t pkw_ev0 = nullptr, pkw_ev1 = nullptr;
+  bool pkw_pending = false;
   // one stream written as joined spans: md_set_option "deflate_span_kib" (the span of a call that passes 0) and the counts of
   // the last md_deflate_spans_* call (md_deflate_spans_last)
   size_t span_bytes = md::kSpanDefault;

@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "mdeflate.h"
+#include "pack_write.hpp"
 
 // statuses of the library's own, beside mdeflate.h's MD_* (none of which they equal)
 constexpr int MD_PIECE_AWAIT = 1000;  // a stream in pieces: the matcher waits for input the piece does not hold
@@ -294,6 +295,26 @@ struct Repeat {
 };
 }  // namespace pk
 
+namespace pkw {
+// Making deltas (pack_write_kernels.hip; the definition is mdeflate.h's, its constants pack_write.hpp's).  A base is indexed
+// by its blocks of kBlock bytes: the hash of a block's four little-endian words, x = (x + w) * kHashMul from 0, picks by its
+// top `bits` bits (table_bits) a slot of the base's table of 2^bits words; a slot holds the lowest block index that maps
+// to it, kEmpty where none does.
+// One distinct base of a call: src[off, off + 16 blocks), its table at tables + table_off (in words), first_block = the
+// blocks of the bases in front of it (the index kernel finds a thread's base by it).  Only bases with a block are listed.
+struct Base {
+  uint64_t off, table_off, first_block;
+  uint32_t bits, reserved;
+};
+static_assert(sizeof(Base) == 32, "Base is uploaded as is");
+// One pair: base and target in src, the delta's place in dst, the base's table (bits == 0: the base has no block, no table)
+struct Pair {
+  uint64_t base_off, base_len, tgt_off, tgt_len, out_off, out_cap, table_off;
+  uint32_t bits, reserved;
+};
+static_assert(sizeof(Pair) == 64, "Pair is uploaded as is");
+}  // namespace pkw
+
 namespace sha {
 // SHA-1 of many messages, one a lane (sha1_kernels.hip).  Message m is data[off[m], off[m] + len[m]) with the header of
 // a git object of type[m] in front (1 commit, 2 tree, 3 blob, 4 tag; 0, or type == null: the bytes as they are), len[m] at
@@ -519,6 +540,17 @@ int md_launch_pk_delta_sizes(uint32_t count, const md::pk::Stream *s, const uint
 // one level of a round: one wavefront per delta
 int md_launch_pk_apply(uint32_t count, const md::pk::Delta *d, uint8_t *buf, int32_t *status, hipStream_t stream);
 int md_launch_pk_repeats(uint32_t count, const md::pk::Repeat *r, uint8_t *buf, hipStream_t stream);
+
+// ---- pack_write_kernels.hip: making deltas (md_pack_delta_batch_*) ----
+// one thread per block of the nbases listed bases (`blocks` in all) into tables preset to all ones
+int md_launch_pkw_index(uint32_t nbases, uint64_t blocks, const md::pkw::Base *bases, const uint8_t *src, uint32_t *tables, hipStream_t stream);
+// one wavefront per pair: the delta at dst + out_off, out_len and status (MD_OK, or MD_UNEXPECTED_END_OF_OUTPUT with out_len 0)
+int md_launch_pkw_delta(uint32_t count, const md::pkw::Pair *pairs, const uint8_t *src, const uint32_t *tables, uint8_t *dst, uint64_t *out_len,
+                        int32_t *status, hipStream_t stream);
+// md_pack_write: every object's header bytes (head + kHeaderMax i, head_len[i] of them) and stream (slots + slot_off[i], zlen[i]
+// bytes) to pack + offset[i]
+int md_launch_pkw_assemble(uint32_t n, const uint64_t *offset, const uint8_t *head, const uint8_t *head_len, const uint8_t *slots,
+                           const uint64_t *slot_off, const uint64_t *zlen, uint8_t *pack, hipStream_t stream);
 
 // ---- pack_build_kernels.hip: the candidates of md_pack_index_build ----
 // bits / cnt as md_launch_gzs_mark's (every word of bits is written: no memset), for the positions of [lo, hi] whose two

@@ -253,6 +253,46 @@ class Engine:
         self._check(self.lib.md_sha1_last(self.ctx, ctypes.byref(s)))
         return {k: getattr(s, k) for k in ("messages", "blocks", "launches", "device_ns")}
 
+    def pack_deltas(self, src, pairs, caps=None):
+        """md_pack_delta_batch_host: the deltas of pairs = [(base_off, base_len, tgt_off, tgt_len)] into the bytes `src` ->
+        [(status, delta bytes)], status 0 = Ok, 2 = the delta passed its room (then no bytes).  caps[i]: the room of delta i;
+        default tgt_len + tgt_len // 127 + 16, which always suffices (nothing but inserts).  Synchronous."""
+        n = len(pairs)
+        src = bytes(src)
+        if caps is None:
+            caps = [p[3] + p[3] // 127 + 16 for p in pairs]
+        if len(caps) != n:
+            raise Error("Invalid argument: one room per pair")
+        rows, at = (_lib.PackDeltaPair * max(n, 1))(), 0
+        for r, p, cap in zip(rows, pairs, caps):
+            r.base_off, r.base_len, r.tgt_off, r.tgt_len = (int(v) for v in p)
+            r.out_off, r.out_cap = at, int(cap)
+            at += (int(cap) + 15) & ~15
+        out = ctypes.create_string_buffer(max(at, 1))
+        out_len, status = (ctypes.c_uint64 * max(n, 1))(), (ctypes.c_int32 * max(n, 1))()
+        self._check(self.lib.md_pack_delta_batch_host(self.ctx, n, rows, src, len(src), out, at, out_len, status))
+        raw = out.raw
+        return [(status[i], raw[rows[i].out_off:rows[i].out_off + out_len[i]]) for i in range(n)]
+
+    def pack_deltas_device(self, pairs, d_src, d_out):
+        """md_pack_delta_batch_device: pairs = [(base_off, base_len, tgt_off, tgt_len, out_off, out_cap)] (host) into the device
+        tensors d_src / d_out -> (out_len int64 tensor, status int32 tensor), device, async"""
+        n = len(pairs)
+        rows = (_lib.PackDeltaPair * max(n, 1))()
+        for r, p in zip(rows, pairs):
+            r.base_off, r.base_len, r.tgt_off, r.tgt_len, r.out_off, r.out_cap = (int(v) for v in p)
+        out_len = self.torch.zeros(max(n, 1), dtype=self.torch.int64, device=self.device)
+        status = self.torch.zeros(max(n, 1), dtype=self.torch.int32, device=self.device)
+        self._check(self.lib.md_pack_delta_batch_device(self.ctx, n, rows, _ptr(d_src), _ptr(d_out), _ptr(out_len), _ptr(status)))
+        return out_len[:n], status[:n]
+
+    def pack_write_last(self):
+        """md_pack_write_last: pairs, kept, dropped_size, dropped_depth, payload_before, payload_after, launches, delta_ns of the
+        last pack written or delta batch made"""
+        s = _lib.PackWriteStats()
+        self._check(self.lib.md_pack_write_last(self.ctx, ctypes.byref(s)))
+        return {k: getattr(s, k) for k, _ in _lib.PackWriteStats._fields_}
+
     def set_option(self, key, value):
         self._check(self.lib.md_set_option(self.ctx, key.encode(), int(value)))
         if key == "deflate_span_prime":  # (the library has no query: `deflate_spans(prime=)` puts this back)

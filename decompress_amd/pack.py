@@ -1,11 +1,13 @@
 """git packfiles (pack v2 / v3 with an idx v2) through the C ABI's md_pack_* entry points: the idx is read on the host, the
 table of all objects - type, size, base, depth, status - is built once on the GPU, and a read decodes every selected object
 and the bases it hangs off in one inflate launch a round, then applies the deltas level by level.  A pack without an idx
-gets one from the GPU (`build_index`, git index-pack's bytes)."""
+gets one from the GPU (`build_index`, git index-pack's bytes).  `write` makes a pack and its idx from objects and the
+bases the caller chooses, the deltas made by a batched kernel (`make_deltas` is that kernel alone)."""
 import ctypes
 
 from . import engine as _engine
 from ._lib import PackBuildResult, PackBuildStats, PackIndexEntry, PackIndexInfo, PackInfo, PackObject, PackResult, PackStats
+from ._lib import PackSource, PackWriteResult
 from ._lib import load as _load
 
 TYPE_NAMES = {0: None, 1: "commit", 2: "tree", 3: "blob", 4: "tag"}
@@ -13,6 +15,8 @@ VERIFY_CRC = 1
 VERIFY_NAMES = 2
 NO_BASE = (1 << 64) - 1
 BUILD_CHECK_TRAILER = 1
+WRITE_NO_DELTA = 1
+_WRITE_RESULT_KEYS = ("n", "deltas", "max_depth")
 _INFO_KEYS = ("n", "deltas", "max_depth", "total_size", "failed")
 _OBJECT_KEYS = ("size", "offset", "packed_len", "base", "depth", "type", "status")
 _STATS_KEYS = ("rounds", "inflate_launches", "apply_launches", "objects", "bytes_in", "apply_ns")
@@ -127,6 +131,62 @@ def build_last(device=0):
     s = PackBuildStats()
     eng._check(eng.lib.md_pack_build_last(eng.ctx, ctypes.byref(s)))
     return {k: getattr(s, k) for k in _BUILD_STATS_KEYS}
+
+
+def make_deltas(pairs, device=0):
+    """md_pack_delta_batch_host for pairs = [(base bytes, target bytes)] -> [delta bytes]: the deltas of mdeflate.h's
+    definition, made on the GPU, one wavefront a pair; any reader of git's delta format applies them.  A base object shared
+    by several pairs (the same bytes object) is laid out and indexed once."""
+    blob, place, rows = bytearray(), {}, []
+    for base, target in pairs:
+        for b in (base, target):
+            if id(b) not in place:
+                place[id(b)] = len(blob)
+                blob += bytes(b)
+        rows.append((place[id(base)], len(base), place[id(target)], len(target)))
+    got = _engine.default_engine(device).pack_deltas(bytes(blob), rows)
+    for st, _ in got:
+        if st != 0:
+            raise _engine.Error(_status_name(st))
+    return [d for _, d in got]
+
+
+def write_raw(objects, bases=None, level=6, max_depth=50, flags=0, pack_cap=None, device=0):
+    """md_pack_write as it is: objects = [(type, bytes)] -> (return value, pack bytes, pack_len, entries as dicts,
+    md_pack_write_result as a dict).  pack_cap None: md_pack_write_bound's."""
+    eng, n = _engine.default_engine(device), len(objects)
+    by_name = {v: k for k, v in TYPE_NAMES.items() if v}
+    src = (PackSource * max(n, 1))()
+    blob, at = b"".join(bytes(b) for _, b in objects), 0
+    for i, (s, (t, b)) in enumerate(zip(src, objects)):
+        s.off, s.len, s.type = at, len(b), by_name[t] if isinstance(t, str) else int(t)
+        s.base = NO_BASE if bases is None or bases[i] is None else int(bases[i])
+        at += len(b)
+    cap = int(eng.lib.md_pack_write_bound(n, src)) if pack_cap is None else pack_cap
+    out = ctypes.create_string_buffer(max(cap, 1))
+    ents, need, res = (PackIndexEntry * max(n, 1))(), ctypes.c_size_t(0), PackWriteResult()
+    rc = eng.lib.md_pack_write(eng.ctx, level, flags, max_depth, n, src, blob, len(blob), out if cap else None, cap, ctypes.byref(need), ents,
+                               ctypes.byref(res))
+    entries = [{"name": bytes(e.name), "offset": e.offset, "crc32": e.crc32} for e in ents[:n]] if rc == 0 else []
+    return rc, out.raw[:need.value] if rc == 0 else b"", need.value, entries, {k: getattr(res, k) for k in _WRITE_RESULT_KEYS}
+
+
+def write(objects, bases=None, level=6, max_depth=50, deltas=True, device=0):
+    """md_pack_write and md_pack_index_write: objects = [(type, bytes)] in pack order, type 1 commit, 2 tree, 3 blob, 4 tag (or
+    those words); bases[i] = the index of an EARLIER object of the same type whose content object i may be a delta against,
+    or None -> (pack, idx): a pack version 2 with OFS_DELTAs and its idx version 2.  Names, deltas, zlib streams and CRCs are
+    the GPU's.  max_depth 0: no limit; deltas False: every object whole.  Raises `Error` ("Invalid index") for two objects
+    with one name, and for what the call refuses."""
+    rc, pack, _, entries, _ = write_raw(objects, bases, level, max_depth, 0 if deltas else WRITE_NO_DELTA, device=device)
+    if rc != 0:
+        _engine.default_engine(device)._check(rc)
+    return pack, write_index(entries, pack[-20:])
+
+
+def write_last(device=0):
+    """md_pack_write_last: pairs, kept, dropped_size, dropped_depth, payload_before, payload_after, launches, delta_ns of the
+    engine's last `write` or `make_deltas`"""
+    return _engine.default_engine(device).pack_write_last()
 
 
 class Pack:

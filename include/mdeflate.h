@@ -1113,7 +1113,7 @@ int md_bgzf_read_last(const md_ctx *ctx, md_bgzf_read_stats *stats);
  * is in front of them, *idx_ok the same for the idx (one serial message each: not a shape for the device).  An idx shorter
  * than an empty idx (8 + 1024 + 40 bytes) is MD_INVALID_INDEX, a pack shorter than an empty pack (32) MD_INVALID_PACK, and
  * neither flag is written; NULL pointers are MD_E_INVALID_ARGUMENT.
- * Out of scope: writing packs, idx v1, .rev, multi-pack-index, bitmaps, the SHA-256 object
+ * Out of scope (writing packs: md_pack_write below): idx v1, .rev, multi-pack-index, bitmaps, the SHA-256 object
  * format, SHA-1 collision detection, hashing the trailers on the device, completing a thin pack from another, objects above
  * MD_MAX_STREAM, handing one very long object to the whole-chip decoder. */
 #define MD_PACK_VERIFY_CRC 1u
@@ -1268,6 +1268,92 @@ int md_sha1_batch_device(md_ctx *ctx, size_t n, const uint8_t *d_data, const uin
 int md_sha1_batch_host(md_ctx *ctx, size_t n, const uint8_t *data, size_t data_len, const uint64_t *off, const uint64_t *len,
                        const uint8_t *type, uint8_t *digest);
 int md_sha1_last(const md_ctx *ctx, md_sha1_stats *stats);
+
+/* ---- git packs: writing one, the deltas made by a batched kernel (csrc/pack_write_kernels.hip, csrc/pack_write.hpp) ----------
+ * THE DELTA of a target T (nt bytes) against a base B (nb bytes) is defined here byte for byte.  The bytes are this
+ * library's own, not git diff-delta's; every reader of git's delta format applies them (md_pack_read's apply step among them).
+ * They are a pure function of B and T.
+ *  Index of the base.  Block j is B[16 j, 16 j + 16) for j < nb / 16 (integer division).  Its hash: the four little-endian
+ *   32-bit words w0 .. w3 of the block, x = 0, then x = (x + w) * 0x9E3779B1 mod 2^32 for each word in turn.  k is the smallest
+ *   integer >= 10 with 2^k >= 2 * (nb / 16); slot = x >> (32 - k).  A slot holds the LOWEST block index that maps to it; a
+ *   block that loses its slot is never found: that costs size, never correctness.
+ *  Parse, greedy.  lit is the end of the previous copy, 0 at the start.  (1) Find the smallest p >= lit with p + 16 <= nt
+ *   whose slot holds a block j with B[16 j, 16 j + 16) == T[p, p + 16).  (2) Forward: L = 16 + the common prefix of
+ *   B[16 j + 16 ..) and T[p + 16 ..).  (3) Backward: e = the largest value with e <= p - lit, e <= 16 j and the e bytes in
+ *   front of both places equal.  (4) T[lit, p - e) goes out as inserts, then a copy of (16 j - e, L + e); lit = p + L.
+ *   (5) Behind the last match T[lit, nt) goes out as inserts.
+ *  Encoding.  varint(nb) varint(nt) (7 bits a byte, least significant first), then the ops.  An insert has 1 .. 127 bytes: a
+ *   run is cut into 127s with the rest last.  A copy longer than 0x10000 is cut into 0x10000s with the rest last.  A copy op
+ *   is 0x80 | mask and only the NON-ZERO bytes of its 32-bit offset (mask bits 0 - 3) and 16-bit size (bits 4, 5); a size
+ *   of exactly 0x10000 has no size byte (pack version 2 has no third size byte, bit 6 is never set).
+ *
+ * md_pack_delta_batch_device makes n deltas in one launch (two with the index), asynchronously on the context's stream.
+ * `pairs` is a HOST array - the host sizes the bases' tables from the lengths and finds the DISTINCT bases: a base that
+ * several targets share (same base_off and base_len) is indexed once -; d_src, d_out, d_out_len and d_status are device
+ * pointers.  Pair i: base = d_src[base_off, base_off + base_len), target = d_src[tgt_off, tgt_off + tgt_len), at any byte
+ * address, overlapping or not; the delta goes to d_out[out_off, out_off + out_cap).  status[i] = MD_OK and out_len[i] = its
+ * length, or, as soon as an op would pass out_cap, MD_UNEXPECTED_END_OF_OUTPUT and out_len[i] = 0 (the bytes of the room
+ * are then unspecified; nothing outside it is written).  Pairs are independent.  The caller's duties, which the host cannot
+ * check: the ranges lie in d_src and d_out, the rooms do not overlap.  md_pack_delta_batch_host (host pointers; copy in,
+ * kernels, copy out, synchronise) checks every range against src_len and out_bytes; it writes out[0, max(out_off + out_cap))
+ * as a whole, so what lies between the rooms is unspecified too.
+ * MD_E_INVALID_ARGUMENT: a NULL pointer, n above 2^31 - 16, base_len or tgt_len above MD_MAX_STREAM, a range that overflows
+ * (host form: that leaves its buffer).  n == 0 is MD_OK and launches nothing.  The tables take 4 * 2^k bytes a distinct base
+ * - between half the base's size and its size, 4 KiB at the least - in one workspace; one that cannot be allocated is
+ * MD_E_OUT_OF_MEMORY: this first version has no rounds.
+ * Known limit: one wavefront makes one delta, so one very large target is slow (it scans 64 positions a step); many pairs
+ * are what is fast.
+ *
+ * md_pack_write writes the pack (version 2, OFS_DELTA only) of n objects in INPUT order.  Object i is src[off, off + len)
+ * of type 1 .. 4; base is an EARLIER index whose content its delta may be made against, or MD_PACK_NO_BASE.  The caller
+ * chooses the bases; searching for them (git's window) is out of scope.  MD_E_INVALID_ARGUMENT as the call's return value:
+ * NULL pointers, base >= i, a base of another type, a type outside 1 .. 4, len > MD_MAX_STREAM, an object beyond src_len, an
+ * unknown flag, a level outside 0 .. 9, n above 2^31 - 16.  Steps: copy in; the names of all objects by one
+ * md_sha1_batch_device; the deltas - tried iff a base is given, len >= 64 and the base's len >= 16, with out_cap = len / 2 - 20 -
+ * always against the base's CONTENT, so all pairs are independent and go in one launch; the delta lengths are read back and
+ * the host decides in index order: a delta is KEPT iff it fitted and its chain of kept deltas stays within max_depth (0: no
+ * limit); an object whose delta is dropped is written whole and counts as depth 0 for what hangs off it.  Then ONE
+ * md_deflate_batch_device (MD_FORMAT_ZLIB, the parameters md_zip_compress derives from `level`) over all payloads - a kept
+ * delta's payload is the delta, otherwise the content -, the lengths are read back, the host walks offsets and headers
+ * (an OFS_DELTA's distance varint depends on the offsets in front of it), a kernel places every header and stream, one
+ * CRC-32 launch runs over the packed objects, the pack is copied out and the HOST hashes the trailer (one serial message, as
+ * in md_pack_check_trailers).  MD_PACK_WRITE_NO_DELTA in flags ignores the bases.
+ * entries[i] = {offset, crc32, name} in input order, ready for md_pack_index_write - which is the call that reports two
+ * objects with one name (MD_INVALID_INDEX); md_pack_write writes both.  res: objects, deltas kept, the pack's deepest chain.
+ * n == 0 gives the empty pack of 32 bytes.  A pack_cap below the pack's length returns MD_UNEXPECTED_END_OF_OUTPUT with
+ * *pack_len = the need; nothing valid is promised in pack or entries.  md_pack_write_bound: room that always suffices (host
+ * arithmetic: 32 + the sum of 16 + len + len / 8 + 256; 0 for NULL objs with n != 0 or a len above MD_MAX_STREAM; len + len / 8
+ * + 256 is also the room every payload's stream gets on the device, and one that passed it would fail the call).  Workspace
+ * that cannot be allocated is MD_E_OUT_OF_MEMORY: no rounds in this first version, everything of the call is resident at once.
+ * md_pack_write_last: of the context's last md_pack_write or md_pack_delta_batch_* the pairs tried, the deltas kept, dropped by
+ * size and dropped by depth, the bytes of payload before the deltas (the contents) and after (what went to the encoder), the
+ * kernel launches of the call's own steps (index, delta, assembly, CRC; not those inside the SHA-1 and deflate batches) and
+ * the device time of the index and delta launches (two events around them).  After the delta batch alone only pairs,
+ * launches and delta_ns are set; after its device form the call waits for the second event.
+ * Out of scope: choosing bases, REF_DELTA and thin packs, .rev and bitmaps, SHA-256, reusing an existing pack's deltas. */
+#define MD_PACK_WRITE_NO_DELTA 1u
+typedef struct md_pack_delta_pair {
+  uint64_t base_off, base_len, tgt_off, tgt_len, out_off, out_cap;
+} md_pack_delta_pair;
+typedef struct md_pack_source {
+  uint64_t off, len, base; /* base: an earlier index, or MD_PACK_NO_BASE */
+  uint32_t type;           /* 1 commit, 2 tree, 3 blob, 4 tag */
+} md_pack_source;
+typedef struct md_pack_write_result {
+  uint64_t n, deltas, max_depth;
+} md_pack_write_result;
+typedef struct md_pack_write_stats {
+  uint64_t pairs, kept, dropped_size, dropped_depth, payload_before, payload_after, launches, delta_ns;
+} md_pack_write_stats;
+int md_pack_delta_batch_device(md_ctx *ctx, size_t n, const md_pack_delta_pair *pairs, const uint8_t *d_src, uint8_t *d_out,
+                               uint64_t *d_out_len, int32_t *d_status);
+int md_pack_delta_batch_host(md_ctx *ctx, size_t n, const md_pack_delta_pair *pairs, const uint8_t *src, size_t src_len, uint8_t *out,
+                             size_t out_bytes, uint64_t *out_len, int32_t *status);
+size_t md_pack_write_bound(size_t n, const md_pack_source *objs);
+int md_pack_write(md_ctx *ctx, int level, unsigned flags, uint32_t max_depth, size_t n, const md_pack_source *objs, const uint8_t *src,
+                  size_t src_len, uint8_t *pack, size_t pack_cap, size_t *pack_len, md_pack_index_entry *entries,
+                  md_pack_write_result *res);
+int md_pack_write_last(const md_ctx *ctx, md_pack_write_stats *stats);
 
 #ifdef __cplusplus
 }

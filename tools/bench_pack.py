@@ -27,7 +27,16 @@ With --build, for DESIGN 4k, the idx from the pack alone:
   git index-pack            over the same pack, one CPU process, if git is on the machine
 and md_pack_build_last's counts (candidates against n, generations).
 
-    python tools/bench_pack.py [--objects 16384] [--depth 8] [--mib 64] [--reps 7] [--warmup 1] [--names] [--build]
+With --write, for DESIGN 4l, instead of the read legs: the same objects written as a pack again, the chains as bases:
+  write               md_pack_write (level 6, max_depth 50) with every version's predecessor as its base
+  write_no_delta      the same with MD_PACK_WRITE_NO_DELTA
+  deflate_batch_host  md_deflate_batch_host over the same objects: what a caller could do before - payloads, not a pack
+  git pack-objects    --window=10 --depth=50 on this machine's CPU from a scratch repository filled by git unpack-objects, if git
+                      is on the machine; a yardstick of another shape: it also searches the bases
+and the three packs' sizes, md_pack_write_last's counts and the device time of the index and delta launches.  Both written
+packs are read back by md_pack_index_build and md_pack_read with both checks and compared with the objects.
+
+    python tools/bench_pack.py [--objects 16384] [--depth 8] [--mib 64] [--reps 7] [--warmup 1] [--names] [--build] [--write]
 
 The legs are alternated in one process; every leg reports the median and the spread (min .. max) of its repeats, host to
 host (perf_counter around a call that ends in a synchronise).  read_all's bytes are compared with the writer's."""
@@ -141,6 +150,91 @@ def time_git_index_pack(pack, reps):
             return times, f.read()
 
 
+def time_git_pack_objects(pack, reps):
+    """git pack-objects --window=10 --depth=50 over the objects of `pack`, from a scratch repository filled by git
+    unpack-objects -> (times, the pack's length) or None"""
+    git = shutil.which("git")
+    if not git:
+        return None
+    env = dict(os.environ, GIT_CONFIG_GLOBAL="/dev/null", GIT_CONFIG_SYSTEM="/dev/null")
+    with tempfile.TemporaryDirectory() as tmp:
+        repo = os.path.join(tmp, "r.git")
+        subprocess.run([git, "init", "-q", "--bare", repo], check=True, env=env, capture_output=True)
+        subprocess.run([git, "-C", repo, "unpack-objects", "-q"], input=pack, check=True, env=env, capture_output=True)
+        names = subprocess.run([git, "-C", repo, "cat-file", "--batch-all-objects", "--batch-check=%(objectname)"], check=True, env=env,
+                               capture_output=True).stdout
+        times, size = [], 0
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            r = subprocess.run([git, "-C", repo, "pack-objects", "--window=10", "--depth=50", "--stdout", "-q"], input=names, env=env,
+                               stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+            times.append((time.perf_counter() - t0) * 1e3)
+            assert r.returncode == 0, r.stderr
+            size = len(r.stdout)
+        return times, size
+
+
+def write_mode(a, eng, entries, layout):
+    """--write, for DESIGN 4l: the objects of the read benchmark's pack written again on the device, the chains as bases"""
+    lib, n = eng.lib, len(layout)
+    blob = np.frombuffer(b"".join(lay["data"] for lay in layout), dtype=np.uint8)
+    lens = np.array([len(lay["data"]) for lay in layout], dtype=np.uint64)
+    offs = np.concatenate(([0], np.cumsum(lens)[:-1])).astype(np.uint64)
+    src = (_lib.PackSource * n)()
+    for s, e, o, ln in zip(src, entries, offs, lens):
+        s.off, s.len, s.type, s.base = int(o), int(ln), 3, mp.NO_BASE if e.get("base") is None else e["base"]
+    bound = int(lib.md_pack_write_bound(n, src))
+    out = np.empty(bound, dtype=np.uint8)
+    ents, need, res = (_lib.PackIndexEntry * n)(), ctypes.c_size_t(0), _lib.PackWriteResult()
+    made, last = {}, {}
+
+    def write_with(name, flags):
+        def run():
+            eng._check(lib.md_pack_write(eng.ctx, 6, flags, 50, n, src, blob.ctypes.data, blob.size, out.ctypes.data, out.size, ctypes.byref(need), ents,
+                                         ctypes.byref(res)))
+            last[name] = mp.write_last()
+            if name not in made:
+                made[name] = (out[:need.value].tobytes(), [{"name": bytes(e.name), "offset": e.offset, "crc32": e.crc32} for e in ents], res.deltas)
+        return run
+
+    caps = np.array([int(lib.md_zl_def_ns_compress_bound(int(ln))) + 64 + int(ln) // 8 for ln in lens], dtype=np.uint64)
+    z_off = np.concatenate(([0], np.cumsum(caps)[:-1])).astype(np.uint64)
+    z_out = np.empty(int(caps.sum()) + 1, dtype=np.uint8)
+    z = {}
+
+    def payloads():
+        z["len"], z["status"], _ = eng.deflate_batch_host(_engine.FORMAT_ZLIB, blob, offs, lens, z_out, z_off, caps, level=6)
+
+    legs = {"write": write_with("write", 0), "write_no_delta": write_with("write_no_delta", mp.WRITE_NO_DELTA), "deflate_batch_host": payloads}
+    times = {k: [] for k in legs}
+    for r in range(a.warmup + a.reps):
+        for k, fn in legs.items():
+            t0 = time.perf_counter()
+            fn()
+            if r >= a.warmup:
+                times[k].append((time.perf_counter() - t0) * 1e3)
+    assert not z["status"].any()
+    sizes = {}
+    for name, (pack, entries_out, deltas) in made.items():  # what was written is a pack: the library's own reader takes it back
+        idx = mp.write_index(entries_out, pack[-20:])
+        assert mp.build_index(pack) == idx
+        p = mp.Pack(pack, idx)
+        got = p.read(verify_crc=True, verify_names=True)
+        where = {e["name"]: i for i, e in enumerate(mp.index(idx)[0])}
+        assert all(got[where[lay["name"]]] == ("Ok", (3, lay["data"])) for lay in layout), name
+        sizes[name] = {"pack_bytes": len(pack), "deltas": int(deltas), "max_depth": p.info["max_depth"]}
+        p.close()
+    out_res = {"mode": "write", "objects": n, "depth": a.depth, "object_bytes": int(lens[0]), "total_size": int(lens.sum()), "level": 6, "reps": a.reps,
+               "warmup": a.warmup, "times": {k: stats(v) for k, v in times.items()}, "packs": sizes, "payloads_bytes": int(z["len"].sum()), "last": last,
+               "delta_launches_device_ms": round(last["write"]["delta_ns"] / 1e6, 4)}
+    git = time_git_pack_objects(made["write"][0], min(a.reps, 3))
+    if git:
+        out_res["git_pack_objects"] = dict(stats(git[0]), pack_bytes=git[1])
+    else:
+        out_res["git_pack_objects"] = "git is not on this machine: this leg was not run"
+    print(json.dumps(out_res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--objects", type=int, default=16384)
@@ -150,11 +244,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--names", action="store_true")
     ap.add_argument("--build", action="store_true")
+    ap.add_argument("--write", action="store_true")
     a = ap.parse_args()
     eng = _engine.default_engine(0)
     lib = eng.lib
     size = max(64, (a.mib << 20) // a.objects)
-    pack, idx, layout = pw.write_pack(version_chains(a.objects, a.depth, size))
+    entries = version_chains(a.objects, a.depth, size)
+    pack, idx, layout = pw.write_pack(entries)
+    if a.write:
+        return write_mode(a, eng, entries, layout)
     order = pw.idx_order(layout)
     p = mp.Pack(pack, idx)
     n = p.info["n"]
