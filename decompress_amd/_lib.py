@@ -189,6 +189,12 @@ SYMBOLS = [
     ("md_pack_write_bound", c_sz, [c_sz, c_vp]),
     ("md_pack_write", ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_uint, ctypes.c_uint32, c_sz, c_vp, c_vp, c_sz, c_vp, c_sz, c_szp, c_vp, c_vp]),
     ("md_pack_write_last", ctypes.c_int, [c_vp, c_vp]),
+    ("md_pack_sketch_device", ctypes.c_int, [c_vp, c_sz, c_vp, c_vp, c_vp, c_vp]),
+    ("md_pack_sketch_host", ctypes.c_int, [c_vp, c_sz, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    ("md_pack_delta_sizes_device", ctypes.c_int, [c_vp, c_sz, c_vp, c_vp, c_vp, c_vp]),
+    ("md_pack_delta_sizes_host", ctypes.c_int, [c_vp, c_sz, c_vp, c_vp, c_sz, c_vp, c_vp]),
+    ("md_pack_choose_bases", ctypes.c_int, [c_vp, ctypes.c_uint32, ctypes.c_uint32, c_sz, c_vp, c_vp, c_sz, c_vp, c_vp]),
+    ("md_pack_search_last", ctypes.c_int, [c_vp, c_vp]),
 ]
 
 
@@ -272,6 +278,11 @@ class PackSource(ctypes.Structure):
 class PackWriteResult(ctypes.Structure):
     """md_pack_write_result of include/mdeflate.h"""
     _fields_ = [(k, ctypes.c_uint64) for k in ("n", "deltas", "max_depth")]
+
+
+class PackSearchStats(ctypes.Structure):
+    """md_pack_search_stats of include/mdeflate.h"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("featured", "pairs", "fitted", "chosen", "launches", "sketch_ns", "score_ns", "host_ns")]
 
 
 class PackWriteStats(ctypes.Structure):

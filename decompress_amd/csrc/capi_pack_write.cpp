@@ -13,15 +13,6 @@
 #include "pack_write.hpp"
 #include "sha1_host.hpp"
 
-namespace {
-
-// the pairs as the kernels take them, the distinct bases that have a block, and what their tables need
-struct DeltaPlan {
-  std::vector<md::pkw::Pair> pairs;
-  std::vector<md::pkw::Base> bases;
-  uint64_t blocks = 0, table_words = 0;
-};
-
 void plan_deltas(size_t n, const md_pack_delta_pair *in, DeltaPlan *plan) {
   plan->pairs.resize(n);
   std::vector<uint32_t> by_base(n);
@@ -48,11 +39,8 @@ void plan_deltas(size_t n, const md_pack_delta_pair *in, DeltaPlan *plan) {
   }
 }
 
-// the index launch and the delta launch between the context's two events, on its stream; `extra` carves what the caller
-// wants from kPkwDesc beside the rows.  Nothing is read back.
-template <class Extra>
-int enqueue_deltas(md_ctx *ctx, const DeltaPlan &plan, const uint8_t *d_src, uint8_t *d_out, uint64_t **d_out_len, int32_t **d_status, Extra extra,
-                   md_pack_write_stats *stats) {
+int enqueue_delta_plan(md_ctx *ctx, const DeltaPlan &plan, const uint8_t *d_src, const std::function<void(md::Carver &)> &extra, const DeltaRun &run,
+                       uint64_t *launches) {
   const size_t n = plan.pairs.size();
   hipStream_t st = ctx->stream;
   md::pkw::Pair *d_pairs = nullptr;
@@ -70,23 +58,21 @@ int enqueue_deltas(md_ctx *ctx, const DeltaPlan &plan, const uint8_t *d_src, uin
   HIP_TRY(ctx, hipEventRecord(ctx->pkw_ev0, st));
   if (plan.blocks) {
     MD_LAUNCH_TRY(ctx, md_launch_pkw_index((uint32_t)plan.bases.size(), plan.blocks, d_bases, d_src, tables, st));
-    stats->launches++;
+    ++*launches;
   }
-  MD_LAUNCH_TRY(ctx, md_launch_pkw_delta((uint32_t)n, d_pairs, d_src, tables, d_out, *d_out_len, *d_status, st));
-  stats->launches++;
+  MD_LAUNCH_TRY(ctx, run(d_pairs, tables));
+  ++*launches;
   HIP_TRY(ctx, hipEventRecord(ctx->pkw_ev1, st));
-  stats->pairs = n;
   return MD_OK;
 }
 
-// the time between the two events, behind a synchronise (an event that cannot be read leaves 0)
-uint64_t event_ns(md_ctx *ctx) {
+uint64_t pkw_event_ns(md_ctx *ctx) {
   float ms = 0;
   if (hipEventElapsedTime(&ms, ctx->pkw_ev0, ctx->pkw_ev1) != hipSuccess) ms = 0, (void)hipGetLastError();
   return (uint64_t)((double)ms * 1e6);
 }
 
-int check_pairs(md_ctx *ctx, size_t n, const md_pack_delta_pair *pairs, bool host, size_t src_len, size_t out_bytes) {
+int check_delta_pairs(md_ctx *ctx, size_t n, const md_pack_delta_pair *pairs, bool host, size_t src_len, size_t out_bytes) {
   if (n > 0x7ffffff0ull) return fail(ctx, MD_E_INVALID_ARGUMENT, "too many pairs in one call");
   for (size_t i = 0; i < n; i++) {
     const md_pack_delta_pair &p = pairs[i];
@@ -96,6 +82,22 @@ int check_pairs(md_ctx *ctx, size_t n, const md_pack_delta_pair *pairs, bool hos
     if (host && (p.base_off + p.base_len > src_len || p.tgt_off + p.tgt_len > src_len || p.out_off + p.out_cap > out_bytes))
       return fail(ctx, MD_E_INVALID_ARGUMENT, "a pair beyond its buffer");
   }
+  return MD_OK;
+}
+
+namespace {
+
+// the index launch and the delta launch between the context's two events, on its stream; `extra` carves what the caller
+// wants from kPkwDesc beside the rows.  Nothing is read back.
+template <class Extra>
+int enqueue_deltas(md_ctx *ctx, const DeltaPlan &plan, const uint8_t *d_src, uint8_t *d_out, uint64_t **d_out_len, int32_t **d_status, Extra extra,
+                   md_pack_write_stats *stats) {
+  hipStream_t st = ctx->stream;
+  const int rc = enqueue_delta_plan(ctx, plan, d_src, extra, [&](const md::pkw::Pair *d_pairs, const uint32_t *tables) {
+    return md_launch_pkw_delta((uint32_t)plan.pairs.size(), d_pairs, d_src, tables, d_out, *d_out_len, *d_status, st);
+  }, &stats->launches);
+  if (rc != MD_OK) return rc;
+  stats->pairs = plan.pairs.size();
   return MD_OK;
 }
 
@@ -110,7 +112,7 @@ int md_pack_delta_batch_device(md_ctx *ctx, size_t n, const md_pack_delta_pair *
     return MD_OK;
   }
   if (!pairs || !d_src || !d_out || !d_out_len || !d_status) return fail(ctx, MD_E_INVALID_ARGUMENT, "md_pack_delta_batch_device: null pointer");
-  int rc = check_pairs(ctx, n, pairs, false, 0, 0);
+  int rc = check_delta_pairs(ctx, n, pairs, false, 0, 0);
   if (rc != MD_OK) return rc;
   MD_ON_DEVICE(ctx);
   md_pack_write_stats stats = {};
@@ -134,7 +136,7 @@ int md_pack_delta_batch_host(md_ctx *ctx, size_t n, const md_pack_delta_pair *pa
     return MD_OK;
   }
   if (!pairs || (!src && src_len) || (!out && out_bytes) || !out_len || !status) return fail(ctx, MD_E_INVALID_ARGUMENT, "md_pack_delta_batch_host: null pointer");
-  int rc = check_pairs(ctx, n, pairs, true, src_len, out_bytes);
+  int rc = check_delta_pairs(ctx, n, pairs, true, src_len, out_bytes);
   if (rc != MD_OK) return rc;
   uint64_t need = 0;
   for (size_t i = 0; i < n; i++) need = std::max(need, pairs[i].out_off + pairs[i].out_cap);
@@ -157,7 +159,7 @@ int md_pack_delta_batch_host(md_ctx *ctx, size_t n, const md_pack_delta_pair *pa
   HIP_TRY(ctx, md::to_host(out_len, d_out_len, n, st));
   HIP_TRY(ctx, md::to_host(status, d_status, n, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
-  stats.delta_ns = event_ns(ctx);
+  stats.delta_ns = pkw_event_ns(ctx);
   ctx->pack_write_last = stats;
   ctx->pkw_pending = false;
   return MD_OK;
@@ -248,7 +250,7 @@ int pack_write(md_ctx *ctx, int level, bool deltas, uint32_t max_depth, size_t n
     HIP_TRY(ctx, md::to_host(h_dl_len.data(), dl_len, np, st));
     HIP_TRY(ctx, md::to_host(h_dl_status.data(), dl_status, np, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
-    stats.delta_ns = event_ns(ctx);
+    stats.delta_ns = pkw_event_ns(ctx);
     for (size_t i = 0; i < n; i++) fitted[i] = tried[i] && h_dl_status[pair_of[i]] == MD_OK;
   }
   std::vector<uint32_t> depth(n), h_type32(n);
@@ -353,7 +355,7 @@ int md_pack_write_last(const md_ctx *cctx, md_pack_write_stats *stats) {
   if (ctx->pkw_pending) {
     MD_ON_DEVICE(ctx);
     HIP_TRY(ctx, hipEventSynchronize(ctx->pkw_ev1));
-    ctx->pack_write_last.delta_ns = event_ns(ctx);
+    ctx->pack_write_last.delta_ns = pkw_event_ns(ctx);
     ctx->pkw_pending = false;
   }
   *stats = ctx->pack_write_last;

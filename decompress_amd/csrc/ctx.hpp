@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <functional>
 #include <new>
 #include <string>
 #include <utility>
@@ -152,7 +153,8 @@ enum Scratch {
   kShaDesc,
   // making deltas (md_pack_delta_batch_*): pairs, bases and the host form's results; the bases' tables.  Writing a pack
   // (md_pack_write): the per-object arrays, the compressed payloads (the objects and behind them the deltas stand in kHostIn,
-  // the pack in kHostOut)
+  // the pack in kHostOut).  Choosing bases (md_pack_sketch_*, md_pack_delta_sizes_*, md_pack_choose_bases): segments and features,
+  // then pairs, bases and results in kPkwDesc, the candidates' tables in kPkwTables, the objects in kHostIn
   kPkwDesc, kPkwTables, kPkwObjs, kPkwSlots,
   kScratchCount
 };
@@ -234,6 +236,8 @@ struct md_ctx {
   md_pack_write_stats pack_write_last = {};
   hipEvent_t pkw_ev0 = nullptr, pkw_ev1 = nullptr;
   bool pkw_pending = false;
+  // choosing bases: the counts and times of the last md_pack_choose_bases (md_pack_search_last)
+  md_pack_search_stats pack_search_last = {};
   // one stream written as joined spans: md_set_option "deflate_span_kib" (the span of a call that passes 0) and the counts of
   // the last md_deflate_spans_* call (md_deflate_spans_last)
   size_t span_bytes = md::kSpanDefault;
@@ -499,6 +503,24 @@ struct PackNameSink {
 };
 int pack_verify_names(md_ctx *ctx, const md_pack *P, const uint64_t *select, size_t k, int32_t *status, md_pack_result *res,
                       const PackNameSink *sink);
+// ---- capi_pack_write.cpp: what md_pack_delta_sizes_* and md_pack_choose_bases (capi_pack_search.cpp) share with the delta batch ----
+// the pairs as the kernels take them, the distinct bases that have a block, and what their tables need
+struct DeltaPlan {
+  std::vector<md::pkw::Pair> pairs;
+  std::vector<md::pkw::Base> bases;
+  uint64_t blocks = 0, table_words = 0;
+};
+void plan_deltas(size_t n, const md_pack_delta_pair *in, DeltaPlan *plan);
+// The plan's rows to kPkwDesc (with what `extra` carves behind them), its tables preset in kPkwTables, then pkw_ev0, the
+// index launch, the launch `run` makes over the pairs and the tables, and pkw_ev1, all on the context's stream.  Nothing is
+// read back.  Adds the launches to *launches.
+using DeltaRun = std::function<int(const md::pkw::Pair *d_pairs, const uint32_t *tables)>;
+int enqueue_delta_plan(md_ctx *ctx, const DeltaPlan &plan, const uint8_t *d_src, const std::function<void(md::Carver &)> &extra, const DeltaRun &run,
+                       uint64_t *launches);
+// the ranges of md_pack_delta_batch_*'s pairs (host: against src_len, and out_off + out_cap against out_bytes)
+int check_delta_pairs(md_ctx *ctx, size_t n, const md_pack_delta_pair *pairs, bool host, size_t src_len, size_t out_bytes);
+// the time between pkw_ev0 and pkw_ev1, behind a synchronise (an event that cannot be read leaves 0)
+uint64_t pkw_event_ns(md_ctx *ctx);
 // ---- capi_long_stream.cpp: both return MD_NOT_HANDLED for what the serial path has to answer ----
 int continue_parallel(md_ctx *ctx, const uint8_t *src, size_t src_len, unsigned start_bit, uint8_t *dst, size_t hist_len,
                       size_t dst_cap, uint32_t adler_in, unsigned flags, size_t *dst_len, int *status, md_inf_resume *resume);

@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "mdeflate.h"
+#include "pack_search.hpp"
 #include "pack_write.hpp"
 
 // statuses of the library's own, beside mdeflate.h's MD_* (none of which they equal)
@@ -315,6 +316,16 @@ struct Pair {
 static_assert(sizeof(Pair) == 64, "Pair is uploaded as is");
 }  // namespace pkw
 
+namespace pks {
+// Choosing bases (pack_search_kernels.hip; the sketch's definition is mdeflate.h's, its constants pack_search.hpp's).
+// One segment of an object: the positions [0, npos) from src + off, npos at most kSegPositions; obj: whose features it folds into
+struct Seg {
+  uint64_t off;
+  uint32_t npos, obj;
+};
+static_assert(sizeof(Seg) == 16, "Seg is uploaded as is");
+}  // namespace pks
+
 namespace sha {
 // SHA-1 of many messages, one a lane (sha1_kernels.hip).  Message m is data[off[m], off[m] + len[m]) with the header of
 // a git object of type[m] in front (1 commit, 2 tree, 3 blob, 4 tag; 0, or type == null: the bytes as they are), len[m] at
@@ -551,6 +562,13 @@ int md_launch_pkw_delta(uint32_t count, const md::pkw::Pair *pairs, const uint8_
 // bytes) to pack + offset[i]
 int md_launch_pkw_assemble(uint32_t n, const uint64_t *offset, const uint8_t *head, const uint8_t *head_len, const uint8_t *slots,
                            const uint64_t *slot_off, const uint64_t *zlen, uint8_t *pack, hipStream_t stream);
+
+// ---- pack_search_kernels.hip: sketches and count-only deltas (md_pack_sketch_*, md_pack_delta_sizes_*, md_pack_choose_bases) ----
+// one wavefront per segment: atomicMin into features + kFeatures * obj, preset to all ones
+int md_launch_pks_sketch(uint32_t count, const md::pks::Seg *segs, const uint8_t *src, uint32_t *features, hipStream_t stream);
+// one wavefront per pair, against tables md_launch_pkw_index filled: out_len and status as md_launch_pkw_delta's, no delta byte
+int md_launch_pks_sizes(uint32_t count, const md::pkw::Pair *pairs, const uint8_t *src, const uint32_t *tables, uint64_t *out_len, int32_t *status,
+                        hipStream_t stream);
 
 // ---- pack_build_kernels.hip: the candidates of md_pack_index_build ----
 // bits / cnt as md_launch_gzs_mark's (every word of bits is written: no memset), for the positions of [lo, hi] whose two

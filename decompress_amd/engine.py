@@ -293,6 +293,62 @@ class Engine:
         self._check(self.lib.md_pack_write_last(self.ctx, ctypes.byref(s)))
         return {k: getattr(s, k) for k, _ in _lib.PackWriteStats._fields_}
 
+    def pack_sketch(self, src, objects):
+        """md_pack_sketch_host: the four features of every object (off, len) of the bytes `src` -> [(F0, F1, F2, F3)]; an
+        object shorter than 16 bytes has none, its words are all ones.  Synchronous."""
+        n, src = len(objects), bytes(src)
+        off = (ctypes.c_uint64 * max(n, 1))(*[int(o) for o, _ in objects])
+        length = (ctypes.c_uint64 * max(n, 1))(*[int(k) for _, k in objects])
+        feats = (ctypes.c_uint32 * (4 * max(n, 1)))()
+        self._check(self.lib.md_pack_sketch_host(self.ctx, n, off, length, src, len(src), feats))
+        return [tuple(feats[4 * i:4 * i + 4]) for i in range(n)]
+
+    def pack_sketch_device(self, objects, d_src):
+        """md_pack_sketch_device: objects = [(off, len)] (host) in the device tensor d_src -> int32 tensor of 4 n words (the
+        features' bit patterns), device, async"""
+        n = len(objects)
+        off = (ctypes.c_uint64 * max(n, 1))(*[int(o) for o, _ in objects])
+        length = (ctypes.c_uint64 * max(n, 1))(*[int(k) for _, k in objects])
+        feats = self.torch.zeros(4 * max(n, 1), dtype=self.torch.int32, device=self.device)
+        self._check(self.lib.md_pack_sketch_device(self.ctx, n, off, length, _ptr(d_src), _ptr(feats)))
+        return feats[:4 * n]
+
+    def pack_delta_sizes(self, src, pairs, caps=None):
+        """md_pack_delta_sizes_host: what `pack_deltas` would report for pairs = [(base_off, base_len, tgt_off, tgt_len)] of the
+        bytes `src`, without the deltas -> [(status, length)], status 2 and length 0 where the delta would pass caps[i]
+        (default: no bound).  Synchronous."""
+        n, src = len(pairs), bytes(src)
+        if caps is None:
+            caps = [(1 << 64) - 1] * n
+        if len(caps) != n:
+            raise Error("Invalid argument: one bound per pair")
+        rows = (_lib.PackDeltaPair * max(n, 1))()
+        for r, p, cap in zip(rows, pairs, caps):
+            r.base_off, r.base_len, r.tgt_off, r.tgt_len = (int(v) for v in p)
+            r.out_off, r.out_cap = 0, int(cap)
+        out_len, status = (ctypes.c_uint64 * max(n, 1))(), (ctypes.c_int32 * max(n, 1))()
+        self._check(self.lib.md_pack_delta_sizes_host(self.ctx, n, rows, src, len(src), out_len, status))
+        return [(status[i], out_len[i]) for i in range(n)]
+
+    def pack_delta_sizes_device(self, pairs, d_src):
+        """md_pack_delta_sizes_device: pairs = [(base_off, base_len, tgt_off, tgt_len, out_cap)] (host) in the device tensor
+        d_src -> (out_len int64 tensor, status int32 tensor), device, async"""
+        n = len(pairs)
+        rows = (_lib.PackDeltaPair * max(n, 1))()
+        for r, p in zip(rows, pairs):
+            r.base_off, r.base_len, r.tgt_off, r.tgt_len, r.out_cap = (int(v) for v in p)
+        out_len = self.torch.zeros(max(n, 1), dtype=self.torch.int64, device=self.device)
+        status = self.torch.zeros(max(n, 1), dtype=self.torch.int32, device=self.device)
+        self._check(self.lib.md_pack_delta_sizes_device(self.ctx, n, rows, _ptr(d_src), _ptr(out_len), _ptr(status)))
+        return out_len[:n], status[:n]
+
+    def pack_search_last(self):
+        """md_pack_search_last: featured, pairs, fitted, chosen, launches, sketch_ns, score_ns, host_ns of the last
+        `pack.choose_bases`"""
+        s = _lib.PackSearchStats()
+        self._check(self.lib.md_pack_search_last(self.ctx, ctypes.byref(s)))
+        return {k: getattr(s, k) for k, _ in _lib.PackSearchStats._fields_}
+
     def set_option(self, key, value):
         self._check(self.lib.md_set_option(self.ctx, key.encode(), int(value)))
         if key == "deflate_span_prime":  # (the library has no query: `deflate_spans(prime=)` puts this back)

@@ -2,7 +2,8 @@
 table of all objects - type, size, base, depth, status - is built once on the GPU, and a read decodes every selected object
 and the bases it hangs off in one inflate launch a round, then applies the deltas level by level.  A pack without an idx
 gets one from the GPU (`build_index`, git index-pack's bytes).  `write` makes a pack and its idx from objects and the
-bases the caller chooses, the deltas made by a batched kernel (`make_deltas` is that kernel alone)."""
+bases the caller chooses - or, with bases="search", the bases `choose_bases` finds by content sketches -, the deltas made
+by a batched kernel (`make_deltas` is that kernel alone)."""
 import ctypes
 
 from . import engine as _engine
@@ -171,12 +172,57 @@ def write_raw(objects, bases=None, level=6, max_depth=50, flags=0, pack_cap=None
     return rc, out.raw[:need.value] if rc == 0 else b"", need.value, entries, {k: getattr(res, k) for k in _WRITE_RESULT_KEYS}
 
 
-def write(objects, bases=None, level=6, max_depth=50, deltas=True, device=0):
+def _typed(objects):
+    by_name = {v: k for k, v in TYPE_NAMES.items() if v}
+    return [(by_name[t] if isinstance(t, str) else int(t), b) for t, b in objects]
+
+
+def choose_bases_raw(objects, window=4, max_depth=50, device=0):
+    """md_pack_choose_bases as it is: objects = [(type, bytes)] -> (return value, order, bases): order[r] = the input index at
+    rank r of the pack order, bases[r] = the RANK of the base chosen for the object at rank r, or None."""
+    eng, n = _engine.default_engine(device), len(objects)
+    src, out = (PackSource * max(n, 1))(), (PackSource * max(n, 1))()
+    order = (ctypes.c_uint64 * max(n, 1))()
+    blob, at = b"".join(bytes(b) for _, b in objects), 0
+    for s, (t, b) in zip(src, _typed(objects)):
+        s.off, s.len, s.type, s.base = at, len(b), t, NO_BASE
+        at += len(b)
+    rc = eng.lib.md_pack_choose_bases(eng.ctx, window, max_depth, n, src, blob, len(blob), out, order)
+    if rc != 0:
+        return rc, [], []
+    return rc, list(order[:n]), [None if o.base == NO_BASE else o.base for o in out[:n]]
+
+
+def choose_bases(objects, window=4, max_depth=50, device=0):
+    """md_pack_choose_bases: for a bag of objects = [(type, bytes)] -> (order, bases): the pack order - by type, longest
+    first - as input indices, and for the object at every rank the rank of the base that gives it the smallest delta among
+    the at most 4 * window objects in front of it that share one of its four content features, or None.
+    `write([objects[i] for i in order], bases, max_depth=max_depth)` keeps every one of these deltas; `write(objects,
+    bases="search")` is both steps.  Sketches and delta sizes are the GPU's, order, grouping and choice the host's."""
+    rc, order, bases = choose_bases_raw(objects, window, max_depth, device)
+    if rc != 0:
+        _engine.default_engine(device)._check(rc)
+    return order, bases
+
+
+def search_last(device=0):
+    """md_pack_search_last: featured, pairs, fitted, chosen, launches, sketch_ns, score_ns, host_ns of the engine's last
+    `choose_bases`"""
+    return _engine.default_engine(device).pack_search_last()
+
+
+def write(objects, bases=None, level=6, max_depth=50, deltas=True, device=0, window=4):
     """md_pack_write and md_pack_index_write: objects = [(type, bytes)] in pack order, type 1 commit, 2 tree, 3 blob, 4 tag (or
     those words); bases[i] = the index of an EARLIER object of the same type whose content object i may be a delta against,
     or None -> (pack, idx): a pack version 2 with OFS_DELTAs and its idx version 2.  Names, deltas, zlib streams and CRCs are
-    the GPU's.  max_depth 0: no limit; deltas False: every object whole.  Raises `Error` ("Invalid index") for two objects
-    with one name, and for what the call refuses."""
+    the GPU's.  max_depth 0: no limit; deltas False: every object whole.  bases="search": the objects come in any order,
+    `choose_bases(objects, window, max_depth)` orders them and chooses, and the pack holds them in that order.  Raises
+    `Error` ("Invalid index") for two objects with one name, and for what the call refuses."""
+    if isinstance(bases, str):
+        if bases != "search":
+            raise ValueError('bases is a list or "search"')
+        order, bases = choose_bases(objects, window, max_depth, device)
+        objects = [objects[i] for i in order]
     rc, pack, _, entries, _ = write_raw(objects, bases, level, max_depth, 0 if deltas else WRITE_NO_DELTA, device=device)
     if rc != 0:
         _engine.default_engine(device)._check(rc)

@@ -1306,7 +1306,7 @@ int md_sha1_last(const md_ctx *ctx, md_sha1_stats *stats);
  *
  * md_pack_write writes the pack (version 2, OFS_DELTA only) of n objects in INPUT order.  Object i is src[off, off + len)
  * of type 1 .. 4; base is an EARLIER index whose content its delta may be made against, or MD_PACK_NO_BASE.  The caller
- * chooses the bases; searching for them (git's window) is out of scope.  MD_E_INVALID_ARGUMENT as the call's return value:
+ * chooses the bases, or has md_pack_choose_bases (below) choose them.  MD_E_INVALID_ARGUMENT as the call's return value:
  * NULL pointers, base >= i, a base of another type, a type outside 1 .. 4, len > MD_MAX_STREAM, an object beyond src_len, an
  * unknown flag, a level outside 0 .. 9, n above 2^31 - 16.  Steps: copy in; the names of all objects by one
  * md_sha1_batch_device; the deltas - tried iff a base is given, len >= 64 and the base's len >= 16, with out_cap = len / 2 - 20 -
@@ -1330,7 +1330,7 @@ int md_sha1_last(const md_ctx *ctx, md_sha1_stats *stats);
  * kernel launches of the call's own steps (index, delta, assembly, CRC; not those inside the SHA-1 and deflate batches) and
  * the device time of the index and delta launches (two events around them).  After the delta batch alone only pairs,
  * launches and delta_ns are set; after its device form the call waits for the second event.
- * Out of scope: choosing bases, REF_DELTA and thin packs, .rev and bitmaps, SHA-256, reusing an existing pack's deltas. */
+ * Out of scope: REF_DELTA and thin packs, .rev and bitmaps, SHA-256, reusing an existing pack's deltas. */
 #define MD_PACK_WRITE_NO_DELTA 1u
 typedef struct md_pack_delta_pair {
   uint64_t base_off, base_len, tgt_off, tgt_len, out_off, out_cap;
@@ -1354,6 +1354,63 @@ int md_pack_write(md_ctx *ctx, int level, unsigned flags, uint32_t max_depth, si
                   size_t src_len, uint8_t *pack, size_t pack_cap, size_t *pack_len, md_pack_index_entry *entries,
                   md_pack_write_result *res);
 int md_pack_write_last(const md_ctx *ctx, md_pack_write_stats *stats);
+
+/* ---- git packs: choosing the bases by content sketches (csrc/pack_search_kernels.hip, csrc/pack_search.hpp) -----------------
+ * THE SKETCH of an object T of n bytes is defined here byte for byte.  For n >= 16 and every position p with p + 16 <= n,
+ * h(p) is the delta index's block hash over T[p, p + 16): the four little-endian 32-bit words w0 .. w3, x = 0, then
+ * x = (x + w) * 0x9E3779B1 mod 2^32 for each word in turn.  Feature i (i < 4) is
+ *   F_i = min over p of ((h(p) XOR S_i) * 0x9E3779B1 mod 2^32),   S = {0, 0x85EBCA6B, 0xC2B2AE35, 0x27D4EB2F}.
+ * An object shorter than 16 bytes has NO features: its four words are written as all ones, and it is never a candidate and
+ * never a target - by its length, not by the stored value (an object of 16 bytes or more may have a feature of all ones).
+ * The features are a pure function of the bytes.  Two objects that share most of their 16-byte windows share a feature with
+ * a probability near the share, and each of the four independently.
+ *
+ * md_pack_sketch_device writes features[4 i .. 4 i + 3] of object i = d_src[off[i], off[i] + len[i]), at any byte address;
+ * off and len are HOST arrays (the host cuts every object into segments of 4 096 positions, one wavefront each, so that
+ * one very large object is not the call's length), d_src and d_features device pointers; one launch, asynchronous on the
+ * context's stream.  Nothing outside an object's range is read.  md_pack_sketch_host: host pointers, ranges checked against
+ * src_len, synchronous.  MD_E_INVALID_ARGUMENT: a NULL pointer, n above 2^31 - 16, len above MD_MAX_STREAM, a range that
+ * overflows (host form: that leaves src), more than 2^31 - 16 segments.  n == 0 is MD_OK.
+ *
+ * md_pack_delta_sizes_device / _host take md_pack_delta_batch_*'s pairs and return exactly the out_len and status that call
+ * returns for them - out_cap is the bound, the first op that would pass it ends the pair with MD_UNEXPECTED_END_OF_OUTPUT and
+ * out_len 0 - and write no delta byte: out_off is ignored and there is no output buffer.  One launch (two with the index).
+ * Arguments, errors and workspace as md_pack_delta_batch_*'s; md_pack_write_last counts the call as a delta batch.
+ *
+ * md_pack_choose_bases picks for every object of a batch the base that gives the smallest delta and returns the objects in
+ * an order md_pack_write accepts as they stand.  objs[i] = {off, len, type} in src (host), base is ignored.
+ *  1. Pack order: by (type, len descending, input index).  order[r] = the input index at rank r.
+ *  2. Candidates of a target t: for each feature i the at most `window` objects nearest in front of t in pack order that
+ *     have t's type and t's F_i; the union over the four features counts each object once (at most 4 * window).  A pair is
+ *     scored iff md_pack_write would try it: the target's len >= 64, the base's len >= 16; its bound is len / 2 - 20.  A base
+ *     always stands in front of its target, so no cycle can arise.
+ *  3. Scores: one index launch over all distinct candidates, one md_pack_delta_sizes launch over all pairs.
+ *  4. Choice, on the host in pack order: among the candidates whose delta fitted and whose depth is < max_depth (0: no
+ *     limit) the smallest delta, on a tie the candidate earlier in pack order; depth[t] = depth[base] + 1.  No such
+ *     candidate: the object is written whole, depth 0.
+ *  5. sorted[r] = {off, len, type} of objs[order[r]] with base = the RANK of the chosen base or MD_PACK_NO_BASE.
+ *     md_pack_write(.., max_depth, n, sorted, ..) with the same max_depth keeps every chosen delta: its deltas equal the
+ *     bases chosen and it drops none.
+ * MD_E_INVALID_ARGUMENT: NULL pointers, window outside 1 .. 64, n * 4 * window above 2^31 - 16, a type outside 1 .. 4, len >
+ * MD_MAX_STREAM, an object beyond src_len.  n == 0 is MD_OK.  Everything of the call is resident at once (the objects,
+ * then the candidates' tables): workspace that cannot be had is MD_E_OUT_OF_MEMORY, there are no rounds.
+ * md_pack_search_last: of the context's last md_pack_choose_bases the objects with features, the pairs scored, the pairs that
+ * fitted, the bases chosen, the kernel launches (sketch, index, size), the device time of the sketch launch and that of the
+ * index and size launches (two events around each) and the host time of order, grouping and choice.
+ * Out of scope: path-name heuristics, a device sort (the grouping is host sorts), rounds, other feature counts or seeds. */
+typedef struct md_pack_search_stats {
+  uint64_t featured, pairs, fitted, chosen, launches, sketch_ns, score_ns, host_ns;
+} md_pack_search_stats;
+int md_pack_sketch_device(md_ctx *ctx, size_t n, const uint64_t *off, const uint64_t *len, const uint8_t *d_src, uint32_t *d_features);
+int md_pack_sketch_host(md_ctx *ctx, size_t n, const uint64_t *off, const uint64_t *len, const uint8_t *src, size_t src_len,
+                        uint32_t *features);
+int md_pack_delta_sizes_device(md_ctx *ctx, size_t n, const md_pack_delta_pair *pairs, const uint8_t *d_src, uint64_t *d_out_len,
+                               int32_t *d_status);
+int md_pack_delta_sizes_host(md_ctx *ctx, size_t n, const md_pack_delta_pair *pairs, const uint8_t *src, size_t src_len,
+                             uint64_t *out_len, int32_t *status);
+int md_pack_choose_bases(md_ctx *ctx, uint32_t window, uint32_t max_depth, size_t n, const md_pack_source *objs, const uint8_t *src,
+                         size_t src_len, md_pack_source *sorted, uint64_t *order);
+int md_pack_search_last(const md_ctx *ctx, md_pack_search_stats *stats);
 
 #ifdef __cplusplus
 }

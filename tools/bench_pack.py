@@ -36,7 +36,17 @@ With --write, for DESIGN 4l, instead of the read legs: the same objects written 
 and the three packs' sizes, md_pack_write_last's counts and the device time of the index and delta launches.  Both written
 packs are read back by md_pack_index_build and md_pack_read with both checks and compared with the objects.
 
-    python tools/bench_pack.py [--objects 16384] [--depth 8] [--mib 64] [--reps 7] [--warmup 1] [--names] [--build] [--write]
+With --search, for DESIGN 4m, instead of the read legs: the same objects in SHUFFLED order, as a caller has them who knows no bases:
+  choose              md_pack_choose_bases alone (window 4, max_depth 50)
+  choose_write        md_pack_choose_bases, then md_pack_write (level 6) on what it returned
+  write_true          md_pack_write with every version's true predecessor as its base, the objects in the chains' order
+  write_no_delta      md_pack_write with MD_PACK_WRITE_NO_DELTA: what a caller without bases had before
+  git pack-objects    as with --write
+and the packs' sizes, how many chosen bases are the target's true predecessor or of its chain, and md_pack_search_last's split:
+the sketch launch, the index and size launches, the host's grouping and choice.  The searched pack is read back by
+md_pack_index_build and md_pack_read with both checks and compared with the objects.
+
+    python tools/bench_pack.py [--objects 16384] [--depth 8] [--mib 64] [--reps 7] [--warmup 1] [--names] [--build] [--write] [--search]
 
 The legs are alternated in one process; every leg reports the median and the spread (min .. max) of its repeats, host to
 host (perf_counter around a call that ends in a synchronise).  read_all's bytes are compared with the writer's."""
@@ -235,6 +245,89 @@ def write_mode(a, eng, entries, layout):
     print(json.dumps(out_res))
 
 
+def search_mode(a, eng, entries, layout):
+    """--search, for DESIGN 4m: the objects of the read benchmark's pack in shuffled order, the bases chosen on the device"""
+    lib, n = eng.lib, len(layout)
+    perm = list(range(n))
+    random.Random(7).shuffle(perm)
+    chain_of, c = [], -1
+    for e in entries:
+        c += e.get("base") is None
+        chain_of.append(c)
+
+    def sources(idx, with_bases):
+        blob = np.frombuffer(b"".join(layout[i]["data"] for i in idx), dtype=np.uint8)
+        src, at = (_lib.PackSource * n)(), 0
+        for s, i in zip(src, idx):
+            s.off, s.len, s.type = at, len(layout[i]["data"]), 3
+            s.base = entries[i]["base"] if with_bases and entries[i].get("base") is not None else mp.NO_BASE
+            at += s.len
+        return blob, src
+
+    sh_blob, sh_src = sources(perm, False)
+    tr_blob, tr_src = sources(range(n), True)
+    sorted_src, order = (_lib.PackSource * n)(), (ctypes.c_uint64 * n)()
+    out = np.empty(int(lib.md_pack_write_bound(n, tr_src)), dtype=np.uint8)
+    ents, need, res = (_lib.PackIndexEntry * n)(), ctypes.c_size_t(0), _lib.PackWriteResult()
+    made, last = {}, {}
+
+    def choose():
+        eng._check(lib.md_pack_choose_bases(eng.ctx, a.window, 50, n, sh_src, sh_blob.ctypes.data, sh_blob.size, sorted_src, order))
+        last["search"] = mp.search_last()
+
+    def write(name, src, blob, flags):
+        eng._check(lib.md_pack_write(eng.ctx, 6, flags, 50, n, src, blob.ctypes.data, blob.size, out.ctypes.data, out.size, ctypes.byref(need), ents,
+                                     ctypes.byref(res)))
+        last[name] = mp.write_last()
+        if name not in made:
+            made[name] = (out[:need.value].tobytes(), [{"name": bytes(e.name), "offset": e.offset, "crc32": e.crc32} for e in ents], int(res.deltas),
+                          int(res.max_depth))
+
+    def choose_write():
+        choose()
+        write("choose_write", sorted_src, sh_blob, 0)
+
+    legs = {"choose": choose, "choose_write": choose_write, "write_true": lambda: write("write_true", tr_src, tr_blob, 0),
+            "write_no_delta": lambda: write("write_no_delta", sh_src, sh_blob, mp.WRITE_NO_DELTA)}
+    times = {k: [] for k in legs}
+    for r in range(a.warmup + a.reps):
+        for k, fn in legs.items():
+            t0 = time.perf_counter()
+            fn()
+            if r >= a.warmup:
+                times[k].append((time.perf_counter() - t0) * 1e3)
+    # what the search chose, against the chains the objects were made as
+    ranks = [perm[int(i)] for i in order]  # rank -> the object's index in the chains' order
+    chosen = [(ranks[r], ranks[int(s.base)]) for r, s in enumerate(sorted_src) if s.base != mp.NO_BASE]
+    quality = {"chosen": len(chosen), "true_predecessor": sum(entries[t].get("base") == b for t, b in chosen),
+               "true_successor": sum(entries[b].get("base") == t for t, b in chosen), "own_chain": sum(chain_of[t] == chain_of[b] for t, b in chosen),
+               "possible": sum(e.get("base") is not None for e in entries)}
+    pack, entries_out, deltas, depth = made["choose_write"]  # what was written is a pack: the library's own reader takes it back
+    idx = mp.write_index(entries_out, pack[-20:])
+    assert mp.build_index(pack) == idx and deltas == len(chosen) and last["choose_write"]["dropped_size"] == last["choose_write"]["dropped_depth"] == 0
+    p = mp.Pack(pack, idx)
+    got = p.read(verify_crc=True, verify_names=True)
+    where = {e["name"]: i for i, e in enumerate(mp.index(idx)[0])}
+    assert all(got[where[lay["name"]]] == ("Ok", (3, lay["data"])) for lay in layout)
+    p.close()
+    sizes = {k: {"pack_bytes": len(v[0]), "deltas": v[2], "max_depth": v[3]} for k, v in made.items()}
+    med = {k: statistics.median(v) for k, v in times.items()}
+    s = last["search"]
+    out_res = {"mode": "search", "objects": n, "depth": a.depth, "object_bytes": len(layout[0]["data"]), "total_size": int(sh_blob.size), "window": a.window,
+               "level": 6, "reps": a.reps, "warmup": a.warmup, "times": {k: stats(v) for k, v in times.items()}, "packs": sizes, "quality": quality, "last": last,
+               "search_split_ms": {"sketch_device": round(s["sketch_ns"] / 1e6, 4), "index_and_sizes_device": round(s["score_ns"] / 1e6, 4),
+                                   "host_grouping_and_choice": round(s["host_ns"] / 1e6, 4), "choose_median": round(med["choose"], 3)},
+               "choose_write_over_write_true": round(med["choose_write"] / med["write_true"], 3),
+               "write_no_delta_over_choose_write": round(med["write_no_delta"] / med["choose_write"], 3),
+               "searched_pack_over_true_pack": round(sizes["choose_write"]["pack_bytes"] / sizes["write_true"]["pack_bytes"], 4)}
+    git = time_git_pack_objects(made["write_true"][0], min(a.reps, 3))
+    if git:
+        out_res["git_pack_objects"] = dict(stats(git[0]), pack_bytes=git[1])
+    else:
+        out_res["git_pack_objects"] = "git is not on this machine: this leg was not run"
+    print(json.dumps(out_res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--objects", type=int, default=16384)
@@ -245,6 +338,8 @@ def main():
     ap.add_argument("--names", action="store_true")
     ap.add_argument("--build", action="store_true")
     ap.add_argument("--write", action="store_true")
+    ap.add_argument("--search", action="store_true")
+    ap.add_argument("--window", type=int, default=4)
     a = ap.parse_args()
     eng = _engine.default_engine(0)
     lib = eng.lib
@@ -253,6 +348,8 @@ def main():
     pack, idx, layout = pw.write_pack(entries)
     if a.write:
         return write_mode(a, eng, entries, layout)
+    if a.search:
+        return search_mode(a, eng, entries, layout)
     order = pw.idx_order(layout)
     p = mp.Pack(pack, idx)
     n = p.info["n"]
