@@ -135,12 +135,13 @@ md_ctx *md_create(int device, void *hip_stream) {
     }
     ctx->own_stream = true;
   }
-  if (hipEventCreate(&ctx->ev0) != hipSuccess || hipEventCreate(&ctx->ev1) != hipSuccess || hipEventCreate(&ctx->sha_ev0) != hipSuccess ||
-      hipEventCreate(&ctx->sha_ev1) != hipSuccess || hipEventCreate(&ctx->pkw_ev0) != hipSuccess || hipEventCreate(&ctx->pkw_ev1) != hipSuccess) {
-    md_destroy(ctx);
-    fail(nullptr, MD_E_HIP, "hipEventCreate");
-    return nullptr;
-  }
+  for (md::EventSpan *span : {&ctx->timing, &ctx->sha1_span, &ctx->pkw_span})
+    for (hipEvent_t &ev : span->ev)
+      if (hipEventCreate(&ev) != hipSuccess) {
+        md_destroy(ctx);
+        fail(nullptr, MD_E_HIP, "hipEventCreate");
+        return nullptr;
+      }
   {
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) ctx->cus = cus;
@@ -159,12 +160,9 @@ md_ctx *md_create(int device, void *hip_stream) {
 void md_destroy(md_ctx *ctx) {
   if (!ctx) return;
   md::DeviceGuard guard(ctx->device);
-  if (ctx->ev0) hipEventDestroy(ctx->ev0);
-  if (ctx->ev1) hipEventDestroy(ctx->ev1);
-  if (ctx->sha_ev0) hipEventDestroy(ctx->sha_ev0);
-  if (ctx->sha_ev1) hipEventDestroy(ctx->sha_ev1);
-  if (ctx->pkw_ev0) hipEventDestroy(ctx->pkw_ev0);
-  if (ctx->pkw_ev1) hipEventDestroy(ctx->pkw_ev1);
+  for (md::EventSpan *span : {&ctx->timing, &ctx->sha1_span, &ctx->pkw_span})
+    for (hipEvent_t ev : span->ev)
+      if (ev) hipEventDestroy(ev);
   if (ctx->s_in) hipStreamDestroy(ctx->s_in);
   if (ctx->s_out) hipStreamDestroy(ctx->s_out);
   if (ctx->own_stream && ctx->stream) hipStreamDestroy(ctx->stream);
@@ -181,16 +179,16 @@ int md_synchronize(md_ctx *ctx) {
 int md_timing_begin(md_ctx *ctx) {
   if (!ctx) return MD_E_INVALID_ARGUMENT;
   MD_ON_DEVICE(ctx);
-  HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  HIP_TRY(ctx, ctx->timing.begin(ctx->stream));
   return MD_OK;
 }
 
 int md_timing_end(md_ctx *ctx, float *ms) {
   if (!ctx || !ms) return MD_E_INVALID_ARGUMENT;
   MD_ON_DEVICE(ctx);
-  HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-  HIP_TRY(ctx, hipEventSynchronize(ctx->ev1));
-  HIP_TRY(ctx, hipEventElapsedTime(ms, ctx->ev0, ctx->ev1));
+  HIP_TRY(ctx, ctx->timing.end(ctx->stream));
+  HIP_TRY(ctx, hipEventSynchronize(ctx->timing.ev[1]));
+  HIP_TRY(ctx, hipEventElapsedTime(ms, ctx->timing.ev[0], ctx->timing.ev[1]));
   return MD_OK;
 }
 

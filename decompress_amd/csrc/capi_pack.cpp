@@ -85,18 +85,17 @@ int pack_open(md_ctx *ctx, const uint8_t *pack, size_t pack_len, const uint8_t *
   std::vector<md_pack_index_entry> ent((size_t)ii.n);
   rc = md::pack::read_index(idx, idx_len, &ii, ent.data(), ent.size());
   if (rc != MD_OK) return fail(ctx, rc, "md_pack_open: the idx");
-  if (pack_len < 12 + 20 || memcmp(pack, "PACK", 4) != 0) return fail(ctx, MD_INVALID_PACK, "md_pack_open: no pack");
-  const uint32_t version = md::pack::be32(pack + 4);
-  if (version != 2 && version != 3) return fail(ctx, MD_PACK_UNSUPPORTED, "md_pack_open: the pack's version is neither 2 nor 3");
+  if ((rc = md::pack::pack_header_status(pack, pack_len)) != MD_OK)
+    return fail(ctx, rc, rc == MD_INVALID_PACK ? "md_pack_open: no pack" : "md_pack_open: the pack's version is neither 2 nor 3");
   if (md::pack::be32(pack + 8) != ii.n) return fail(ctx, MD_INVALID_INDEX, "md_pack_open: the idx counts other objects than the pack");
   if (memcmp(pack + pack_len - 20, ii.pack_checksum, 20) != 0) return fail(ctx, MD_INVALID_INDEX, "md_pack_open: the idx belongs to another pack");
   const size_t n = (size_t)ii.n;
   if (n > 0x7ffffff0ull) return fail(ctx, MD_E_INVALID_ARGUMENT, "md_pack_open: too many objects");
-  const uint64_t body_end = pack_len - 20;
+  const uint64_t body_end = pack_len - md::pack::kPackTrailer;
   // the objects in pack order: object i is pack[off_i, the next offset)
   std::vector<std::pair<uint64_t, uint32_t>> order(n);
   for (size_t i = 0; i < n; i++) {
-    if (ent[i].offset < 12 || ent[i].offset >= body_end) return fail(ctx, MD_INVALID_INDEX, "md_pack_open: an offset outside the pack");
+    if (ent[i].offset < md::pack::kPackHeader || ent[i].offset >= body_end) return fail(ctx, MD_INVALID_INDEX, "md_pack_open: an offset outside the pack");
     order[i] = {ent[i].offset, (uint32_t)i};
   }
   std::sort(order.begin(), order.end());
@@ -327,7 +326,7 @@ int pack_read(md_ctx *ctx, const md_pack *P, const uint8_t *pack, const uint64_t
   if (need > dst_cap) return MD_UNEXPECTED_END_OF_OUTPUT;
   ctx->pack_last = {};
   const bool names = (flags & MD_PACK_VERIFY_NAME) != 0 || sink;
-  if (names) ctx->sha1_last = {}, ctx->sha1_pending = false;
+  if (names) ctx->sha1_last = {}, ctx->sha1_span.pending = false;
   if (k == 0) return MD_OK;
 
   // -- the plan, from the table alone.  The buffer of a round: the output as it lies in dst, then the round's scratch.

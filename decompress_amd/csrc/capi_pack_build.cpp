@@ -15,13 +15,6 @@
 
 namespace {
 
-void host_sha1(const uint8_t *p, size_t len, uint8_t digest[20]) {
-  md::sha::Sha1 s;
-  md::sha::sha1_init(&s);
-  md::sha::sha1_update(&s, p, len);
-  md::sha::sha1_final(&s, digest);
-}
-
 // what the device knows of every candidate, read back (z ascending)
 struct CandidateTable {
   std::vector<uint64_t> z, consumed, out_len;
@@ -71,7 +64,7 @@ int candidates(md_ctx *ctx, const uint8_t *pack, uint64_t pack_len, bool check_t
   HIP_TRY(ctx, md::to_host(t->status.data(), status, (size_t)C, st));
   if (check_trailer) {  // one serial message: the host's, under the device's count
     uint8_t digest[20];
-    host_sha1(pack, (size_t)end, digest);
+    md::sha::sha1_of(pack, (size_t)end, digest);
     *trailer_ok = memcmp(digest, pack + end, 20) == 0;
   }
   HIP_TRY(ctx, hipStreamSynchronize(st));
@@ -238,9 +231,8 @@ int md_pack_index_build(md_ctx *ctx, const uint8_t *pack, size_t pack_len, unsig
   memset(res, 0, sizeof *res);
   res->bad_offset = MD_PACK_NO_BASE;
   if (flags & ~MD_PACK_BUILD_CHECK_TRAILER) return fail(ctx, MD_E_INVALID_ARGUMENT, "md_pack_index_build: unknown flag");
-  if (pack_len < 12 + 20 || memcmp(pack, "PACK", 4) != 0) return fail(ctx, MD_INVALID_PACK, "md_pack_index_build: no pack");
-  const uint32_t version = md::pack::be32(pack + 4);
-  if (version != 2 && version != 3) return fail(ctx, MD_PACK_UNSUPPORTED, "md_pack_index_build: the pack's version is neither 2 nor 3");
+  if (const int rc = md::pack::pack_header_status(pack, pack_len))
+    return fail(ctx, rc, rc == MD_INVALID_PACK ? "md_pack_index_build: no pack" : "md_pack_index_build: the pack's version is neither 2 nor 3");
   return no_bad_alloc(ctx, "host memory for the pack's objects",
                       [&] { return index_build(ctx, pack, pack_len, flags, idx, idx_cap, offsets, status, cap, res); });
 }

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "ctx.hpp"
+#include "pack_index.hpp"
 #include "sha1_host.hpp"
 
 namespace {
@@ -27,13 +28,6 @@ int carve_batch(md_ctx *ctx, size_t n, Sha1Batch *b) {
     b->type = c.take<uint8_t>(n);
     b->digest = c.take<uint8_t>(n * kSha1Bytes), b->expect = c.take<uint8_t>(n * kSha1Bytes);
   });
-}
-
-// the time between the context's two SHA-1 events, behind a synchronise (an event that cannot be read leaves 0)
-uint64_t event_ns(md_ctx *ctx) {
-  float ms = 0;
-  if (hipEventElapsedTime(&ms, ctx->sha_ev0, ctx->sha_ev1) != hipSuccess) ms = 0, (void)hipGetLastError();
-  return (uint64_t)((double)ms * 1e6);
 }
 
 }  // namespace
@@ -81,7 +75,7 @@ int md_sha1_batch_host(md_ctx *ctx, size_t n, const uint8_t *data, size_t data_l
   if (!ctx) return MD_E_INVALID_ARGUMENT;
   if (n == 0) {
     ctx->sha1_last = {};
-    ctx->sha1_pending = false;
+    ctx->sha1_span.pending = false;
     return MD_OK;
   }
   if (n > 0x7fffffffull || (!data && data_len) || !off || !len || !digest) return fail(ctx, MD_E_INVALID_ARGUMENT, "md_sha1_batch_host: null pointer");
@@ -96,16 +90,16 @@ int md_sha1_batch_host(md_ctx *ctx, size_t n, const uint8_t *data, size_t data_l
   if (rc != MD_OK) return rc;
   Sha1Batch b;
   md_sha1_stats stats = {};
-  HIP_TRY(ctx, hipEventRecord(ctx->sha_ev0, st));
+  HIP_TRY(ctx, ctx->sha1_span.begin(st));
   rc = no_bad_alloc(ctx, "host memory for the batch's order",
                     [&] { return sha1_enqueue(ctx, n, ctx->scratch[kHostIn].as<uint8_t>(), off, len, type, &b, &stats); });
   if (rc != MD_OK) return rc;
-  HIP_TRY(ctx, hipEventRecord(ctx->sha_ev1, st));
+  HIP_TRY(ctx, ctx->sha1_span.end(st));
   HIP_TRY(ctx, md::to_host(digest, b.digest, n * kSha1Bytes, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
-  stats.device_ns = event_ns(ctx);
+  stats.device_ns = ctx->sha1_span.ns();
   ctx->sha1_last = stats;
-  ctx->sha1_pending = false;
+  ctx->sha1_span.pending = false;
   return MD_OK;
 }
 
@@ -114,7 +108,7 @@ int md_sha1_batch_device(md_ctx *ctx, size_t n, const uint8_t *d_data, const uin
   if (!ctx) return MD_E_INVALID_ARGUMENT;
   if (n == 0) {
     ctx->sha1_last = {};
-    ctx->sha1_pending = false;
+    ctx->sha1_span.pending = false;
     return MD_OK;
   }
   if (n > 0x7fffffffull || !d_off || !d_len || !d_digest || max_len > MD_MAX_STREAM) return fail(ctx, MD_E_INVALID_ARGUMENT, "bad sha1 batch");
@@ -128,27 +122,25 @@ int md_sha1_batch_device(md_ctx *ctx, size_t n, const uint8_t *d_data, const uin
   a.data = d_data, a.off = d_off, a.len = d_len, a.type = d_type, a.state = state, a.digest = d_digest;
   const uint64_t longest = blocks_of(1, max_len);  // (the longest header: a commit's)
   md_sha1_stats stats = {};
-  HIP_TRY(ctx, hipEventRecord(ctx->sha_ev0, st));
+  HIP_TRY(ctx, ctx->sha1_span.begin(st));
   for (uint64_t at = 0; at < longest; at += a.blocks) {
     a.fresh = at == 0;
     MD_LAUNCH_TRY(ctx, md_launch_sha1(&a, st));
     stats.launches++;
   }
-  HIP_TRY(ctx, hipEventRecord(ctx->sha_ev1, st));
+  HIP_TRY(ctx, ctx->sha1_span.end(st));
   stats.messages = n;  // (blocks: the lengths are the device's, the host has no count)
   ctx->sha1_last = stats;
-  ctx->sha1_pending = true;
+  ctx->sha1_span.pending = true;
   return MD_OK;
 }
 
 int md_sha1_last(const md_ctx *cctx, md_sha1_stats *stats) {
   if (!cctx || !stats) return MD_E_INVALID_ARGUMENT;
   md_ctx *ctx = const_cast<md_ctx *>(cctx);  // (the device form's time is fetched when it is asked for)
-  if (ctx->sha1_pending) {
+  if (ctx->sha1_span.pending) {
     MD_ON_DEVICE(ctx);
-    HIP_TRY(ctx, hipEventSynchronize(ctx->sha_ev1));
-    ctx->sha1_last.device_ns = event_ns(ctx);
-    ctx->sha1_pending = false;
+    HIP_TRY(ctx, ctx->sha1_span.settle(&ctx->sha1_last.device_ns));
   }
   *stats = ctx->sha1_last;
   return MD_OK;
@@ -157,7 +149,7 @@ int md_sha1_last(const md_ctx *cctx, md_sha1_stats *stats) {
 int md_pack_check_trailers(const uint8_t *pack, size_t pack_len, const uint8_t *idx, size_t idx_len, int *pack_ok, int *idx_ok) {
   if (!pack || !idx || !pack_ok || !idx_ok) return MD_E_INVALID_ARGUMENT;
   if (idx_len < 8 + 1024 + 40) return MD_INVALID_INDEX;
-  if (pack_len < 12 + 20) return MD_INVALID_PACK;
+  if (pack_len < md::pack::kPackHeader + md::pack::kPackTrailer) return MD_INVALID_PACK;
   uint8_t digest[20];
   const struct {
     const uint8_t *p;
@@ -165,10 +157,7 @@ int md_pack_check_trailers(const uint8_t *pack, size_t pack_len, const uint8_t *
     int *ok;
   } files[2] = {{pack, pack_len, pack_ok}, {idx, idx_len, idx_ok}};
   for (const auto &f : files) {
-    md::sha::Sha1 s;
-    md::sha::sha1_init(&s);
-    md::sha::sha1_update(&s, f.p, f.len - 20);
-    md::sha::sha1_final(&s, digest);
+    md::sha::sha1_of(f.p, f.len - 20, digest);
     *f.ok = memcmp(digest, f.p + f.len - 20, 20) == 0;
   }
   return MD_OK;

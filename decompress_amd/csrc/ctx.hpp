@@ -7,7 +7,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <functional>
 #include <new>
 #include <string>
 #include <utility>
@@ -112,6 +111,31 @@ struct Buffer {
 using DevBuf = Buffer<false>;
 using PinnedBuf = Buffer<true>;
 
+// The device's time for a stretch of the context's stream: begin and end record the two events around it.  A call that
+// waits for the stream reads ns() behind its synchronise; one that reads nothing back sets `pending`, and whoever asks for
+// the time later settles it.  md_create makes the events, md_destroy frees them.
+struct EventSpan {
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  bool pending = false;
+  hipError_t begin(hipStream_t st) { return hipEventRecord(ev[0], st); }
+  hipError_t end(hipStream_t st) { return hipEventRecord(ev[1], st); }
+  // behind a synchronise (an event that cannot be read leaves 0)
+  uint64_t ns() const {
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, ev[0], ev[1]) != hipSuccess) ms = 0, (void)hipGetLastError();
+    return (uint64_t)((double)ms * 1e6);
+  }
+  // a pending time into *out, behind a wait for the end event; nothing when none is pending
+  hipError_t settle(uint64_t *out) {
+    if (!pending) return hipSuccess;
+    const hipError_t e = hipEventSynchronize(ev[1]);
+    if (e != hipSuccess) return e;
+    *out = ns();
+    pending = false;
+    return hipSuccess;
+  }
+};
+
 }  // namespace md
 
 // The context's grow-only scratch.  md_set_option "release_workspace" gives back exactly these, in this order (they grow
@@ -151,10 +175,11 @@ enum Scratch {
   // SHA-1 of many messages (md_sha1_batch_*, the names of a round of md_pack_read / md_pack_verify): descriptors, states
   // and digests (the host form's bytes go through kHostIn)
   kShaDesc,
-  // making deltas (md_pack_delta_batch_*): pairs, bases and the host form's results; the bases' tables.  Writing a pack
-  // (md_pack_write): the per-object arrays, the compressed payloads (the objects and behind them the deltas stand in kHostIn,
-  // the pack in kHostOut).  Choosing bases (md_pack_sketch_*, md_pack_delta_sizes_*, md_pack_choose_bases): segments and features,
-  // then pairs, bases and results in kPkwDesc, the candidates' tables in kPkwTables, the objects in kHostIn
+  // a delta plan on the device (md_pack_delta_batch_*, md_pack_delta_sizes_*, the deltas of md_pack_write, the scores of
+  // md_pack_choose_bases): pairs, bases and - unless they are the caller's - the results in kPkwDesc; the bases' tables.
+  // Writing a pack: the per-object arrays, the compressed payloads (the objects and behind them the deltas stand in
+  // kHostIn, the pack in kHostOut).  Sketches (md_pack_sketch_*, md_pack_choose_bases): segments and features in kPkwDesc,
+  // in front of the plan that md_pack_choose_bases puts there next; the objects in kHostIn
   kPkwDesc, kPkwTables, kPkwObjs, kPkwSlots,
   kScratchCount
 };
@@ -175,7 +200,7 @@ struct md_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
   bool own_stream = false;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  md::EventSpan timing;  // md_timing_begin / md_timing_end
   md::DevBuf scratch[kScratchCount];
   // GZip: per-stream scratch (body_off[n], body_len[n] u64, hstatus[n] i32, crc[n] u32), grow-only, and the header to write
   md::DevBuf gz_tmp;
@@ -226,16 +251,16 @@ struct md_ctx {
   md_pack_stats pack_last = {};
   md_pack_build_stats pack_build_last = {};  // of the last md_pack_index_build (md_pack_build_last)
   // SHA-1 batches: md_set_option "sha1_launch_blocks" (blocks of 64 bytes by which one launch advances a message) and the
-  // counts of the last batch (md_sha1_last).  The device form reads nothing back: its two events are asked when the counts are
+  // counts of the last batch (md_sha1_last), with the span around its launches.  The device form reads nothing back: its
+  // time is pending until the counts are asked for
   uint32_t sha1_launch_blocks = md::sha::kLaunchBlocksDefault;
   md_sha1_stats sha1_last = {};
-  hipEvent_t sha_ev0 = nullptr, sha_ev1 = nullptr;
-  bool sha1_pending = false;
-  // making deltas and writing packs: the counts of the last md_pack_delta_batch_* / md_pack_write (md_pack_write_last) and the two
-  // events around the index and delta launches; the device form of the delta batch reads nothing back (pkw_pending)
+  md::EventSpan sha1_span;
+  // making deltas and writing packs: the counts of the last md_pack_delta_batch_* / md_pack_delta_sizes_* / md_pack_write
+  // (md_pack_write_last) and the span around the index launch and the delta or size launch; the device forms leave it pending.
+  // md_pack_choose_bases times its sketch launch and its scores with the same span, one after the other
   md_pack_write_stats pack_write_last = {};
-  hipEvent_t pkw_ev0 = nullptr, pkw_ev1 = nullptr;
-  bool pkw_pending = false;
+  md::EventSpan pkw_span;
   // choosing bases: the counts and times of the last md_pack_choose_bases (md_pack_search_last)
   md_pack_search_stats pack_search_last = {};
   // one stream written as joined spans: md_set_option "deflate_span_kib" (the span of a call that passes 0) and the counts of
@@ -503,24 +528,44 @@ struct PackNameSink {
 };
 int pack_verify_names(md_ctx *ctx, const md_pack *P, const uint64_t *select, size_t k, int32_t *status, md_pack_result *res,
                       const PackNameSink *sink);
-// ---- capi_pack_write.cpp: what md_pack_delta_sizes_* and md_pack_choose_bases (capi_pack_search.cpp) share with the delta batch ----
-// the pairs as the kernels take them, the distinct bases that have a block, and what their tables need
+// ---- capi_pack_write.cpp: the delta batch, as md_pack_delta_sizes_* and md_pack_choose_bases (capi_pack_search.cpp) use it too ----
+// The pairs as the kernels take them, the distinct bases that have a block, and what their tables need.  A builder calls
+// add_base once per distinct base, in the order the tables shall stand in, and pair() for every pair with its base's place.
 struct DeltaPlan {
   std::vector<md::pkw::Pair> pairs;
   std::vector<md::pkw::Base> bases;
-  uint64_t blocks = 0, table_words = 0;
+  md::pkw::TableRoom room;
+  md::pkw::TablePlace add_base(uint64_t off, uint64_t len) {
+    const md::pkw::TablePlace at = room.add(len);
+    if (at.bits) bases.push_back(md::pkw::Base{off, at.table_off, at.first_block, at.bits, 0});
+    return at;
+  }
+  static md::pkw::Pair pair(const md_pack_delta_pair &p, const md::pkw::TablePlace &at) {
+    return md::pkw::Pair{p.base_off, p.base_len, p.tgt_off, p.tgt_len, p.out_off, p.out_cap, at.table_off, at.bits, 0};
+  }
 };
+// pairs in the caller's order; the distinct bases are found by sorting the pairs by (base_off, base_len), and stand in that order
 void plan_deltas(size_t n, const md_pack_delta_pair *in, DeltaPlan *plan);
-// The plan's rows to kPkwDesc (with what `extra` carves behind them), its tables preset in kPkwTables, then pkw_ev0, the
-// index launch, the launch `run` makes over the pairs and the tables, and pkw_ev1, all on the context's stream.  Nothing is
-// read back.  Adds the launches to *launches.
-using DeltaRun = std::function<int(const md::pkw::Pair *d_pairs, const uint32_t *tables)>;
-int enqueue_delta_plan(md_ctx *ctx, const DeltaPlan &plan, const uint8_t *d_src, const std::function<void(md::Carver &)> &extra, const DeltaRun &run,
+// what the second launch over a plan's pairs is: the deltas' bytes, or their lengths alone (md_launch_pks_sizes)
+enum class DeltaKind { kWrite, kSizes };
+// every pair's length and status on the device.  Both null on the way in: they are carved behind the plan's rows in kPkwDesc
+struct DeltaResults {
+  uint64_t *out_len = nullptr;
+  int32_t *status = nullptr;
+};
+// On the context's stream: the plan's rows to kPkwDesc, its tables preset in kPkwTables, then pkw_span around the index launch
+// (if a base has a block) and the delta or size launch.  d_out: where the deltas go (kSizes: unused).  Nothing is read back.
+// Adds the launches to *launches.
+int enqueue_delta_plan(md_ctx *ctx, const DeltaPlan &plan, const uint8_t *d_src, DeltaKind kind, uint8_t *d_out, DeltaResults *res,
                        uint64_t *launches);
-// the ranges of md_pack_delta_batch_*'s pairs (host: against src_len, and out_off + out_cap against out_bytes)
-int check_delta_pairs(md_ctx *ctx, size_t n, const md_pack_delta_pair *pairs, bool host, size_t src_len, size_t out_bytes);
-// the time between pkw_ev0 and pkw_ev1, behind a synchronise (an event that cannot be read leaves 0)
-uint64_t pkw_event_ns(md_ctx *ctx);
+// md_pack_delta_batch_* and md_pack_delta_sizes_* behind their null checks.  host: src, out and res are the caller's host
+// memory, the call uploads, reads back and waits; else they are device memory and the time stays pending.  kSizes: out_off
+// is ignored and there is no out.
+int delta_batch(md_ctx *ctx, bool host, DeltaKind kind, size_t n, const md_pack_delta_pair *pairs, const uint8_t *src, size_t src_len, uint8_t *out,
+                size_t out_bytes, DeltaResults res);
+// what md_pack_write and md_pack_choose_bases ask of every row: a type of 1 .. 4, the object inside the source and no longer
+// than MD_MAX_STREAM.  `who` begins the error's text.
+int check_sources(md_ctx *ctx, const char *who, size_t n, const md_pack_source *objs, size_t src_len);
 // ---- capi_long_stream.cpp: both return MD_NOT_HANDLED for what the serial path has to answer ----
 int continue_parallel(md_ctx *ctx, const uint8_t *src, size_t src_len, unsigned start_bit, uint8_t *dst, size_t hist_len,
                       size_t dst_cap, uint32_t adler_in, unsigned flags, size_t *dst_len, int *status, md_inf_resume *resume);

@@ -24,7 +24,8 @@
 namespace md {
 namespace pkb {
 
-constexpr uint64_t kPackHeader = 12, kPackTrailer = 20;
+using pack::kPackHeader;
+using pack::kPackTrailer;
 // a candidate needs this many bytes in front of the trailer (no zlib stream is shorter)
 constexpr uint64_t kCandidateMin = 6;
 
@@ -150,10 +151,7 @@ inline int write_index(const md_pack_index_entry *e, size_t n, const uint8_t pac
   }
   uint8_t *tail = big + 8 * m;
   memcpy(tail, pack_checksum, pack::kName);
-  sha::Sha1 s;
-  sha::sha1_init(&s);
-  sha::sha1_update(&s, idx, (size_t)(tail + pack::kName - idx));
-  sha::sha1_final(&s, tail + pack::kName);
+  sha::sha1_of(idx, (size_t)(tail + pack::kName - idx), tail + pack::kName);
   return MD_OK;
 }
 

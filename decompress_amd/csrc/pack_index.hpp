@@ -22,9 +22,18 @@ namespace md {
 namespace pack {
 
 constexpr size_t kIdxHeader = 8, kIdxFan = 1024, kIdxTrailer = 40, kName = 20;
+// the pack itself: "PACK", u32 version, u32 count in front of the objects, the SHA-1 of all that behind them
+constexpr uint64_t kPackHeader = 12, kPackTrailer = 20;
 
 inline uint32_t be32(const uint8_t *p) { return (uint32_t)p[0] << 24 | (uint32_t)p[1] << 16 | (uint32_t)p[2] << 8 | (uint32_t)p[3]; }
 inline uint64_t be64(const uint8_t *p) { return (uint64_t)be32(p) << 32 | be32(p + 4); }
+
+// MD_INVALID_PACK: too short for a header and a trailer, or no "PACK"; MD_PACK_UNSUPPORTED: a version that is neither 2 nor 3
+inline int pack_header_status(const uint8_t *pack, size_t len) {
+  if (len < kPackHeader + kPackTrailer || memcmp(pack, "PACK", 4) != 0) return MD_INVALID_PACK;
+  const uint32_t version = be32(pack + 4);
+  return version == 2 || version == 3 ? MD_OK : MD_PACK_UNSUPPORTED;
+}
 
 // MD_OK, MD_INVALID_INDEX or MD_PACK_UNSUPPORTED; info is filled on MD_OK, and the first min(cap, n) entries
 inline int read_index(const uint8_t *idx, size_t idx_len, md_pack_index_info *info, md_pack_index_entry *entries, size_t cap) {

@@ -1,12 +1,14 @@
 // pack_write.hpp — the host's arithmetic of md_pack_delta_batch_* and md_pack_write (mdeflate.h; capi_pack_write.cpp): the
-// constants of the delta definition, the size of a base's table, the bytes of an object's header and of an OFS_DELTA's
-// distance, the rule that says which deltas are kept, the sequential walk from compressed lengths to offsets, and the
-// bound.  Plain C++: no device code, no md_ctx (tests/pack_write_check.cpp drives it alone under the sanitizers).
+// constants of the delta definition, the size of a base's table and where the tables of a batch's bases go, the bytes of an
+// object's header and of an OFS_DELTA's distance, the rule that says which deltas are kept, the sequential walk from
+// compressed lengths to offsets, and the bound.  Plain C++: no device code, no md_ctx (tests/pack_write_check.cpp drives it
+// alone under the sanitizers).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
 
 #include "mdeflate.h"
+#include "pack_index.hpp"
 
 namespace md {
 namespace pkw {
@@ -22,8 +24,28 @@ inline uint32_t table_bits(uint64_t blocks) {
   return k;
 }
 
+// Where the tables of a batch's distinct bases go.  A base with a block gets, in the order the bases are added, the next
+// run of blocks of the index launch and the next 2^bits words of the tables; a base of fewer than kBlock bytes gets no table
+// (bits 0) and is no row of the index launch.
+struct TablePlace {
+  uint64_t table_off, first_block;
+  uint32_t bits;
+};
+struct TableRoom {
+  uint64_t blocks = 0, words = 0;  // of the bases added so far
+  TablePlace add(uint64_t base_len) {
+    const uint64_t nb = base_len / kBlock;
+    if (nb == 0) return TablePlace{0, 0, 0};
+    const TablePlace at = {words, blocks, table_bits(nb)};
+    blocks += nb;
+    words += (uint64_t)1 << at.bits;
+    return at;
+  }
+};
+
 // ---- md_pack_write ----
-constexpr uint64_t kPackHeader = 12, kPackTrailer = 20;
+using pack::kPackHeader;
+using pack::kPackTrailer;
 constexpr uint32_t kOfsDelta = 6;
 // a delta is tried for a target of at least kDeltaMinTarget bytes on a base of at least kBlock, into nt / 2 - kDeltaSlack bytes
 constexpr uint64_t kDeltaMinTarget = 64, kDeltaSlack = 20;

@@ -155,6 +155,14 @@ inline void sha1_final(Sha1 *s, uint8_t digest[20]) {
   for (int i = 0; i < 20; i++) digest[i] = (uint8_t)(s->h[i >> 2] >> (24 - 8 * (i & 3)));
 }
 
+// one buffer, one message: the trailers of a pack and of an idx
+inline void sha1_of(const void *p, size_t len, uint8_t digest[20]) {
+  Sha1 s;
+  sha1_init(&s);
+  sha1_update(&s, p, len);
+  sha1_final(&s, digest);
+}
+
 // SHA-1 of a git object (type 1 .. 4), or of the bytes as they are (kPlain): the kernel's CPU twin
 inline void sha1_object(uint32_t type, const uint8_t *data, uint32_t size, uint8_t digest[20]) {
   Sha1 s;

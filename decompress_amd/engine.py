@@ -253,6 +253,23 @@ class Engine:
         self._check(self.lib.md_sha1_last(self.ctx, ctypes.byref(s)))
         return {k: getattr(s, k) for k in ("messages", "blocks", "launches", "device_ns")}
 
+    @staticmethod
+    def _delta_rows(pairs, fields=(), caps=None):
+        """md_pack_delta_pair rows: base_off, base_len, tgt_off, tgt_len and then `fields` from each of pairs, out_cap from caps"""
+        rows = (_lib.PackDeltaPair * max(len(pairs), 1))()
+        for i, (r, p) in enumerate(zip(rows, pairs)):
+            for f, v in zip(("base_off", "base_len", "tgt_off", "tgt_len") + fields, p, strict=True):
+                setattr(r, f, int(v))
+            if caps is not None:
+                r.out_cap = int(caps[i])
+        return rows
+
+    @staticmethod
+    def _ranges(objects):
+        """objects = [(off, len)] -> the offsets and the lengths as the sketch calls take them"""
+        u64s = ctypes.c_uint64 * max(len(objects), 1)
+        return u64s(*[int(o) for o, _ in objects]), u64s(*[int(k) for _, k in objects])
+
     def pack_deltas(self, src, pairs, caps=None):
         """md_pack_delta_batch_host: the deltas of pairs = [(base_off, base_len, tgt_off, tgt_len)] into the bytes `src` ->
         [(status, delta bytes)], status 0 = Ok, 2 = the delta passed its room (then no bytes).  caps[i]: the room of delta i;
@@ -263,11 +280,10 @@ class Engine:
             caps = [p[3] + p[3] // 127 + 16 for p in pairs]
         if len(caps) != n:
             raise Error("Invalid argument: one room per pair")
-        rows, at = (_lib.PackDeltaPair * max(n, 1))(), 0
-        for r, p, cap in zip(rows, pairs, caps):
-            r.base_off, r.base_len, r.tgt_off, r.tgt_len = (int(v) for v in p)
-            r.out_off, r.out_cap = at, int(cap)
-            at += (int(cap) + 15) & ~15
+        rows, at = self._delta_rows(pairs, caps=caps), 0
+        for r in rows[:n]:
+            r.out_off = at
+            at += (r.out_cap + 15) & ~15
         out = ctypes.create_string_buffer(max(at, 1))
         out_len, status = (ctypes.c_uint64 * max(n, 1))(), (ctypes.c_int32 * max(n, 1))()
         self._check(self.lib.md_pack_delta_batch_host(self.ctx, n, rows, src, len(src), out, at, out_len, status))
@@ -278,9 +294,7 @@ class Engine:
         """md_pack_delta_batch_device: pairs = [(base_off, base_len, tgt_off, tgt_len, out_off, out_cap)] (host) into the device
         tensors d_src / d_out -> (out_len int64 tensor, status int32 tensor), device, async"""
         n = len(pairs)
-        rows = (_lib.PackDeltaPair * max(n, 1))()
-        for r, p in zip(rows, pairs):
-            r.base_off, r.base_len, r.tgt_off, r.tgt_len, r.out_off, r.out_cap = (int(v) for v in p)
+        rows = self._delta_rows(pairs, ("out_off", "out_cap"))
         out_len = self.torch.zeros(max(n, 1), dtype=self.torch.int64, device=self.device)
         status = self.torch.zeros(max(n, 1), dtype=self.torch.int32, device=self.device)
         self._check(self.lib.md_pack_delta_batch_device(self.ctx, n, rows, _ptr(d_src), _ptr(d_out), _ptr(out_len), _ptr(status)))
@@ -297,8 +311,7 @@ class Engine:
         """md_pack_sketch_host: the four features of every object (off, len) of the bytes `src` -> [(F0, F1, F2, F3)]; an
         object shorter than 16 bytes has none, its words are all ones.  Synchronous."""
         n, src = len(objects), bytes(src)
-        off = (ctypes.c_uint64 * max(n, 1))(*[int(o) for o, _ in objects])
-        length = (ctypes.c_uint64 * max(n, 1))(*[int(k) for _, k in objects])
+        off, length = self._ranges(objects)
         feats = (ctypes.c_uint32 * (4 * max(n, 1)))()
         self._check(self.lib.md_pack_sketch_host(self.ctx, n, off, length, src, len(src), feats))
         return [tuple(feats[4 * i:4 * i + 4]) for i in range(n)]
@@ -307,8 +320,7 @@ class Engine:
         """md_pack_sketch_device: objects = [(off, len)] (host) in the device tensor d_src -> int32 tensor of 4 n words (the
         features' bit patterns), device, async"""
         n = len(objects)
-        off = (ctypes.c_uint64 * max(n, 1))(*[int(o) for o, _ in objects])
-        length = (ctypes.c_uint64 * max(n, 1))(*[int(k) for _, k in objects])
+        off, length = self._ranges(objects)
         feats = self.torch.zeros(4 * max(n, 1), dtype=self.torch.int32, device=self.device)
         self._check(self.lib.md_pack_sketch_device(self.ctx, n, off, length, _ptr(d_src), _ptr(feats)))
         return feats[:4 * n]
@@ -322,10 +334,7 @@ class Engine:
             caps = [(1 << 64) - 1] * n
         if len(caps) != n:
             raise Error("Invalid argument: one bound per pair")
-        rows = (_lib.PackDeltaPair * max(n, 1))()
-        for r, p, cap in zip(rows, pairs, caps):
-            r.base_off, r.base_len, r.tgt_off, r.tgt_len = (int(v) for v in p)
-            r.out_off, r.out_cap = 0, int(cap)
+        rows = self._delta_rows(pairs, caps=caps)
         out_len, status = (ctypes.c_uint64 * max(n, 1))(), (ctypes.c_int32 * max(n, 1))()
         self._check(self.lib.md_pack_delta_sizes_host(self.ctx, n, rows, src, len(src), out_len, status))
         return [(status[i], out_len[i]) for i in range(n)]
@@ -334,9 +343,7 @@ class Engine:
         """md_pack_delta_sizes_device: pairs = [(base_off, base_len, tgt_off, tgt_len, out_cap)] (host) in the device tensor
         d_src -> (out_len int64 tensor, status int32 tensor), device, async"""
         n = len(pairs)
-        rows = (_lib.PackDeltaPair * max(n, 1))()
-        for r, p in zip(rows, pairs):
-            r.base_off, r.base_len, r.tgt_off, r.tgt_len, r.out_cap = (int(v) for v in p)
+        rows = self._delta_rows(pairs, ("out_cap",))
         out_len = self.torch.zeros(max(n, 1), dtype=self.torch.int64, device=self.device)
         status = self.torch.zeros(max(n, 1), dtype=self.torch.int32, device=self.device)
         self._check(self.lib.md_pack_delta_sizes_device(self.ctx, n, rows, _ptr(d_src), _ptr(out_len), _ptr(status)))

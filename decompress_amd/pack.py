@@ -12,6 +12,7 @@ from ._lib import PackSource, PackWriteResult
 from ._lib import load as _load
 
 TYPE_NAMES = {0: None, 1: "commit", 2: "tree", 3: "blob", 4: "tag"}
+_TYPE_OF = {v: k for k, v in TYPE_NAMES.items() if v}
 VERIFY_CRC = 1
 VERIFY_NAMES = 2
 NO_BASE = (1 << 64) - 1
@@ -37,6 +38,24 @@ def _flags(crc, names):
     return (VERIFY_CRC if crc else 0) | (VERIFY_NAMES if names else 0)
 
 
+def _type(t):
+    return _TYPE_OF[t] if isinstance(t, str) else int(t)
+
+
+def _sources(objects, bases=None):
+    """objects = [(type, bytes)] laid out back to back -> (the md_pack_source rows, that blob); bases[i]: an index or None"""
+    src, at = (PackSource * max(len(objects), 1))(), 0
+    for i, (s, (t, b)) in enumerate(zip(src, objects)):
+        s.off, s.len, s.type = at, len(b), _type(t)
+        s.base = NO_BASE if bases is None or bases[i] is None else int(bases[i])
+        at += len(b)
+    return src, b"".join(bytes(b) for _, b in objects)
+
+
+def _select(select, k):
+    return None if select is None else (ctypes.c_uint64 * max(k, 1))(*[int(i) for i in select])
+
+
 def index(idx):
     """md_pack_index (host arithmetic, no device needed) -> (entries, info): one dict per object in the idx's order - name
     (20 bytes), offset, crc32 - and a dict of the idx's: n, has_64bit_table, pack_checksum.  Raises `Error` ("Invalid
@@ -57,8 +76,7 @@ def index(idx):
 def hash_objects(types, bufs, device=0):
     """`git hash-object` for a batch: the 20-byte names of the objects whose contents are `bufs` and whose types are `types`
     (1 commit, 2 tree, 3 blob, 4 tag, or those words), hashed on the GPU (md_sha1_batch_host)"""
-    by_name = {v: k for k, v in TYPE_NAMES.items() if v}
-    types = [by_name[t] if isinstance(t, str) else int(t) for t in types]
+    types = [_type(t) for t in types]
     if any(not 1 <= t <= 4 for t in types):
         raise ValueError("a git object is a commit, a tree, a blob or a tag")
     return _engine.default_engine(device).sha1_batch(bufs, types)
@@ -156,13 +174,7 @@ def write_raw(objects, bases=None, level=6, max_depth=50, flags=0, pack_cap=None
     """md_pack_write as it is: objects = [(type, bytes)] -> (return value, pack bytes, pack_len, entries as dicts,
     md_pack_write_result as a dict).  pack_cap None: md_pack_write_bound's."""
     eng, n = _engine.default_engine(device), len(objects)
-    by_name = {v: k for k, v in TYPE_NAMES.items() if v}
-    src = (PackSource * max(n, 1))()
-    blob, at = b"".join(bytes(b) for _, b in objects), 0
-    for i, (s, (t, b)) in enumerate(zip(src, objects)):
-        s.off, s.len, s.type = at, len(b), by_name[t] if isinstance(t, str) else int(t)
-        s.base = NO_BASE if bases is None or bases[i] is None else int(bases[i])
-        at += len(b)
+    src, blob = _sources(objects, bases)
     cap = int(eng.lib.md_pack_write_bound(n, src)) if pack_cap is None else pack_cap
     out = ctypes.create_string_buffer(max(cap, 1))
     ents, need, res = (PackIndexEntry * max(n, 1))(), ctypes.c_size_t(0), PackWriteResult()
@@ -172,21 +184,12 @@ def write_raw(objects, bases=None, level=6, max_depth=50, flags=0, pack_cap=None
     return rc, out.raw[:need.value] if rc == 0 else b"", need.value, entries, {k: getattr(res, k) for k in _WRITE_RESULT_KEYS}
 
 
-def _typed(objects):
-    by_name = {v: k for k, v in TYPE_NAMES.items() if v}
-    return [(by_name[t] if isinstance(t, str) else int(t), b) for t, b in objects]
-
-
 def choose_bases_raw(objects, window=4, max_depth=50, device=0):
     """md_pack_choose_bases as it is: objects = [(type, bytes)] -> (return value, order, bases): order[r] = the input index at
     rank r of the pack order, bases[r] = the RANK of the base chosen for the object at rank r, or None."""
     eng, n = _engine.default_engine(device), len(objects)
-    src, out = (PackSource * max(n, 1))(), (PackSource * max(n, 1))()
+    (src, blob), out = _sources(objects), (PackSource * max(n, 1))()
     order = (ctypes.c_uint64 * max(n, 1))()
-    blob, at = b"".join(bytes(b) for _, b in objects), 0
-    for s, (t, b) in zip(src, _typed(objects)):
-        s.off, s.len, s.type, s.base = at, len(b), t, NO_BASE
-        at += len(b)
     rc = eng.lib.md_pack_choose_bases(eng.ctx, window, max_depth, n, src, blob, len(blob), out, order)
     if rc != 0:
         return rc, [], []
@@ -275,7 +278,7 @@ class Pack:
     def read_raw(self, select=None, verify_crc=False, dst_cap=None, verify_names=False):
         """md_pack_read as it is: (return value, statuses, out_off, bytes of dst, md_pack_result as a dict)"""
         k = len(self.objects) if select is None else len(select)
-        sel = None if select is None else (ctypes.c_uint64 * max(k, 1))(*[int(i) for i in select])
+        sel = _select(select, k)
         need = sum(self.objects[i]["size"] for i in (range(k) if select is None else select) if 0 <= i < len(self.objects))
         cap = need if dst_cap is None else dst_cap
         dst = ctypes.create_string_buffer(max(cap, 1))
@@ -299,7 +302,7 @@ class Pack:
     def verify_raw(self, select=None, flags=VERIFY_CRC | VERIFY_NAMES):
         """md_pack_verify as it is: (return value, statuses, md_pack_result as a dict)"""
         k = len(self.objects) if select is None else len(select)
-        sel = None if select is None else (ctypes.c_uint64 * max(k, 1))(*[int(i) for i in select])
+        sel = _select(select, k)
         status, res = (ctypes.c_int32 * max(k, 1))(), PackResult()
         rc = self._eng.lib.md_pack_verify(self._eng.ctx, self._h, self._pack, len(self._pack), sel, k, flags, status, ctypes.byref(res))
         return rc, list(status[:k]), {"entries": res.entries, "failed": res.failed, "written": res.written}

@@ -22,6 +22,7 @@ SKETCH_EDGES = {
 SEARCH_EDGES = {
     "a group larger than window", "one candidate through two features", "equal lengths by index", "two types never paired", "target below 64, base below 16",
     "two identical objects", "max_depth 1 2 0 on a chain", "equal delta lengths", "nothing fits", "n = 0", "shuffled version chains",
+    "one base of three targets, two bases of equal bytes",
 }
 ALIGNMENTS = wc.ALIGNMENTS
 rnd = wc.rnd
@@ -102,6 +103,17 @@ def shuffled_chains():
     return [objects[i] for i in perm], [int(i) // 8 for i in perm]
 
 
+def plan_objects():
+    """Seven blobs for window 1, where a target is scored against the nearest object in front of it in each of its four groups.
+    S carries a planted block for each of the features 0, 1 and 2, and T0, T1, T2 are its three thirds, one block in each
+    and no window in common: S is the base of all three, and none of them of another.  C stands twice, and D is C's first 400 bytes: the second C is scored against the first, D
+    against the second - two bases of equal bytes at two addresses."""
+    parts = [rnd(150, 940 + k) for k in range(4)]
+    S = parts[0] + sm.planted(0, 944) + parts[1] + sm.planted(1, 945) + parts[2] + sm.planted(2, 946) + parts[3]
+    C = rnd(200, 947) + sm.planted(3, 948) + rnd(500, 949)
+    return [(3, S), (3, S[:216]), (3, S[216:432]), (3, S[432:]), (3, C), (3, C), (3, C[:400])]
+
+
 @functools.lru_cache(maxsize=None)
 def search_cases():
     out = []
@@ -152,6 +164,10 @@ def search_cases():
                 [t["bases"] for t in ts] == [[None, 0, 0, 0, 0], [None, 0, 1, 1, 1], [None, 0, 1, 2, 3]] and
                 [t["depth"] for t in ts] == [[0, 1, 1, 1, 1], [0, 1, 2, 2, 2], [0, 1, 2, 3, 4]] and
                 (2, 1) in ts[0]["skipped"] and (3, 2) in ts[1]["skipped"] and ts[2]["skipped"] == []})
+    # -- what the plan of a delta batch is made of: a base shared by three pairs, equal bytes at two addresses (window 1)
+    out.append({"name": "one base, three targets", "edges": {"one base of three targets, two bases of equal bytes"}, "objects": plan_objects(), "window": 1,
+                "runs": [50], "claim": lambda ts: ts[0]["order"] == [4, 5, 0, 6, 1, 2, 3] and ts[0]["pairs"] == [(1, 0), (3, 1), (4, 2), (5, 2), (6, 2)] and
+                all(st == dm.MD_OK for st, _ in ts[0]["scores"]) and ts[0]["bases"] == [None, 0, None, 1, 2, 2, 2]})
     out.append({"name": "nothing", "edges": {"n = 0"}, "objects": [], "window": 4, "runs": [50],
                 "claim": lambda ts: ts[0]["order"] == [] and ts[0]["last"] == {"featured": 0, "pairs": 0, "fitted": 0, "chosen": 0}})
     objs, chain = shuffled_chains()

@@ -3,6 +3,7 @@
 //   T <blocks>                                          -> table_bits
 //   H <type> <size>                                     -> the object header's bytes in hex
 //   O <distance>                                        -> the OFS_DELTA distance's bytes in hex
+//   P <n> then n x <base len>                           -> "<blocks> <table words>" then n x "<table_off>:<first_block>:<bits>"
 //   B <n> then n x <len>                                -> write_bound
 //   K <max_depth> <n> then n x (<base> <tried> <fitted>) -> "<kept> <dropped_size> <dropped_depth>" then n x "<keep>:<depth>"
 //   W <n> then n x (<type> <size> <base> <keep> <zlen>)  -> offset[n] then n x "<offset>:<header bytes in hex>"
@@ -52,6 +53,15 @@ int main(int argc, char **argv) {
       hex(out, md::pkw::ofs_varint(strtoull(p, &p, 10), out));
       printf("\n");
       free(out);
+    } else if (kind == 'P') {
+      const size_t n = strtoull(p, &p, 10);
+      md::pkw::TablePlace *at = exact<md::pkw::TablePlace>(n);
+      md::pkw::TableRoom room;
+      for (size_t i = 0; i < n; i++) at[i] = room.add(strtoull(p, &p, 10));
+      printf("%llu %llu", (unsigned long long)room.blocks, (unsigned long long)room.words);
+      for (size_t i = 0; i < n; i++) printf(" %llu:%llu:%u", (unsigned long long)at[i].table_off, (unsigned long long)at[i].first_block, at[i].bits);
+      printf("\n");
+      free(at);
     } else if (kind == 'B') {
       const size_t n = strtoull(p, &p, 10);
       md_pack_source *objs = exact<md_pack_source>(n);

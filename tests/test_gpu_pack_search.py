@@ -111,6 +111,22 @@ def test_delta_sizes_device_form(eng, family):
         assert eng.pack_write_last()["delta_ns"] > 0
 
 
+def test_a_sketch_leaves_the_writers_stats_alone(eng):
+    """md_pack_write_last after a device-form delta batch and a stand-alone sketch behind it: the batch's counts, a time, and
+    the same answer when asked again (the sketch records into no span of the batch's)"""
+    import torch
+    a = wc.rnd(600, 31)
+    blob = a + a[:300] + a[100:500]
+    d_src = torch.from_numpy(np.frombuffer(blob, dtype=np.uint8).copy()).to(eng.device)
+    d_out = torch.zeros(512, dtype=torch.uint8, device=eng.device)
+    _, status = eng.pack_deltas_device([(0, 600, 600, 300, 0, 256), (0, 600, 900, 400, 256, 256)], d_src, d_out)
+    assert len(eng.pack_sketch(blob, [(0, 600), (600, 300), (900, 400)])) == 3
+    last = eng.pack_write_last()
+    assert last["pairs"] == 2 and last["launches"] == 2 and last["delta_ns"] > 0
+    assert eng.pack_write_last() == last
+    assert status.cpu().tolist() == [dm.MD_OK, dm.MD_OK]
+
+
 def _written(mp, objects, bases, level, max_depth):
     rc, pack, need, entries, res = mp.write_raw(objects, bases, level=level, max_depth=max_depth)
     assert rc == 0 and need == len(pack)

@@ -78,6 +78,32 @@ def test_every_case_device_form(eng, family):
             assert raw[o + c:nxt] == b"\xee" * (int(nxt) - int(o) - c)
 
 
+def test_one_plan_from_two_routes(eng):
+    """md_pack_choose_bases lays the tables of its candidates out by rank; md_pack_delta_sizes_host finds the distinct bases of
+    the same pairs by sorting them.  Both go through one builder: the sizes of the pairs the search scores for
+    pack_search_cases.plan_objects() with window 1 - one base of three targets, equal bytes at two addresses as two bases -
+    are the scores the search's model saw.  A search never scores a base shorter than its target, and no target has fewer
+    than 64 bytes, so the base of 15 bytes (no table) and the one of exactly 16 (one block) come as two pairs more, without a
+    bound, against the delta model."""
+    from tests import pack_search_cases as sc
+    case = sc.case("one base, three targets")
+    trace = sc.search_model(case["name"])[0]
+    datas = [case["objects"][i][1] for i in trace["order"]]  # by rank
+    target = datas[3]
+    blob, rows = sc.laid_out(datas + [target[:15], target[:16]])
+    pairs = [rows[b] + rows[t] for t, b in trace["pairs"]] + [rows[7] + rows[3], rows[8] + rows[3]]
+    caps = [dm.delta_cap(rows[t][1]) for t, _ in trace["pairs"]] + [1 << 40] * 2
+    want = list(trace["scores"]) + [dm.delta_result(target[:k], target, 1 << 40)[:2] for k in (15, 16)]
+    # the case on the CPU: five distinct bases, four with a table of 2^10 words, two of them of equal bytes
+    bases = sorted({p[:2] for p in pairs})
+    assert [n for _, n in bases] == [716, 716, 648, 15, 16] and datas[0] == datas[1] and rows[0][0] != rows[1][0]
+    assert [dm.table_bits(n // dm.BLOCK) for _, n in bases if n >= dm.BLOCK] == [10] * 4
+    assert sorted(p[:2] for p in pairs).count(rows[2]) == 3 and all(st == dm.MD_OK for st, _ in want)
+    assert eng.pack_delta_sizes(blob, pairs, caps) == want
+    last = eng.pack_write_last()
+    assert last["pairs"] == 7 and last["launches"] == 2 and last["delta_ns"] > 0
+
+
 def test_delta_batch_misuse(eng):
     from decompress_amd import _lib
     lib = eng.lib

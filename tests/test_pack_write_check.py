@@ -1,4 +1,4 @@
-"""csrc/pack_write.hpp - the table's size, the header and distance bytes, the keep rule, the walk over the offsets and the
+"""csrc/pack_write.hpp - the table's size, where the tables of a batch's bases go, the header and distance bytes, the keep rule, the walk over the offsets and the
 bound - under AddressSanitizer and UBSan, as a stand-alone host program (pack_write_check.cpp, nothing preloaded, no
 device), against the model's numbers (tests/pack_delta_model.py, tests/pack_writer.py) for the same inputs: the values at
 which a varint grows, every pack of tests/pack_write_cases.py as the model laid it out, and keep rules over made-up chains."""
@@ -21,6 +21,16 @@ def _lines():
     out = []
     for blocks in (0, 1, 511, 512, 513, 1024, 1025, 1 << 20, (1 << 20) + 1, (1 << 28) - 1):
         out.append(("T %d" % blocks, "%d" % dm.table_bits(blocks)))
+    # the tables of a batch's distinct bases, in the order they are added: test_gpu_pack_write.test_one_plan_from_two_routes'
+    # bases as the delta batch meets them and as the search does, and bases at which a table grows
+    for lens in ([716, 716, 648, 15, 16], [716, 716, 648], [], [15], [16], [15, 31, 32, 0, 47], [8207, 8208, 15, 16400, 1 << 20, 0xFFFFFFF0, 16]):
+        blocks = words = 0
+        places = []
+        for n in lens:
+            nb = n // dm.BLOCK
+            places.append(" %d:%d:%d" % ((words, blocks, dm.table_bits(nb)) if nb else (0, 0, 0)))
+            blocks, words = blocks + nb, words + ((1 << dm.table_bits(nb)) if nb else 0)
+        out.append(("P %d %s" % (len(lens), " ".join(map(str, lens))), "%d %d" % (blocks, words) + "".join(places)))
     sizes = [0, 1, 15, 16, 2047, 2048, (1 << 18) - 1, 1 << 18, (1 << 25) - 1, 1 << 25, 0xFFFFFFF0, (1 << 64) - 1]
     for t in (1, 2, 3, 4, 6):
         for s in sizes:
