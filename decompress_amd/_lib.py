@@ -195,6 +195,13 @@ SYMBOLS = [
     ("md_pack_delta_sizes_host", ctypes.c_int, [c_vp, c_sz, c_vp, c_vp, c_sz, c_vp, c_vp]),
     ("md_pack_choose_bases", ctypes.c_int, [c_vp, ctypes.c_uint32, ctypes.c_uint32, c_sz, c_vp, c_vp, c_sz, c_vp, c_vp]),
     ("md_pack_search_last", ctypes.c_int, [c_vp, c_vp]),
+    ("md_pack_graph_build", ctypes.c_int, [c_vp, c_vp, c_vp, c_sz, ctypes.c_uint, ctypes.POINTER(c_vp)]),
+    ("md_pack_graph_get", ctypes.c_int, [c_vp, c_vp]),
+    ("md_pack_graph_edges", ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_sz]),
+    ("md_pack_graph_status", ctypes.c_int, [c_vp, c_vp]),
+    ("md_pack_reachable", ctypes.c_int, [c_vp, c_vp, c_vp, c_sz, c_vp, c_sz, c_vp, c_vp]),
+    ("md_pack_reach_last", ctypes.c_int, [c_vp, c_vp]),
+    ("md_pack_graph_free", None, [c_vp]),
 ]
 
 
@@ -283,6 +290,17 @@ class PackWriteResult(ctypes.Structure):
 class PackSearchStats(ctypes.Structure):
     """md_pack_search_stats of include/mdeflate.h"""
     _fields_ = [(k, ctypes.c_uint64) for k in ("featured", "pairs", "fitted", "chosen", "launches", "sketch_ns", "score_ns", "host_ns")]
+
+
+class PackGraphInfo(ctypes.Structure):
+    """md_pack_graph_info of include/mdeflate.h"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("n", "edges", "absent", "mistyped", "malformed", "failed", "parsed", "rounds", "parse_launches",
+                                                "device_ns")]
+
+
+class PackReachStats(ctypes.Structure):
+    """md_pack_reach_stats of include/mdeflate.h"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("host_closed", "seeds", "rounds", "expanded", "marked", "device_ns")]
 
 
 class PackWriteStats(ctypes.Structure):

@@ -31,7 +31,12 @@ struct RoundDesc {
   int32_t *status = nullptr;
   Delta *deltas = nullptr;
   Repeat *repeats = nullptr;
-  void carve(md::Carver *c, size_t count, size_t ndelta, size_t nrepeat) {
+  // the link pass of md_pack_graph_build (nlink = count, else 0): where every stream's object stands, its size, type and
+  // object, and the streams that are trees / commits and tags
+  uint64_t *l_off = nullptr, *l_size = nullptr;
+  uint32_t *l_obj = nullptr, *l_trees = nullptr, *l_others = nullptr;
+  uint8_t *l_type = nullptr;
+  void carve(md::Carver *c, size_t count, size_t ndelta, size_t nrepeat, size_t nlink = 0) {
     rows = c->take<Stream>(count);
     uint64_t **m64[10] = {&in_off, &in_len, &out_off, &out_cap, &out_len, &consumed, &p_off, &p_len, &base_size, &result_size};
     for (uint64_t **p : m64) *p = c->take<uint64_t>(count);
@@ -39,6 +44,9 @@ struct RoundDesc {
     status = c->take<int32_t>(count);
     deltas = c->take<Delta>(ndelta);
     repeats = c->take<Repeat>(nrepeat);
+    l_off = c->take<uint64_t>(nlink), l_size = c->take<uint64_t>(nlink);
+    l_obj = c->take<uint32_t>(nlink), l_trees = c->take<uint32_t>(nlink), l_others = c->take<uint32_t>(nlink);
+    l_type = c->take<uint8_t>(nlink);
   }
 };
 
@@ -266,30 +274,7 @@ int pack_table(md_ctx *ctx, const uint8_t *pack, size_t pack_len, const PackTabl
 }
 
 namespace {
-// pairs of events around a step of the rounds of a read - the apply launches (md_pack_stats::apply_ns), the hash passes
-// (md_sha1_stats::device_ns); an event that cannot be had leaves the time 0, never fails the read
-struct PairTimers {
-  std::vector<hipEvent_t> ev;
-  void mark(hipStream_t st) {
-    hipEvent_t e = nullptr;
-    if (hipEventCreate(&e) != hipSuccess) e = nullptr, (void)hipGetLastError();
-    if (e && hipEventRecord(e, st) != hipSuccess) (void)hipGetLastError();
-    ev.push_back(e);
-  }
-  uint64_t total_ns() const {  // (behind a synchronise of the stream)
-    double ms = 0;
-    for (size_t k = 0; k + 1 < ev.size(); k += 2) {
-      float t = 0;
-      if (ev[k] && ev[k + 1] && hipEventElapsedTime(&t, ev[k], ev[k + 1]) == hipSuccess) ms += t;
-      else (void)hipGetLastError();
-    }
-    return (uint64_t)(ms * 1e6);
-  }
-  ~PairTimers() {
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
-};
+using md::PairTimers;
 
 // one round of a read
 struct ReadRound : RoundStreams {
@@ -308,14 +293,17 @@ struct ReadRound : RoundStreams {
   std::vector<uint32_t> differs;
   std::vector<uint8_t> digest;  // md_pack_index_build: what the hash pass found, 20 bytes a slot
   Sha1Batch sha;
+  std::vector<uint32_t> trees, others;  // md_pack_graph_build: the streams whose object is a tree / a commit or a tag
 };
 
 // md_pack_read (keep: the selected objects stand in dst, out_off[k + 1] says where) and md_pack_verify (!keep: they stand in
 // the round's scratch like the bases, dst and out_off are null, nothing but the statuses comes back).  sink (with !keep:
 // md_pack_index_build): the hash pass runs, an object whose name is not known yet gets what the pass found written to
 // sink->names, one that has a name is compared as MD_PACK_VERIFY_NAME compares it; the pack is on the device already.
+// links (with !keep: md_pack_graph_build): the link pass runs behind every round's last apply launch, over every object
+// of the round where it stands.
 int pack_read(md_ctx *ctx, const md_pack *P, const uint8_t *pack, const uint64_t *select, size_t k, unsigned flags, bool keep, uint8_t *dst,
-              size_t dst_cap, uint64_t *out_off, int32_t *status, md_pack_result *res, const PackNameSink *sink) {
+              size_t dst_cap, uint64_t *out_off, int32_t *status, md_pack_result *res, const PackNameSink *sink, PackLinkSink *links) {
   const size_t n = P->objs.size();
   for (size_t j = 0; select && j < k; j++)
     if (select[j] >= n) return fail(ctx, MD_E_INVALID_ARGUMENT, "selected object out of range");
@@ -408,14 +396,18 @@ int pack_read(md_ctx *ctx, const md_pack *P, const uint8_t *pack, const uint64_t
     for (size_t q = 0; q < perm.size(); q++) dl[q] = R.deltas[perm[q]], dd[q] = R.delta_depth[perm[q]];
     R.deltas.swap(dl), R.delta_depth.swap(dd);
     R.status.assign(R.obj.size(), 0);
-    if (names) {
-      R.differs.assign(R.obj.size(), 0);
+    if (names) R.differs.assign(R.obj.size(), 0);
+    if (names || links)
       for (uint32_t o : R.obj) {
         R.size.push_back(P->objs[o].size);
         R.type.push_back((uint8_t)P->objs[o].type);
-        R.names.insert(R.names.end(), P->objs[o].name, P->objs[o].name + 20);
+        if (names) R.names.insert(R.names.end(), P->objs[o].name, P->objs[o].name + 20);
       }
-    }
+    if (links)
+      for (uint32_t q = 0; q < R.obj.size(); q++) {  // (an object of another type has no links: neither kernel sees it)
+        if (R.type[q] == 2) R.trees.push_back(q);
+        else if (R.type[q] == 1 || R.type[q] == 4) R.others.push_back(q);
+      }
     max_scratch = std::max(max_scratch, R.scratch);
     max_count = std::max(max_count, R.obj.size());
     max_deltas = std::max(max_deltas, R.deltas.size());
@@ -430,14 +422,14 @@ int pack_read(md_ctx *ctx, const md_pack *P, const uint8_t *pack, const uint64_t
   if (rc == MD_OK) rc = ctx->scratch[kHostOut].reserve(ctx, scratch0 + max_scratch + 64, "hipMalloc(pack output and scratch)");
   if (rc != MD_OK) return rc;
   RoundDesc d;
-  rc = carve(ctx, ctx->scratch[kPackRound], "hipMalloc(pack round descriptors)", [&](md::Carver &c) { d.carve(&c, max_count, max_deltas, max_repeats); });
+  rc = carve(ctx, ctx->scratch[kPackRound], "hipMalloc(pack round descriptors)", [&](md::Carver &c) { d.carve(&c, max_count, max_deltas, max_repeats, links ? max_count : 0); });
   if (rc != MD_OK) return rc;
   const uint8_t *d_pack = ctx->scratch[kHostIn].as<uint8_t>();
   uint8_t *d_buf = ctx->scratch[kHostOut].as<uint8_t>();
   md_pack_stats &stats = ctx->pack_last;
   stats.bytes_in = P->pack_len;
   const bool verify = (flags & MD_PACK_VERIFY_CRC) != 0;
-  PairTimers timers, hash_timers;
+  PairTimers timers, hash_timers, link_timers;
   md_sha1_stats &hashed = ctx->sha1_last;
   // -- the rounds, one behind the other on the context's stream: only the statuses come back
   for (ReadRound &R : rounds) {
@@ -466,6 +458,21 @@ int pack_read(md_ctx *ctx, const md_pack *P, const uint8_t *pack, const uint64_t
         HIP_TRY(ctx, md::to_host(R.digest.data(), R.sha.digest, count * kSha1Bytes, st));
       }
     }
+    if (links) {  // behind the round's last apply launch as well: what every commit, tree and tag of the round names
+      HIP_TRY(ctx, md::to_device(d.l_off, R.res_off, st));
+      HIP_TRY(ctx, md::to_device(d.l_size, R.size, st));
+      HIP_TRY(ctx, md::to_device(d.l_type, R.type, st));
+      HIP_TRY(ctx, md::to_device(d.l_obj, R.obj, st));
+      HIP_TRY(ctx, md::to_device(d.l_trees, R.trees, st));
+      HIP_TRY(ctx, md::to_device(d.l_others, R.others, st));
+      md::pkg::Round rr = {(uint32_t)R.trees.size(), d.l_trees, d.l_obj, d.l_off, d.l_size, d.l_type, d.status};
+      link_timers.mark(st);
+      MD_LAUNCH_TRY(ctx, md_launch_pkg_tree_links(&rr, &links->links, d_buf, st));
+      rr.count = (uint32_t)R.others.size(), rr.slot = d.l_others;
+      MD_LAUNCH_TRY(ctx, md_launch_pkg_object_links(&rr, &links->links, d_buf, st));
+      link_timers.mark(st);
+      links->launches += !R.trees.empty() + !R.others.empty();
+    }
     if (!R.repeats.empty()) {
       HIP_TRY(ctx, md::to_device(d.repeats, R.repeats, st));
       MD_LAUNCH_TRY(ctx, md_launch_pk_repeats((uint32_t)R.repeats.size(), d.repeats, d_buf, st));
@@ -477,6 +484,7 @@ int pack_read(md_ctx *ctx, const md_pack *P, const uint8_t *pack, const uint64_t
   }
   HIP_TRY(ctx, hipStreamSynchronize(st));
   stats.apply_ns = timers.total_ns();
+  if (links) links->device_ns = link_timers.total_ns();
   if (names) {
     hashed.device_ns = hash_timers.total_ns();
     // The names' verdicts, in the order of the header's rules: a status of its own stays; else a failed base; else the
@@ -509,7 +517,12 @@ int pack_read(md_ctx *ctx, const md_pack *P, const uint8_t *pack, const uint64_t
 }  // namespace
 
 int pack_verify_names(md_ctx *ctx, const md_pack *P, const uint64_t *select, size_t k, int32_t *status, md_pack_result *res, const PackNameSink *sink) {
-  return pack_read(ctx, P, nullptr, select, k, 0, false, nullptr, 0, nullptr, status, res, sink);
+  return pack_read(ctx, P, nullptr, select, k, 0, false, nullptr, 0, nullptr, status, res, sink, nullptr);
+}
+
+int pack_link_rounds(md_ctx *ctx, const md_pack *P, const uint8_t *pack, const uint64_t *select, size_t k, unsigned flags, int32_t *status,
+                     md_pack_result *res, PackLinkSink *links) {
+  return pack_read(ctx, P, pack, select, k, flags, false, nullptr, 0, nullptr, status, res, nullptr, links);
 }
 
 int md_pack_index(const uint8_t *idx, size_t idx_len, md_pack_index_info *info, md_pack_index_entry *entries, size_t cap) {
@@ -581,7 +594,7 @@ int md_pack_read(md_ctx *ctx, const md_pack *p, const uint8_t *pack, size_t pack
   const int rc = pack_checks(ctx, false, out_off && (dst || !dst_cap), p, pack, pack_len, select, nselect, flags, status, res, &k);
   if (rc != MD_OK) return rc;
   return no_bad_alloc(ctx, "host memory for the read's plan",
-                      [&] { return pack_read(ctx, p, pack, select, k, flags, true, dst, dst_cap, out_off, status, res, nullptr); });
+                      [&] { return pack_read(ctx, p, pack, select, k, flags, true, dst, dst_cap, out_off, status, res, nullptr, nullptr); });
 }
 
 int md_pack_verify(md_ctx *ctx, const md_pack *p, const uint8_t *pack, size_t pack_len, const uint64_t *select, size_t nselect, unsigned flags,
@@ -591,5 +604,5 @@ int md_pack_verify(md_ctx *ctx, const md_pack *p, const uint8_t *pack, size_t pa
   const int rc = pack_checks(ctx, true, true, p, pack, pack_len, select, nselect, flags, status, res, &k);
   if (rc != MD_OK) return rc;
   return no_bad_alloc(ctx, "host memory for the verification's plan",
-                      [&] { return pack_read(ctx, p, pack, select, k, flags, false, nullptr, 0, nullptr, status, res, nullptr); });
+                      [&] { return pack_read(ctx, p, pack, select, k, flags, false, nullptr, 0, nullptr, status, res, nullptr, nullptr); });
 }

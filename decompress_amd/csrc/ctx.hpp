@@ -136,6 +136,32 @@ struct EventSpan {
   }
 };
 
+// pairs of events around a step that a call repeats - the apply launches of a read's rounds (md_pack_stats::apply_ns), the
+// hash passes (md_sha1_stats::device_ns), the link passes and the steps of a walk (capi_pack_graph.cpp); an event that
+// cannot be had leaves the time 0, never fails the call
+struct PairTimers {
+  std::vector<hipEvent_t> ev;
+  void mark(hipStream_t st) {
+    hipEvent_t e = nullptr;
+    if (hipEventCreate(&e) != hipSuccess) e = nullptr, (void)hipGetLastError();
+    if (e && hipEventRecord(e, st) != hipSuccess) (void)hipGetLastError();
+    ev.push_back(e);
+  }
+  uint64_t total_ns() const {  // (behind a synchronise of the stream)
+    double ms = 0;
+    for (size_t k = 0; k + 1 < ev.size(); k += 2) {
+      float t = 0;
+      if (ev[k] && ev[k + 1] && hipEventElapsedTime(&t, ev[k], ev[k + 1]) == hipSuccess) ms += t;
+      else (void)hipGetLastError();
+    }
+    return (uint64_t)(ms * 1e6);
+  }
+  ~PairTimers() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+
 }  // namespace md
 
 // The context's grow-only scratch.  md_set_option "release_workspace" gives back exactly these, in this order (they grow
@@ -181,6 +207,10 @@ enum Scratch {
   // kHostIn, the pack in kHostOut).  Sketches (md_pack_sketch_*, md_pack_choose_bases): segments and features in kPkwDesc,
   // in front of the plan that md_pack_choose_bases puts there next; the objects in kHostIn
   kPkwDesc, kPkwTables, kPkwObjs, kPkwSlots,
+  // the object graph of a pack (md_pack_graph_build): the names, fan-out and types the link kernels look up in, the slots'
+  // offsets, the edge counts and the malformed flags in kPkgDesc, the bound-sized edge slots in kPkgSlots (the compacted
+  // edges are the graph's own).  md_pack_reachable: marks, frontiers, seeds and the result in kPkgDesc
+  kPkgDesc, kPkgSlots,
   kScratchCount
 };
 
@@ -263,6 +293,8 @@ struct md_ctx {
   md::EventSpan pkw_span;
   // choosing bases: the counts and times of the last md_pack_choose_bases (md_pack_search_last)
   md_pack_search_stats pack_search_last = {};
+  // walking a pack's graph: the counts and the time of the last md_pack_reachable (md_pack_reach_last)
+  md_pack_reach_stats pack_reach_last = {};
   // one stream written as joined spans: md_set_option "deflate_span_kib" (the span of a call that passes 0) and the counts of
   // the last md_deflate_spans_* call (md_deflate_spans_last)
   size_t span_bytes = md::kSpanDefault;
@@ -528,6 +560,15 @@ struct PackNameSink {
 };
 int pack_verify_names(md_ctx *ctx, const md_pack *P, const uint64_t *select, size_t k, int32_t *status, md_pack_result *res,
                       const PackNameSink *sink);
+// md_pack_verify's rounds with the link pass (md_pack_graph_build, capi_pack_graph.cpp): behind every round's last apply launch
+// the two link kernels run over every object of the round where it stands, into `links` (device arrays, the caller's).  The
+// call adds its launches of them and leaves their device time; status[j] is the read's for select[j].
+struct PackLinkSink {
+  md::pkg::Links links = {};
+  uint64_t launches = 0, device_ns = 0;
+};
+int pack_link_rounds(md_ctx *ctx, const md_pack *P, const uint8_t *pack, const uint64_t *select, size_t k, unsigned flags, int32_t *status,
+                     md_pack_result *res, PackLinkSink *links);
 // ---- capi_pack_write.cpp: the delta batch, as md_pack_delta_sizes_* and md_pack_choose_bases (capi_pack_search.cpp) use it too ----
 // The pairs as the kernels take them, the distinct bases that have a block, and what their tables need.  A builder calls
 // add_base once per distinct base, in the order the tables shall stand in, and pair() for every pair with its base's place.

@@ -326,6 +326,44 @@ struct Seg {
 static_assert(sizeof(Seg) == 16, "Seg is uploaded as is");
 }  // namespace pks
 
+namespace pkg {
+// The object graph of a pack (pack_graph_kernels.hip; the rules are mdeflate.h's, the parse functions pack_graph.hpp's).
+// What the link kernels look names up in and where their edges go.  names / fan / type: the idx's names (n of 20 bytes,
+// ascending: name k is object k's), its fan-out (fan[b] = the names whose first byte is at most b) and every object's type
+// (its root's; 0: not known).  Object o's edges go to to / kind from slot_off[o] on - a slot holds pack_graph.hpp's
+// edge_bound of them -, their number to deg[o]; bad[o] = 1: its links cannot be read (deg[o] is 0 then).
+struct Links {
+  const uint8_t *names;
+  const uint32_t *fan;
+  const uint8_t *type;
+  uint64_t n;
+  const uint64_t *slot_off;
+  uint32_t *to;
+  uint8_t *kind;
+  uint32_t *deg;
+  uint8_t *bad;
+};
+// The streams of a round of a read that one of the two kernels looks at, q = slot[0 .. count): object obj[q] of type
+// type[q] stands at buf + off[q], size[q] bytes, where the round's last apply launch left it with status[q]
+struct Round {
+  uint32_t count;
+  const uint32_t *slot, *obj;
+  const uint64_t *off, *size;
+  const uint8_t *type;
+  const int32_t *status;
+};
+// bytes of a tree that one step of the tree kernel looks at: an aligned dword a lane
+constexpr uint32_t kTreeWindow = 256;
+// One walk over the graph: first / to are the compacted edges (first: n + 1), mark one word an object (0 or 1), next / next_len
+// the frontier that a step appends to
+struct Reach {
+  const uint64_t *first;
+  const uint32_t *to;
+  uint32_t *mark;
+  uint32_t *next, *next_len;
+};
+}  // namespace pkg
+
 namespace sha {
 // SHA-1 of many messages, one a lane (sha1_kernels.hip).  Message m is data[off[m], off[m] + len[m]) with the header of
 // a git object of type[m] in front (1 commit, 2 tree, 3 blob, 4 tag; 0, or type == null: the bytes as they are), len[m] at
@@ -569,6 +607,21 @@ int md_launch_pks_sketch(uint32_t count, const md::pks::Seg *segs, const uint8_t
 // one wavefront per pair, against tables md_launch_pkw_index filled: out_len and status as md_launch_pkw_delta's, no delta byte
 int md_launch_pks_sizes(uint32_t count, const md::pkw::Pair *pairs, const uint8_t *src, const uint32_t *tables, uint64_t *out_len, int32_t *status,
                         hipStream_t stream);
+
+// ---- pack_graph_kernels.hip: the object graph (md_pack_graph_build, md_pack_reachable) ----
+// behind a round's last apply launch: one wavefront per tree of r / one thread per commit or tag of r, the objects in buf
+int md_launch_pkg_tree_links(const md::pkg::Round *r, const md::pkg::Links *l, const uint8_t *buf, hipStream_t stream);
+int md_launch_pkg_object_links(const md::pkg::Round *r, const md::pkg::Links *l, const uint8_t *buf, hipStream_t stream);
+// the edges out of their slots, one thread per edge: to[first[o] .. first[o + 1]) = slot_to[slot_off[o] ..) for every object o
+// of the n (first: the scan of Links::deg, first[n] = edges)
+int md_launch_pkg_gather(uint64_t n, uint64_t edges, const uint64_t *slot_off, const uint64_t *first, const uint32_t *slot_to,
+                         const uint8_t *slot_kind, uint32_t *to, uint8_t *kind, hipStream_t stream);
+// mark[seed[k]] = 1 for the count seeds of a walk
+int md_launch_pkg_seed(uint32_t count, const uint32_t *seed, uint32_t *mark, hipStream_t stream);
+// one wavefront per object of the frontier: its targets marked, those marked first that have edges appended to r->next
+int md_launch_pkg_reach_step(const md::pkg::Reach *r, const uint32_t *frontier, uint32_t count, hipStream_t stream);
+// out[i] = mark[i] and not excluded[i] (null: nothing is), one byte an object; *count += how many
+int md_launch_pkg_reach_finish(uint64_t n, const uint32_t *mark, const uint32_t *excluded, uint8_t *out, uint32_t *count, hipStream_t stream);
 
 // ---- pack_build_kernels.hip: the candidates of md_pack_index_build ----
 // bits / cnt as md_launch_gzs_mark's (every word of bits is written: no memset), for the positions of [lo, hi] whose two

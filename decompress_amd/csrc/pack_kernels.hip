@@ -17,6 +17,7 @@
 #include "copy_bytes.hpp"
 #include "internal.hpp"
 #include "mdeflate.h"
+#include "pack_lookup.hpp"
 
 namespace md {
 namespace pk {
@@ -89,17 +90,9 @@ __global__ void headers_kernel(Table t, const uint8_t *__restrict__ pack) {
     if (e - p < 20) st = MD_INVALID_PACK;
     else {
       const uint8_t *want = pack + p;
-      uint64_t lo = 0, hi = t.n_names;
-      bool found = false;
-      while (lo < hi && !found) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        const uint8_t *nm = t.names + mid * 20;
-        int c = 0;
-        for (uint32_t k = 0; k < 20 && c == 0; k++) c = (int)nm[k] - (int)want[k];
-        if (c == 0) found = true, base = t.name_obj ? t.name_obj[mid] : (uint32_t)mid;
-        else if (c < 0) lo = mid + 1;
-        else hi = mid;
-      }
+      uint64_t at = 0;
+      const bool found = find_name(t.names, 0, t.n_names, [&](uint32_t k) { return want[k]; }, &at);
+      if (found) base = t.name_obj ? t.name_obj[at] : (uint32_t)at;
       p += 20;
       if (!found) st = MD_PACK_MISSING_BASE;
       else if (base == i) st = MD_INVALID_PACK;  // (a cycle of one)

@@ -3,12 +3,15 @@ table of all objects - type, size, base, depth, status - is built once on the GP
 and the bases it hangs off in one inflate launch a round, then applies the deltas level by level.  A pack without an idx
 gets one from the GPU (`build_index`, git index-pack's bytes).  `write` makes a pack and its idx from objects and the
 bases the caller chooses - or, with bases="search", the bases `choose_bases` finds by content sketches -, the deltas made
-by a batched kernel (`make_deltas` is that kernel alone)."""
+by a batched kernel (`make_deltas` is that kernel alone).  `Pack.graph` reads what every commit, tree and tag names - the
+object graph, on the GPU -, `Graph.reachable` walks it from roots, and `Pack.extract` writes the pack of what is reachable."""
 import ctypes
+
+import numpy as _np
 
 from . import engine as _engine
 from ._lib import PackBuildResult, PackBuildStats, PackIndexEntry, PackIndexInfo, PackInfo, PackObject, PackResult, PackStats
-from ._lib import PackSource, PackWriteResult
+from ._lib import PackGraphInfo, PackReachStats, PackSource, PackWriteResult
 from ._lib import load as _load
 
 TYPE_NAMES = {0: None, 1: "commit", 2: "tree", 3: "blob", 4: "tag"}
@@ -23,6 +26,15 @@ _INFO_KEYS = ("n", "deltas", "max_depth", "total_size", "failed")
 _OBJECT_KEYS = ("size", "offset", "packed_len", "base", "depth", "type", "status")
 _STATS_KEYS = ("rounds", "inflate_launches", "apply_launches", "objects", "bytes_in", "apply_ns")
 _BUILD_RESULT_KEYS = ("n", "failed", "idx_len", "bad_offset", "bad_status")
+_GRAPH_INFO_KEYS = ("n", "edges", "absent", "mistyped", "malformed", "failed", "parsed", "rounds", "parse_launches", "device_ns")
+_REACH_STATS_KEYS = ("host_closed", "seeds", "rounds", "expanded", "marked", "device_ns")
+NO_LINK = 0xFFFFFFFF
+INVALID_OBJECT = 27
+# an edge's kind (its low bits) and its two flags
+COMMIT_TREE, COMMIT_PARENT, TAG_TARGET, TREE_BLOB, TREE_TREE, TREE_GITLINK = 1, 2, 3, 4, 5, 6
+EDGE_ABSENT, EDGE_MISTYPED = 0x40, 0x80
+# the graph's own status: engine.STATUS_NAMES and md_status_string end at 26
+_GRAPH_STATUS_NAMES = {INVALID_OBJECT: "Invalid object"}
 _BUILD_STATS_KEYS = ("candidates", "generations", "rounds", "inflate_launches", "apply_launches", "objects", "bytes_in")
 
 
@@ -31,6 +43,8 @@ def _raw(src):
 
 
 def _status_name(st):
+    if st in _GRAPH_STATUS_NAMES:
+        return _GRAPH_STATUS_NAMES[st]
     return _engine.STATUS_NAMES.get(st, _load().md_status_string(st).decode())
 
 
@@ -326,9 +340,111 @@ class Pack:
         """md_pack_build_last of this pack's engine"""
         return build_last(self._device)
 
+    def graph(self, verify_crc=False):
+        """md_pack_graph_build -> `Graph`: what every commit, tree and tag of the pack names, read on the GPU"""
+        return Graph(self, verify_crc)
+
+    def extract(self, roots, exclude=(), **write_kw):
+        """the pack of what is reachable from `roots` and not from `exclude` (`Graph.reachable`): those objects read and
+        written again with bases="search" -> (pack, idx) as `write` returns them; write_kw: `write`'s level, max_depth, window"""
+        g = self.graph()
+        try:
+            keep = [int(i) for i in g.reachable(roots, exclude)]
+        finally:
+            g.close()
+        objects = []
+        for i, (tag, got) in zip(keep, self.read(keep)):
+            if tag != "Ok":
+                raise _engine.Error("object %s: %s" % (self.objects[i]["name"].hex(), got))
+            objects.append(got)
+        return write(objects, bases="search", device=self._device, **write_kw)
+
     def close(self):
         if getattr(self, "_h", None):
             self._eng.lib.md_pack_free(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+class Graph:
+    """md_pack_graph_build: the object graph of a `Pack`.  `first` (n + 1), `to`, `kind`: the edges as a CSR over the objects
+    in idx order - object i's are to[first[i]:first[i + 1]], NO_LINK where the name is not in the pack or is a gitlink's;
+    kind: COMMIT_TREE .. TREE_GITLINK, with EDGE_ABSENT / EDGE_MISTYPED or-ed in.  `status`: one per object, INVALID_OBJECT
+    for a commit, tree or tag whose links cannot be read (it has no edges).  `info`: n, edges, absent, mistyped, malformed,
+    failed, parsed, rounds, parse_launches, device_ns.  Blobs are not decoded."""
+
+    def __init__(self, pack, verify_crc=False):
+        self._pack, self._eng = pack, pack._eng
+        lib, h = self._eng.lib, ctypes.c_void_p()
+        st = lib.md_pack_graph_build(self._eng.ctx, pack._h, pack._pack, len(pack._pack), VERIFY_CRC if verify_crc else 0, ctypes.byref(h))
+        if st != 0:
+            self._eng._check(st)
+        self._h = h
+        info = PackGraphInfo()
+        lib.md_pack_graph_get(h, ctypes.byref(info))
+        self.info = {k: getattr(info, k) for k in _GRAPH_INFO_KEYS}
+        n, e = info.n, info.edges
+        self.first, self.to = _np.zeros(n + 1, dtype=_np.uint64), _np.zeros(e, dtype=_np.uint32)
+        self.kind, self.status = _np.zeros(e, dtype=_np.uint8), _np.zeros(n, dtype=_np.int32)
+        self._eng._check(lib.md_pack_graph_edges(h, self.first.ctypes.data, self.to.ctypes.data, self.kind.ctypes.data, e))
+        self._eng._check(lib.md_pack_graph_status(h, self.status.ctypes.data))
+
+    def edges_of(self, i):
+        """object i's edges -> [(from, position, to or None, kind)]"""
+        a, b = int(self.first[i]), int(self.first[i + 1])
+        return [(i, k - a, None if self.to[k] == NO_LINK else int(self.to[k]), int(self.kind[k])) for k in range(a, b)]
+
+    def _flagged(self, flag):
+        own = _np.searchsorted(self.first, _np.nonzero(self.kind & flag)[0], side="right") - 1
+        return [e for i in dict.fromkeys(own.tolist()) for e in self.edges_of(i) if e[3] & flag]
+
+    def missing(self):
+        """the edges whose name the pack does not hold"""
+        return self._flagged(EDGE_ABSENT)
+
+    def mistyped(self):
+        """the edges whose target is of another type than the edge calls for"""
+        return self._flagged(EDGE_MISTYPED)
+
+    def connected(self):
+        """no edge is absent or mistyped and every object's status is Ok"""
+        return self.info["absent"] == 0 and self.info["mistyped"] == 0 and not self.status.any()
+
+    def _indices(self, what):
+        out = []
+        for r in what:
+            if isinstance(r, (bytes, bytearray)):
+                i = self._pack.find(r)
+                if i < 0:
+                    raise KeyError(bytes(r).hex())
+                r = i
+            out.append(int(r))
+        return out
+
+    def reachable(self, roots, exclude=()):
+        """md_pack_reachable: roots / exclude - indices or 20-byte names (`KeyError` for a name the pack does not hold) ->
+        the sorted indices of what is reached from the roots and not from `exclude`.  Raises `Error` for an index out of range."""
+        roots, exclude, n = self._indices(roots), self._indices(exclude), int(self.info["n"])
+        r, x = (ctypes.c_uint64 * max(len(roots), 1))(*roots), (ctypes.c_uint64 * max(len(exclude), 1))(*exclude)
+        mark, count = _np.zeros(max(n, 1), dtype=_np.uint8), ctypes.c_uint64(0)
+        st = self._eng.lib.md_pack_reachable(self._eng.ctx, self._h, r if roots else None, len(roots), x if exclude else None, len(exclude),
+                                             mark.ctypes.data, ctypes.byref(count))
+        if st != 0:
+            self._eng._check(st)
+        got = _np.nonzero(mark[:n])[0]
+        assert len(got) == count.value
+        return got
+
+    def reach_last(self):
+        """md_pack_reach_last: host_closed, seeds, rounds, expanded, marked, device_ns of the engine's last `reachable`"""
+        s = PackReachStats()
+        self._eng._check(self._eng.lib.md_pack_reach_last(self._eng.ctx, ctypes.byref(s)))
+        return {k: getattr(s, k) for k in _REACH_STATS_KEYS}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._eng.lib.md_pack_graph_free(self._h)
             self._h = None
 
     __del__ = close

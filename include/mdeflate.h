@@ -77,7 +77,10 @@ enum {
   MD_INVALID_DELTA = 23,     /* "Invalid delta": a delta's instructions or sizes */
   MD_INVALID_PACK_BASE = 24, /* "Invalid delta base": the object is a delta and an object of its chain of bases failed */
   MD_PACK_MISSING_BASE = 25, /* "Missing delta base": a REF_DELTA names an object the pack does not hold (a thin pack) */
-  MD_PACK_UNSUPPORTED = 26   /* "Unsupported pack": a pack version other than 2 and 3, an idx version other than 2 */
+  MD_PACK_UNSUPPORTED = 26,  /* "Unsupported pack": a pack version other than 2 and 3, an idx version other than 2 */
+  /* the object graph of a pack (md_pack_graph_* below): a status of md_pack_graph_status alone - no call returns it and
+   * md_status_string does not name it */
+  MD_INVALID_OBJECT = 27     /* "Invalid object": a commit, tree or tag whose links cannot be read */
 };
 
 /* Call-level errors (negative): misuse raises Invalid_argument in the
@@ -1411,6 +1414,90 @@ int md_pack_delta_sizes_host(md_ctx *ctx, size_t n, const md_pack_delta_pair *pa
 int md_pack_choose_bases(md_ctx *ctx, uint32_t window, uint32_t max_depth, size_t n, const md_pack_source *objs, const uint8_t *src,
                          size_t src_len, md_pack_source *sorted, uint64_t *order);
 int md_pack_search_last(const md_ctx *ctx, md_pack_search_stats *stats);
+
+/* ---- git packs: the object graph and what is reachable from roots (csrc/pack_graph_kernels.hip, csrc/pack_graph.hpp) ---------
+ * A commit names a tree and parents, a tree names blobs and trees, a tag names a target.  md_pack_graph_build reads those
+ * links on the device for every object of a table (md_pack_open) and keeps them as a graph; md_pack_reachable walks it.
+ * Objects are indexed in idx order, as in md_pack_objects; an object's type is its root's.  Only commits (1), trees (2) and
+ * tags (4) whose status in the table is MD_OK are decoded - by md_pack_verify's plan and rounds ("pack_workspace"), with
+ * the bases they hang off - and parsed behind each round's last apply launch.  BLOBS ARE NEVER INFLATED: a blob's damage is
+ * md_pack_verify's to find.  flags: 0 or MD_PACK_VERIFY_CRC (the read's meaning, for what is decoded); anything else is
+ * MD_E_INVALID_ARGUMENT.  A pack other than the table's is MD_INVALID_INDEX, as in md_pack_read.  Limit: n < 2^31.
+ *
+ * An edge is (from, to, kind).  to: a uint32_t index, or MD_PACK_NO_LINK.  kind: one byte, its low bits one of
+ *   1 COMMIT_TREE  2 COMMIT_PARENT  3 TAG_TARGET  4 TREE_BLOB  5 TREE_TREE  6 TREE_GITLINK
+ * with two flags that may be or-ed in:
+ *   0x40 MD_PACK_EDGE_ABSENT     the name is not among the pack's names; to is MD_PACK_NO_LINK
+ *   0x80 MD_PACK_EDGE_MISTYPED   the name is found, the target's type is known (1 .. 4) and is not the type the edge calls
+ *                                for: a tree for COMMIT_TREE and TREE_TREE, a commit for COMMIT_PARENT, a blob for TREE_BLOB,
+ *                                the type its `type` line states for TAG_TARGET
+ * A TREE_GITLINK is never looked up: to = MD_PACK_NO_LINK and neither flag.  A target whose own status is not MD_OK is still
+ * linked to.  Edges stand in the object's own order - tree entries as they lie; a commit's tree, then its parents; a tag's
+ * one target -, so the edge list is a function of the pack's bytes.
+ *
+ * The parse rules are those of git's readers (decode_tree_entry, parse_commit_buffer, parse_tag_buffer).
+ * Tree of `size` bytes, at entry start s with rem = size - s: rem == 0 ends the tree (an empty tree is well formed, 0 edges);
+ * otherwise rem >= 23 and byte[size - 21] == 0 are required; the mode is one or more bytes '0' .. '7' up to a space (an empty
+ * mode or any other byte in front of the space is malformed), its value mode = (mode << 3) + digit in 32 bits, wrapping; the
+ * name runs from behind the space to the first NUL and must not be empty; 20 name bytes follow and must fit in size; the next
+ * entry starts behind them.  Kind by mode & 0170000 (git's canon_mode): 0100000 or 0120000 TREE_BLOB, 0040000 TREE_TREE
+ * ("040000" with the leading zero is accepted), anything else - mode 0 and wrapped modes included - TREE_GITLINK.
+ * Commit: size > 46, "tree ", 40 hex digits of either case, '\n' at byte 45.  At p = 46: while p + 47 < size and the bytes at
+ * p are "parent ": size > p + 48, 40 hex digits and '\n' at p + 47 are required, else the commit is malformed; p += 48.
+ * Nothing behind that is read: a parent line in the message is no parent; a commit that ends in "parent " + 40 hex without a
+ * newline has no parent from that line, and with the newline and nothing behind it is malformed.
+ * Tag: size >= 64; "object " + 40 hex + '\n'; "type " + one of blob, tree, commit, tag + '\n'; then, at p, p + 4 < size and
+ * the bytes "tag ".
+ * A malformed object gets MD_INVALID_OBJECT and has NO EDGES AT ALL, not the ones in front of the fault.  An object that did
+ * not decode keeps md_pack_read's status for it (MD_INVALID_PACK_BASE for what hangs off it) and has no edges.  A failed
+ * object never fails the call or its neighbours.  md_pack_graph_status: every object's status - the table's for what is not
+ * decoded (blobs, objects that failed in md_pack_open), else the above.
+ *
+ * md_pack_graph_edges: first (n + 1 entries) is a CSR over all n objects - blobs and failed objects have empty ranges -, to and
+ * kind the edges, cap of them at least info.edges (else MD_UNEXPECTED_END_OF_OUTPUT); cap == 0 with NULL arrays only asks:
+ * md_pack_graph_get's info.edges says how many.  info: n; edges, and how many of them are absent and mistyped; malformed
+ * objects; failed = objects whose status is neither MD_OK nor MD_INVALID_OBJECT; parsed = objects decoded and parsed (a base
+ * decoded in two rounds counts twice, as md_pack_stats::objects does); rounds as md_pack_last's; parse_launches = launches of
+ * the two link kernels; device_ns = their device time (two events around them, per round).
+ * The graph keeps first, to and kind resident on the context's device, and its COMMIT_PARENT and TAG_TARGET edges on the host.
+ *
+ * md_pack_reachable: mark[i] = 1 iff i is a root or is reached from a root over edges with to != MD_PACK_NO_LINK.  An object
+ * is walked through by the edges it has, whatever type the edge expected.  With an exclude list the result is
+ * R(roots) \ R(exclude), the exact set difference.  This is this library's definition, not git rev-list's boundary
+ * heuristics; on graphs with no MISTYPED edges and no exclusions it is the object set of
+ * `git rev-list --objects --missing=print <roots>`.  *count = the marks set.  A root or exclude index >= n, a NULL array with
+ * a non-zero count: MD_E_INVALID_ARGUMENT.  How it walks: a history is a long thin chain, so the HOST first closes the roots
+ * over COMMIT_PARENT and TAG_TARGET edges; what that reached seeds the device's first frontier, and one launch per
+ * non-empty frontier follows all edges, one wavefront per frontier object, with the next frontier's length (4 bytes) read
+ * back between launches.  Without MISTYPED edges that is at most d + 2 launches, d = the deepest nesting of trees below a root
+ * tree.  With exclusions the exclude walk runs first into a second mark.
+ * md_pack_reach_last, summed over both walks of the context's last md_pack_reachable: host_closed = objects the host's closure
+ * held (the roots included), seeds = objects of the first frontiers (the closed ones that have an edge), rounds = launches of
+ * the step kernel, expanded = objects that stood on a frontier (each exactly once a walk), marked = *count, device_ns. */
+#define MD_PACK_NO_LINK 0xffffffffu
+#define MD_PACK_EDGE_COMMIT_TREE 1
+#define MD_PACK_EDGE_COMMIT_PARENT 2
+#define MD_PACK_EDGE_TAG_TARGET 3
+#define MD_PACK_EDGE_TREE_BLOB 4
+#define MD_PACK_EDGE_TREE_TREE 5
+#define MD_PACK_EDGE_TREE_GITLINK 6
+#define MD_PACK_EDGE_ABSENT 0x40
+#define MD_PACK_EDGE_MISTYPED 0x80
+typedef struct md_pack_graph md_pack_graph;
+typedef struct md_pack_graph_info {
+  uint64_t n, edges, absent, mistyped, malformed, failed, parsed, rounds, parse_launches, device_ns;
+} md_pack_graph_info;
+typedef struct md_pack_reach_stats {
+  uint64_t host_closed, seeds, rounds, expanded, marked, device_ns;
+} md_pack_reach_stats;
+int md_pack_graph_build(md_ctx *ctx, const md_pack *p, const uint8_t *pack, size_t pack_len, unsigned flags, md_pack_graph **g);
+int md_pack_graph_get(const md_pack_graph *g, md_pack_graph_info *info);
+int md_pack_graph_edges(const md_pack_graph *g, uint64_t *first, uint32_t *to, uint8_t *kind, size_t cap);
+int md_pack_graph_status(const md_pack_graph *g, int32_t *status);
+int md_pack_reachable(md_ctx *ctx, const md_pack_graph *g, const uint64_t *roots, size_t nroots, const uint64_t *exclude, size_t nexclude,
+                      uint8_t *mark, uint64_t *count);
+int md_pack_reach_last(const md_ctx *ctx, md_pack_reach_stats *stats);
+void md_pack_graph_free(md_pack_graph *g);
 
 #ifdef __cplusplus
 }
