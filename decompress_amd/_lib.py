@@ -202,6 +202,11 @@ SYMBOLS = [
     ("md_pack_reachable", ctypes.c_int, [c_vp, c_vp, c_vp, c_sz, c_vp, c_sz, c_vp, c_vp]),
     ("md_pack_reach_last", ctypes.c_int, [c_vp, c_vp]),
     ("md_pack_graph_free", None, [c_vp]),
+    ("md_pack_diff", ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_sz, c_sz, c_vp, c_vp, ctypes.c_uint, ctypes.POINTER(c_vp)]),
+    ("md_pack_diff_get", ctypes.c_int, [c_vp, c_vp]),
+    ("md_pack_diff_changes", ctypes.c_int, [c_vp, c_vp, c_sz, c_vp, c_sz]),
+    ("md_pack_diff_status", ctypes.c_int, [c_vp, c_vp]),
+    ("md_pack_diff_free", None, [c_vp]),
 ]
 
 
@@ -296,6 +301,18 @@ class PackGraphInfo(ctypes.Structure):
     """md_pack_graph_info of include/mdeflate.h"""
     _fields_ = [(k, ctypes.c_uint64) for k in ("n", "edges", "absent", "mistyped", "malformed", "failed", "parsed", "rounds", "parse_launches",
                                                 "device_ns")]
+
+
+class TreeChange(ctypes.Structure):
+    """md_tree_change of include/mdeflate.h"""
+    _fields_ = [("pair", ctypes.c_uint32), ("parent", ctypes.c_uint32), ("kind", ctypes.c_uint8), ("flags", ctypes.c_uint8),
+                ("a_mode", ctypes.c_uint32), ("b_mode", ctypes.c_uint32), ("a_obj", ctypes.c_uint32), ("b_obj", ctypes.c_uint32),
+                ("name_len", ctypes.c_uint32), ("name_off", ctypes.c_uint64), ("a_name", ctypes.c_uint8 * 20), ("b_name", ctypes.c_uint8 * 20)]
+
+
+class PackDiffInfo(ctypes.Structure):
+    """md_pack_diff_info of include/mdeflate.h"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("pairs", "changes", "name_bytes", "levels", "opaque", "failed", "trees_read", "launches", "device_ns")]
 
 
 class PackReachStats(ctypes.Structure):

@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 SO = os.environ.get("MD_SO_OUT") or os.path.join(HERE, "libmdeflate.so")  # MD_SO_OUT: measurement builds (tools/dbg)
-SOURCES = ["inflate_wave.hip", "inflate_count.hip", "inflate_chunked.hip", "deflate_front.hip", "deflate_chunked.hip", "deflate_kernel.hip", "deflate_ns.hip", "gz_kernels.hip", "gz_members.hip", "gz_spec.hip", "deflate_spans.hip", "zip_kernels.hip", "zindex_kernels.hip", "bgzf_read.hip", "inflate_batch.hip", "lzo_kernels.hip", "pack_kernels.hip", "pack_build_kernels.hip", "sha1_kernels.hip", "pack_write_kernels.hip", "pack_search_kernels.hip", "pack_graph_kernels.hip", "capi.cpp", "capi_inflate.cpp", "capi_inflate_sizes.cpp", "capi_long_stream.cpp", "capi_deflate.cpp", "capi_deflate_spans.cpp", "capi_gz_members.cpp", "capi_zip.cpp", "capi_zindex.cpp", "capi_bgzf_read.cpp", "capi_lzo.cpp", "capi_pack.cpp", "capi_pack_build.cpp", "capi_sha1.cpp", "capi_pack_write.cpp", "capi_pack_search.cpp", "capi_pack_graph.cpp",
+SOURCES = ["inflate_wave.hip", "inflate_count.hip", "inflate_chunked.hip", "deflate_front.hip", "deflate_chunked.hip", "deflate_kernel.hip", "deflate_ns.hip", "gz_kernels.hip", "gz_members.hip", "gz_spec.hip", "deflate_spans.hip", "zip_kernels.hip", "zindex_kernels.hip", "bgzf_read.hip", "inflate_batch.hip", "lzo_kernels.hip", "pack_kernels.hip", "pack_build_kernels.hip", "sha1_kernels.hip", "pack_write_kernels.hip", "pack_search_kernels.hip", "pack_graph_kernels.hip", "pack_diff_kernels.hip", "capi.cpp", "capi_inflate.cpp", "capi_inflate_sizes.cpp", "capi_long_stream.cpp", "capi_deflate.cpp", "capi_deflate_spans.cpp", "capi_gz_members.cpp", "capi_zip.cpp", "capi_zindex.cpp", "capi_bgzf_read.cpp", "capi_lzo.cpp", "capi_pack.cpp", "capi_pack_build.cpp", "capi_sha1.cpp", "capi_pack_write.cpp", "capi_pack_search.cpp", "capi_pack_graph.cpp", "capi_pack_diff.cpp",
            "stream_inf.cpp", "stream_def.cpp"]
 
 

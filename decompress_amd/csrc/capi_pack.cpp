@@ -302,8 +302,11 @@ struct ReadRound : RoundStreams {
 // sink->names, one that has a name is compared as MD_PACK_VERIFY_NAME compares it; the pack is on the device already.
 // links (with !keep: md_pack_graph_build): the link pass runs behind every round's last apply launch, over every object
 // of the round where it stands.
+// d_kept (with keep: md_pack_diff's levels): the device-resident form - the selected objects stay where the rounds put them,
+// *d_kept + out_off[j], nothing of them is copied to the host and dst is not looked at; pack == null: it is in kHostIn already.
 int pack_read(md_ctx *ctx, const md_pack *P, const uint8_t *pack, const uint64_t *select, size_t k, unsigned flags, bool keep, uint8_t *dst,
-              size_t dst_cap, uint64_t *out_off, int32_t *status, md_pack_result *res, const PackNameSink *sink, PackLinkSink *links) {
+              size_t dst_cap, uint64_t *out_off, int32_t *status, md_pack_result *res, const PackNameSink *sink, PackLinkSink *links,
+              const uint8_t **d_kept = nullptr) {
   const size_t n = P->objs.size();
   for (size_t j = 0; select && j < k; j++)
     if (select[j] >= n) return fail(ctx, MD_E_INVALID_ARGUMENT, "selected object out of range");
@@ -418,7 +421,7 @@ int pack_read(md_ctx *ctx, const md_pack *P, const uint8_t *pack, const uint64_t
   // -- device memory: the pack, the buffer, one block of descriptors for the largest round
   MD_ON_DEVICE(ctx);
   hipStream_t st = ctx->stream;
-  int rc = sink ? MD_OK : upload_host_in(ctx, pack, P->pack_len);
+  int rc = sink || !pack ? MD_OK : upload_host_in(ctx, pack, P->pack_len);
   if (rc == MD_OK) rc = ctx->scratch[kHostOut].reserve(ctx, scratch0 + max_scratch + 64, "hipMalloc(pack output and scratch)");
   if (rc != MD_OK) return rc;
   RoundDesc d;
@@ -506,7 +509,8 @@ int pack_read(md_ctx *ctx, const md_pack *P, const uint8_t *pack, const uint64_t
     for (const ReadRound &R : rounds)
       for (size_t q = 0; q < R.obj.size(); q++)
         if (R.status[q] == MD_OK && !sink->known[R.obj[q]]) memcpy(sink->names + (size_t)R.obj[q] * kSha1Bytes, &R.digest[q * kSha1Bytes], kSha1Bytes), sink->named[R.obj[q]] = 1;
-  if (keep && need) HIP_TRY(ctx, hipMemcpy(dst, d_buf, (size_t)need, hipMemcpyDeviceToHost));
+  if (d_kept) *d_kept = d_buf;
+  else if (keep && need) HIP_TRY(ctx, hipMemcpy(dst, d_buf, (size_t)need, hipMemcpyDeviceToHost));
   for (size_t j = 0; j < k; j++) {
     const uint32_t s = (uint32_t)sel(j);
     status[j] = P->objs[s].status != MD_OK ? P->objs[s].status : refused[s] ? MD_E_OUT_OF_MEMORY : rounds[sel_round[s]].status[sel_slot[s]];
@@ -523,6 +527,11 @@ int pack_verify_names(md_ctx *ctx, const md_pack *P, const uint64_t *select, siz
 int pack_link_rounds(md_ctx *ctx, const md_pack *P, const uint8_t *pack, const uint64_t *select, size_t k, unsigned flags, int32_t *status,
                      md_pack_result *res, PackLinkSink *links) {
   return pack_read(ctx, P, pack, select, k, flags, false, nullptr, 0, nullptr, status, res, nullptr, links);
+}
+
+int pack_read_resident(md_ctx *ctx, const md_pack *P, const uint8_t *pack, const uint64_t *select, size_t k, uint64_t *out_off, int32_t *status,
+                       md_pack_result *res, const uint8_t **d_objs) {
+  return pack_read(ctx, P, pack, select, k, 0, true, nullptr, SIZE_MAX, out_off, status, res, nullptr, nullptr, d_objs);
 }
 
 int md_pack_index(const uint8_t *idx, size_t idx_len, md_pack_index_info *info, md_pack_index_entry *entries, size_t cap) {

@@ -13,23 +13,13 @@
 #include "ctx.hpp"
 #include "pack_graph.hpp"
 
-// The graph of a pack: the statuses and the CSR's rows on the host, the edges on the device, and of the edges those a
-// history is made of - COMMIT_PARENT and TAG_TARGET, with a target - on the host as a CSR of their own.
-struct md_pack_graph {
-  int device = 0;
-  md_pack_graph_info info = {};
-  std::vector<int32_t> status;
-  std::vector<uint64_t> first, hist_first;
-  std::vector<uint32_t> hist_to;
-  md::DevBuf d_first, d_to, d_kind;
-};
-
 namespace {
 namespace pg = md::pg;
 
 int graph_build(md_ctx *ctx, const md_pack *P, const uint8_t *pack, unsigned flags, md_pack_graph *G) {
   const size_t n = P->objs.size();
   G->device = ctx->device;
+  memcpy(G->pack_checksum, P->pack_checksum, 20);
   G->info.n = n;
   G->first.assign(n + 1, 0);
   G->hist_first.assign(n + 1, 0);

@@ -211,6 +211,9 @@ enum Scratch {
   // offsets, the edge counts and the malformed flags in kPkgDesc, the bound-sized edge slots in kPkgSlots (the compacted
   // edges are the graph's own).  md_pack_reachable: marks, frontiers, seeds and the result in kPkgDesc
   kPkgDesc, kPkgSlots,
+  // trees diffed (md_pack_diff): a level's descriptors, tables of entries, counts and places in kPkdDesc, its records and their
+  // names in kPkdOut (the level's trees stand in kHostOut, where the read left them)
+  kPkdDesc, kPkdOut,
   kScratchCount
 };
 
@@ -569,6 +572,23 @@ struct PackLinkSink {
 };
 int pack_link_rounds(md_ctx *ctx, const md_pack *P, const uint8_t *pack, const uint64_t *select, size_t k, unsigned flags, int32_t *status,
                      md_pack_result *res, PackLinkSink *links);
+// md_pack_read's plan and rounds with the selected objects LEFT ON THE DEVICE (md_pack_diff, capi_pack_diff.cpp): object select[j]
+// stands at *d_objs + out_off[j] (out_off: k + 1 entries, back to back as in md_pack_read's dst) until the next call that uses
+// kHostOut; nothing but the statuses comes back.  pack == null: the pack is in kHostIn already.  k is not 0.
+int pack_read_resident(md_ctx *ctx, const md_pack *P, const uint8_t *pack, const uint64_t *select, size_t k, uint64_t *out_off, int32_t *status,
+                       md_pack_result *res, const uint8_t **d_objs);
+// ---- capi_pack_graph.cpp: the graph of a pack, as md_pack_diff reads it ----
+// The statuses and the CSR's rows on the host, the edges on the device, and of the edges those a history is made of -
+// COMMIT_PARENT and TAG_TARGET, with a target - on the host as a CSR of their own.  pack_checksum: of the table it was built from.
+struct md_pack_graph {
+  int device = 0;
+  md_pack_graph_info info = {};
+  uint8_t pack_checksum[20] = {0};
+  std::vector<int32_t> status;
+  std::vector<uint64_t> first, hist_first;
+  std::vector<uint32_t> hist_to;
+  md::DevBuf d_first, d_to, d_kind;
+};
 // ---- capi_pack_write.cpp: the delta batch, as md_pack_delta_sizes_* and md_pack_choose_bases (capi_pack_search.cpp) use it too ----
 // The pairs as the kernels take them, the distinct bases that have a block, and what their tables need.  A builder calls
 // add_base once per distinct base, in the order the tables shall stand in, and pair() for every pair with its base's place.

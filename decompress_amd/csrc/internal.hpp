@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "mdeflate.h"
+#include "pack_diff.hpp"
 #include "pack_search.hpp"
 #include "pack_write.hpp"
 
@@ -364,6 +365,40 @@ struct Reach {
 };
 }  // namespace pkg
 
+namespace pkd {
+// Trees diffed on the device (pack_diff_kernels.hip; the rules are mdeflate.h's, the functions pack_diff.hpp's).  One level of
+// md_pack_diff: its distinct trees stand in the read's buffer, tree t at buf + off[t], size[t] bytes, decoded with status[t],
+// object obj[t] of the graph.  The table kernel writes tree t's entries as rows from rows + row_off[t] on (a slot holds
+// size / 24 of them), their number to cnt[t], and ok[t] = 1: it decoded, every entry is read and the keys ascend strictly.
+using Row = pd::Entry;
+struct Trees {
+  uint32_t count;
+  const uint64_t *off, *size, *row_off;
+  const int32_t *status;
+  const uint32_t *obj;
+  Row *rows;
+  uint32_t *cnt;
+  uint8_t *ok;
+};
+// The level's pairs: a[q] / b[q] are trees of the level (indices into Trees) or pd::kNone, the empty tree; id[q] and parent[q] go
+// into the records as they are.  first / to: the graph's resident edges - tree o's entry e names object to[first[o] + e].
+// The count form leaves nrec[q] and nbytes[q] (records, bytes of their names); the write form stores pair q's records from
+// out + rec_first[q] on and their names from names + name_first[q] on (the scans of the counts), a record's name_off being
+// name_base + its place in names.  A pair with a side that is not ok has no records.
+struct Pairs {
+  uint32_t count;
+  const uint32_t *a, *b, *id, *parent;
+  const uint64_t *first;
+  const uint32_t *to;
+  uint32_t *nrec;
+  uint64_t *nbytes;
+  const uint64_t *rec_first, *name_first;
+  md_tree_change *out;
+  uint8_t *names;
+  uint64_t name_base;
+};
+}  // namespace pkd
+
 namespace sha {
 // SHA-1 of many messages, one a lane (sha1_kernels.hip).  Message m is data[off[m], off[m] + len[m]) with the header of
 // a git object of type[m] in front (1 commit, 2 tree, 3 blob, 4 tag; 0, or type == null: the bytes as they are), len[m] at
@@ -622,6 +657,12 @@ int md_launch_pkg_seed(uint32_t count, const uint32_t *seed, uint32_t *mark, hip
 int md_launch_pkg_reach_step(const md::pkg::Reach *r, const uint32_t *frontier, uint32_t count, hipStream_t stream);
 // out[i] = mark[i] and not excluded[i] (null: nothing is), one byte an object; *count += how many
 int md_launch_pkg_reach_finish(uint64_t n, const uint32_t *mark, const uint32_t *excluded, uint8_t *out, uint32_t *count, hipStream_t stream);
+
+// ---- pack_diff_kernels.hip: trees diffed (md_pack_diff) ----
+// one wavefront per tree of t, the trees in buf: rows, counts and verdicts
+int md_launch_pkd_tree_table(const md::pkd::Trees *t, const uint8_t *buf, hipStream_t stream);
+// one wavefront per pair of p over the tables of t: write == 0 counts (nrec, nbytes), else the records and names are stored
+int md_launch_pkd_tree_diff(const md::pkd::Trees *t, const md::pkd::Pairs *p, const uint8_t *buf, int write, hipStream_t stream);
 
 // ---- pack_build_kernels.hip: the candidates of md_pack_index_build ----
 // bits / cnt as md_launch_gzs_mark's (every word of bits is written: no memset), for the positions of [lo, hi] whose two

@@ -4,14 +4,16 @@ and the bases it hangs off in one inflate launch a round, then applies the delta
 gets one from the GPU (`build_index`, git index-pack's bytes).  `write` makes a pack and its idx from objects and the
 bases the caller chooses - or, with bases="search", the bases `choose_bases` finds by content sketches -, the deltas made
 by a batched kernel (`make_deltas` is that kernel alone).  `Pack.graph` reads what every commit, tree and tag names - the
-object graph, on the GPU -, `Graph.reachable` walks it from roots, and `Pack.extract` writes the pack of what is reachable."""
+object graph, on the GPU -, `Graph.reachable` walks it from roots, and `Pack.extract` writes the pack of what is reachable.
+`Pack.diff` diffs pairs of trees on the GPU, all pairs at once and level by level, and `Pack.changes` every commit against
+its first parent's tree."""
 import ctypes
 
 import numpy as _np
 
 from . import engine as _engine
 from ._lib import PackBuildResult, PackBuildStats, PackIndexEntry, PackIndexInfo, PackInfo, PackObject, PackResult, PackStats
-from ._lib import PackGraphInfo, PackReachStats, PackSource, PackWriteResult
+from ._lib import PackDiffInfo, PackGraphInfo, PackReachStats, PackSource, PackWriteResult
 from ._lib import load as _load
 
 TYPE_NAMES = {0: None, 1: "commit", 2: "tree", 3: "blob", 4: "tag"}
@@ -35,6 +37,15 @@ COMMIT_TREE, COMMIT_PARENT, TAG_TARGET, TREE_BLOB, TREE_TREE, TREE_GITLINK = 1, 
 EDGE_ABSENT, EDGE_MISTYPED = 0x40, 0x80
 # the graph's own status: engine.STATUS_NAMES and md_status_string end at 26
 _GRAPH_STATUS_NAMES = {INVALID_OBJECT: "Invalid object"}
+# trees diffed: the empty tree as a side of a pair, md_pack_diff's flag, a record's two flags
+TREE_NONE = 0xFFFFFFFF
+DIFF_RECURSIVE = 1
+CHANGE_TREE, CHANGE_OPAQUE = 1, 2
+# md_tree_change of include/mdeflate.h as numpy reads it (tests/test_pack_diff_abi.py holds it to the ctypes mirror)
+_CHANGE_DTYPE = _np.dtype({"names": ["pair", "parent", "kind", "flags", "a_mode", "b_mode", "a_obj", "b_obj", "name_len", "name_off", "a_name", "b_name"],
+                           "formats": ["<u4", "<u4", "u1", "u1", "<u4", "<u4", "<u4", "<u4", "<u4", "<u8", ("u1", 20), ("u1", 20)],
+                           "offsets": [0, 4, 8, 9, 12, 16, 20, 24, 28, 32, 40, 60], "itemsize": 80})
+_DIFF_INFO_KEYS = ("pairs", "changes", "name_bytes", "levels", "opaque", "failed", "trees_read", "launches", "device_ns")
 _BUILD_STATS_KEYS = ("candidates", "generations", "rounds", "inflate_launches", "apply_launches", "objects", "bytes_in")
 
 
@@ -358,6 +369,101 @@ class Pack:
                 raise _engine.Error("object %s: %s" % (self.objects[i]["name"].hex(), got))
             objects.append(got)
         return write(objects, bases="search", device=self._device, **write_kw)
+
+    def _diff_call(self, pairs, recursive, graph, cap=None, names_cap=None):
+        """md_pack_diff and its getters -> (return value, the records as a numpy array of _CHANGE_DTYPE, names, statuses, info)"""
+        eng, lib = self._eng, self._eng.lib
+        g = graph or self.graph()
+        try:
+            k = len(pairs)
+            a = _np.array([TREE_NONE if x is None else int(x) for x, _ in pairs], dtype=_np.int64).astype(_np.uint32)
+            b = _np.array([TREE_NONE if y is None else int(y) for _, y in pairs], dtype=_np.int64).astype(_np.uint32)
+            h = ctypes.c_void_p()
+            rc = lib.md_pack_diff(eng.ctx, self._h, g._h, self._pack, len(self._pack), k, a.ctypes.data if k else None, b.ctypes.data if k else None,
+                                  DIFF_RECURSIVE if recursive else 0, ctypes.byref(h))
+        finally:
+            if graph is None:
+                g.close()
+        none = _np.zeros(0, dtype=_CHANGE_DTYPE)
+        if rc != 0:
+            return rc, none, b"", [], {}
+        try:
+            info = PackDiffInfo()
+            lib.md_pack_diff_get(h, ctypes.byref(info))
+            self._diff_last = {key: getattr(info, key) for key in _DIFF_INFO_KEYS}
+            cap = info.changes if cap is None else cap
+            names_cap = info.name_bytes if names_cap is None else names_cap
+            recs, names = _np.zeros(cap, dtype=_CHANGE_DTYPE), _np.zeros(names_cap, dtype=_np.uint8)
+            status = _np.zeros(k, dtype=_np.int32)
+            lib.md_pack_diff_status(h, status.ctypes.data if k else None)
+            rc = lib.md_pack_diff_changes(h, recs.ctypes.data if cap else None, cap, names.ctypes.data if names_cap else None, names_cap)
+            if rc != 0:
+                return rc, none, b"", status.tolist(), dict(self._diff_last)
+            return 0, recs[:info.changes], names[:info.name_bytes].tobytes(), status.tolist(), dict(self._diff_last)
+        finally:
+            lib.md_pack_diff_free(h)
+
+    def diff_raw(self, pairs, recursive=True, graph=None, cap=None, names_cap=None):
+        """md_pack_diff as it is: pairs = [(a, b)], indices of trees or None for the empty tree -> (return value, records as
+        dicts in their order, the names blob, statuses, md_pack_diff_info as a dict).  cap / names_cap None: what the call needs."""
+        rc, recs, names, status, info = self._diff_call(pairs, recursive, graph, cap, names_cap)
+        out = [{"pair": int(r["pair"]), "parent": None if r["parent"] == TREE_NONE else int(r["parent"]), "kind": chr(r["kind"]), "flags": int(r["flags"]),
+                "a_mode": int(r["a_mode"]), "b_mode": int(r["b_mode"]), "a_obj": None if r["a_obj"] == NO_LINK else int(r["a_obj"]),
+                "b_obj": None if r["b_obj"] == NO_LINK else int(r["b_obj"]), "name_len": int(r["name_len"]), "name_off": int(r["name_off"]),
+                "a_name": r["a_name"].tobytes(), "b_name": r["b_name"].tobytes()} for r in recs]
+        return rc, out, names, status, info
+
+    def diff(self, pairs, recursive=True, graph=None):
+        """md_pack_diff: pairs = [(a, b)] of trees - indices, or None for the empty tree - diffed on the GPU, all pairs at once
+        and level by level -> per pair ("Ok", [(kind, a_mode, b_mode, a_name, b_name, path, flags)]) or (status name, None).
+        kind: "A", "D", "M", "T"; modes canonical, 0 and twenty zero bytes on the side that has no entry; path: the names
+        from the pair's root down, joined with "/"; flags: CHANGE_TREE for a directory's own record (`git diff-tree -t`'s
+        lines), CHANGE_OPAQUE for a directory that could not be descended.  recursive False: the top level alone
+        (`git diff-tree` without -r).  graph: a `Graph` of this pack to use (else one is built for the call).  No renames."""
+        rc, recs, names, status, _ = self._diff_call(pairs, recursive, graph)
+        if rc != 0:
+            self._eng._check(rc)
+        out, paths = [[] for _ in pairs], []
+        col = {key: recs[key].tolist() for key in ("pair", "parent", "kind", "flags", "a_mode", "b_mode", "name_len", "name_off")}
+        an, bn = recs["a_name"].tobytes(), recs["b_name"].tobytes()
+        for k, (pair, parent, kind, flags, am, bm, ln, off) in enumerate(zip(*col.values())):
+            name = names[off:off + ln]
+            paths.append(name if parent == TREE_NONE else paths[parent] + b"/" + name)
+            out[pair].append((chr(kind), am, bm, an[20 * k:20 * k + 20], bn[20 * k:20 * k + 20], paths[-1], flags))
+        return [("Ok", out[q]) if st == 0 else (_status_name(st), None) for q, st in enumerate(status)]
+
+    def changes(self, commits=None, graph=None):
+        """what every commit changed: each commit of `commits` (indices; None: every commit of the pack, in idx order) against
+        its first parent's tree, a commit without a parent in the pack against the empty tree - the shape of `git log --raw
+        --no-renames -m --first-parent` -> (commits, `diff`'s list).  A commit whose tree the pack does not hold is diffed
+        as the empty tree.  The trees come from the graph's COMMIT_TREE and COMMIT_PARENT edges."""
+        g = graph or self.graph()
+        try:
+            if commits is None:
+                commits = [i for i, o in enumerate(self.objects) if o["type"] == 1 and g.status[i] == 0]
+            commits = [int(c) for c in commits]
+            # a commit's edges are its tree, then its parents (a malformed commit has none)
+            first, to = g.first.astype(_np.int64), _np.append(g.to, _np.uint32(NO_LINK)).astype(_np.int64)
+            none = len(to) - 1
+
+            def tree_of(c):
+                ok = (c >= 0) & (first[_np.maximum(c, 0)] < first[_np.maximum(c, 0) + 1])
+                return _np.where(ok, to[_np.where(ok, first[_np.maximum(c, 0)], none)], NO_LINK)
+
+            c = _np.array(commits, dtype=_np.int64).reshape(-1)
+            has_parent = first[c + 1] - first[c] >= 2 if len(c) else _np.zeros(0, dtype=bool)
+            parent = _np.where(has_parent, to[_np.where(has_parent, first[c] + 1, none)], NO_LINK)
+            ta, tb = tree_of(_np.where(parent == NO_LINK, -1, parent)), tree_of(c)
+            pairs = [(None if x == NO_LINK else x, None if y == NO_LINK else y) for x, y in zip(ta.tolist(), tb.tolist())]
+            return commits, self.diff(pairs, True, g)
+        finally:
+            if graph is None:
+                g.close()
+
+    def diff_last(self):
+        """md_pack_diff_get of this pack's last `diff` / `changes`: pairs, changes, name_bytes, levels, opaque, failed,
+        trees_read, launches, device_ns"""
+        return dict(getattr(self, "_diff_last", {}))
 
     def close(self):
         if getattr(self, "_h", None):

@@ -1499,6 +1499,70 @@ int md_pack_reachable(md_ctx *ctx, const md_pack_graph *g, const uint64_t *roots
 int md_pack_reach_last(const md_ctx *ctx, md_pack_reach_stats *stats);
 void md_pack_graph_free(md_pack_graph *g);
 
+/* ---- git packs: trees diffed, what every commit changed (csrc/pack_diff_kernels.hip, csrc/pack_diff.hpp) ----------------------
+ * md_pack_diff diffs npairs pairs of trees (a[q], b[q]) - indices of the table's objects, or MD_TREE_NONE for the empty tree -
+ * on the device: `git diff-tree` (flags 0) or `git diff-tree -r -t` (MD_PACK_DIFF_RECURSIVE) for every pair at once, without
+ * rename detection.  The graph g (md_pack_graph_build of the same table) gives the objects that entries name.
+ *
+ * Canonical mode: git's canon_mode of the entry's octal mode, parsed as above (32 bits, wrapping): (m & 0170000) == 0100000
+ * gives 0100755 if m & 0100, else 0100644; 0120000 gives 0120000; 0040000 gives 0040000; anything else 0160000.  An entry is a
+ * directory iff its canonical mode is 040000.
+ * Key and order: an entry's key is its name bytes, with '/' appended iff it is a directory; keys compare bytewise, a proper
+ * prefix first (git's base_name_compare).  A tree is sorted iff its keys ascend strictly.
+ * A tree is unreadable for the diff when the tree rules above refuse it, when it is not sorted, when its status in the graph is
+ * not MD_OK, when its type is not tree, and when the read refused it.
+ *
+ * A pair (A, B): entries match iff their keys are equal and both or neither is a directory (a file and a directory of one name
+ * never match).  Matched non-directories: equal canonical modes and equal 20 bytes give nothing, otherwise 'T' if the canonical
+ * modes differ in & 0170000, else 'M'.  Matched directories: equal 20 bytes give nothing, otherwise one 'M' record with
+ * MD_TREE_CHANGE_TREE and, when recursive, the sub-pair (A's subtree, B's subtree).  An entry only in A gives 'D', with
+ * MD_TREE_CHANGE_TREE and the sub-pair (subtree, MD_TREE_NONE) if it is a directory; one only in B gives 'A', with the sub-pair
+ * (MD_TREE_NONE, subtree).  Gitlinks are leaves: their 20 bytes are compared and never looked up.  A sub-pair with an unreadable
+ * side (or whose subtree the pack does not hold) is not descended: its directory record gets MD_TREE_CHANGE_OPAQUE.  A pair of
+ * the call with an unreadable side has no records and the status MD_INVALID_OBJECT, or the graph's or the read's own status
+ * where there is one (A's in front of B's); it never fails the call or its neighbours.  A == B gives MD_OK and no records, and
+ * neither tree is read.
+ *
+ * Records stand breadth first: level 0 holds every pair's records in pair order, level k + 1 the sub-pairs' records in the order
+ * of their directory records; within one pair first the records of A's entries in A's order ('D', 'M', 'T'), then those of the
+ * entries only B has in B's order ('A').  So the records are a function of pack, graph and pairs; it is not the order git
+ * prints in.  A record's path is the chain of names through `parent`.  name_off counts in the names blob, where the records'
+ * names stand in record order; a_obj / b_obj are the graph's `to` of the entry.
+ *
+ * How: per level, the host lists the level's distinct trees, the read decodes them and KEEPS THEM ON THE DEVICE, one launch
+ * writes every tree's table of entries (once a tree however many pairs share it), the diff kernel counts, two scans place the
+ * records, the diff kernel writes them, and the host derives the next level's sub-pairs.  A level's trees must fit the device
+ * beside the read's rounds ("pack_workspace"): a tree the read refuses (MD_E_OUT_OF_MEMORY) is unreadable.
+ * info: pairs; changes = records; name_bytes; levels = levels that had a pair to diff; opaque = records with
+ * MD_TREE_CHANGE_OPAQUE; failed = pairs whose status is not MD_OK; trees_read = trees decoded, summed over the levels; launches
+ * of the table and diff kernels and the scans (at most 5 a level, whatever the number of pairs); device_ns of the two kernels.
+ * md_pack_diff_changes: cap records and names_cap bytes at least info's (else MD_UNEXPECTED_END_OF_OUTPUT); cap == 0 with NULL
+ * arrays only asks.  An index >= n that is not MD_TREE_NONE, a flag other than MD_PACK_DIFF_RECURSIVE: MD_E_INVALID_ARGUMENT; a
+ * graph of another table or a pack other than the table's: MD_INVALID_INDEX.
+ * Not built: renames and copies, combined diffs of merges, pathspecs, blob contents. */
+#define MD_TREE_NONE 0xffffffffu
+#define MD_PACK_DIFF_RECURSIVE 1u
+#define MD_TREE_CHANGE_TREE 1
+#define MD_TREE_CHANGE_OPAQUE 2
+typedef struct md_tree_change {
+  uint32_t pair, parent;        /* the caller's pair; the directory record this one lies in, or MD_TREE_NONE at level 0 (parent < own index) */
+  uint8_t  kind, flags;         /* 'A' 'D' 'M' 'T'; MD_TREE_CHANGE_TREE, MD_TREE_CHANGE_OPAQUE */
+  uint32_t a_mode, b_mode;      /* canonical; 0 on the side that has no entry */
+  uint32_t a_obj, b_obj;        /* the graph's `to` for the entry, MD_PACK_NO_LINK where absent / gitlink / no entry */
+  uint32_t name_len; uint64_t name_off;   /* the entry's own name (not the path) in the names blob */
+  uint8_t  a_name[20], b_name[20];        /* zeros on the side that has no entry */
+} md_tree_change;
+typedef struct md_pack_diff_result md_pack_diff_result;
+typedef struct md_pack_diff_info {
+  uint64_t pairs, changes, name_bytes, levels, opaque, failed, trees_read, launches, device_ns;
+} md_pack_diff_info;
+int md_pack_diff(md_ctx *ctx, const md_pack *p, const md_pack_graph *g, const uint8_t *pack, size_t pack_len, size_t npairs, const uint32_t *a,
+                 const uint32_t *b, unsigned flags, md_pack_diff_result **r);
+int md_pack_diff_get(const md_pack_diff_result *r, md_pack_diff_info *info);
+int md_pack_diff_changes(const md_pack_diff_result *r, md_tree_change *changes, size_t cap, uint8_t *names, size_t names_cap);
+int md_pack_diff_status(const md_pack_diff_result *r, int32_t *status);
+void md_pack_diff_free(md_pack_diff_result *r);
+
 #ifdef __cplusplus
 }
 #endif
